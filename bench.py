@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — element-residual-grad evaluations per second of the PINN+GD hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--elems E] [--workload ex4|ex3]
+    python bench.py --gpus N --steps K --warmup W [--elems E] [--workload ex4|ex3] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else the benchmark
+measures: the per-kernel HIP-event pass and the roofline, the repeat statistic, the side configurations, metric (ii)
+(GD iterations to tolerance) and the CPU baseline.  --dump-outputs DIR writes the state the timed steps leave behind
+(displacements, network parameters, the last iteration's losses and norms) as DIR/<name>.npy.
 
 One "step" is one complete GD iteration (FEM/python/fem/solver.py:254-355) over a synthetic
 collinear 2-D truss (SURVEY.md §8(d) inputs): MLP forward for E and A at every element, element
@@ -228,6 +233,77 @@ def side_config(workload, n_elems, dev, steps, mesh="chain"):
             "steps": steps}
 
 
+def roofline(slot_ms, e1, widths, n_local, value, world, workload):
+    """Roofline entry of the dominant kernel of the HIP-event pass (--full)."""
+    from pinn_fem_amd import _capi
+    names = _capi.KERNEL_SLOT_NAMES
+    fused = e1.fusion_info()
+    dom = int(np.argmax(slot_ms))
+    # roofline of the dominant kernel.  The net_backward kernels are bound by f32 matrix/vector
+    # throughput (dense MLP GEMM work); the node kernels by HBM.
+    if names[dom].startswith("net_backward"):
+        both = bool(fused & _capi.PF_FUSED_BACKWARD)         # ONE launch carries the backward of both nets
+        if both:
+            flops, kname = sum(net_flops(w) for w in widths[:2] if w is not None), "net_backward (young + area, one launch)"
+        else:
+            flops, kname = net_flops(widths[0] if names[dom].endswith("young") else widths[1]), names[dom]
+        # the launch's own duration: HIP events around 20 back-to-back launches on the engine's stream (the eager
+        # slot time above also contains the gap to the next launch of the event pass)
+        launch_ms = float(slot_ms[dom])
+        if both:
+            try:
+                launch_ms = float(e1.time_step_launch("backward", 20))
+            except Exception:
+                pass
+        ach = flops * n_local / (launch_ms * 1e-3) / 1e12
+        roof = {"kernel": kname, "bound": "mfma", "achieved": ach, "peak": F32_PEAK_TFLOPS,
+                "unit": "TFLOP/s", "frac": ach / F32_PEAK_TFLOPS, "traffic": None,
+                "avg_launch_ms": launch_ms, "eager_slot_ms": float(slot_ms[dom]),
+                "note": "algorithmic float32 flops (forward recompute + backward) against the dense f32 peak; the "
+                        "engine executes every f32-grade product as three f16 MFMAs (2-way split operands), and the "
+                        "kernel is bound by vector-ALU / transcendental issue, not by the matrix pipe (DESIGN.md §4)"}
+    else:
+        # share of the 144 B/eval the kernel is responsible for is not separable: price the
+        # whole per-eval figure against this kernel's time (upper bound on its byte rate)
+        ach = ALGO_BYTES_PER_EVAL * n_local / (slot_ms[dom] * 1e-3) / 1e9
+        roof = {"kernel": names[dom], "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
+                "avg_launch_ms": float(slot_ms[dom])}
+    # HBM traffic of the dominant kernel: rocprofv3 PMC (FETCH_SIZE, WRITE_SIZE in separate passes,
+    # gfx950 correction applied) of this same command, committed under profiles/
+    try:
+        with open(os.path.join(ROOT, "profiles", "r03_traffic.json")) as f:
+            tr = json.load(f)["kernels"]
+        key = {"net_backward_young": "k_net32_backward2<10, 8, 2, 3>" if fused & _capi.PF_FUSED_BACKWARD
+               else "k_net32_backward<10, 2, 3, true>", "net_backward_area": "k_net32_backward<8, 2, 3, false>",
+               "node_residual": "k_node_residual<2>", "node_gradu_adam": "k_node_gradu<2, true>"}.get(names[dom])
+        if key in tr and n_local == 1_000_000 and workload == "ex4":
+            roof["traffic"] = tr[key]["hbm_bytes_corrected"]
+            roof["traffic_source"] = "profiles/r03_traffic.json (rocprofv3 --pmc, per launch)"
+    except Exception:
+        pass
+    it_bytes = ALGO_BYTES_PER_EVAL * value / world / 1e9
+    roof["iteration_hbm_GBs_per_gpu"] = it_bytes
+    roof["iteration_hbm_frac"] = it_bytes / HBM_PEAK_GBS
+    return roof
+
+
+DUMP_MAX_VALUES = 8 * 1024 * 1024      # per array: 32 MB of float32, so that a dump stays under 64 MB in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array; an array of more than DUMP_MAX_VALUES values is written as its values at a fixed,
+    seeded sample of sorted flat indices (the same sample for the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.size > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_VALUES, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_workers(n: int) -> int:
     """python -m torch.distributed.run --nnodes=1 --nproc-per-node n ... bench.py <same arguments>"""
     import socket
@@ -258,6 +334,11 @@ def main():
     ap.add_argument("--total-elems", type=int, default=0,
                     help="elements of the WHOLE bar (overrides --elems with total/gpus); BASELINE.json configs[3] is "
                          "--gpus 8 --total-elems 10000000")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed steps leave behind as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the HIP-event pass + roofline, the repeat statistic, the side configurations, metric (ii) "
+                         "and the CPU baseline (the --cpu-*, --no-*, --repeat options apply to these)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -325,15 +406,19 @@ def main():
         run_events = lambda n: eng.iterate_timed(n)
         graph_count = lambda: 0
 
-    # (1) K steps launched eagerly with a HIP event before every kernel on the launch stream: the per-kernel
+    # (1) --full: K steps launched eagerly with a HIP event before every kernel on the launch stream: the per-kernel
     # durations of the roofline (not part of `value`).  Run first, so that the timed region below starts on a chip
-    # that has already left its idle clocks; the W warm-up steps still come right before the timed K.
+    # that has already left its idle clocks; the W warm-up steps still come right before the timed K.  A plain run
+    # replays the same K steps as warm-up instead: the timed region starts after as many iterations either way.
     t1 = time.perf_counter()
-    slot_ms = run_events(args.steps)
+    if args.full:
+        slot_ms = run_events(args.steps)
+    else:
+        run_warm(args.steps)
     torch.cuda.synchronize(dev)
     dt_events = time.perf_counter() - t1
     iters_before = args.steps
-    if world > 1:
+    if world > 1 and args.full:
         # the event pass ran this rank's kernels WITHOUT the collective, so the replicated state (theta, interface
         # dofs) has drifted apart between ranks: start the sharded solve again (theta re-broadcast, fresh Adam state)
         eng.begin(None, 0.1, cfg)
@@ -368,9 +453,27 @@ def main():
     st = eng.state()
     assert st.iter == iters_before + n_warm + args.steps, (st.iter, iters_before + n_warm + args.steps)
     assert graph_count() == graphs_before, "a hipGraph was captured inside the timed region"
+    if args.dump_outputs:
+        # what solve_gd hands its caller after these iterations: displacements, network parameters (flat, young ->
+        # area -> density) and the last history row (loss_total, loss_physics, loss_data, u_norm, residual_norm, theta_norm)
+        e1 = eng if world == 1 else eng.backend.eng
+        if world == 1:
+            u = e1.u.cpu().numpy()
+        else:
+            from pinn_fem_amd.dist import gather_global_vector
+            be = eng.backend
+            ng = be.shard.nodes_global.astype(np.int64)
+            be.dofs_global = np.stack([2 * ng, 2 * ng + 1], axis=1).reshape(-1)
+            u = gather_global_vector(e1.u, be, 2 * (n_local * world + 1))
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {
+                "displacements": u.reshape(-1, 2),
+                "nn_parameters": e1.theta.flat[: e1.n_theta].cpu().numpy(),
+                "history_last": np.array([st.loss_total, st.loss_physics, st.loss_data, st.u_norm, st.residual_norm,
+                                          st.theta_norm], dtype=np.float64)})
     # repeat statistic (not `value`): R further regions of K steps each, timed the same way
     rep_ms = []
-    for _ in range(max(args.repeat, 0)):
+    for _ in range(max(args.repeat, 0) if args.full else 0):
         torch.cuda.synchronize(dev)
         if world > 1:
             dist.barrier()
@@ -391,7 +494,7 @@ def main():
     # weak-scaling headline (--elems per rank) does not reproduce: measured here as well, the same way (collective: every
     # rank takes part), unless the headline already is that configuration
     also_c3 = None
-    if world > 1 and not args.no_also and n_local * world != 10_000_000:
+    if world > 1 and args.full and not args.no_also and n_local * world != 10_000_000:
         from pinn_fem_amd.dist import ShardedChainEngine
         n3 = (10_000_000 if not rehearsal else 100_000) // world
         eng3 = ShardedChainEngine(n3, args.workload, rank, world, dev)
@@ -416,55 +519,8 @@ def main():
     if rank == 0:
         total_elems = n_local * world
         value = total_elems * args.steps / dt
-        names = _capi.KERNEL_SLOT_NAMES
-        fused = (eng if world == 1 else eng.backend.eng).fusion_info()
-        dom = int(np.argmax(slot_ms))
-        # roofline of the dominant kernel.  The net_backward kernels are bound by f32 matrix/vector
-        # throughput (dense MLP GEMM work); the node kernels by HBM.
-        if names[dom].startswith("net_backward"):
-            both = bool(fused & _capi.PF_FUSED_BACKWARD)         # ONE launch carries the backward of both nets
-            if both:
-                flops, kname = sum(net_flops(w) for w in widths[:2] if w is not None), "net_backward (young + area, one launch)"
-            else:
-                flops, kname = net_flops(widths[0] if names[dom].endswith("young") else widths[1]), names[dom]
-            # the launch's own duration: HIP events around 20 back-to-back launches on the engine's stream (the eager
-            # slot time above also contains the gap to the next launch of the event pass)
-            launch_ms = float(slot_ms[dom])
-            if both:
-                try:
-                    launch_ms = float((eng if world == 1 else eng.backend.eng).time_step_launch("backward", 20))
-                except Exception:
-                    pass
-            ach = flops * n_local / (launch_ms * 1e-3) / 1e12
-            roof = {"kernel": kname, "bound": "mfma", "achieved": ach, "peak": F32_PEAK_TFLOPS,
-                    "unit": "TFLOP/s", "frac": ach / F32_PEAK_TFLOPS, "traffic": None,
-                    "avg_launch_ms": launch_ms, "eager_slot_ms": float(slot_ms[dom]),
-                    "note": "algorithmic float32 flops (forward recompute + backward) against the dense f32 peak; the "
-                            "engine executes every f32-grade product as three f16 MFMAs (2-way split operands), and the "
-                            "kernel is bound by vector-ALU / transcendental issue, not by the matrix pipe (DESIGN.md §4)"}
-        else:
-            # share of the 144 B/eval the kernel is responsible for is not separable: price the
-            # whole per-eval figure against this kernel's time (upper bound on its byte rate)
-            ach = ALGO_BYTES_PER_EVAL * n_local / (slot_ms[dom] * 1e-3) / 1e9
-            roof = {"kernel": names[dom], "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
-                    "avg_launch_ms": float(slot_ms[dom])}
-        # HBM traffic of the dominant kernel: rocprofv3 PMC (FETCH_SIZE, WRITE_SIZE in separate passes,
-        # gfx950 correction applied) of this same command, committed under profiles/
-        try:
-            with open(os.path.join(ROOT, "profiles", "r03_traffic.json")) as f:
-                tr = json.load(f)["kernels"]
-            key = {"net_backward_young": "k_net32_backward2<10, 8, 2, 3>" if fused & _capi.PF_FUSED_BACKWARD
-                   else "k_net32_backward<10, 2, 3, true>", "net_backward_area": "k_net32_backward<8, 2, 3, false>",
-                   "node_residual": "k_node_residual<2>", "node_gradu_adam": "k_node_gradu<2, true>"}.get(names[dom])
-            if key in tr and n_local == 1_000_000 and args.workload == "ex4":
-                roof["traffic"] = tr[key]["hbm_bytes_corrected"]
-                roof["traffic_source"] = "profiles/r03_traffic.json (rocprofv3 --pmc, per launch)"
-        except Exception:
-            pass
-        it_bytes = ALGO_BYTES_PER_EVAL * value / world / 1e9
-        roof["iteration_hbm_GBs_per_gpu"] = it_bytes
-        roof["iteration_hbm_frac"] = it_bytes / HBM_PEAK_GBS
+        e1 = eng if world == 1 else eng.backend.eng
+        fused = e1.fusion_info()
         out = {
             "metric": "element-residual-grad evals/sec (PINN+GD iteration: MLP fwd+bwd, stiffness, "
                       "assembly, residual, Adam), collinear truss",
@@ -480,12 +536,6 @@ def main():
                                    f"{n_local} elements per GPU, collinear 2-D truss h=1, "
                                    f"alpha_data=100 with measurements at every node, load factor 0.1",
                        "elements_total": total_elems, "parallelism": f"elements sharded x{world}"},
-            "repeat": ({"regions": len(rep_ms), "steps_each": args.steps, "ms_per_step_each": [float(x) for x in rep_ms],
-                        "ms_per_step_median": float(np.median(rep_ms)),
-                        "ms_per_step_min": float(np.min(rep_ms)), "ms_per_step_max": float(np.max(rep_ms)),
-                        "value_at_median": total_elems * 1e3 / float(np.median(rep_ms))} if rep_ms else None),
-            "ms_per_step_eager_with_events": dt_events / args.steps * 1e3,
-            "kernel_ms": {n: float(m) for n, m in zip(names, slot_ms)},
             "fused_launches": {"forward_young+area": bool(fused & _capi.PF_FUSED_FORWARD),
                                "backward_young+area": bool(fused & _capi.PF_FUSED_BACKWARD),
                                "theta_update_in_next_forward (graph)": bool(fused & _capi.PF_FUSED_THETA_UPDATE),
@@ -494,15 +544,23 @@ def main():
                                "replays_chained (a replay hands its last iteration's updates and bookkeeping to the next one)":
                                    bool(world == 1 and all(getattr(eng, "_chain_graphs", {}).get(f) for f in (2, 3))),
                                "note": "a fused launch is booked on the first of its two kernel_ms slots"},
-            "roofline": roof,
         }
+        if args.full:
+            out["repeat"] = ({"regions": len(rep_ms), "steps_each": args.steps,
+                              "ms_per_step_each": [float(x) for x in rep_ms],
+                              "ms_per_step_median": float(np.median(rep_ms)),
+                              "ms_per_step_min": float(np.min(rep_ms)), "ms_per_step_max": float(np.max(rep_ms)),
+                              "value_at_median": total_elems * 1e3 / float(np.median(rep_ms))} if rep_ms else None)
+            out["ms_per_step_eager_with_events"] = dt_events / args.steps * 1e3
+            out["kernel_ms"] = {n: float(m) for n, m in zip(_capi.KERNEL_SLOT_NAMES, slot_ms)}
+            out["roofline"] = roofline(slot_ms, e1, widths, n_local, value, world, args.workload)
         if world > 1:
             from pinn_fem_amd.dist import shard_driver_info
             out["config"].update(shard_driver_info(eng.backend))
             if also_c3 is not None:
                 name = "configs[3]: 1e7-element bar sharded over the ranks" if not rehearsal else "configs[3] rehearsal (1e5 total)"
                 out["also"] = {name: also_c3}
-        if world == 1 and not args.no_also:
+        if world == 1 and args.full and not args.no_also:
             # BASELINE.json configs[1] (example3 shape, E = NN, 10^5 elements) for the record; the headline
             # `value` above stays the 10^6-element configuration the metric is quoted on
             out["also"] = {"configs[1]: ex3 shape, 1e5 elements, 1 GPU": side_config("ex3", 100_000, dev, args.steps),
@@ -511,7 +569,7 @@ def main():
                                                                                          mesh="warren")}
             # metric (ii) of SURVEY.md section 8(d): GD iterations to tolerance on the synthetic bar
             out["also"]["iters_to_tol"] = iters_to_tol(dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             threads = args.cpu_threads or min(64, _usable_cpus())
             out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_sample, args.cpu_iters, threads)
         print(json.dumps(out))

@@ -1445,7 +1445,7 @@ def test_bench_contract_single_gpu():
     """`bench.py` at a small size: one JSON line with the driver's keys, the roofline and cpu_baseline objects, no
     graph capture inside the timed region (asserted inside bench.py), K timed steps."""
     d = _bench_line(["--gpus", "1", "--steps", "20", "--warmup", "5", "--elems", "50000", "--cpu-sample", "20000",
-                     "--cpu-iters", "2", "--no-also"])
+                     "--cpu-iters", "2", "--no-also", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -1457,6 +1457,29 @@ def test_bench_contract_single_gpu():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and len(cb["rows"]) >= 7
     assert any(r["mode"].startswith("V (vectorised CPU PyTorch") and r["torch_num_threads"] == cb["cores"] for r in cb["rows"])
     assert d["repeat"]["regions"] == 5 and d["repeat"]["steps_each"] == 20
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain `bench.py` run: the headline keys and none of what --full adds; --dump-outputs writes the state the K
+    timed steps leave behind, and a second run with the same arguments writes the same values bit for bit."""
+    dumps = []
+    for k in range(2):
+        out_dir = tmp_path / f"run{k}"
+        d = _bench_line(["--gpus", "1", "--steps", "20", "--warmup", "5", "--elems", "50000", "--dump-outputs", str(out_dir)])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        for key in ("roofline", "kernel_ms", "repeat", "also", "cpu_baseline"):
+            assert key not in d, key
+        assert d["steps"] == 20 and d["dtype"] == "f32"
+        assert abs(d["value"] - 50000 * 20 / (d["ms_per_step"] * 20e-3)) < 1e-6 * d["value"]
+        dumps.append({f: np.load(out_dir / (f + ".npy")) for f in ("displacements", "nn_parameters", "history_last")})
+    a, b = dumps
+    assert a["displacements"].shape == (50001, 2) and a["displacements"].dtype == np.float32
+    assert a["nn_parameters"].dtype == np.float32 and a["nn_parameters"].size > 0
+    assert a["history_last"].shape == (6,) and a["history_last"].dtype == np.float64 and a["history_last"][0] > 0
+    for f in a:
+        assert np.all(np.isfinite(a[f])), f
+        assert np.array_equal(a[f], b[f]), f
 
 
 def test_bench_iters_to_tol_entry():
@@ -1471,12 +1494,14 @@ def test_bench_iters_to_tol_entry():
         assert np.isfinite(v["final_loss_total"])
 
 
-def test_bench_two_rank_rehearsal():
+def test_bench_two_rank_rehearsal(tmp_path):
     """`bench.py --gpus 2` without a launcher starts its own two ranks; here both on this one GPU over gloo
     (PINNFEM_BENCH_ONE_GPU=1: a rehearsal of the N>1 code path, not a multi-GPU number): the sharded driver runs, the
-    line reports the whole job (2 x elems per step) and which shard driver ran."""
-    d = _bench_line(["--gpus", "2", "--steps", "10", "--warmup", "2", "--elems", "30000", "--no-cpu-baseline", "--repeat", "2"],
-                    {"PINNFEM_BENCH_ONE_GPU": "1"})
+    line reports the whole job (2 x elems per step) and which shard driver ran; --dump-outputs writes the whole bar."""
+    d = _bench_line(["--gpus", "2", "--steps", "10", "--warmup", "2", "--elems", "30000", "--no-cpu-baseline", "--repeat", "2",
+                     "--full", "--dump-outputs", str(tmp_path)], {"PINNFEM_BENCH_ONE_GPU": "1"})
+    u = np.load(tmp_path / "displacements.npy")
+    assert u.shape == (60001, 2) and np.all(np.isfinite(u)) and np.any(u != 0)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and "REHEARSAL" in d["data"]
     # the fixed-total configuration beside the weak-scaling headline (configs[3]; 1e5 elements in the rehearsal)
     (c3,) = d["also"].values()

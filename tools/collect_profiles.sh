@@ -8,12 +8,12 @@ ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
 O=$ROOT/gpurun_out/prof_$V
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 echo bench done
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-also --repeat 2"
+ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-also --repeat 2 --full"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 $ROOT/bench.py $ARGS > $O/stats.log 2>&1
 echo stats done
-PARGS="--steps 10 --warmup 10 --no-cpu-baseline --no-also --repeat 0"
+PARGS="--steps 10 --warmup 10 --no-cpu-baseline --no-also --repeat 0 --full"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -o p -- python3 $ROOT/bench.py $PARGS > $O/fetch.log 2>&1
 echo fetch done
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -o p -- python3 $ROOT/bench.py $PARGS > $O/write.log 2>&1

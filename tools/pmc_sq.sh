@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc_sq
 mkdir -p $OUT
-ARGS="--steps 10 --warmup 10 --no-cpu-baseline --no-also"
+ARGS="--steps 10 --warmup 10 --no-cpu-baseline --no-also --full"
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d $OUT/p1 -- python3 bench.py $ARGS > $OUT/p1.log 2>&1
 echo pass1 done
