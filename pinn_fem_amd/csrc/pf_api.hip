@@ -145,10 +145,9 @@ static int net_forward_impl(const pf_problem* p, int which, hipStream_t s, int s
 }
 
 // both nets in ONE launch (pf_net32.hip: k_net32_forward2) where the engine has it: MFMA32, both nets enabled, same
-// number of hidden layers and inputs.  PF_FUSE_FWD=0: experiment knob (two launches, as before round 3).
+// number of hidden layers and inputs.
 static bool can_fuse_forward(const pf_problem* p) {
-  static const int knob = getenv("PF_FUSE_FWD") ? atoi(getenv("PF_FUSE_FWD")) : 1;
-  return knob != 0 && p->wg_mode == PF_WG_MFMA32 && p->net[0].enabled && p->net[1].enabled &&
+  return p->wg_mode == PF_WG_MFMA32 && p->net[0].enabled && p->net[1].enabled &&
          p->net[0].n_hidden == p->net[1].n_hidden && p->net[0].in_dim == p->net[1].in_dim;
 }
 #define PF_NR0_SWITCH(PREFIX)                                     \
@@ -181,19 +180,17 @@ static int net_forward_all(const pf_problem* p, hipStream_t s, const pf_fwd2_opt
   return PF_OK;
 }
 // Can the iteration graph fold the parameter update of iteration t into the forward launch of t+1?  MFMA32 engine with
-// the second state half present; PF_FUSE_S2=0: experiment knob (stand-alone update launch every iteration).
+// the second state half present.
 static bool can_fuse_theta_update(const pf_problem* p) {
-  static const int knob = getenv("PF_FUSE_S2") ? atoi(getenv("PF_FUSE_S2")) : 1;
-  return knob != 0 && p->wg_mode == PF_WG_MFMA32 && p->theta_alt != nullptr && p->n_theta_active > 0 &&
+  return p->wg_mode == PF_WG_MFMA32 && p->theta_alt != nullptr && p->n_theta_active > 0 &&
          (p->net[0].enabled || p->net[1].enabled);
 }
 
 // Can the iteration graph fold the displacement update (dL/du + Adam(u) + clamp) of iteration t into the fused forward
 // launch of t+1 (pf_net32.hip: k_net32_forward2, gu_nb; pf_node.h)?  The graph is then a plain chain: no side branch, no
-// fork, no join, no second displacement vector.  PF_FUSE_GU=0: experiment knob (gradu on its own branch, as in round 2).
+// fork, no join, no second displacement vector.
 static bool can_fuse_gradu(const pf_problem* p) {
-  static const int knob = getenv("PF_FUSE_GU") ? atoi(getenv("PF_FUSE_GU")) : 1;
-  return knob != 0 && can_fuse_forward(p) && pf_n32_fwd2_can_update_u(p, pf_node_blocks(p->mesh.n_nodes));
+  return can_fuse_forward(p) && pf_n32_fwd2_can_update_u(p, pf_node_blocks(p->mesh.n_nodes));
 }
 
 static int net_backward(const pf_problem* p, int which, hipStream_t s) {
@@ -204,12 +201,7 @@ static int net_backward(const pf_problem* p, int which, hipStream_t s) {
 }
 
 // Is the element adjoint (dL/d(EA) per element) computed inside the first net's backward kernel?
-static bool fuse_gea_for(const pf_problem* p) {
-  static const int knob = getenv("PF_FUSE_GEA") ? atoi(getenv("PF_FUSE_GEA")) : -1;   // experiment knob
-  if (p->wg_mode == PF_WG_MFMA44) return true;
-  if (p->wg_mode == PF_WG_MFMA32) return knob < 0 ? true : knob != 0;
-  return false;
-}
+static bool fuse_gea_for(const pf_problem* p) { return p->wg_mode == PF_WG_MFMA44 || p->wg_mode == PF_WG_MFMA32; }
 // backward that also computes and stores the element adjoint g_ea
 static int net_backward_gea(const pf_problem* p, int which, hipStream_t s) {
   if (p->wg_mode == PF_WG_MFMA32 && p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH(pf_launch_net32b_backward_gea_) }
@@ -218,44 +210,54 @@ static int net_backward_gea(const pf_problem* p, int which, hipStream_t s) {
 }
 
 // both backward passes (the first with the fused element adjoint) in ONE launch, two phases (pf_net32.hip:
-// k_net32_backward2).  PF_FUSE_BWD=0: experiment knob.
+// k_net32_backward2).
 static bool can_fuse_backward(const pf_problem* p) {
-  static const int knob = getenv("PF_FUSE_BWD") ? atoi(getenv("PF_FUSE_BWD")) : 1;
-  return knob != 0 && can_fuse_forward(p) && p->net[0].n_hidden == 2 && fuse_gea_for(p);
+  return can_fuse_forward(p) && p->net[0].n_hidden == 2 && fuse_gea_for(p);
 }
-// reduce_rows != 0: the launch also does theta stage 1 (the last block of every row group sums the group's rows into the
-// second-level row, the arithmetic of k_theta_stage1): no pf_launch_theta_stage1 behind it.  OFF by default
-// (PF_FUSE_S1=1 switches it on): bit-identical, but measured SLOWER on MI355X — the backward launch grew from 79 to 92 us
-// (every block drains its stores, takes a ticket, and the 16 last blocks read 16 rows each through sc1 loads) for a 7 us
-// kernel saved: 0.1547 against 0.1500 ms per iteration (profiles/r03_ab.txt).
-static bool fuse_s1_knob() {
-  static const int knob = getenv("PF_FUSE_S1") ? atoi(getenv("PF_FUSE_S1")) : 0;
-  return knob != 0;
-}
-static int net_backward2(const pf_problem* p, hipStream_t s, int reduce_rows = 0) {
+static int net_backward2(const pf_problem* p, hipStream_t s) {
 #define PF_NR0_SWITCH_B(PREFIX)                                   \
   switch (pf_net32_bucket(p->net[0].width)) {                     \
-    case 2: return PREFIX##2(p, s, reduce_rows);                  \
-    case 4: return PREFIX##4(p, s, reduce_rows);                  \
-    case 6: return PREFIX##6(p, s, reduce_rows);                  \
-    case 8: return PREFIX##8(p, s, reduce_rows);                  \
-    case 10: return PREFIX##10(p, s, reduce_rows);                \
-    case 12: return PREFIX##12(p, s, reduce_rows);                \
-    case 15: return PREFIX##15(p, s, reduce_rows);                \
+    case 2: return PREFIX##2(p, s);                               \
+    case 4: return PREFIX##4(p, s);                               \
+    case 6: return PREFIX##6(p, s);                               \
+    case 8: return PREFIX##8(p, s);                               \
+    case 10: return PREFIX##10(p, s);                             \
+    case 12: return PREFIX##12(p, s);                             \
+    case 15: return PREFIX##15(p, s);                             \
   }                                                               \
   return fail(PF_ERR_UNSUPPORTED, "MFMA32 engine: net width outside 1..30");
   if (p->mlp_dtype == PF_MLP_BF16) { PF_NR0_SWITCH_B(pf_launch_net32b_backward2_) }
   PF_NR0_SWITCH_B(pf_launch_net32_backward2_)
 }
-// element adjoint + backward of every enabled net; with the MFMA44 engine the adjoint is fused into
-// the first net's backward kernel
-
 
 #define PF_TRY(expr, what)                       \
   do {                                           \
     int rc__ = check_launch((expr), what);       \
     if (rc__ != PF_OK) return rc__;              \
   } while (0)
+
+// element adjoint + backward of every enabled net (at least one): both nets in one launch where the engine has it, else
+// one after the other with the adjoint fused into the first net's backward (fuse_gea_for) or in a launch of its own.
+// adj_done (graph capture): recorded on `s` right behind the launch that computes the adjoint, the last reader of u.
+static int enqueue_backwards(const pf_problem* p, hipStream_t s, hipEvent_t adj_done = nullptr) {
+  auto mark = [&]() { return !adj_done || hipEventRecord(adj_done, s) == hipSuccess; };
+  if (can_fuse_backward(p)) {
+    PF_TRY(net_backward2(p, s), "net_backward2");
+    return mark() ? PF_OK : fail(PF_ERR_HIP, "graph edge failed");
+  }
+  const bool fuse_gea = fuse_gea_for(p);
+  const int first = p->net[0].enabled ? 0 : 1;
+  if (!fuse_gea) {
+    PF_TRY(pf_launch_elem_adjoint(p, s), "elem_adjoint");
+    if (!mark()) return fail(PF_ERR_HIP, "graph edge failed");
+  }
+  for (int k = 0; k < 2; ++k) {
+    if (!p->net[k].enabled) continue;
+    PF_TRY(fuse_gea && k == first ? net_backward_gea(p, k, s) : net_backward(p, k, s), "net_backward");
+    if (fuse_gea && k == first && !mark()) return fail(PF_ERR_HIP, "graph edge failed");
+  }
+  return PF_OK;
+}
 
 extern "C" {
 
@@ -317,7 +319,7 @@ int pf_net_op_count(int in_dim, int width, int n_hidden) {
 
 long long pf_partials_count(const pf_problem* p) {
   if (!p) return PF_ERR_ARG;
-  return (long long)PF_PART_WG + ((long long)p->n_part_blocks + PF_RG) * (long long)p->pad_total + PF_TICKETS;
+  return (long long)PF_PART_WG + ((long long)p->n_part_blocks + PF_RG) * (long long)p->pad_total;
 }
 
 int pf_fusion_info(const pf_problem* p) {
@@ -356,19 +358,8 @@ int pf_net_forward_all(const pf_problem* p, void* stream) {
 int pf_net_backward_all(const pf_problem* p, void* stream) {
   int rc = check_problem(p);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
   if (!(p->net[0].enabled || p->net[1].enabled)) return PF_OK;
-  if (can_fuse_backward(p)) {
-    PF_TRY(net_backward2(p, s), "net_backward2");
-    return PF_OK;
-  }
-  const bool fuse_gea = fuse_gea_for(p);
-  const int first = p->net[0].enabled ? 0 : 1;
-  if (!fuse_gea) PF_TRY(pf_launch_elem_adjoint(p, s), "elem_adjoint");
-  for (int k = 0; k < 2; ++k)
-    if (p->net[k].enabled)
-      PF_TRY(fuse_gea && k == first ? net_backward_gea(p, k, s) : net_backward(p, k, s), "net_backward");
-  return PF_OK;
+  return enqueue_backwards(p, (hipStream_t)stream);
 }
 
 int pf_internal_force(const pf_problem* p, const float* u, float* f_int_out, void* stream) {
@@ -497,34 +488,42 @@ int pf_gd_iterations(const pf_problem* p, int n_iter, void* stream) {
   return PF_OK;
 }
 
-// Iterations as a dependency graph instead of a chain (only meaningful while capturing a hipGraph).
-// What each kernel of iteration t really waits for:
+// The iteration graph (pf_graph_create*): `iters` GD iterations captured on c.s, in one of two forms.
+//
+// ONE CHAIN (below PF_GRAPH_DAG_MIN_ELEMS elements, and wherever the forward launch can carry the displacement update):
+// every launch on c.s, no events: forward, residual, backwards, theta stage 1, gradu.  The forward launch of iteration i
+// also runs the parameter update of i-1 (can_fuse_theta_update; fwd_theta_prologue) and, where it can, the displacement
+// update of i-1 (dL/du + Adam(u) + clamp: can_fuse_gradu; it reads the stiffness records of i-1 = the other half, which is
+// why it needs prop_double); node_residual's block 0 runs the bookkeeping of i-1 (pf_mesh.hip: k_node_residual,
+// fin_prev) from the other half of the residual's partial sums (pf_problem.part_half).  Only the replay's last iteration
+// keeps the stand-alone parameter and displacement updates, in place, and the bookkeeping follows as a launch of its own.
+//
+// DAG (the larger problems whose forward launch cannot carry the displacement update: one net, unequal depths, the
+// non-MFMA32 engines): gradu runs on the side branch c.a.  What each kernel of iteration t really waits for:
 //   forward (E and A in one launch)   the second-level gradient rows of t-1 [theta stage 1 of t-1]: its prologue IS the
-//                       parameter update of t-1 (every block for itself; MFMA32 engine);  nothing reads the properties
-//                       or stiffness records of the other half any more  [gradu of t-1]
+//                       parameter update of t-1 (every block for itself; MFMA32 engine);  with prop_double nothing
+//                       reads the properties or stiffness records of the other half any more, else [gradu of t-1]
 //   node_residual       forward, u(t) [gradu of t-1]; its block 0 = finalize(t-1): the update of t-1, gradu of t-1, and the
 //                       OTHER half of the residual's partial sums (part_half)
 //   backward #1 (+gea)  g_f; it is the last reader of u(t)
 //   gradu + Adam(u)     g_f, the stiffness records, backward #1 done; the Adam scalars          [finalize of t-1]
 //   backward #2, theta stage 1   in this order after backward #1 (the last iteration of a replay: + the stand-alone update)
 //   finalize(t)         the update and gradu of t: it runs inside node_residual(t+1)
-// so gradu (HBM bound) runs on branch A beside backward #2 and the theta reduction (compute bound).  The stop flag
-// is read by every kernel at its start; a kernel of t+1 that misses a stop raised by finalize(t) only rewrites scratch
-// (properties, g_f, partial sums): everything that changes solver state (both Adam kernels, the next finalize)
-// is ordered behind finalize(t) and returns at once, so the final state is the reference's `break`.
-#define PF_CAP_EV 6
-// below this many elements the kernels are too short to hide anything behind: the branches' fork/join cost
-// (~5 us each against ~1.5 us for a plain boundary) would only add to a launch-bound iteration
+// so gradu (HBM bound) runs beside backward #2 and the theta reduction (compute bound).  With the second displacement
+// vector (pf_problem.u_alt, even replay length) the update of iteration i reads U[i & 1] like the residual and the element
+// adjoint of i and WRITES U[(i + 1) & 1]: it forks right behind the residual and runs beside the whole backward launch.
+// Without it, it forks behind the last read of u.  The runtime keeps the FIRST-created child of a node on its parent's
+// hardware queue and moves later children to other queues; every fork or join on the main chain costs ~5 us (kernel
+// trace).  So the side branch is created after the main chain's nodes of its iteration.
+//
+// The stop flag is read by every kernel at its start; a kernel of t+1 that misses a stop raised by finalize(t) only
+// rewrites scratch (properties, g_f, partial sums): everything that changes solver state (both Adam kernels, the next
+// finalize) is ordered behind finalize(t) and returns at once, so the final state is the reference's `break`.
+#define PF_CAP_EV 2
 struct pf_capture {
-  hipStream_t s, a, b;
-  hipEvent_t* ev;   // PF_CAP_EV per iteration: u readers done | gradu done | theta done | finalize done | forward fork | join
+  hipStream_t s, a;   // the captured stream and the side branch
+  hipEvent_t* ev;     // PF_CAP_EV per iteration: the last reader of u is done | gradu done
 };
-
-static int cap_edge(hipEvent_t e, hipStream_t from, hipStream_t to) {
-  if (hipEventRecord(e, from) != hipSuccess || hipStreamWaitEvent(to, e, 0) != hipSuccess)
-    return fail(PF_ERR_HIP, "graph edge failed");
-  return PF_OK;
-}
 
 // Does pf_problem.pad_index hold exactly what pf_pad_index_of computes (the layout pinn_fem_amd builds and INTEGRATION.md
 // describes: nets in order, pf_net_pad_index + pad_off)?  Then the forward launch's update prologue computes the index
@@ -540,156 +539,107 @@ static bool pad_index_is_canonical(const pf_problem* p) {
   return same;
 }
 
+// The buffers iteration i of the graph works on.  Properties and stiffness records ping-pong between iterations
+// (prop_double), so the forwards of iteration i do not wait for gradu(i-1), the last reader of the other half.  The
+// residual's partial sums always do (part_half).
+static pf_problem graph_iteration_view(const pf_problem& p, int i) {
+  pf_problem q = p;
+  if (p.prop_double != 0 && (i & 1)) {
+    q.prop_e += q.mesh.n_elems;
+    q.prop_a += q.mesh.n_elems;
+    if (q.elem_k) q.elem_k += (size_t)q.mesh.n_elems * (q.mesh.dim == 2 ? 3 : 1);
+  }
+  q.part_half = i & 1;
+  return q;
+}
+
 // head_cont: iteration 0 also carries the updates and the bookkeeping of the iteration BEFORE the replay (left pending by a
 // no_tail replay); no_tail: the replay ends behind the last iteration's gradient-row reduction, its parameter update,
 // displacement update and bookkeeping stay pending (pf_graph_create_ex).  Both only in the one-chain form.
 static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_capture& c, bool calc_index = false,
                                     bool head_cont = false, bool no_tail = false) {
-  const bool any_net = p->net[0].enabled || p->net[1].enabled;
   hipStream_t s = c.s;
-  // PF_GRAPH_SERIAL=1: experiment knob, the plain chain of launches inside the graph (no branches)
-  static const int serial_knob = getenv("PF_GRAPH_SERIAL") ? atoi(getenv("PF_GRAPH_SERIAL")) : -1;
-  bool serial = serial_knob >= 0 ? serial_knob != 0 : p->mesh.n_elems < PF_GRAPH_DAG_MIN_ELEMS;
-  if (!any_net) {
+  if (!(p->net[0].enabled || p->net[1].enabled)) {
     for (int i = 0; i < iters; ++i) {
       int rc = enqueue_iteration(p, 1, 0, s, nullptr);
       if (rc != PF_OK) return rc;
     }
     return PF_OK;
   }
-  // serial: the same kernels as ONE chain on `s` (no side branch, no events): forward, residual [+ finalize of the
-  // previous iteration in its block 0], backwards, theta stage 1, gradu — neither the bookkeeping nor the parameter update
-  // costs a launch of its own there either.
-  static const bool pp_knob = !(getenv("PF_GRAPH_PINGPONG") && atoi(getenv("PF_GRAPH_PINGPONG")) == 0);
-  const bool pingpong = p->prop_double != 0 && pp_knob;
-  // The displacement update of iteration i-1 (dL/du + Adam(u) + clamp) runs INSIDE iteration i's forward launch, as node
-  // tasks between its element tasks (can_fuse_gradu; it reads the stiffness records of i-1 = the other half, which is
-  // why it needs the two halves): the graph is then ONE chain.  Only the replay's last iteration keeps the stand-alone
-  // kernel, in place.
-  const bool fuse_gu = pingpong && p->elem_k != nullptr && can_fuse_gradu(p);
-  if (fuse_gu) serial = true;
-  hipStream_t sa = serial ? s : c.a;
-  auto ev_wait = [&](hipStream_t st, hipEvent_t e) { return serial || hipStreamWaitEvent(st, e, 0) == hipSuccess; };
-  auto ev_rec = [&](hipEvent_t e, hipStream_t st) { return serial || hipEventRecord(e, st) == hipSuccess; };
-  const bool fuse_gea = fuse_gea_for(p);
-  const int first = p->net[0].enabled ? 0 : 1;
-  // The runtime keeps the FIRST-created child of a node on its parent's hardware queue and moves later
-  // children to other queues; every fork or join on the main chain costs ~5 us (kernel trace).  So the nodes are
-  // created in the order that keeps the critical chain (forwards, residual, backwards, theta) on one queue, and
-  // the bookkeeping kernel has NO node of its own: finalize(i-1) runs as block 0 of node_residual(i)
-  // (pf_mesh.hip: k_node_residual, fin_prev) from the other half of the residual's partial sums
-  // (pf_problem.part_half), finalize of the graph's last iteration as a stand-alone launch at its end.
-  const int tn_ready = p->wg_mode == PF_WG_MFMA32 ? 1 : 0;   // k_theta_stage2 leaves the theta-norm monitor in the state
-  // The parameter update of iteration i-1 (theta stage 2: second-level rows -> Adam -> operand images) runs in the
-  // PROLOGUE of iteration i's forward launch, by every block for itself (pf_net32.hip: fwd_theta_prologue); the state
-  // ping-pongs between its two halves so that block 0's stores never meet another block's loads.  Only the replay's
-  // last iteration keeps the stand-alone update, which also brings the state back to half 0.
+  const bool fuse_gu = p->prop_double != 0 && p->elem_k != nullptr && can_fuse_gradu(p);
+  const bool dag = !fuse_gu && p->mesh.n_elems >= PF_GRAPH_DAG_MIN_ELEMS;
+  const bool upp = dag && p->u_alt != nullptr && (iters % 2) == 0;    // DAG with the second displacement vector
   const bool fuse_s2 = can_fuse_theta_update(p);
-  // Displacement vectors ping-pong too (pf_problem.u_alt; DAG form, even replay length): the update of iteration i reads
-  // U[i & 1] like the residual and the element adjoint of i and WRITES U[(i + 1) & 1], so it forks right behind the
-  // residual and runs beside the whole backward launch.  PF_GRAPH_UPP=0: experiment knob (in place, fork behind the
-  // adjoint's last read of u).
-  static const bool upp_knob = !(getenv("PF_GRAPH_UPP") && atoi(getenv("PF_GRAPH_UPP")) == 0);
-  const bool upp = !serial && upp_knob && p->u_alt != nullptr && (iters % 2) == 0;
-  const float* c_elem_k = p->elem_k;
+  const int tn_ready = p->wg_mode == PF_WG_MFMA32 ? 1 : 0;   // k_theta_stage2 leaves the theta-norm monitor in the state
+  const size_t k_half = (size_t)p->mesh.n_elems * (p->mesh.dim == 2 ? 3 : 1);   // floats of one half of the records
   for (int i = 0; i < iters; ++i) {
     hipEvent_t* e = c.ev + PF_CAP_EV * i;
     hipEvent_t* ep = c.ev + PF_CAP_EV * (i - 1);
-    // Property buffers ping-pong between iterations (prop_double), so the forwards of iteration i do not wait
-    // for gradu(i-1), the last reader of the other half: the main chain then has ONE incoming edge from another
-    // queue per iteration (gradu(i-1) -> residual(i): u, and the u-norm partials finalize(i-1) reads there).
-    // Without the second half the forwards wait for gradu(i-1) (an 11 us hole in the kernel trace).
-    pf_problem q = *p;
-    const pf_problem* p = &q;   // (shadows the argument for the rest of this iteration)
-    if (pingpong && (i & 1)) {
-      q.prop_e += q.mesh.n_elems;
-      q.prop_a += q.mesh.n_elems;
-      if (q.elem_k) q.elem_k += (size_t)q.mesh.n_elems * (q.mesh.dim == 2 ? 3 : 1);
-    }
-    q.part_half = i & 1;
+    pf_problem q = graph_iteration_view(*p, i);
     float* u_next = nullptr;
     if (upp) {
       u_next = (i & 1) ? q.u : q.u_alt;
       if (i & 1) q.u = q.u_alt;                       // what this iteration's kernels READ
     }
-    if (i > 0 && !pingpong && !ev_wait(s, ep[1])) return fail(PF_ERR_HIP, "graph edge failed");
-    // (both nets in one launch where the engine has it; else one after the other: side by side on two branches they
-    // measured slower, the same issue pipe, and the second one writes the stiffness records from both)
     const bool carries = i > 0 || head_cont;      // this iteration's forward / residual carry the previous iteration's work
-    const float* k_prev = nullptr;        // the records iteration i-1 wrote (the other half)
-    if (fuse_gu && carries) k_prev = ((i - 1) & 1) ? c_elem_k + (size_t)q.mesh.n_elems * (q.mesh.dim == 2 ? 3 : 1) : c_elem_k;
     pf_fwd2_opts fo;
     if (fuse_s2 && carries) fo.s2_half = (i - 1) & 1;       // (i = 0 in a continuation: the previous replay's last = half 1)
     fo.calc_index = calc_index;
-    if (k_prev) {
+    if (fuse_gu && carries) {
       fo.gu_nb = pf_node_blocks(q.mesh.n_nodes);
-      fo.gu_k = k_prev;
+      fo.gu_k = p->elem_k + (((i - 1) & 1) ? k_half : 0);   // the records iteration i-1 wrote (the other half)
     }
-    PF_TRY(net_forward_all(p, s, fo), "net_forward");
+    // (DAG without the second property half: the forwards wait for gradu(i-1), an 11 us hole in the kernel trace)
+    if (dag && i > 0 && p->prop_double == 0 && hipStreamWaitEvent(s, ep[1], 0) != hipSuccess)
+      return fail(PF_ERR_HIP, "graph edge failed");
+    // (both nets in one launch where the engine has it; else one after the other: side by side on two branches they
+    // measured slower, the same issue pipe, and the second one writes the stiffness records from both)
+    PF_TRY(net_forward_all(&q, s, fo), "net_forward");
     // residual(i) reads u(i) [gradu(i-1)]; its block 0 is finalize(i-1): behind the theta update of i-1 (this chain:
     // the forward launch above, or the stand-alone kernel) and gradu(i-1)
-    if (i > 0 && !ev_wait(s, ep[1])) return fail(PF_ERR_HIP, "graph edge failed");
-    PF_TRY(pf_launch_node_residual(p, nullptr, 1, s, carries ? (tn_ready ? 2 : 1) : 0), "node_residual");
-    if (upp && !ev_rec(e[0], s)) return fail(PF_ERR_HIP, "graph edge failed");      // gradu forks here
-    if (!fuse_gea) {
-      PF_TRY(pf_launch_elem_adjoint(p, s), "elem_adjoint");
-      if (!upp && !ev_rec(e[0], s)) return fail(PF_ERR_HIP, "graph edge failed");
+    if (dag && i > 0 && hipStreamWaitEvent(s, ep[1], 0) != hipSuccess) return fail(PF_ERR_HIP, "graph edge failed");
+    PF_TRY(pf_launch_node_residual(&q, nullptr, 1, s, carries ? (tn_ready ? 2 : 1) : 0), "node_residual");
+    if (upp && hipEventRecord(e[0], s) != hipSuccess) return fail(PF_ERR_HIP, "graph edge failed");   // gradu forks here
+    if (const int rc = enqueue_backwards(&q, s, dag && !upp ? e[0] : nullptr)) return rc;   // (... or here)
+    PF_TRY(pf_launch_theta_stage1(&q, s), "theta_stage1");
+    if (!fuse_s2 || (i == iters - 1 && !no_tail)) PF_TRY(pf_launch_theta_stage2(&q, 1, s), "theta_stage2");
+    if (!dag) {
+      if (!fuse_gu || (i == iters - 1 && !no_tail)) PF_TRY(pf_launch_node_gradu(&q, 1, s, 0, nullptr), "node_gradu");
+      continue;                                   // (else the next forward launch carries it)
     }
-    if (can_fuse_backward(p)) {
-      // both backward passes in one launch (without the second displacement vector gradu can only fork behind it)
-      PF_TRY(net_backward2(p, s, fuse_s1_knob() ? 1 : 0), "net_backward2");
-      if (!upp && !ev_rec(e[0], s)) return fail(PF_ERR_HIP, "graph edge failed");
-    } else {
-      for (int k = 0; k < 2; ++k) {
-        if (!p->net[k].enabled) continue;
-        PF_TRY(fuse_gea && k == first ? net_backward_gea(p, k, s) : net_backward(p, k, s), "net_backward");
-        if (!upp && fuse_gea && k == first && !ev_rec(e[0], s)) return fail(PF_ERR_HIP, "graph edge failed");
-      }
-    }
-    if (!(can_fuse_backward(p) && fuse_s1_knob())) PF_TRY(pf_launch_theta_stage1(p, s), "theta_stage1");
-    if (!fuse_s2 || (i == iters - 1 && !no_tail)) PF_TRY(pf_launch_theta_stage2(p, 1, s), "theta_stage2");
-    // branch A (created after the main chain's nodes of this iteration): gradu behind the last reader of u
-    if (fuse_gu && (i < iters - 1 || no_tail)) continue;   // (the next forward launch carries it)
-    if (!ev_wait(sa, e[0])) return fail(PF_ERR_HIP, "graph edge failed");
-    PF_TRY(pf_launch_node_gradu(p, 1, sa, 0, u_next), "node_gradu");
-    if (!ev_rec(e[1], sa)) return fail(PF_ERR_HIP, "graph edge failed");
+    // side branch: gradu behind the last reader of u
+    if (hipStreamWaitEvent(c.a, e[0], 0) != hipSuccess) return fail(PF_ERR_HIP, "graph edge failed");
+    PF_TRY(pf_launch_node_gradu(&q, 1, c.a, 0, u_next), "node_gradu");
+    if (hipEventRecord(e[1], c.a) != hipSuccess) return fail(PF_ERR_HIP, "graph edge failed");
   }
   // finalize of the last iteration: behind stage 2 (this chain) and the last gradu
   if (no_tail) return PF_OK;
-  if (!serial && !ev_wait(s, c.ev[PF_CAP_EV * (iters - 1) + 1])) return fail(PF_ERR_HIP, "graph join failed");
+  if (dag && hipStreamWaitEvent(s, c.ev[PF_CAP_EV * (iters - 1) + 1], 0) != hipSuccess)
+    return fail(PF_ERR_HIP, "graph join failed");
   if (upp) PF_TRY(pf_launch_u_home(p, s), "u_home");      // (only a stop in mid-replay leaves anything to copy)
-  {
-    pf_problem q = *p;
-    q.part_half = (iters - 1) & 1;
-    PF_TRY(pf_launch_finalize(&q, 0, 0, s, tn_ready), "finalize");
-  }
+  pf_problem q = *p;
+  q.part_half = (iters - 1) & 1;
+  PF_TRY(pf_launch_finalize(&q, 0, 0, s, tn_ready), "finalize");
   return PF_OK;
 }
 
 }  // extern "C"
-// capture fn(capture streams/events) on `s` (+ two side streams) and instantiate the graph
+// capture fn(capture streams/events) on `s` (+ a side stream) and instantiate the graph
 template <class F>
 static int capture_graph(hipStream_t s, int nev, hipStreamCaptureMode mode, void** graph_out, F&& fn) {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  hipStream_t side[2] = {nullptr, nullptr};
+  hipStream_t side = nullptr;
   hipEvent_t* ev = new hipEvent_t[nev];
   int made = 0;
-  // PF_GRAPH_SIDE_PRIO (experiment knob): priority of the capture's side streams (-1 high, 0 default, 1 low)
-  static const int prio_knob = getenv("PF_GRAPH_SIDE_PRIO") ? atoi(getenv("PF_GRAPH_SIDE_PRIO")) : 0;
-  int lo = 0, hi = 0;
-  (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-  const int prio = prio_knob < 0 ? hi : (prio_knob > 0 ? lo : 0);
-  bool ok = hipStreamCreateWithPriority(&side[0], hipStreamNonBlocking, prio) == hipSuccess &&
-            hipStreamCreateWithPriority(&side[1], hipStreamNonBlocking, prio) == hipSuccess;
+  bool ok = hipStreamCreateWithFlags(&side, hipStreamNonBlocking) == hipSuccess;
   for (; ok && made < nev; ++made)
     if (hipEventCreateWithFlags(&ev[made], hipEventDisableTiming) != hipSuccess) break;
   ok = ok && made == nev;
   auto cleanup = [&]() {
     for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
     delete[] ev;
-    for (int k = 0; k < 2; ++k)
-      if (side[k]) (void)hipStreamDestroy(side[k]);
+    if (side) (void)hipStreamDestroy(side);
   };
   if (!ok) {
     cleanup();
@@ -699,7 +649,7 @@ static int capture_graph(hipStream_t s, int nev, hipStreamCaptureMode mode, void
     cleanup();
     return fail(PF_ERR_HIP, "hipStreamBeginCapture failed");
   }
-  pf_capture cap{s, side[0], side[1], ev};
+  pf_capture cap{s, side, ev};
   const int rc = fn(cap);
   const hipError_t e = hipStreamEndCapture(s, &graph);
   cleanup();
@@ -719,20 +669,12 @@ static int capture_graph(hipStream_t s, int nev, hipStreamCaptureMode mode, void
 extern "C" {
 
 int pf_graph_create(const pf_problem* p, int iters_per_graph, void* stream, void** graph_out) {
-  int rc = check_gd(p);
-  if (rc) return rc;
-  if (!graph_out || iters_per_graph < 1) return fail(PF_ERR_ARG, "pf_graph_create: bad argument");
-  static const int ci_knob = getenv("PF_CALC_INDEX") ? atoi(getenv("PF_CALC_INDEX")) : 1;   // 0: experiment knob (index table)
-  const bool calc_index = ci_knob != 0 && can_fuse_theta_update(p) && pad_index_is_canonical(p);
-  return capture_graph((hipStream_t)stream, PF_CAP_EV * iters_per_graph, hipStreamCaptureModeThreadLocal, graph_out,
-                       [&](pf_capture& cap) { return enqueue_graph_iterations(p, iters_per_graph, cap, calc_index); });
+  return pf_graph_create_ex(p, iters_per_graph, 0, stream, graph_out);
 }
 
 // can the iteration graph of this problem be cut into replays that hand their last iteration's updates to the next one?
 static bool can_chain_replays(const pf_problem* p, int iters) {
-  static const bool pp_knob = !(getenv("PF_GRAPH_PINGPONG") && atoi(getenv("PF_GRAPH_PINGPONG")) == 0);
-  return (iters % 2) == 0 && p->prop_double != 0 && pp_knob && p->elem_k != nullptr && can_fuse_gradu(p) &&
-         can_fuse_theta_update(p);
+  return (iters % 2) == 0 && p->prop_double != 0 && p->elem_k != nullptr && can_fuse_gradu(p) && can_fuse_theta_update(p);
 }
 
 int pf_graph_create_ex(const pf_problem* p, int iters_per_graph, int flags, void* stream, void** graph_out) {
@@ -741,8 +683,7 @@ int pf_graph_create_ex(const pf_problem* p, int iters_per_graph, int flags, void
   if (!graph_out || iters_per_graph < 1) return fail(PF_ERR_ARG, "pf_graph_create_ex: bad argument");
   if ((flags & (PF_GRAPH_CONT_HEAD | PF_GRAPH_NO_TAIL)) && !can_chain_replays(p, iters_per_graph))
     return fail(PF_ERR_UNSUPPORTED, "pf_graph_create_ex: replays of this problem's graph cannot hand over their tail");
-  static const int ci_knob = getenv("PF_CALC_INDEX") ? atoi(getenv("PF_CALC_INDEX")) : 1;
-  const bool calc_index = ci_knob != 0 && can_fuse_theta_update(p) && pad_index_is_canonical(p);
+  const bool calc_index = can_fuse_theta_update(p) && pad_index_is_canonical(p);
   const bool head = (flags & PF_GRAPH_CONT_HEAD) != 0, no_tail = (flags & PF_GRAPH_NO_TAIL) != 0;
   return capture_graph((hipStream_t)stream, PF_CAP_EV * iters_per_graph, hipStreamCaptureModeThreadLocal, graph_out,
                        [&](pf_capture& cap) { return enqueue_graph_iterations(p, iters_per_graph, cap, calc_index, head, no_tail); });
@@ -754,14 +695,7 @@ int pf_graph_tail(const pf_problem* p, int iters_per_graph, void* stream) {
   if (rc) return rc;
   if (!can_chain_replays(p, iters_per_graph)) return fail(PF_ERR_UNSUPPORTED, "pf_graph_tail: not a chained replay");
   hipStream_t s = (hipStream_t)stream;
-  pf_problem q = *p;                      // the last iteration's halves (iters even: the second ones)
-  const int i = iters_per_graph - 1;
-  if (i & 1) {
-    q.prop_e += q.mesh.n_elems;
-    q.prop_a += q.mesh.n_elems;
-    if (q.elem_k) q.elem_k += (size_t)q.mesh.n_elems * (q.mesh.dim == 2 ? 3 : 1);
-  }
-  q.part_half = i & 1;
+  const pf_problem q = graph_iteration_view(*p, iters_per_graph - 1);   // the last iteration's halves
   PF_TRY(pf_launch_theta_stage2(&q, 1, s), "theta_stage2");
   PF_TRY(pf_launch_node_gradu(&q, 1, s, 0, nullptr), "node_gradu");
   PF_TRY(pf_launch_finalize(&q, 0, 0, s, q.wg_mode == PF_WG_MFMA32 ? 1 : 0), "finalize");
@@ -865,16 +799,8 @@ int pf_shard_backward(const pf_problem* p, float* buf, const float* u2_local, vo
   PF_TRY(pf_launch_node_residual(p, nullptr, 1, s), "node_residual");
   if (any_net) {
     const pf_problem q = own_view(p);
-    const bool fuse_gea = fuse_gea_for(&q);
-    const int first = q.net[0].enabled ? 0 : 1;
-    if (can_fuse_backward(&q)) {
-      PF_TRY(net_backward2(&q, s), "net_backward2");
-    } else {
-      if (!fuse_gea) PF_TRY(pf_launch_elem_adjoint(&q, s), "elem_adjoint");
-      for (int k = 0; k < 2; ++k)
-        if (q.net[k].enabled)
-          PF_TRY(fuse_gea && k == first ? net_backward_gea(&q, k, s) : net_backward(&q, k, s), "net_backward");
-    }
+    rc = enqueue_backwards(&q, s);
+    if (rc) return rc;
     PF_TRY(pf_launch_theta_stage1(&q, s), "theta_stage1");
   }
   PF_TRY(pf_launch_shard_pack(p, buf, u2_local, s), "shard_pack");
@@ -912,32 +838,14 @@ int pf_shard_graph_capture(const pf_problem* p, int iters, float* buf, float* u2
       hipEvent_t* e = c.ev + 2 * i;
       PF_TRY(net_forward_all(p, s), "net_forward");
       PF_TRY(pf_launch_node_residual(p, nullptr, 1, s), "node_residual");
-      bool marked = false;                  // e[0]: the last reader of u (the element adjoint) is done
-      auto mark = [&]() {
-        marked = true;
-        return hipEventRecord(e[0], s) == hipSuccess;
-      };
+      // e[0]: the last reader of u (the element adjoint) is done
       if (any_net) {
         const pf_problem q = own_view(p);
-        const bool fuse_gea = fuse_gea_for(&q);
-        const int first = q.net[0].enabled ? 0 : 1;
-        if (can_fuse_backward(&q)) {
-          PF_TRY(net_backward2(&q, s), "net_backward2");
-          if (!mark()) return fail(PF_ERR_HIP, "graph edge failed");
-        } else {
-          if (!fuse_gea) {
-            PF_TRY(pf_launch_elem_adjoint(&q, s), "elem_adjoint");
-            if (!mark()) return fail(PF_ERR_HIP, "graph edge failed");
-          }
-          for (int k = 0; k < 2; ++k) {
-            if (!q.net[k].enabled) continue;
-            PF_TRY(fuse_gea && k == first ? net_backward_gea(&q, k, s) : net_backward(&q, k, s), "net_backward");
-            if (fuse_gea && k == first && !mark()) return fail(PF_ERR_HIP, "graph edge failed");
-          }
-        }
+        if (const int rb = enqueue_backwards(&q, s, e[0])) return rb;
         PF_TRY(pf_launch_theta_stage1(&q, s), "theta_stage1");
+      } else if (hipEventRecord(e[0], s) != hipSuccess) {
+        return fail(PF_ERR_HIP, "graph edge failed");
       }
-      if (!marked && !mark()) return fail(PF_ERR_HIP, "graph edge failed");
       PF_TRY(pf_launch_shard_pack(p, buf, u2_local, s), "shard_pack");
       // the side branch is created AFTER the chain's nodes of this iteration: the runtime keeps the first-created child of
       // a node on its parent's hardware queue, and the chain must be the one that stays (pf_graph_create, same rule)

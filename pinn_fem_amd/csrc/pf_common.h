@@ -17,10 +17,8 @@
 #define PF_PART_D2H(h) ((h) ? 4 * PF_NODE_SLOTS : PF_NODE_SLOTS)
 #define PF_PART_U2 (2 * PF_NODE_SLOTS)
 #define PF_PART_WG (5 * PF_NODE_SLOTS)
-// after the [n_part_blocks][pad_total] rows: [PF_RG][pad_total] second-level partial rows, then PF_RG + 16 int32 row-group
-// tickets (zero between launches) of the fused backward launch, which does the first reduction level itself
+// after the [n_part_blocks][pad_total] rows: [PF_RG][pad_total] second-level partial rows
 #define PF_RG 16
-#define PF_TICKETS (PF_RG + 16)
 
 // elements per block-iteration of the net kernels (2 waves)
 #define PF_NET_THREADS 128
@@ -345,9 +343,7 @@ __device__ __forceinline__ float pf_elem_gea(const pf_problem& P, int e) {
 #define PF_NET44_CS 36   /* floats per LDS column (Row<L>::CS) */
 __host__ __device__ constexpr int pf_net44_row_len(int hp, int nh) { return nh * hp + 8 + nh * (hp + 4); }
 inline int pf_net44_threads(const pf_problem* p) {
-  // PF_NET44_THREADS (128 | 256 | 512): experiment knob
-  static const int knob = getenv("PF_NET44_THREADS") ? atoi(getenv("PF_NET44_THREADS")) : PF_NET44_MAX_THREADS;
-  int waves = (knob >= 128 && knob <= PF_NET44_MAX_THREADS ? knob : PF_NET44_MAX_THREADS) / 64;
+  int waves = PF_NET44_MAX_THREADS / 64;
   for (int k = 0; k < 2; ++k) {
     if (!p->net[k].enabled) continue;
     const int hp = ((p->net[k].width + 3) / 4) * 4;
@@ -357,10 +353,10 @@ inline int pf_net44_threads(const pf_problem* p) {
 }
 // MFMA32 engine, backward: one block of 8 or 12 waves per CU (pf_net32.hip decides per kernel), every wave walks
 // 64-element tasks.  Both backward launches of a problem use the same number of blocks (= partial gradient rows).
+#define PF_NET32_MAX_BLOCKS 256
 inline int pf_net32_blocks(const pf_problem* p) {
-  static const int cap = getenv("PF_NET32_BLOCKS") ? atoi(getenv("PF_NET32_BLOCKS")) : 256;
   int nb = (p->mesh.n_elems + 511) / 512;
-  if (nb > cap) nb = cap;
+  if (nb > PF_NET32_MAX_BLOCKS) nb = PF_NET32_MAX_BLOCKS;
   if (nb > p->n_part_blocks) nb = p->n_part_blocks;
   if (nb < 1) nb = 1;
   return nb;
@@ -418,8 +414,8 @@ struct pf_fwd2_opts {
   int pf_launch_net32b_backward_gea_##NRB(const pf_problem* p, int which, hipStream_t s); \
   int pf_launch_net32_forward2_##NRB(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o);    \
   int pf_launch_net32b_forward2_##NRB(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o);   \
-  int pf_launch_net32_backward2_##NRB(const pf_problem* p, hipStream_t s, int reduce_rows); \
-  int pf_launch_net32b_backward2_##NRB(const pf_problem* p, hipStream_t s, int reduce_rows);
+  int pf_launch_net32_backward2_##NRB(const pf_problem* p, hipStream_t s);                \
+  int pf_launch_net32b_backward2_##NRB(const pf_problem* p, hipStream_t s);
 PF_DECL_NET32_LAUNCHERS(2)
 PF_DECL_NET32_LAUNCHERS(4)
 PF_DECL_NET32_LAUNCHERS(6)

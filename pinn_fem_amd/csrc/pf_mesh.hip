@@ -88,9 +88,7 @@ __device__ void finalize_body(const pf_problem& P, int nb_node, int mode, int wi
 // fin_prev (1, or 2 = with tn_ready): block 0 does the bookkeeping of the PREVIOUS iteration (finalize_body: monitors, history row, stop test,
 // next Adam scalars) from the other half of the residual sums while the remaining blocks work on this iteration's
 // nodes — the single-block, latency-bound finalize then costs nothing and needs no branch of its own in the graph.
-#ifndef PF_RESIDUAL_NODES
 #define PF_RESIDUAL_NODES 2
-#endif
 template <int DIM>
 __global__ __launch_bounds__(PF_NODE_THREADS) __attribute__((amdgpu_num_sgpr(72))) void k_node_residual(pf_problem P, float* f_int_out,
                                                                     int compute_loss, int fin_prev) {
@@ -795,8 +793,7 @@ int pf_node_blocks(int n_nodes) {
   // measured at 10^6 nodes (MI355X) with the pairwise walk of the node kernels (two nodes of a thread at a time):
   // 1024 blocks (4 waves per SIMD, two pairs per thread) 0.1398 ms per iteration against 0.1412 (2048), 0.1417 (1280),
   // 0.1419 (768), 0.1432 (512) (profiles/r03_ab.txt; the one-node-at-a-time kernels of round 2 were best at 2048).
-  // PF_NODE_BLOCKS: experiment knob.
-  static const int cap = getenv("PF_NODE_BLOCKS") ? atoi(getenv("PF_NODE_BLOCKS")) : 1024;
+  constexpr int cap = 1024;
   int nb = (n_nodes + PF_NODE_THREADS - 1) / PF_NODE_THREADS;
   if (nb > cap) nb = cap;
   if (nb > PF_MAX_NODE_BLOCKS) nb = PF_MAX_NODE_BLOCKS;
@@ -826,15 +823,11 @@ int pf_launch_node_gradu(const pf_problem* p, int fuse_adam, hipStream_t s, int 
   const int nb = pf_node_blocks(p->mesh.n_nodes);
   const dim3 g(nb), b(PF_NODE_THREADS);
   const int out_alt = u_out != nullptr && u_out == p->u_alt ? 1 : 0;
-  // PF_GRADU_LDS (experiment knob): dynamic LDS bytes the side-branch launch of the iteration graph (u_out != null) asks
-  // for without using them — caps how many of its blocks a CU holds, so that a forward block always finds room beside them
-  static const int lds_knob = getenv("PF_GRADU_LDS") ? atoi(getenv("PF_GRADU_LDS")) : 0;
-  const size_t lds = u_out ? (size_t)lds_knob : 0;
   if (p->mesh.dim == 2) {
-    if (fuse_adam) hipLaunchKernelGGL((k_node_gradu<2, true>), g, b, lds, s, *p, skip_shared, u_out, out_alt);
+    if (fuse_adam) hipLaunchKernelGGL((k_node_gradu<2, true>), g, b, 0, s, *p, skip_shared, u_out, out_alt);
     else hipLaunchKernelGGL((k_node_gradu<2, false>), g, b, 0, s, *p, skip_shared, (float*)nullptr, 0);
   } else {
-    if (fuse_adam) hipLaunchKernelGGL((k_node_gradu<1, true>), g, b, lds, s, *p, skip_shared, u_out, out_alt);
+    if (fuse_adam) hipLaunchKernelGGL((k_node_gradu<1, true>), g, b, 0, s, *p, skip_shared, u_out, out_alt);
     else hipLaunchKernelGGL((k_node_gradu<1, false>), g, b, 0, s, *p, skip_shared, (float*)nullptr, 0);
   }
   return PF_CHECK_LAUNCH();

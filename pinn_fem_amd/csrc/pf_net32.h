@@ -141,18 +141,16 @@ __device__ inline void pf_n32_pack(const pf_net& net, const float* th, unsigned 
 }
 
 // ---- host side of the fused forward launch (pf_net32.hip: k_net32_forward2) ------------------------------------------
-// blocks of the fused forward launch: one 1024-thread block per CU (PF_FWD32_BLOCKS: experiment knob)
+// blocks of the forward launches (k_net32_forward, k_net32_forward2): one 1024-thread block per CU
+#define PF_FWD32_MAX_BLOCKS 256
 inline int pf_n32_fwd2_blocks(int n_elems) {
-  static const int cap = getenv("PF_FWD32_BLOCKS") ? atoi(getenv("PF_FWD32_BLOCKS")) : 256;
   int nb = (n_elems + 1023) / 1024;
-  if (nb > cap) nb = cap;
+  if (nb > PF_FWD32_MAX_BLOCKS) nb = PF_FWD32_MAX_BLOCKS;
   if (nb < 1) nb = 1;
   return nb;
 }
 // nodes per lane of a node task inside the fused forward launch (k_net32_forward2, gu_nb)
-#ifndef PF_GU_M
 #define PF_GU_M 2
-#endif
 // Can the fused forward launch also run the displacement update of the previous iteration (gu_nb = entries of the
 // u-norm partial sums the bookkeeping reads)?  It needs the other-end adjacency, a single-GPU mesh (no ghost elements, no
 // shared dofs), every block's partial inside what the bookkeeping sums, and its node tasks inside the block's LDS table.

@@ -45,20 +45,6 @@
 #ifndef PF_N32_DBG_ENABLE
 #define PF_N32_DBG_ENABLE 0
 #endif
-// Experiment knobs of the backward's block shape (build-time; pinn_fem_amd/build.py: PINNFEM_BW2_NOPAIR=1 sets them for the
-// fused two-net translation units): PF_BW_PAIR 0 = recompute tile by tile (fewer registers, see bw_pair),
-// PF_BW_MAX_THREADS = cap on the block size.
-// PF_N32_PIPE 1: in the two-tile hidden layer, tile 1's matrix products carry tile 0's first tanh stage in their gaps
-// (MI355X_MICROARCH.md / tools/pipe_probe.hip: an MFMA gap hides 24 cycles of vector issue): same values, other order.
-#ifndef PF_N32_PIPE
-#define PF_N32_PIPE 1
-#endif
-#ifndef PF_BW_PAIR
-#define PF_BW_PAIR 1
-#endif
-#ifndef PF_BW_MAX_THREADS
-#define PF_BW_MAX_THREADS 1024
-#endif
 #define PF_CAT2(a, b) a##b
 #define PF_CAT(a, b) PF_CAT2(a, b)
 
@@ -491,7 +477,10 @@ struct Eng {
       const LayerW& w = wl[LL - 2];
       f32x16 acc0 = bias_acc(w), acc1 = acc0;
       constexpr float CZ = C2 / (PF_N32_KA * PF_N32_KW);
-      if constexpr (PF_N32_PIPE && !PF_N32_DBG_ENABLE) {
+      if constexpr (!PF_N32_DBG_ENABLE) {
+        // pipelined (the product build): tile 1's matrix products carry tile 0's first tanh stage in their gaps
+        // (MI355X_MICROARCH.md / tools/pipe_probe.hip: an MFMA gap hides 24 cycles of vector issue): same values, other
+        // order.  The diagnostic build takes the plain form below: [all MFMAs][all tanh stages].
         // tile 0's products, then tile 1's with tile 0's mul + exp2 stage spread over their gaps (each gap: <= PER
         // registers = PER x (4 + 8) cycles of issue against the 24 a gap hides); sched_barriers pin the order
         sfor<0, KS>([&](auto s) {
@@ -647,12 +636,11 @@ struct Eng {
   // -> MFMA dependency chain better than a third wave does.  Used where it compiles without spills (ScratchSize 0 in
   // every bucket): two hidden layers, or three with PF_NR <= 8; one hidden layer keeps the per-tile form at 16 waves.
   template <int L>
-  static constexpr bool bw_pair() { return PF_BW_PAIR && (L == 2 || (L == 3 && NR <= 8)); }
+  static constexpr bool bw_pair() { return L == 2 || (L == 3 && NR <= 8); }
   template <int L, bool GEA>
   static constexpr int bw_threads() {
     if (bw_pair<L>()) return 512;
-    constexpr int t = !COMPACT ? 512 : (L == 1 ? 1024 : (L == 2 && !(GEA && NR > 10) ? 768 : 512));
-    return t < PF_BW_MAX_THREADS ? t : PF_BW_MAX_THREADS;
+    return !COMPACT ? 512 : (L == 1 ? 1024 : (L == 2 && !(GEA && NR > 10) ? 768 : 512));
   }
 
   // lane's pairs (hi or lo) of registers 0..15 -> split `sp` of the region at byte offset `reg` of the wave scratch.
@@ -807,39 +795,6 @@ struct Eng {
 
 };
 
-// Stores of a block's partial gradient row; wt: agent-scope write-through (global_store ... sc1).  With PF_FUSE_S1=1 the
-// fused backward launch hands the rows to the LAST block of each row group inside the launch (rows_reduce_last below), and a hand-off without a
-// release fence needs every handed-off byte stored this way (MI355X_MICROARCH.md, inter-workgroup visibility, valid forms).
-__device__ __forceinline__ void row_store(float* p, float v, bool wt) {
-  if (wt) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;                                       // (the usual case: the rows are read by the NEXT launch)
-}
-__device__ __forceinline__ float row_load(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The arithmetic of k_theta_stage1 for row group g, by one whole block: four interleaved row sums per column, combined
-// (0 + 1) + (2 + 3).  wt_loads: the rows were stored write-through inside this launch; wt_store: the group's row is handed to
-// other blocks of this launch (agent-scope store).
-__device__ __forceinline__ void stage1_group(const pf_problem& P, int nb_rows, int g, bool wt_loads, bool wt_store) {
-  const int rpg = (nb_rows + PF_RG - 1) / PF_RG;
-  const int r0 = g * rpg, r1 = min(r0 + rpg, nb_rows);
-  float* __restrict__ out = P.partials + PF_PART_WG + (size_t)P.n_part_blocks * P.pad_total + (size_t)g * P.pad_total;
-  for (int col = threadIdx.x; col < P.pad_total; col += blockDim.x) {
-    const float* rows = P.partials + PF_PART_WG + col;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int r = r0; r < r1; r += 4) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (r + k < r1) {
-          const float* src = rows + (size_t)(r + k) * P.pad_total;
-          a[k] += wt_loads ? row_load(src) : *src;
-        }
-    }
-    row_store(out + col, (a[0] + a[1]) + (a[2] + a[3]), wt_store);
-  }
-}
-
 // ---- the parameter update of the PREVIOUS iteration, run by a forward launch for itself (pf_problem.theta_alt) --------
 // Every block: second-level partial rows -> gradient -> Adam step from state half `half_in` (pf_theta_update: the
 // arithmetic of the stand-alone update kernel, bit for bit) -> its own LDS copy of the new parameters -> the operand
@@ -988,13 +943,15 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward(pf_problem P, int 
 // One launch instead of two: the wave's 64 elements go through the E net and then the A net (both operand images sit in
 // LDS), the coordinates are loaded and exchanged between the half-waves once, and the stiffness record is formed from
 // both values in registers — no second launch floor, no second prologue, no round trip of the first property through
-// memory.  Same block shape and lockstep scheme as k_net32_forward; the four wave groups pass their ONE barrier per task
-// at: task start | after the E net's first activation | after the A net's hidden layers | task end.
+// memory.  Same block shape as k_net32_forward, but no lockstep barriers: the block owns a contiguous run of tasks and
+// its waves draw them from a counter in LDS, so no wave ever waits for another one — the age-ordered arbitration of a
+// SIMD lets its oldest wave run ahead, and with a queue that wave simply takes more tasks (the waves drift out of phase
+// by themselves).
 // s2: this launch is also the THETA UPDATE of the previous iteration (the iteration graph): every block sums the
 // second-level partial rows, applies Adam to its own copy of theta and builds both operand images straight into its LDS
 // (all blocks compute the same bits); block 0 stores theta, the moments, the images and the theta-norm monitor — see
 // fwd2_theta_prologue.
-// gu_nb > 0 (the iteration graph, queue form only): this launch is also the DISPLACEMENT UPDATE of the previous iteration
+// gu_nb > 0 (the iteration graph): this launch is also the DISPLACEMENT UPDATE of the previous iteration
 // (dL/du + Adam(u) + clamp: what k_node_gradu does, pf_node.h).  The block owns a contiguous run of node tasks (PF_GU_M x
 // 64 nodes each) beside its element tasks and its waves draw one of them after every `gu_every` element tasks: the node
 // tasks are three dependent round trips through memory with next to no arithmetic, the element tasks vector-issue bound —
@@ -1003,12 +960,9 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward(pf_problem P, int 
 // and the block adds them in index order: the monitor does not depend on which wave drew what.  The block's sum goes to
 // partials[PF_PART_U2 + block]; entries up to gu_nb (what the bookkeeping sums: pf_node_blocks) are zeroed.  gu_k: the
 // stiffness records of the previous iteration (the half this launch does NOT write).
-#ifndef PF_GU_M
-#define PF_GU_M 2
-#endif
 #define PF_GU_MAX_TASKS 1024
 template <int NRE, int NRA, int L, int IN>
-__global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int dbg_arg, int s2_half, int queue, int gu_nb,
+__global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int dbg_arg, int s2_half, int gu_nb,
                                                                const float* __restrict__ gu_k) {
   using EE = Eng<NRE>;
   using EA = Eng<NRA>;
@@ -1027,14 +981,6 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, waves = blockDim.x >> 6;
   const int n = P.mesh.n_elems;
   const int ntasks = (n + 63) >> 6;
-  // Two ways to hand the 64-element tasks to the waves.  queue (default): the block owns a contiguous run of tasks and
-  // its waves draw them from a counter in LDS, so no wave ever waits for another one — the age-ordered arbitration of a
-  // SIMD lets its oldest wave run ahead, and with a queue that wave simply takes more tasks (the waves drift out of
-  // phase by themselves).  Lockstep (queue == 0, round 2): block-uniform rounds of one task per wave with ONE s_barrier
-  // per task, passed at a different place of the task body by each of the four wave groups.
-  const int grp = (queue || (dbg & 32)) ? -1 : __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
-  const int per_round = gridDim.x * waves;
-  const int rounds = (ntasks + per_round - 1) / per_round;
   const int per_block = (ntasks + (int)gridDim.x - 1) / (int)gridDim.x;
   const int t0 = (int)blockIdx.x * per_block, t1 = min(t0 + per_block, ntasks);
   __shared__ int s_next, s_next_n;
@@ -1043,7 +989,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     s_next = waves;           // tasks t0 .. t0+waves-1 go to the waves in order, the rest through the queue
     s_next_n = 0;
   }
-  int task = queue ? t0 + wv : (int)blockIdx.x * waves + wv;
+  int task = t0 + wv;
   float xn[3];
   ElemGeo gn = ElemGeo{0.f, 0.f, 0.f, 1.f};
   if (n > 0) {
@@ -1056,7 +1002,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
   const int n_ntasks = gu_nb > 0 ? (P.mesh.n_nodes + GUN - 1) / GUN : 0;
   const int npb = (n_ntasks + (int)gridDim.x - 1) / (int)gridDim.x;
   const int nt0 = (int)blockIdx.x * npb, nn_b = max(min(nt0 + npb, n_ntasks) - nt0, 0);
-  const int gu_every = nn_b > 0 ? max((t1 - t0) / nn_b + (int)(signed char)(queue >> 8), 0) : 0;     // (queue >> 8: experiment, PF_GU_EVERY_ADD)
+  const int gu_every = nn_b > 0 ? max((t1 - t0) / nn_b, 0) : 0;
   bool gu = nn_b > 0;
   int since = nn_b > 0 ? wv % (gu_every + 1) : 0;     // (the waves start out of phase)
   __shared__ int s_done;
@@ -1095,7 +1041,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
   if (s_done || n <= 0) return;
   const float bo_e = reinterpret_cast<const float*>(img_e + pf_n32_off_bo())[0];
   const float bo_a = reinterpret_cast<const float*>(img_a + pf_n32_off_bo())[0];
-  for (int r = 0; queue ? (task < t1 || gu) : r < rounds; ++r) {
+  while (task < t1 || gu) {
     if (gu && (since >= gu_every || task >= t1)) {
       // a node task: the next element task's inputs (already on their way) are not touched
       since = 0;
@@ -1104,19 +1050,11 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     }
     if (task >= t1) break;
     ++since;
-    if (grp == 0) __builtin_amdgcn_s_barrier();
-    // the task after this one: drawn now (queue) so that its inputs travel while this one computes
-    int nxt;
-    bool more;
-    if (queue) {
-      int k = 0;
-      if (lane == 0) k = atomicAdd(&s_next, 1);
-      nxt = t0 + __builtin_amdgcn_readfirstlane(k);
-      more = nxt < t1;
-    } else {
-      nxt = task + per_round;
-      more = r + 1 < rounds;
-    }
+    // the task after this one: drawn now so that its inputs travel while this one computes
+    int k = 0;
+    if (lane == 0) k = atomicAdd(&s_next, 1);
+    const int nxt = t0 + __builtin_amdgcn_readfirstlane(k);
+    const bool more = nxt < t1;
     const int e = task * 64 + lane;
     float x0[3], x1[3];
     sfor<0, 3>([&](auto c) { constexpr int C = c; both_tiles(xn[C], x0[C], x1[C]); });
@@ -1130,13 +1068,13 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     {
       typename EE::template TileAct<L, false> A0, A1;
       float p0, p1;
-      EE::template forward_tiles<L, IN, false>(img_e, lane, x0, x1, A0, A1, p0, p1, dbg, grp == 1 ? 1 : -1);
+      EE::template forward_tiles<L, IN, false>(img_e, lane, x0, x1, A0, A1, p0, p1, dbg);
       ze = own_total(p0, p1) * (1.0f / PF_N32_KA) + bo_e;
     }
     {
       typename EA::template TileAct<L, false> A0, A1;
       float p0, p1;
-      EA::template forward_tiles<L, IN, false>(img_a, lane, x0, x1, A0, A1, p0, p1, dbg, grp == 2 ? 2 : -1);
+      EA::template forward_tiles<L, IN, false>(img_a, lane, x0, x1, A0, A1, p0, p1, dbg);
       za = own_total(p0, p1) * (1.0f / PF_N32_KA) + bo_a;
     }
     if (e < n) {
@@ -1146,7 +1084,6 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
       P.prop_a[e] = va;
       if (P.elem_k) store_k<IN - 1>(P.elem_k, e, g, (ve * va) / g.l0);    // (young * area) / l0, nn_assembly.py:74, :37
     }
-    if (grp == 3) __builtin_amdgcn_s_barrier();
     task = nxt;
   }
   if (dstamps && lane == 0) dstamps[5] = __builtin_amdgcn_s_memrealtime();
@@ -1163,29 +1100,6 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     for (int j = (int)blockIdx.x + (int)gridDim.x + (int)threadIdx.x * (int)gridDim.x; j < gu_nb; j += (int)blockDim.x * (int)gridDim.x)
       P.partials[PF_PART_U2 + j] = 0.f;
   }
-}
-
-// First level of the parameter-gradient reduction INSIDE the backward launch (what the k_theta_stage1 launch does
-// otherwise, to the bit: same row groups, same summation order): the block's row is complete and stored; every wave drains
-// its stores, the block takes a ticket of its row group, and the block that draws the group's last ticket sums the
-// group's rows into the group's second-level row.  No block ever waits for another one.  tickets: PF_RG counters, zero
-// between launches (the last block of a group resets its counter).
-__device__ __forceinline__ void rows_reduce_last(const pf_problem& P, int nb_rows) {
-  __shared__ int s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's row stores have left
-  __syncthreads();
-  const int rpg = (nb_rows + PF_RG - 1) / PF_RG;
-  const int g = (int)blockIdx.x / rpg;
-  const int r0 = g * rpg, r1 = min(r0 + rpg, nb_rows);
-  int* tickets = reinterpret_cast<int*>(P.partials + PF_PART_WG + ((size_t)P.n_part_blocks + PF_RG) * P.pad_total);
-  if (threadIdx.x == 0) {
-    const int old = __hip_atomic_fetch_add(tickets + g, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = old == (r1 - r0) - 1;
-    if (s_last) __hip_atomic_store(tickets + g, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last) return;
-  stage1_group(P, nb_rows, g, true, false);
 }
 
 // ---- a wave's finished gradient tiles parked in LDS, and the block's row from the parked tiles ---------------------------
@@ -1220,13 +1134,13 @@ __device__ __forceinline__ void bw_park(float* __restrict__ mine, const f32x16 (
 // one between the row's zero fill and its entries.
 template <int NR, int L, int IN>
 __device__ __forceinline__ void bw_row_from_parked(const pf_problem& P, int which, int hp, const float* __restrict__ park,
-                                                   float kl, float kx, bool wt) {
+                                                   float kl, float kx) {
   const pf_net net = P.net[which];
   const int waves = blockDim.x >> 6, W = net.width;
   constexpr int PS = bw_park_floats<L>();
   float* __restrict__ prow = P.partials + PF_PART_WG + (size_t)blockIdx.x * P.pad_total + net.pad_off;
   const int padc = pf_pad_count(hp, L);
-  for (int i = threadIdx.x; i < padc; i += blockDim.x) row_store(prow + i, 0.f, wt);
+  for (int i = threadIdx.x; i < padc; i += blockDim.x) prow[i] = 0.f;
   __syncthreads();
   sfor<0, L>([&](auto l) {
     constexpr int LL = l + 1;                      // layer whose weight gradient tile T[LL-1] holds
@@ -1249,21 +1163,22 @@ __device__ __forceinline__ void bw_row_from_parked(const pf_problem& P, int whic
         if (c < IN) { dst = j * 4 + c; k *= c == 0 ? kl : kx; }
         else if (c == IN) dst = j * 4 + IN;                                           // bias (input 1.0)
       }
-      if (dst >= 0) row_store(prow + dst, t / k, wt);
+      if (dst >= 0) prow[dst] = t / k;
     }
   });
+  float* const pwo = prow + pf_pad_wo(hp, L);      // the output unit's weights, then its bias
   if (threadIdx.x < 32) {
     const int hh = threadIdx.x >> 4, r = threadIdx.x & 15, u = 2 * r + hh;
     if (r < NR && u < W) {
       float t = 0.f;
       for (int q = 0; q < waves; ++q) t += park[q * PS + L * 1024 + hh * 16 + r];
-      row_store(prow + pf_pad_wo(hp, L) + u, t * (1.0f / PF_N32_KA), wt);
+      pwo[u] = t * (1.0f / PF_N32_KA);
     }
   }
   if (threadIdx.x == 32) {
     float t = 0.f;
     for (int q = 0; q < waves; ++q) t += park[q * PS + L * 1024 + 32];
-    row_store(prow + pf_pad_wo(hp, L) + hp, t, wt);
+    pwo[hp] = t;
   }
 }
 
@@ -1278,7 +1193,7 @@ __device__ __forceinline__ void bw_row_from_parked(const pf_problem& P, int whic
 // block barrier, park, block barrier, own row.
 template <int NR, int L, int IN, bool GEA, int MODE = 0, class FirstRow = int>
 __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, int hp, int dbg, const unsigned char* smem,
-                                               unsigned char* cst, unsigned char* wscr, bool wt = false,
+                                               unsigned char* cst, unsigned char* wscr,
                                                unsigned long long* stamps = nullptr, float* park = nullptr,
                                                FirstRow first_row = FirstRow(), int shift8 = 0) {
   using E = Eng<NR>;
@@ -1320,8 +1235,8 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
   const int partner = elder ? slot + hw : slot - hw;
   const int c_own = slot < ntasks_all ? (ntasks_all - 1 - slot) / per_round + 1 : 0;
   const int c_par = (hw > 0 && partner < ntasks_all) ? (ntasks_all - 1 - partner) / per_round + 1 : 0;
-  // (shift8 & 15: the handicap; a handicap can never exceed the younger wave's column)
-  const int sh = min(((shift8 & 15) > 0 && hw > 0 && (waves & 1) == 0) ? (((elder ? c_par : c_own) * (shift8 & 15) + 4) >> 3) : 0,
+  // (a handicap can never exceed the younger wave's column)
+  const int sh = min((shift8 > 0 && hw > 0 && (waves & 1) == 0) ? (((elder ? c_par : c_own) * shift8 + 4) >> 3) : 0,
                      elder ? c_par : c_own);
   const int n_mine = elder ? c_own + sh : c_own - sh;
   auto task_base = [&](int k) {                  // element base of the wave's k-th task; past its last one: the last element
@@ -1463,7 +1378,7 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     __syncthreads();                               // the parked tiles are read
     bw_park<NR, L>(park + (size_t)wv * bw_park_floats<L>(), T, go, gbo, lane);
     __syncthreads();
-    bw_row_from_parked<NR, L, IN>(P, which, hp, park, kl, kx, wt);
+    bw_row_from_parked<NR, L, IN>(P, which, hp, park, kl, kx);
     if (PF_N32_DBG_ENABLE && stamps) stamps[2] = __builtin_amdgcn_s_memrealtime();
     return;
   }
@@ -1474,7 +1389,7 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
   const int W = net.width;
   float* __restrict__ prow = P.partials + PF_PART_WG + (size_t)blockIdx.x * P.pad_total + net.pad_off;
   const int padc = pf_pad_count(hp, L);
-  for (int i = threadIdx.x; i < padc; i += blockDim.x) row_store(prow + i, 0.f, wt);
+  for (int i = threadIdx.x; i < padc; i += blockDim.x) prow[i] = 0.f;
   // scale of d_l relative to the true gradient after the 1/S: 4^(L-l)
   sfor<0, L>([&](auto l) {
     constexpr int LL = l + 1;                      // layer whose weight gradient tile T[LL-1] holds
@@ -1505,7 +1420,7 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
         if (c < IN) { dst = j * 4 + c; k *= c == 0 ? kl : kx; }
         else if (c == IN) dst = j * 4 + IN;                                           // bias (input 1.0)
       }
-      if (dst >= 0) row_store(prow + dst, t / k, wt);
+      if (dst >= 0) prow[dst] = t / k;
     }
   });
   // output unit row: sum over the 32 columns of each half-wave, then over the waves
@@ -1522,18 +1437,19 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     if (lane == 0) stage[waves * 64 + wv] = v;
   }
   __syncthreads();
+  float* const pwo = prow + pf_pad_wo(hp, L);      // the output unit's weights, then its bias
   if (threadIdx.x < 32) {
     const int hh = threadIdx.x >> 4, r = threadIdx.x & 15, u = 2 * r + hh;
     if (r < NR && u < W) {
       float t = 0.f;
       for (int q = 0; q < waves; ++q) t += stage[q * 64 + hh * 16 + r];
-      row_store(prow + pf_pad_wo(hp, L) + u, t * (1.0f / PF_N32_KA), wt);
+      pwo[u] = t * (1.0f / PF_N32_KA);
     }
   }
   if (threadIdx.x == 32) {
     float t = 0.f;
     for (int q = 0; q < waves; ++q) t += stage[waves * 64 + q];
-    row_store(prow + pf_pad_wo(hp, L) + hp, t, wt);
+    pwo[hp] = t;
   }
   if (PF_N32_DBG_ENABLE && stamps) stamps[2] = __builtin_amdgcn_s_memrealtime();
 }
@@ -1573,21 +1489,20 @@ template <int NRE, int NRA>
 constexpr int bw2_wave_scratch() { return Eng<NRE>::WAVE_SCRATCH > Eng<NRA>::WAVE_SCRATCH ? Eng<NRE>::WAVE_SCRATCH : Eng<NRA>::WAVE_SCRATCH; }
 
 // the phases run without a barrier between them (parked tiles) where both buckets use the compact LDS layout (same constant
-// blocks, same scratch) and the block's LDS has room for the parking places; PF_BW_PARK=0: experiment build (barrier form)
-#ifndef PF_BW_PARK
-#define PF_BW_PARK 1
-#endif
+// blocks, same scratch) and the block's LDS has room for the parking places
 template <int NRE, int NRA>
-constexpr bool bw2_parked() { return PF_BW_PARK && Eng<NRE>::COMPACT && Eng<NRA>::COMPACT; }
+constexpr bool bw2_parked() { return Eng<NRE>::COMPACT && Eng<NRA>::COMPACT; }
 template <int NRE, int NRA, int L, int IN>
 constexpr size_t bw2_lds_bytes() {
   return 2 * (size_t)((pf_n32_bytes(L) + 255) & ~255) + bw2_const_bytes<NRE, NRA>() +
          (size_t)(bw2_threads<NRE, NRA, L, IN>() / 64) * bw2_wave_scratch<NRE, NRA>() +
          (bw2_parked<NRE, NRA>() ? (size_t)(bw2_threads<NRE, NRA, L, IN>() / 64) * bw_park_floats<L>() * sizeof(float) : 0);
 }
+// eighths of the younger wave's tasks the older wave of its SIMD takes over (backward_phase, shift8), measured on MI355X
+// (profiles/r03_ab.txt): 0 / 1 / 2 / 3 -> backward launch 72.2 / 69.7 / 68.0 / 71.1 us
+constexpr int PF_BW_SHIFT = 2;
 template <int NRE, int NRA, int L, int IN>
-__global__ __launch_bounds__((bw2_threads<NRE, NRA, L, IN>())) void k_net32_backward2(pf_problem P, int hp_e, int hp_a, int dbg_arg,
-                                                                                     int reduce_rows) {
+__global__ __launch_bounds__((bw2_threads<NRE, NRA, L, IN>())) void k_net32_backward2(pf_problem P, int hp_e, int hp_a, int dbg_arg) {
   const int dbg = PF_N32_DBG_ENABLE ? dbg_arg : 0;
   const unsigned long long t_entry = PF_N32_DBG_ENABLE ? __builtin_amdgcn_s_memrealtime() : 0ull;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -1611,30 +1526,21 @@ __global__ __launch_bounds__((bw2_threads<NRE, NRA, L, IN>())) void k_net32_back
     // no barrier between the phases: a wave parks its young-net tiles and walks on (see backward_phase, MODE)
     float* park = reinterpret_cast<float*>(wscr + (size_t)(blockDim.x >> 6) * bw2_wave_scratch<NRE, NRA>());
     const float kl_e = pf_n32_lam_scale(P.lam), kx_e = __builtin_ldexpf(1.0f, P.coord_exp);
-    const bool wt = (reduce_rows & 1) != 0;
-    auto first_row = [&]() { bw_row_from_parked<NRE, L, IN>(P, 0, hp_e, park, kl_e, kx_e, wt); };
-    backward_phase<NRE, L, IN, true, 1>(P, 0, hp_e, dbg, smem, cst, wscr, wt, st ? st + 1 : nullptr, park, 0, reduce_rows >> 1);
-    backward_phase<NRA, L, IN, false, 2>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr, wt, st ? st + 4 : nullptr, park, first_row,
-                                         reduce_rows >> 1);
+    auto first_row = [&]() { bw_row_from_parked<NRE, L, IN>(P, 0, hp_e, park, kl_e, kx_e); };
+    backward_phase<NRE, L, IN, true, 1>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, park, 0, PF_BW_SHIFT);
+    backward_phase<NRA, L, IN, false, 2>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr, st ? st + 4 : nullptr, park, first_row,
+                                         PF_BW_SHIFT);
   } else {
-    backward_phase<NRE, L, IN, true>(P, 0, hp_e, dbg, smem, cst, wscr, (reduce_rows & 1) != 0, st ? st + 1 : nullptr, nullptr, 0,
-                                     reduce_rows >> 1);
+    backward_phase<NRE, L, IN, true>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, nullptr, 0, PF_BW_SHIFT);
     __syncthreads();                             // the write-out staging of phase 1 is read; scratch and constants are re-initialised
-    backward_phase<NRA, L, IN, false>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr, (reduce_rows & 1) != 0, st ? st + 4 : nullptr,
-                                      nullptr, 0, reduce_rows >> 1);
+    backward_phase<NRA, L, IN, false>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr, st ? st + 4 : nullptr, nullptr, 0, PF_BW_SHIFT);
   }
-  // reduce_rows: the launch is also theta stage 1 (the last block of every row group sums the group's rows)
-  if (reduce_rows & 1) rows_reduce_last(P, (int)gridDim.x);
 }
 
 template <int L, int IN>
 int launch_fwd(const pf_problem* p, int which, hipStream_t s, int s2_half) {
   constexpr int NR = PF_NR;
-  const int n = p->mesh.n_elems;
-  int nb = (n + FW_THREADS - 1) / FW_THREADS;
-  static const int cap = getenv("PF_FWD32_BLOCKS") ? atoi(getenv("PF_FWD32_BLOCKS")) : 256;   // one block per CU
-  if (nb > cap) nb = cap;
-  if (nb < 1) nb = 1;
+  const int nb = pf_n32_fwd2_blocks(p->mesh.n_elems);   // one block per CU
   static const int dbg = getenv("PF_N32_DBG") ? atoi(getenv("PF_N32_DBG")) : 0;   // timing experiments only
   const int ws = p->elem_k != nullptr ? 1 : 0;
   const size_t lds = s2_half < 0 ? (size_t)pf_n32_bytes(L)
@@ -1672,12 +1578,8 @@ int launch_fwd2_t(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o) {
   static const int dbg = getenv("PF_N32_DBG") ? atoi(getenv("PF_N32_DBG")) : 0;
   const size_t lds = 2 * (size_t)((pf_n32_bytes(L) + 255) & ~255) + (s2_half < 0 ? 0 : (size_t)p->n_theta_active * sizeof(float));
   if (lds > 64000) { pf_set_error("too many trainable parameters for the fused theta update"); return PF_ERR_UNSUPPORTED; }
-  // PF_FWD_QUEUE=0: experiment knob (round 2's lockstep rounds instead of the per-block task queue)
-  static const int queue_knob = getenv("PF_FWD_QUEUE") ? atoi(getenv("PF_FWD_QUEUE")) : 1;
-  static const int every_add = getenv("PF_GU_EVERY_ADD") ? atoi(getenv("PF_GU_EVERY_ADD")) : 0;
-  const int queue = (gu_nb > 0 || queue_knob) ? (1 | ((every_add & 0xff) << 8)) : 0;       // (the displacement update rides on the queue form only)
   if (gu_nb > 0 && !pf_n32_fwd2_can_update_u(p, gu_nb)) { pf_set_error("fused forward: displacement update not possible on this problem"); return PF_ERR_UNSUPPORTED; }
-  hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_half >= 0 && o.calc_index ? s2_half + 2 : s2_half, queue, gu_nb, o.gu_k);
+  hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_half >= 0 && o.calc_index ? s2_half + 2 : s2_half, gu_nb, o.gu_k);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_HIP;
 }
 template <int L, int IN>
@@ -1697,7 +1599,7 @@ int launch_fwd2(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o) {
 
 // fused backward of both nets (two phases): E net of this translation unit's bucket, A net's bucket dispatched here
 template <int NRA, int L, int IN>
-int launch_bwd2_t(const pf_problem* p, hipStream_t s, int reduce_rows) {
+int launch_bwd2_t(const pf_problem* p, hipStream_t s) {
   constexpr int NRE = PF_NR;
   const int nb = pf_net_blocks(p);
   const int hp_e = ((p->net[0].width + 3) / 4) * 4, hp_a = ((p->net[1].width + 3) / 4) * 4;
@@ -1705,22 +1607,19 @@ int launch_bwd2_t(const pf_problem* p, hipStream_t s, int reduce_rows) {
   const size_t lds = bw2_lds_bytes<NRE, NRA, L, IN>();
   static_assert(bw2_lds_bytes<NRE, NRA, L, IN>() <= 160 * 1024, "fused backward: LDS budget");
   static const int dbg = getenv("PF_N32_DBG") ? atoi(getenv("PF_N32_DBG")) : 0;
-  // PF_BW_SHIFT: eighths of the younger wave's tasks the older wave of its SIMD takes over (backward_phase, shift8; bits 1..
-  // of the kernel's reduce_rows argument)
-  static const int shift8 = getenv("PF_BW_SHIFT") ? atoi(getenv("PF_BW_SHIFT")) : 2;     // measured best of 0..3 (r03_ab.txt)
-  hipLaunchKernelGGL((k_net32_backward2<NRE, NRA, L, IN>), dim3(nb), dim3(THREADS), lds, s, *p, hp_e, hp_a, dbg, (reduce_rows ? 1 : 0) | (shift8 << 1));
+  hipLaunchKernelGGL((k_net32_backward2<NRE, NRA, L, IN>), dim3(nb), dim3(THREADS), lds, s, *p, hp_e, hp_a, dbg);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_HIP;
 }
 template <int L, int IN>
-int launch_bwd2(const pf_problem* p, hipStream_t s, int reduce_rows) {
+int launch_bwd2(const pf_problem* p, hipStream_t s) {
   switch (pf_net32_bucket(p->net[1].width)) {
-    case 2: return launch_bwd2_t<2, L, IN>(p, s, reduce_rows);
-    case 4: return launch_bwd2_t<4, L, IN>(p, s, reduce_rows);
-    case 6: return launch_bwd2_t<6, L, IN>(p, s, reduce_rows);
-    case 8: return launch_bwd2_t<8, L, IN>(p, s, reduce_rows);
-    case 10: return launch_bwd2_t<10, L, IN>(p, s, reduce_rows);
-    case 12: return launch_bwd2_t<12, L, IN>(p, s, reduce_rows);
-    case 15: return launch_bwd2_t<15, L, IN>(p, s, reduce_rows);
+    case 2: return launch_bwd2_t<2, L, IN>(p, s);
+    case 4: return launch_bwd2_t<4, L, IN>(p, s);
+    case 6: return launch_bwd2_t<6, L, IN>(p, s);
+    case 8: return launch_bwd2_t<8, L, IN>(p, s);
+    case 10: return launch_bwd2_t<10, L, IN>(p, s);
+    case 12: return launch_bwd2_t<12, L, IN>(p, s);
+    case 15: return launch_bwd2_t<15, L, IN>(p, s);
   }
   pf_set_error("MFMA32 engine: area net width outside 1..30");
   return PF_ERR_UNSUPPORTED;
@@ -1796,10 +1695,10 @@ int PF_N32_SYM(forward2_)(const pf_problem* p, hipStream_t s, const pf_fwd2_opts
 // Two hidden layers only (the reference's SimpleNN default and every example): with one or three the two phases in one
 // kernel no longer fit the register budget of their block shapes without spilling (checked in the compiler's asm), and
 // a spill reload in the task loop costs more than a launch boundary — those shapes keep the two launches.
-int PF_N32_SYM(backward2_)(const pf_problem* p, hipStream_t s, int reduce_rows) {
+int PF_N32_SYM(backward2_)(const pf_problem* p, hipStream_t s) {
   const int L = p->net[0].n_hidden, IN = p->net[0].in_dim;
-  if (L == 2 && IN == 3) return launch_bwd2<2, 3>(p, s, reduce_rows);
-  if (L == 2 && IN == 2) return launch_bwd2<2, 2>(p, s, reduce_rows);
+  if (L == 2 && IN == 3) return launch_bwd2<2, 3>(p, s);
+  if (L == 2 && IN == 2) return launch_bwd2<2, 2>(p, s);
   pf_set_error("fused backward: two hidden layers only");
   return PF_ERR_UNSUPPORTED;
 }

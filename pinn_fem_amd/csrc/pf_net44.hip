@@ -528,13 +528,10 @@ template <int L, int IN>
 int launch_fwd(const pf_problem* p, int which, hipStream_t s) {
   const int n = p->mesh.n_elems;
   int nb = (n + 255) / 256;
-  // EXPERIMENT knobs: PF_FWD_BLOCKS caps the grid, PF_FWD_LDS (bytes of dummy dynamic LDS) limits
-  // the blocks resident per CU
-  static const int cap = getenv("PF_FWD_BLOCKS") ? atoi(getenv("PF_FWD_BLOCKS")) : 2048;
-  static const int ldsb = getenv("PF_FWD_LDS") ? atoi(getenv("PF_FWD_LDS")) : 0;
+  constexpr int cap = 2048;
   if (nb > cap) nb = cap;
   if (nb < 1) nb = 1;
-  hipLaunchKernelGGL((k_net44_forward<L, IN>), dim3(nb), dim3(256), ldsb, s, *p, which);
+  hipLaunchKernelGGL((k_net44_forward<L, IN>), dim3(nb), dim3(256), 0, s, *p, which);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_HIP;
 }
 

@@ -969,9 +969,9 @@ def _assert_history_equal(a, b):
 
 
 def test_full_size_graph_equals_eager_bitwise():
-    """10^6 elements, ex4 shape, default element-force formulation: 40 iterations replayed as the dependency-DAG
-    hipGraph (the product path of bench.py) and the same 40 launched eagerly in stream order end in bit-identical
-    u, theta and loss history."""
+    """10^6 elements, ex4 shape, default element-force formulation: 40 iterations replayed as the one-chain hipGraph
+    (the product path of bench.py: the parameter and displacement updates ride in the next forward launch) and the same
+    40 launched eagerly in stream order end in bit-identical u, theta and loss history."""
     from bench import build_model
     from pinn_fem_amd.engine import HipEngine
     from pinn_fem_amd.fem.solver import SolverConfig
@@ -1135,10 +1135,11 @@ def test_chained_replays_equal_plain_replays(n, max_it, tol, n_call, expect):
 
 @pytest.mark.parametrize("max_it,tol,expect", [(40, 1e30, 12), (13, 0.0, 13), (15, 0.0, 15)])
 def test_graph_stop_in_mid_replay_equals_eager(max_it, tol, expect):
-    """The iteration graph ping-pongs the displacement vector and the parameter state between two halves; a stop raised
+    """The iteration graph ping-pongs the parameter state and the element records between two halves; a stop raised
     INSIDE a replay (stop test at iteration 12; max_iterations 13 and 15: odd counts, so the live halves are the
     alternates) must still leave u, theta, the Adam moments and the history where and what the eager launches leave.
-    250000 elements: the dependency-DAG form of the graph (>= 2*10^5 elements)."""
+    250000 elements: above the DAG threshold (2*10^5 elements), but this shape fuses the displacement update, so the
+    graph is the one chain of the product path."""
     from bench import build_model
     from pinn_fem_amd.engine import HipEngine
     from pinn_fem_amd.fem.solver import SolverConfig

@@ -179,6 +179,19 @@ def test_product_never_imports_the_oracle():
                 assert "oracle" not in src, os.path.join(dirpath, fn)
 
 
+def test_library_reads_no_environment_but_the_diagnostic_knob():
+    """The library's behaviour is a function of its inputs: the only variable it reads with getenv is PF_N32_DBG (live
+    only in the PINNFEM_N32_DBG=1 timing build)."""
+    csrc = os.path.join(ROOT, "pinn_fem_amd", "csrc")
+    read = set()
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".h", ".cpp", ".c")):
+            src = open(os.path.join(csrc, fn)).read()
+            for m in re.finditer(r"getenv\s*\(\s*([^)]*)\)", src):
+                read.add(m.group(1).strip())
+    assert read == {'"PF_N32_DBG"'}, read
+
+
 def test_api_pinn_gd_surface(tmp_path):
     """api_pinn_gradient_descent.py surface: parse_input semantics (incl. the reference's elif chain)
     and the error JSON + exit code 1 contract (:206-219)."""
