@@ -275,11 +275,20 @@ int pf_gd_iterations(const pf_problem* p, int n_iter, void* stream);
 /* hipGraph form of pf_gd_iterations: capture `iters_per_graph` iterations once, replay many times
  * (removes the per-launch host cost and most of the inter-kernel gaps).  The graph bakes in the
  * pf_problem record by value: create it after the record is final (one per solve_gd call) and destroy
- * it before changing any field.  *graph_out is an opaque handle owned by the caller.  For >= 2e5 elements the
- * captured iterations are a dependency DAG, not a chain: grad_u + Adam(u) runs beside the second net's backward, and
- * the bookkeeping of iteration t (pf_finalize's work) runs as one extra block of the residual launch of t+1, reading
- * the other half of the residual's partial sums (part_half); the last iteration of a replay gets a stand-alone
- * pf_finalize.  Results are bit-identical to pf_gd_iterations. */
+ * it before changing any field.  *graph_out is an opaque handle owned by the caller.  iters_per_graph >= 1.
+ * In every form the bookkeeping of iteration t (pf_finalize's work) runs as one extra block of the residual launch of
+ * t+1, reading the other half of the residual's partial sums (part_half); the last iteration of a replay gets a
+ * stand-alone pf_finalize.  The form (pf_fusion_info reports it):
+ *  - ONE CHAIN where the forward launch carries the displacement update of the previous iteration (PF_FUSED_U_UPDATE:
+ *    MFMA32 engine, both nets enabled with equal depths, elem_k, adj_other and prop_double present, one GPU), at any
+ *    size; and below 2e5 elements otherwise, with grad_u + Adam(u) as a stand-alone launch on the chain.
+ *  - A DEPENDENCY DAG from 2e5 elements (mesh.n_elems) up when the displacement update is not fused: grad_u + Adam(u)
+ *    runs on a side branch beside the backward launches.  With u_alt and an even iters_per_graph it ping-pongs the
+ *    displacements between u and u_alt (PF_FUSED_U_PINGPONG; a replay always ends with them in u) and starts right
+ *    behind the residual; otherwise it starts behind the last reader of u.
+ * u, theta, both Adam moments, the state and every history column are bit-identical to pf_gd_iterations, with one
+ * exception: in the PF_FUSED_U_UPDATE form the u-norm monitor (history column 3, pf_state.u_norm) sums the same block
+ * partials in another grouping and may differ in the last bits. */
 int pf_graph_create(const pf_problem* p, int iters_per_graph, void* stream, void** graph_out);
 /* Replays that hand their last iteration's tail to the next replay (one-chain form of the graph only, even
  * iters_per_graph; PF_ERR_UNSUPPORTED otherwise).  A plain replay ends with three stand-alone launches — the parameter

@@ -968,6 +968,22 @@ def _assert_history_equal(a, b):
     assert np.allclose(a[:, 3], b[:, 3], rtol=2e-6, atol=0.0)
 
 
+def _assert_history_bitwise(a, b):
+    """Histories of an iteration graph whose displacement update is the stand-alone k_node_gradu (every form without
+    PF_FUSED_U_UPDATE: the same kernel, the same block partials, the same bookkeeping sum as the eager launches) and of
+    eager launches: every column bit for bit, the u-norm monitor included."""
+    assert a.shape == b.shape
+    assert np.array_equal(a, b)
+
+
+def _assert_history_for(mask, a, b):
+    """The history comparison that the graph form `mask` (pf_fusion_info) promises."""
+    if mask & 16:
+        _assert_history_equal(a, b)
+    else:
+        _assert_history_bitwise(a, b)
+
+
 def test_full_size_graph_equals_eager_bitwise():
     """10^6 elements, ex4 shape, default element-force formulation: 40 iterations replayed as the one-chain hipGraph
     (the product path of bench.py: the parameter and displacement updates ride in the next forward launch) and the same
@@ -1037,7 +1053,7 @@ def test_graph_equals_eager_meshes(mesh, n, fe):
             model, mv, md, _ = build_model(n, "ex4", mesh=mesh)
         cfg = SolverConfig(max_iterations=60, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4)
         eng = HipEngine(model, mv, md, fe_mode=fe)
-        assert eng.fusion_info() & 16                           # the displacement update rides in the forward launch
+        assert eng.fusion_info() == 1 + 2 + 4 + 16              # the displacement update rides in the forward launch
         eng.begin(None, 0.1, cfg, want_history=True)
         n_it = 2 * eng.GRAPH_ITERS + 3                          # two whole replays and a part of one
         eng.iterate(n_it, use_graph=use_graph)
@@ -1052,17 +1068,26 @@ def test_graph_equals_eager_meshes(mesh, n, fe):
     assert np.all(np.isfinite(outs[0][-1]))
 
 
-@pytest.mark.parametrize("layers,we,wa,dim", [(1, 7, 4, 2), (3, 8, 12, 2), (2, 27, 30, 2), (3, 30, 5, 1), (1, 16, 16, 1)])
-def test_graph_equals_eager_net_shapes(layers, we, wa, dim):
+@pytest.mark.parametrize("le,la,we,wa,dim,n,mask", [
+    pytest.param(1, 1, 7, 4, 2, 5000, 21, id="1-7-4-2"), pytest.param(3, 3, 8, 12, 2, 5000, 21, id="3-8-12-2"),
+    pytest.param(2, 2, 27, 30, 2, 5000, 23, id="2-27-30-2"), pytest.param(3, 3, 30, 5, 1, 5000, 21, id="3-30-5-1"),
+    pytest.param(1, 1, 16, 16, 1, 5000, 21, id="1-16-16-1"),
+    pytest.param(1, 3, 20, 15, 2, 250_000, 12, id="1+3-20-15-2-250000"),
+    pytest.param(1, 3, 20, 15, 2, 60_000, 4, id="1+3-20-15-2-60000")])
+def test_graph_equals_eager_net_shapes(le, la, we, wa, dim, n, mask):
     """The update prologue of the graph's forward launches computes the padded-image index of every parameter by arithmetic
     (pf_pad_index_of) where the eager update reads pf_problem.pad_index: same bits in theta, the Adam moments and u for one,
-    two and three hidden layers, ragged widths (register buckets 4 ... 15) and both input dimensions."""
+    two and three hidden layers, ragged widths (register buckets 4 ... 15) and both input dimensions.
+    Nets of unequal depth (1 and 3 hidden layers) cannot share a forward launch: the first net's launch runs the parameter
+    update and packs the SECOND net's operand image straight to global memory from its lead block, the second launch reads
+    it there; the displacement update is the stand-alone kernel — on the side branch of the DAG (250000 elements, with the
+    displacement ping-pong) and on the main chain (60000), so every history column is compared bit for bit.
+    Equal depths other than 2 do not fuse the backward passes (pf_fusion_info: 1 + 4 + 16)."""
     from pinn_fem_amd.engine import HipEngine
     from pinn_fem_amd.fem.model import FEMModel, Material
     from pinn_fem_amd.fem.properties import NNProperty
     from pinn_fem_amd.fem.solver import SolverConfig
     from pinn_fem_amd.nets import SimpleNN
-    n = 5000
     outs = []
     for use_graph in (True, False):
         rng = np.random.default_rng(7)
@@ -1078,22 +1103,133 @@ def test_graph_equals_eager_net_shapes(layers, we, wa, dim):
         loads = rng.normal(size=ndof) * 0.1
         md = rng.choice(np.arange(dim, ndof), size=n // 5, replace=False)
         mv = rng.normal(size=len(md)) * 0.02
-        model = FEMModel(nodes, elements, Material(NNProperty(SimpleNN(layers, we, dim + 1), dim + 1, True, 1.5),
-                                                   NNProperty(SimpleNN(layers, wa, dim + 1), dim + 1, True, 0.7)),
+        model = FEMModel(nodes, elements, Material(NNProperty(SimpleNN(le, we, dim + 1), dim + 1, True, 1.5),
+                                                   NNProperty(SimpleNN(la, wa, dim + 1), dim + 1, True, 0.7)),
                          loads, fixed, dimension=dim)
-        cfg = SolverConfig(max_iterations=40, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4)
+        cfg = SolverConfig(max_iterations=60, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4)
         eng = HipEngine(model, mv, md)
         eng.begin(None, 0.2, cfg, want_history=True)
+        assert eng.fusion_info() == mask
         n_it = 2 * eng.GRAPH_ITERS + 1
         eng.iterate(n_it, use_graph=use_graph)
         torch.cuda.synchronize()
         assert eng.state().iter == n_it
+        assert eng.graph_creates == (1 if use_graph else 0)
         outs.append((eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.m_t.cpu().numpy().copy(),
-                     eng.v_t.cpu().numpy().copy(), eng.history(n_it).copy()))
+                     eng.v_t.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(), eng.v_u.cpu().numpy().copy(),
+                     eng.history(n_it).copy()))
         del eng
     for a, b in zip(outs[0][:-1], outs[1][:-1]):
         assert np.array_equal(a, b)
-    _assert_history_equal(outs[0][-1], outs[1][-1])
+    _assert_history_for(mask, outs[0][-1], outs[1][-1])
+    assert np.all(np.isfinite(outs[0][-1]))
+
+
+def _graph_form_model(kind, n):
+    """(model, measured values, measured dofs) of the iteration-graph form tests; a fresh model per call (the engine trains
+    the model's nets in place).  ex4 / ex3: bench.py's workloads (E, A, rho nets / E net, A and rho scalar); area: E and rho
+    scalar, A a net; bar1d: a 1-D bar (one dof per node, one-float stiffness records) with an E net."""
+    from bench import build_model
+    from pinn_fem_amd.fem.model import FEMModel, Material
+    from pinn_fem_amd.fem.properties import NNProperty
+    from pinn_fem_amd.nets import SimpleNN
+    from pinn_fem_amd.plan import chain_mesh
+    if kind in ("ex4", "ex3"):
+        model, mv, md, _ = build_model(n, kind)
+        return model, mv, md
+    if kind == "area":
+        nodes, elements, loads, fixed, mv, md = chain_mesh(n, 1.0)
+        torch.manual_seed(3)
+        mat = Material(1.0, NNProperty(SimpleNN(2, 15, 3), input_dim=3, enforce_positive=True, scale=1.0), 1.0)
+        return FEMModel(nodes, elements, mat, loads, fixed, dimension=2), mv, md
+    assert kind == "bar1d"
+    rng = np.random.default_rng(11)
+    torch.manual_seed(5)
+    nodes = np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 1.5, n))]) * (3.0 / n)
+    elements = np.stack([np.arange(n), np.arange(1, n + 1)], 1)
+    loads = rng.normal(size=n + 1) * 0.1
+    md = rng.choice(np.arange(1, n + 1), size=n // 7, replace=False)
+    mv = rng.normal(size=len(md)) * 0.02
+    mat = Material(NNProperty(SimpleNN(2, 20, 2), 2, True, 1.5), 0.7, 1.0)
+    return FEMModel(nodes, elements, mat, loads, np.array([0]), dimension=1), mv, md
+
+
+def _no_u_alt(P):
+    P.u_alt = None
+
+
+def _no_prop_double(P):
+    P.prop_double = 0
+
+
+def _no_theta_alt(P):
+    P.theta_alt = None
+
+
+# (model, elements, engine arguments, replay length (None: the engine's), change of the pf_problem record, pf_fusion_info)
+GRAPH_FORMS = {
+    "ex3-dag-pingpong": ("ex3", 250_000, {}, None, None, 4 + 8),
+    "ex3-chain": ("ex3", 60_000, {}, None, None, 4),
+    "ex3-below-threshold": ("ex3", 199_999, {}, None, None, 4),
+    "ex3-at-threshold": ("ex3", 200_000, {}, None, None, 4 + 8),
+    "area-only-dag": ("area", 250_000, {}, None, None, 4 + 8),
+    "bar1d-dag": ("bar1d", 250_000, {}, None, None, 4 + 8),
+    "mfma44-dag": ("ex4", 250_000, {"wg_mode": 2}, None, None, 8),
+    "mfma-dag": ("ex4", 250_000, {"wg_mode": 1}, None, None, 8),
+    "shuffle-dag": ("ex4", 250_000, {"wg_mode": 0}, None, None, 8),
+    "bf16-dag": ("ex3", 250_000, {"mlp_dtype": "bf16"}, None, None, 4 + 8),
+    "dag-length-7": ("ex3", 250_000, {}, 7, None, 4 + 8),
+    "dag-length-1": ("ex3", 250_000, {}, 1, None, 4 + 8),
+    "chain-length-7": ("ex4", 60_000, {}, 7, None, 1 + 2 + 4 + 16),
+    "chain-length-1": ("ex4", 60_000, {}, 1, None, 1 + 2 + 4 + 16),
+    "dag-no-u-alt": ("ex3", 250_000, {}, None, _no_u_alt, 4),
+    "dag-no-prop-double": ("ex4", 250_000, {}, None, _no_prop_double, 1 + 2 + 4 + 8),
+    "chain-no-theta-alt": ("ex4", 60_000, {}, None, _no_theta_alt, 1 + 2 + 16),
+}
+
+
+@pytest.mark.parametrize("case", list(GRAPH_FORMS))
+def test_graph_forms_equal_eager(case):
+    """Every form the iteration graph is captured in (enqueue_graph_iterations) against the same iterations launched
+    eagerly: two whole replays and an eager remainder end in the same bits of u, theta, both Adam moments, the iteration
+    count, the stop flags and the history.  The forms: the dependency DAG with the displacement update on the side branch,
+    with and without the displacement ping-pong (u_alt; even replay lengths only) and with the forwards waiting for it
+    (prop_double = 0); the plain chain below 2*10^5 elements and on both sides of that threshold; the single-net forward
+    launch with the parameter-update prologue for the young net, for the area net and on a 1-D bar; the engines without
+    the prologue (MFMA44, MFMA, SHUFFLE: stand-alone parameter update per iteration, separate element adjoint on the VALU
+    engines); bf16 matrix products; odd replay lengths and length 1 (parity of the state halves); the fused displacement
+    update with the stand-alone parameter update (theta_alt = NULL).  Without PF_FUSED_U_UPDATE the displacement update is
+    the eager launches' kernel, so the u-norm column is compared bit for bit too."""
+    from pinn_fem_amd.engine import HipEngine
+    from pinn_fem_amd.fem.solver import SolverConfig
+    kind, n, kw, length, tweak, mask = GRAPH_FORMS[case]
+    outs = []
+    for use_graph in (True, False):
+        model, mv, md = _graph_form_model(kind, n)
+        eng = HipEngine(model, mv, md, **kw)
+        assert eng.GRAPH_ITERS == (20 if n >= 200_000 else 10)      # (switches at the DAG threshold too)
+        if length is not None:
+            eng.GRAPH_ITERS = length
+        cfg = SolverConfig(max_iterations=60, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4)
+        eng.begin(None, 0.1, cfg, want_history=True)
+        if tweak is not None:
+            tweak(eng.P)                                        # the graph is captured from this record by iterate()
+        assert eng.fusion_info() == mask
+        n_it = 2 * eng.GRAPH_ITERS + 3                          # two whole replays and a part of one
+        eng.iterate(n_it, use_graph=use_graph)
+        torch.cuda.synchronize()
+        st = eng.state()
+        assert st.iter == n_it and st.theta_half == 0 and st.u_half == 0
+        assert eng.graph_creates == (1 if use_graph else 0)
+        outs.append((eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.m_t.cpu().numpy().copy(),
+                     eng.v_t.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(), eng.v_u.cpu().numpy().copy(),
+                     (st.iter, st.done, st.converged), eng.history(n_it).copy()))
+        del eng
+    for a, b in zip(outs[0][:-2], outs[1][:-2]):
+        assert np.array_equal(a, b)
+    assert outs[0][-2] == outs[1][-2]
+    _assert_history_for(mask, outs[0][-1], outs[1][-1])
+    assert np.all(np.isfinite(outs[0][-1]))
 
 
 @pytest.mark.parametrize("n,max_it,tol,n_call,expect", [(250_000, 200, 0.0, 3 * 20 + 7, 67), (250_000, 200, 1e30, 60, 12),
@@ -1133,35 +1269,58 @@ def test_chained_replays_equal_plain_replays(n, max_it, tol, n_call, expect):
     assert outs[0][-1] == outs[1][-1]
 
 
-@pytest.mark.parametrize("max_it,tol,expect", [(40, 1e30, 12), (13, 0.0, 13), (15, 0.0, 15)])
-def test_graph_stop_in_mid_replay_equals_eager(max_it, tol, expect):
+@pytest.mark.parametrize("work,mask,max_it,tol,expect", [
+    pytest.param(work, mask, max_it, tol, expect, id=f"{max_it}-{tol}-{expect}" + ("" if work == "ex4" else "-" + work))
+    for work, mask in (("ex4", 1 + 2 + 4 + 16), ("ex3", 4 + 8))
+    for max_it, tol, expect in ((40, 1e30, 12), (13, 0.0, 13), (15, 0.0, 15), (27, 0.0, 27))])
+def test_graph_stop_in_mid_replay_equals_eager(max_it, tol, expect, work, mask):
     """The iteration graph ping-pongs the parameter state and the element records between two halves; a stop raised
     INSIDE a replay (stop test at iteration 12; max_iterations 13 and 15: odd counts, so the live halves are the
-    alternates) must still leave u, theta, the Adam moments and the history where and what the eager launches leave.
-    250000 elements: above the DAG threshold (2*10^5 elements), but this shape fuses the displacement update, so the
-    graph is the one chain of the product path."""
+    alternates; 27: inside the second replay) must still leave u, theta, the Adam moments and the history where and what
+    the eager launches leave.  250000 elements, above the DAG threshold (2*10^5 elements): the ex4 shape fuses the
+    displacement update, so its graph is the one chain of the product path; the ex3 shape (one net) is the dependency DAG
+    with the displacement ping-pong, where an odd count leaves the final u in u_alt and k_u_home brings it home."""
     from bench import build_model
+    from pinn_fem_amd import _capi
     from pinn_fem_amd.engine import HipEngine
     from pinn_fem_amd.fem.solver import SolverConfig
     outs = []
     for use_graph in (True, False):
-        model, mv, md, _ = build_model(250_000, "ex4")
+        model, mv, md, _ = build_model(250_000, work)
         cfg = SolverConfig(max_iterations=max_it, tolerance=tol, learning_rate_u=0.01, learning_rate_theta=5e-4)
         eng = HipEngine(model, mv, md)
-        assert eng.fusion_info() == 1 + 2 + 4 + 16              # every fused form is active on this problem
+        assert eng.fusion_info() == mask
         eng.begin(None, 0.1, cfg, want_history=True)
         eng.iterate(2 * eng.GRAPH_ITERS, use_graph=use_graph)
         torch.cuda.synchronize()
         st = eng.state()
         assert st.iter == expect and st.done == 1 and st.theta_half == 0
         outs.append((eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.m_t.cpu().numpy().copy(),
-                     eng.v_t.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(), eng.history(expect).copy()))
+                     eng.v_t.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(), eng.v_u.cpu().numpy().copy(),
+                     (st.done, st.converged), eng.history(expect).copy()))
         # the nets' operand images belong to the final theta: a property evaluation from the stored images (no re-pack)
         # equals one after re-packing
+        ne = eng.plan.n_elems
+        eng._clear_done()
+        with eng.on_stream():
+            for k, spec in enumerate(eng.specs):
+                if spec.enabled:
+                    _capi.check(eng.lib.pf_net_forward(eng._ref(), k, eng._stream()), "pf_net_forward")
+        torch.cuda.synchronize()
+        stored = [eng.prop_e[:ne].cpu().numpy().copy(), eng.prop_a[:ne].cpu().numpy().copy()]
+        eng.eval_properties()
+        torch.cuda.synchronize()
+        repacked = [eng.prop_e[:ne].cpu().numpy().copy(), eng.prop_a[:ne].cpu().numpy().copy()]
+        assert any(spec.enabled for spec in eng.specs)
+        for k, spec in enumerate(eng.specs):
+            if spec.enabled:
+                assert np.all(np.isfinite(repacked[k]))
+                assert np.array_equal(stored[k], repacked[k]), k
         del eng
-    for a, b in zip(outs[0][:-1], outs[1][:-1]):
+    for a, b in zip(outs[0][:-2], outs[1][:-2]):
         assert np.array_equal(a, b)
-    _assert_history_equal(outs[0][-1], outs[1][-1])
+    assert outs[0][-2] == outs[1][-2]
+    _assert_history_for(mask, outs[0][-1], outs[1][-1])
 
 
 def test_full_size_loss_and_grads_vs_oracle_prefix():
@@ -1376,17 +1535,22 @@ def test_beyond_infinity_cache_1e7_elements():
     assert np.max(np.abs(gu[:k] - ref.grad_u[:k])) < 2e-5 * np.max(np.abs(ref.grad_u[:k]))
 
 
-def test_config1_ex3_shape_1e5_vs_oracle():
-    """BASELINE.json configs[1]: example3 shape (E = NN, A and rho scalar) on a 10^5-element bar: 12 GD iterations of the
-    product path (plain chain inside the hipGraph below 2*10^5 elements) against the oracle, default formulation."""
+@pytest.mark.parametrize("n,max_it", [(100_000, 12), (250_000, 43)])
+def test_config1_ex3_shape_vs_oracle(n, max_it):
+    """BASELINE.json configs[1]: example3 shape (E = NN, A and rho scalar) on a chain bar: GD iterations of the product
+    path against the oracle, default formulation.  10^5 elements: 12 iterations in the plain chain of the hipGraph (below
+    2*10^5 elements); 2.5*10^5 elements: 43 iterations = two 20-iteration replays of the dependency DAG (displacement
+    update on the side branch, displacement ping-pong) and 3 eager ones."""
     from pinn_fem_amd.fem.solver import SolverConfig, solve_gd
-    n = 100_000
     model, pb, mv, md = _chain_model(n, widths=(20, None, None), h=1.0)
-    cfg = SolverConfig(max_iterations=12, learning_rate_u=0.01, learning_rate_theta=1e-3, tolerance=0.0)
+    cfg = SolverConfig(max_iterations=max_it, learning_rate_u=0.01, learning_rate_theta=1e-3, tolerance=0.0)
     res = solve_gd(model, cfg, mv, md, target_load_factor=0.1)
-    ref = orc.solve_gd(pb, orc.SolverConfig(max_iterations=12, learning_rate_u=0.01, learning_rate_theta=1e-3,
+    eng = model._pf_engine_cache[1]
+    assert eng.fusion_info() == (4 + 8 if n >= 200_000 else 4)
+    assert eng.graph_creates == 1                           # (the iterations did replay the graph)
+    ref = orc.solve_gd(pb, orc.SolverConfig(max_iterations=max_it, learning_rate_u=0.01, learning_rate_theta=1e-3,
                                             tolerance=0.0), 0.1)
-    assert len(res.history) == len(ref.history) == 12
+    assert len(res.history) == len(ref.history) == max_it
     got_l = np.array([h["loss_total"] for h in res.history])
     ref_l = np.array([h["loss_total"] for h in ref.history])
     assert np.max(np.abs(got_l - ref_l) / np.abs(ref_l)) < 2e-5
@@ -1394,6 +1558,36 @@ def test_config1_ex3_shape_1e5_vs_oracle():
     th = np.concatenate([t.reshape(-1) for t in pb.theta_list()])
     got_th = np.concatenate([v.reshape(-1) for v in res.nn_parameters.values()])
     assert rel_err(got_th, th) < 2e-5
+
+
+def test_warm_started_solve_gd_on_the_dag_equals_eager(monkeypatch):
+    """Two consecutive solve_gd calls on one example3-shaped model of 2.5*10^5 elements (the dependency DAG with the
+    displacement ping-pong), the second warm-started from the first's displacements, with the iteration graph and with
+    eager launches only (PINNFEM_GRAPH=0): the same iteration counts and the same bits of the displacements and theta.
+    The second call starts while u_alt still holds the first call's values: nothing may read them."""
+    from bench import build_model
+    from pinn_fem_amd.fem.solver import SolverConfig, solve_gd
+    outs = []
+    for graph in ("1", "0"):
+        monkeypatch.setenv("PINNFEM_GRAPH", graph)
+        model, mv, md, _ = build_model(250_000, "ex3")
+        cfg = SolverConfig(max_iterations=43, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4)
+        r1 = solve_gd(model, cfg, mv, md, target_load_factor=0.1)
+        eng = model._pf_engine_cache[1]
+        assert eng.fusion_info() == 4 + 8
+        if graph == "1":
+            assert eng.graph_creates == 1 and bool(torch.any(eng.u_alt != 0))     # u_alt is not clean
+        r2 = solve_gd(model, cfg, mv, md, target_load_factor=0.2,
+                      u_initial=torch.from_numpy(r1.displacements.reshape(-1).astype(np.float32)))
+        assert model._pf_engine_cache[1] is eng
+        assert eng.graph_creates == (2 if graph == "1" else 0)
+        outs.append([(len(r.history), r.converged, r.displacements.copy(),
+                      np.concatenate([v.reshape(-1) for v in r.nn_parameters.values()])) for r in (r1, r2)])
+    for a, b in zip(outs[0], outs[1]):
+        assert a[0] == b[0] == 43 and a[1] == b[1]
+        assert np.array_equal(a[2], b[2])
+        assert np.array_equal(a[3], b[3])
+    assert not np.array_equal(outs[0][0][2], outs[0][1][2])
 
 
 def test_api_pinn_gd_matches_oracle_restatement():
