@@ -377,7 +377,8 @@ int pf_shard_iterations_graph(const pf_problem* p, void* comm, void* graph, int 
 int pf_kv_f64(const pf_problem* p, const double* v, double* out, int zero_fixed, void* stream);
 /* doubles of workspace pf_pcg_* need */
 long long pf_pcg_workspace_count(const pf_problem* p);
-/* start a solve of K_ff x = b (entries of b on fixed dofs are ignored), x = 0; stop when |r| <= rtol*|b| */
+/* start a solve of K_ff x = b (entries of b on fixed dofs are ignored), x = 0; stop when |r| <= rtol*|b|
+ * (rtol >= 0).  Enqueues only: rtol^2 travels as a kernel argument. */
 int pf_pcg_begin(const pf_problem* p, const double* b, double* x, double* ws, double rtol, void* stream);
 /* n_iter CG iterations (no-ops after the stop test fired).  state_out: host double[4] or NULL =
  * [iterations done, stopped (0/1), |r|^2, |b|^2], read back after a stream synchronisation. */

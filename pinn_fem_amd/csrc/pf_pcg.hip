@@ -127,8 +127,9 @@ __global__ __launch_bounds__(256) void k_pcg_ap(pf_problem P, const double* __re
 }
 
 // one block: phase 0 (after init) rz, bb | phase 1 (after ap) pAp -> alpha | phase 2 (after update) rz_new, rr ->
-// beta, stop test
-__global__ __launch_bounds__(1024) void k_pcg_scalars(double* st, const double* __restrict__ part, int nb, int phase) {
+// beta, stop test.  rtol2 is read in phase 0 only (it is stored in the state for the stop tests that follow)
+__global__ __launch_bounds__(1024) void k_pcg_scalars(double* st, const double* __restrict__ part, int nb, int phase,
+                                                      double rtol2) {
   if (phase != 0 && st[ST_DONE] != 0.0) return;
   __shared__ double red[16];
   double a = 0.0, b = 0.0;
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(1024) void k_pcg_scalars(double* st, const double* 
   const double ta = block_sum64(a, red), tb = block_sum64(b, red);
   if (threadIdx.x != 0) return;
   if (phase == 0) {
-    st[ST_RZ] = ta; st[ST_BB] = tb; st[ST_RR] = tb; st[ST_ITERS] = 0.0;
+    st[ST_RZ] = ta; st[ST_BB] = tb; st[ST_RR] = tb; st[ST_ITERS] = 0.0; st[ST_RTOL2] = rtol2;
     st[ST_DONE] = (tb == 0.0) ? 1.0 : 0.0;        // b = 0: x = 0 is the solution
   } else if (phase == 1) {
     st[ST_PAP] = ta;
@@ -205,17 +206,14 @@ int pf_pcg_begin(const pf_problem* p, const double* b, double* x, double* ws, do
   double* part = ws + 5 * (size_t)n;
   double* st = part + 2 * PF_NODE_SLOTS;
   hipStream_t s = (hipStream_t)stream;
-  const double rtol2 = rtol * rtol;
-  if (hipMemsetAsync(st, 0, ST_COUNT * sizeof(double), s) != hipSuccess ||
-      hipMemcpyAsync(st + ST_RTOL2, &rtol2, sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess) {
+  if (hipMemsetAsync(st, 0, ST_COUNT * sizeof(double), s) != hipSuccess) {
     pf_set_error("pf_pcg_begin: state setup failed");
     return PF_ERR_HIP;
   }
-  if (hipStreamSynchronize(s) != hipSuccess) { pf_set_error("pf_pcg_begin: sync failed"); return PF_ERR_HIP; }  // rtol2 lives on the stack
   if (p->mesh.dim == 2) hipLaunchKernelGGL(k_pcg_init<2>, dim3(nb), dim3(256), 0, s, *p, b, x, r, z, pp, dinv, part);
   else hipLaunchKernelGGL(k_pcg_init<1>, dim3(nb), dim3(256), 0, s, *p, b, x, r, z, pp, dinv, part);
   PCG_CHECK("pf_pcg_begin");
-  hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nb, 0);
+  hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nb, 0, rtol * rtol);   // by value: no copy, no sync
   PCG_CHECK("pf_pcg_begin");
   return PF_OK;
 }
@@ -230,9 +228,9 @@ static int pcg_enqueue(const pf_problem* p, double* x, double* ws, int n_iter, h
   for (int it = 0; it < n_iter; ++it) {
     if (p->mesh.dim == 2) hipLaunchKernelGGL(k_pcg_ap<2>, dim3(nb), dim3(256), 0, s, *p, st, pp, ap, part);
     else hipLaunchKernelGGL(k_pcg_ap<1>, dim3(nb), dim3(256), 0, s, *p, st, pp, ap, part);
-    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nb, 1);
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nb, 1, 0.0);
     hipLaunchKernelGGL(k_pcg_update, dim3(nbv), dim3(256), 0, s, st, n, x, r, z, pp, ap, dinv, part);
-    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nbv, 2);
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nbv, 2, 0.0);
     hipLaunchKernelGGL(k_pcg_dir, dim3(nbv), dim3(256), 0, s, st, n, z, pp);
   }
   PCG_CHECK("pf_pcg_iterations");

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import (example_problem, load_npz, load_run, mesh_problem, orc, product_example,
+from helpers import (_random_truss, example_problem, load_npz, load_run, mesh_problem, orc, product_example,
                      product_model, rel_err, theta_from)
 
 pytestmark = pytest.mark.gpu
@@ -546,30 +546,6 @@ def test_cli_synthetic_chain_compact_output(tmp_path):
     res = json.loads((tmp_path / "chain.res.json").read_text())
     assert res["arrays_npz"] == "chain.res.npz" and (tmp_path / "chain.res.npz").exists()
     assert (tmp_path / "chain.log").exists()
-
-
-def _random_truss(n_nodes, rng, hub_degree=0):
-    """Random planar truss: nodes on a jittered grid, elements to nearest neighbours (+ an optional
-    hub node connected to `hub_degree` nodes: skewed node degree)."""
-    side = int(np.ceil(np.sqrt(n_nodes)))
-    ij = np.stack(np.meshgrid(np.arange(side), np.arange(side), indexing="ij"), -1).reshape(-1, 2)[:n_nodes]
-    nodes = ij + rng.uniform(-0.3, 0.3, ij.shape)
-    el = set()
-    idx = {tuple(p): k for k, p in enumerate(ij)}
-    for k, (i, j) in enumerate(ij):
-        for di, dj in ((1, 0), (0, 1), (1, 1), (1, -1)):
-            q = idx.get((i + di, j + dj))
-            if q is not None:
-                el.add((k, q))
-    el = sorted(el)
-    if hub_degree:
-        far = rng.choice(np.arange(1, n_nodes), size=hub_degree, replace=False)
-        el += [(0, int(q)) for q in far if (0, int(q)) not in el]
-    el = np.array(el)
-    rng.shuffle(el)                                   # element order != node order
-    flip = rng.random(len(el)) < 0.5                  # random element orientation
-    el[flip] = el[flip][:, ::-1]
-    return nodes, el
 
 
 @pytest.mark.parametrize("wg", [3, 2])
