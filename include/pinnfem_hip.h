@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 7
+#define PF_ABI_VERSION 8
 
 /* error codes */
 #define PF_OK 0
@@ -214,7 +214,7 @@ int pf_padded_width(int width);
 int pf_net_pad_count(int in_dim, int width, int n_hidden);
 /* padded-image index (inside the net's image) of the net's `local`-th torch parameter */
 int pf_net_pad_index(int in_dim, int width, int n_hidden, int local);
-/* sizeof of the ABI structs: 0 pf_mesh, 1 pf_net, 2 pf_state, 3 pf_problem, 4 pf_scalar_id (binding self-check) */
+/* sizeof of the ABI structs: 0 pf_mesh, 1 pf_net, 2 pf_state, 3 pf_problem, 4 pf_scalar_id, 5 pf_coarse (binding self-check) */
 int pf_sizeof(int what);
 /* floats of operand-image workspace (pf_problem.net_op) one net needs with the MFMA32 engine, or <0 */
 int pf_net_op_count(int in_dim, int width, int n_hidden);
@@ -387,6 +387,44 @@ int pf_pcg_iterations(const pf_problem* p, double* x, double* ws, int n_iter, do
  * state read-back on its own */
 int pf_pcg_graph_create(const pf_problem* p, double* x, double* ws, int n_iter, void* stream, void** graph_out);
 int pf_pcg_state(const pf_problem* p, double* ws, double* state_out, void* stream);
+
+/* ---- two-level preconditioner for the same solve (pf_pcg.hip) ------------------------------------------------------
+ *   M^-1 r = D^-1 r + Z (Z^T K Z)^-1 Z^T r,   D = diag(K_ff)
+ * Z holds per aggregate of nodes its rigid-body modes (2-D: two translations and the rotation about the centroid; 1-D: the
+ * translation), zero on fixed dofs, orthonormalised per aggregate by the host (pinn_fem_amd/coarse.py).  At most
+ * PF_COARSE_MODES columns touch a dof, so Z is held as per-dof coefficients and never formed.  Opt-in: the pf_pcg_* family
+ * above is unchanged.  The workspace is that of pf_pcg_* (same layout) followed by w = Z^T r and y = A^-1 w
+ * (PF_COARSE_MAX doubles each).  All arrays dev, caller-owned. */
+#define PF_COARSE_MAX_AGG 256
+#define PF_COARSE_MODES 3
+#define PF_COARSE_MAX (PF_COARSE_MAX_AGG * PF_COARSE_MODES)
+typedef struct pf_coarse {
+  int32_t n_agg;             /* aggregates, 1..PF_COARSE_MAX_AGG */
+  int32_t n_coarse;          /* columns of Z = agg_off[n_agg], 0..PF_COARSE_MODES*n_agg */
+  const int32_t* node_agg;   /* [n_nodes] aggregate of every node */
+  const int32_t* agg_off;    /* [n_agg+1] first column of every aggregate (0..PF_COARSE_MODES columns each) */
+  const double* zcoef;       /* [n_dofs][PF_COARSE_MODES]: Z[dof][agg_off[a] + k] = zcoef[dof][k], a = node_agg[node of dof];
+                                0 on fixed dofs and for k beyond the aggregate's column count */
+  const int32_t* agg_ptr;    /* [n_agg+1] aggregate -> its nodes in agg_nodes */
+  const int32_t* agg_nodes;  /* [n_nodes] node ids, ascending inside an aggregate: the order of every sum over it */
+  const double* a_inv;       /* [n_coarse][n_coarse] (Z^T K Z)^-1, row-major; the host inverts what pf_coarse_setup
+                                formed (not read by pf_coarse_setup itself) */
+} pf_coarse;
+/* a_c_out (dev [n_coarse][n_coarse], row-major) = Z^T K Z with the element stiffness of pf_kv_f64; one workgroup per
+ * aggregate owns that aggregate's rows, sums over its nodes run in ascending node id, no atomics */
+int pf_coarse_setup(const pf_problem* p, const pf_coarse* c, double* a_c_out, void* stream);
+/* doubles of workspace pf_pcg2_* need */
+long long pf_pcg2_workspace_count(const pf_problem* p);
+/* as pf_pcg_begin / pf_pcg_iterations / pf_pcg_graph_create / pf_pcg_state, with z = M^-1 r in place of z = D^-1 r.
+ * |r|^2, |b|^2 and the stop test are those of pf_pcg_*.  One iteration is a chain of six launches: K p, alpha, the
+ * update of x and r with the restriction w = Z^T r (one workgroup per aggregate), y = A^-1 w with z = D^-1 r + Z y,
+ * beta and the stop test, p = z + beta p. */
+int pf_pcg2_begin(const pf_problem* p, const pf_coarse* c, const double* b, double* x, double* ws, double rtol, void* stream);
+int pf_pcg2_iterations(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, double* state_out,
+                       void* stream);
+int pf_pcg2_graph_create(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, void* stream,
+                         void** graph_out);
+int pf_pcg2_state(const pf_problem* p, double* ws, double* state_out, void* stream);
 
 /* ---- scalar (E, A) identification: the device loop of pinn_inverse_problem_gd -------------------------------------
  * FEM/python/api_pinn_gradient_descent.py:102-121 calls pinn_inverse_problem_gd(nodes, elements, f_ext, fixed_dofs,

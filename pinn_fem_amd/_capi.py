@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PINNFEM_LIB: another build of the same library (experiment builds, A/B runs); no fallback of any kind
 LIB_PATH = os.environ.get("PINNFEM_LIB") or os.path.join(_HERE, "lib", "libpinnfem_hip.so")
 
-PF_ABI_VERSION = 7
+PF_ABI_VERSION = 8
 PF_OK, PF_ERR_ARG, PF_ERR_UNSUPPORTED, PF_ERR_HIP = 0, -1, -2, -3
 PF_DOF_FIXED, PF_DOF_MEASURED, PF_DOF_SHARED, PF_DOF_GHOST = 1, 2, 4, 8
 PF_WG_SHUFFLE, PF_WG_MFMA, PF_WG_MFMA44, PF_WG_MFMA32 = 0, 1, 2, 3
@@ -25,6 +25,8 @@ PF_COMM_ID_BYTES = 128
 PF_MAX_NODE_BLOCKS = 4096
 PF_NODE_SLOTS = PF_MAX_NODE_BLOCKS + 8
 PF_KERNEL_SLOTS = 9
+PF_COARSE_MAX_AGG, PF_COARSE_MODES = 256, 3
+PF_COARSE_MAX = PF_COARSE_MAX_AGG * PF_COARSE_MODES
 PF_GRAPH_CONT_HEAD, PF_GRAPH_NO_TAIL = 1, 2
 PF_FUSED_FORWARD, PF_FUSED_BACKWARD, PF_FUSED_THETA_UPDATE, PF_FUSED_U_PINGPONG, PF_FUSED_U_UPDATE = 1, 2, 4, 8, 16
 KERNEL_SLOT_NAMES = ("net_forward_young", "net_forward_area", "node_residual", "elem_adjoint",
@@ -99,8 +101,17 @@ class PfScalarId(C.Structure):
     ]
 
 
+class PfCoarse(C.Structure):
+    _fields_ = [
+        ("n_agg", C.c_int32), ("n_coarse", C.c_int32),
+        ("node_agg", C.c_void_p), ("agg_off", C.c_void_p), ("zcoef", C.c_void_p),
+        ("agg_ptr", C.c_void_p), ("agg_nodes", C.c_void_p), ("a_inv", C.c_void_p),
+    ]
+
+
 # every symbol include/pinnfem_hip.h declares: name -> (restype, argtypes)
 _PP = C.POINTER(PfProblem)
+_PC = C.POINTER(PfCoarse)
 SYMBOLS = {
     "pf_abi_version": (C.c_int, []),
     "pf_last_error": (C.c_char_p, []),
@@ -143,6 +154,12 @@ SYMBOLS = {
     "pf_pcg_iterations": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "pf_pcg_graph_create": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "pf_pcg_state": (C.c_int, [_PP, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "pf_coarse_setup": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p]),
+    "pf_pcg2_workspace_count": (C.c_longlong, [_PP]),
+    "pf_pcg2_begin": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "pf_pcg2_iterations": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
+    "pf_pcg2_graph_create": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pf_pcg2_state": (C.c_int, [_PP, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "pf_comm_unique_id": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pf_comm_create": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pf_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -204,7 +221,7 @@ def load():
         fn.argtypes = args
     if lib.pf_abi_version() != PF_ABI_VERSION:
         raise PinnFemHipError("libpinnfem_hip.so ABI version mismatch; rebuild the library")
-    for idx, st in enumerate((PfMesh, PfNet, PfState, PfProblem, PfScalarId)):
+    for idx, st in enumerate((PfMesh, PfNet, PfState, PfProblem, PfScalarId, PfCoarse)):
         if lib.pf_sizeof(idx) != C.sizeof(st):
             raise PinnFemHipError(
                 f"struct layout mismatch for {st.__name__}: C {lib.pf_sizeof(idx)} vs ctypes {C.sizeof(st)}")

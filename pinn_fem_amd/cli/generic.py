@@ -18,6 +18,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from ..coarse import check_preconditioner
 from ..fem.model import FEMModel, Material
 from ..fem.properties import NNProperty
 from ..fem.solver import SolverConfig, solve
@@ -77,7 +78,9 @@ def parse_problem(problem_file):
     # "accel": {"synthetic_chain": {"n_elements": N, "h": 1.0, "tip_load": 1.0},   mesh generator
     #           "compact_output": true|false|"auto",  big arrays -> <stem>.res.npz instead of JSON lists
     #           "fe_mode": "reference"|"delta",       element-force formulation
-    #           "mlp_dtype": "f32"|"bf16"}            precision of the MLP matrix products (bf16 study)
+    #           "mlp_dtype": "f32"|"bf16",            precision of the MLP matrix products (bf16 study)
+    #           "nr_preconditioner": "jacobi"|"two-level",  preconditioner of the CG solve inside Newton-Raphson
+    #           "nr_aggregates": N}                   aggregates of the two-level coarse space (default: by mesh size)
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -178,7 +181,7 @@ def parse_problem(problem_file):
 
 def _solver_config_from(data):
     """SolverConfig with the reference's precedence rules (generic.py:377-428)."""
-    sc, pc = data.get("solver_config", {}), data.get("pinn_config", {})
+    sc, pc, accel = data.get("solver_config", {}), data.get("pinn_config", {}), data.get("accel", {})
     solver_type = data.get("solver_type", "auto")
     explicit = sc.get("method", None)
     if explicit:
@@ -202,7 +205,9 @@ def _solver_config_from(data):
         alpha_physics=pc.get("alpha_physics", 1.0),
         alpha_data=pc.get("alpha_data", 100.0),
         preconditioning=pc.get("preconditioning", sc.get("preconditioning", False)),
-        method=method)
+        method=method,
+        nr_preconditioner=check_preconditioner(accel.get("nr_preconditioner", "jacobi")),
+        nr_aggregates=None if accel.get("nr_aggregates") is None else int(accel["nr_aggregates"]))
 
 
 def _parse_synthetic_chain(data, accel, chain):

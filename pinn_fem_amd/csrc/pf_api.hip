@@ -271,6 +271,7 @@ int pf_sizeof(int what) {
     case 2: return (int)sizeof(pf_state);
     case 3: return (int)sizeof(pf_problem);
     case 4: return (int)sizeof(pf_scalar_id);
+    case 5: return (int)sizeof(pf_coarse);
   }
   return PF_ERR_ARG;
 }

@@ -1,4 +1,4 @@
-// pf_pcg.hip — matrix-free K(E,A) v and a Jacobi-preconditioned conjugate-gradient solve in float64:
+// pf_pcg.hip — matrix-free K(E,A) v and a preconditioned conjugate-gradient solve in float64 (Jacobi, or opt-in two-level):
 // the linear solve inside the classical Newton-Raphson solver for scalar materials
 // (FEM/python/fem/solver.py:408-512: `du_f = np.linalg.solve(k_ff, rhs_f)` on the dense float64 tangent
 // of fem/assembly.py:16-75; fem/element.py:45-102).  SURVEY.md §8(f) rank 3: the reference's dense solve
@@ -176,6 +176,201 @@ __global__ __launch_bounds__(256) void k_pcg_dir(const double* __restrict__ st, 
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = z[i] + beta * p[i];
 }
 
+// ---- two-level preconditioner: M^-1 r = dinv r + Z (Z^T K Z)^-1 Z^T r -------------------------------------------------
+// Z is held as per-dof coefficients: column agg_off[a] + k of Z has zcoef[dof][k] on the dofs of aggregate a's nodes and
+// zeros elsewhere (pinnfem_hip.h: pf_coarse).  Every sum over an aggregate runs over its node list (ascending node
+// id) strided over the block's threads and then through block_sum64: a fixed order, no atomics.
+
+// columns of aggregate J at one node: the node's coefficient rows if it belongs to J, zeros otherwise
+template <int DIM>
+__device__ __forceinline__ void coarse_cols(const pf_coarse& C, int node, int J, double (*z)[PF_COARSE_MODES]) {
+  const bool in = C.node_agg[node] == J;
+#pragma unroll
+  for (int c = 0; c < DIM; ++c)
+#pragma unroll
+    for (int k = 0; k < PF_COARSE_MODES; ++k)
+      z[c][k] = in ? C.zcoef[((size_t)node * DIM + c) * PF_COARSE_MODES + k] : 0.0;
+}
+
+// (K z_j)[node] for the (up to 3) columns j of aggregate J: gather64 with z_j evaluated from the coefficients
+template <int DIM>
+__device__ __forceinline__ void gather_kz(const pf_problem& P, const pf_coarse& C, int J, int node,
+                                          double (*kz)[PF_COARSE_MODES]) {
+  const pf_mesh& M = P.mesh;
+#pragma unroll
+  for (int c = 0; c < DIM; ++c)
+#pragma unroll
+    for (int k = 0; k < PF_COARSE_MODES; ++k) kz[c][k] = 0.0;
+  for (int idx = M.adj_ptr[node]; idx < M.adj_ptr[node + 1]; ++idx) {
+    const int code = M.adj[idx];
+    const int e = code >> 1, end = code & 1;
+    const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
+    const ElemGeo g = load_geo(M.egeo, e);
+    const double s = elem_s64(P, e, g.l0);
+    const double sg = end ? -1.0 : 1.0;
+    double zi[DIM][PF_COARSE_MODES], zj[DIM][PF_COARSE_MODES];
+    coarse_cols<DIM>(C, nn.x, J, zi);
+    coarse_cols<DIM>(C, nn.y, J, zj);
+#pragma unroll
+    for (int k = 0; k < PF_COARSE_MODES; ++k) {
+      if (DIM == 2) {
+        const double dx = zj[0][k] - zi[0][k], dy = zj[1][k] - zi[1][k];
+        kz[0][k] += -(sg * s) * ((double)g.c2 * dx + (double)g.cs * dy);
+        kz[1][k] += -(sg * s) * ((double)g.cs * dx + (double)g.s2 * dy);
+      } else {
+        kz[0][k] += -(sg * s) * (zj[0][k] - zi[0][k]);
+      }
+    }
+  }
+}
+
+// A_c = Z^T K Z.  Block I owns the rows of aggregate I: entry (I,ki | J,kj) = sum over the nodes of I of
+// z_(I,ki)[node] . (K z_(J,kj))[node], which is non-zero only when J is I or holds a neighbour of a node of I
+// (nbr[] marks those).  The caller zeroed ac.
+template <int DIM>
+__global__ __launch_bounds__(256) void k_coarse_setup(pf_problem P, pf_coarse C, double* __restrict__ ac) {
+  __shared__ int nbr[PF_COARSE_MAX_AGG];
+  __shared__ double red[8];
+  const pf_mesh& M = P.mesh;
+  const int I = blockIdx.x, lo = C.agg_ptr[I], hi = C.agg_ptr[I + 1];
+  const int offI = C.agg_off[I], nI = C.agg_off[I + 1] - offI, nc = C.n_coarse;
+  if (nI == 0) return;
+  for (int t = threadIdx.x; t < C.n_agg; t += blockDim.x) nbr[t] = 0;
+  __syncthreads();
+  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+    const int node = C.agg_nodes[i];
+    nbr[I] = 1;
+    for (int idx = M.adj_ptr[node]; idx < M.adj_ptr[node + 1]; ++idx) {
+      const int code = M.adj[idx];
+      const int2 nn = reinterpret_cast<const int2*>(M.conn)[code >> 1];
+      nbr[C.node_agg[(code & 1) ? nn.x : nn.y]] = 1;       // every writer stores the same value
+    }
+  }
+  __syncthreads();
+  for (int J = 0; J < C.n_agg; ++J) {
+    const int offJ = C.agg_off[J], nJ = C.agg_off[J + 1] - offJ;
+    if (!nbr[J] || nJ == 0) continue;                       // the same decision in every thread of the block
+    double acc[PF_COARSE_MODES][PF_COARSE_MODES];
+#pragma unroll
+    for (int ki = 0; ki < PF_COARSE_MODES; ++ki)
+#pragma unroll
+      for (int kj = 0; kj < PF_COARSE_MODES; ++kj) acc[ki][kj] = 0.0;
+    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+      const int node = C.agg_nodes[i];
+      double kz[DIM][PF_COARSE_MODES];
+      gather_kz<DIM>(P, C, J, node, kz);
+#pragma unroll
+      for (int c = 0; c < DIM; ++c)
+#pragma unroll
+        for (int ki = 0; ki < PF_COARSE_MODES; ++ki) {
+          const double zi = C.zcoef[((size_t)node * DIM + c) * PF_COARSE_MODES + ki];
+#pragma unroll
+          for (int kj = 0; kj < PF_COARSE_MODES; ++kj) acc[ki][kj] += zi * kz[c][kj];
+        }
+    }
+#pragma unroll
+    for (int ki = 0; ki < PF_COARSE_MODES; ++ki)
+#pragma unroll
+      for (int kj = 0; kj < PF_COARSE_MODES; ++kj) {
+        const double t = block_sum64(acc[ki][kj], red);
+        if (threadIdx.x == 0 && ki < nI && kj < nJ) ac[(size_t)(offI + ki) * nc + offJ + kj] = t;
+      }
+  }
+}
+
+// one workgroup per aggregate (every node belongs to exactly one): x += alpha p, r -= alpha ap on its dofs (update != 0;
+// pf_pcg2_begin restricts the r that k_pcg_init wrote), w = Z^T r for its columns, partial r.r
+template <int DIM>
+__global__ __launch_bounds__(256) void k_pcg2_restrict(pf_coarse C, const double* __restrict__ st, int update, double* x,
+                                                       double* r, const double* __restrict__ p,
+                                                       const double* __restrict__ ap, double* __restrict__ w, double* part) {
+  if (st[ST_DONE] != 0.0) return;
+  __shared__ double red[8];
+  const int a = blockIdx.x, lo = C.agg_ptr[a], hi = C.agg_ptr[a + 1];
+  const int off = C.agg_off[a], nk = C.agg_off[a + 1] - off;
+  const double alpha = update ? st[ST_ALPHA] : 0.0;
+  double acc[PF_COARSE_MODES] = {0.0, 0.0, 0.0}, rr = 0.0;
+  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+    const int node = C.agg_nodes[i];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const size_t dof = (size_t)node * DIM + c;
+      double ri = r[dof];
+      if (update) {
+        x[dof] += alpha * p[dof];
+        ri -= alpha * ap[dof];
+        r[dof] = ri;
+      }
+      rr += ri * ri;
+#pragma unroll
+      for (int k = 0; k < PF_COARSE_MODES; ++k) acc[k] += C.zcoef[dof * PF_COARSE_MODES + k] * ri;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < PF_COARSE_MODES; ++k) {
+    const double t = block_sum64(acc[k], red);
+    if (threadIdx.x == 0 && k < nk) w[off + k] = t;
+  }
+  const double t = block_sum64(rr, red);
+  if (threadIdx.x == 0) part[PF_NODE_SLOTS + a] = t;
+}
+
+// one workgroup per aggregate: y = A^-1 w for the aggregate's columns (one row per wave, wave-wide reduction), then
+// z = dinv r + Z y on its dofs and the partial r.z; p_init != NULL (pf_pcg2_begin): p = z as well
+template <int DIM>
+__global__ __launch_bounds__(256) void k_pcg2_apply(pf_coarse C, const double* __restrict__ st, const double* __restrict__ r,
+                                                    const double* __restrict__ dinv, const double* __restrict__ w,
+                                                    double* __restrict__ y, double* __restrict__ z, double* p_init,
+                                                    double* part) {
+  if (st[ST_DONE] != 0.0) return;
+  __shared__ double red[8];
+  __shared__ double ys[PF_COARSE_MODES];
+  const int a = blockIdx.x, lo = C.agg_ptr[a], hi = C.agg_ptr[a + 1];
+  const int off = C.agg_off[a], nk = C.agg_off[a + 1] - off, nc = C.n_coarse;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave < PF_COARSE_MODES) {
+    double s = 0.0;
+    if (wave < nk) {
+      const double* __restrict__ row = C.a_inv + (size_t)(off + wave) * nc;
+      for (int j = lane; j < nc; j += 64) s += row[j] * w[j];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) {
+      ys[wave] = s;                                         // 0.0 for a column the aggregate does not have
+      if (wave < nk) y[off + wave] = s;
+    }
+  }
+  __syncthreads();
+  const double y0 = ys[0], y1 = ys[1], y2 = ys[2];
+  double rz = 0.0;
+  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+    const int node = C.agg_nodes[i];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const size_t dof = (size_t)node * DIM + c;
+      const double* __restrict__ zc = C.zcoef + dof * PF_COARSE_MODES;
+      const double ri = r[dof];
+      const double zi = dinv[dof] * ri + (zc[0] * y0 + zc[1] * y1 + zc[2] * y2);
+      z[dof] = zi;
+      if (p_init) p_init[dof] = zi;
+      rz += ri * zi;
+    }
+  }
+  const double t = block_sum64(rz, red);
+  if (threadIdx.x == 0) part[a] = t;
+}
+
+// r.z of the start (pf_pcg2_begin): k_pcg_scalars' phase 0 stored the Jacobi value
+__global__ __launch_bounds__(256) void k_pcg2_rz0(double* st, const double* __restrict__ part, int nb) {
+  if (st[ST_DONE] != 0.0) return;
+  __shared__ double red[8];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) a += part[i];
+  const double t = block_sum64(a, red);
+  if (threadIdx.x == 0) st[ST_RZ] = t;
+}
+
 }  // namespace
 
 #define PCG_CHECK(what)                                                      \
@@ -289,6 +484,138 @@ int pf_pcg_graph_create(const pf_problem* p, double* x, double* ws, int n_iter, 
 // [iterations, stopped, |r|^2, |b|^2] of the running solve (synchronises the stream)
 int pf_pcg_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
   if (!p || !ws || !state_out) { pf_set_error("pf_pcg_state: bad argument"); return PF_ERR_ARG; }
+  return pcg_read_state(ws, p->mesh.n_dofs, state_out, (hipStream_t)stream);
+}
+
+// ---- two-level preconditioner ---------------------------------------------------------------------------------------
+static bool coarse_ok(const pf_coarse* c, bool need_inverse) {
+  return c && c->n_agg >= 1 && c->n_agg <= PF_COARSE_MAX_AGG && c->n_coarse >= 0 &&
+         c->n_coarse <= PF_COARSE_MODES * c->n_agg && c->node_agg && c->agg_off && c->zcoef && c->agg_ptr &&
+         c->agg_nodes && (!need_inverse || c->a_inv);
+}
+
+int pf_coarse_setup(const pf_problem* p, const pf_coarse* c, double* a_c_out, void* stream) {
+  if (!p || !coarse_ok(c, false) || !a_c_out) { pf_set_error("pf_coarse_setup: bad argument"); return PF_ERR_ARG; }
+  hipStream_t s = (hipStream_t)stream;
+  if (c->n_coarse == 0) return PF_OK;
+  if (hipMemsetAsync(a_c_out, 0, (size_t)c->n_coarse * c->n_coarse * sizeof(double), s) != hipSuccess) {
+    pf_set_error("pf_coarse_setup: clearing the coarse matrix failed");
+    return PF_ERR_HIP;
+  }
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_coarse_setup<2>, dim3(c->n_agg), dim3(256), 0, s, *p, *c, a_c_out);
+  else hipLaunchKernelGGL(k_coarse_setup<1>, dim3(c->n_agg), dim3(256), 0, s, *p, *c, a_c_out);
+  PCG_CHECK("pf_coarse_setup");
+  return PF_OK;
+}
+
+long long pf_pcg2_workspace_count(const pf_problem* p) {
+  if (!p) return PF_ERR_ARG;
+  return pf_pcg_workspace_count(p) + 2LL * PF_COARSE_MAX;        // ... | w = Z^T r | y = A^-1 w
+}
+
+// z = M^-1 r and r.z for the r in the workspace: restriction, then coarse solve + prolongation (two launches)
+static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int update, double* p_init,
+                              hipStream_t s) {
+  const size_t n = (size_t)p->mesh.n_dofs;
+  double *r = ws, *z = ws + n, *pp = ws + 2 * n, *ap = ws + 3 * n, *dinv = ws + 4 * n;
+  double* part = ws + 5 * n;
+  double* st = part + 2 * PF_NODE_SLOTS;
+  double *w = st + ST_COUNT, *y = w + PF_COARSE_MAX;
+  if (p->mesh.dim == 2) {
+    hipLaunchKernelGGL(k_pcg2_restrict<2>, dim3(c->n_agg), dim3(256), 0, s, *c, st, update, x, r, pp, ap, w, part);
+    hipLaunchKernelGGL(k_pcg2_apply<2>, dim3(c->n_agg), dim3(256), 0, s, *c, st, r, dinv, w, y, z, p_init, part);
+  } else {
+    hipLaunchKernelGGL(k_pcg2_restrict<1>, dim3(c->n_agg), dim3(256), 0, s, *c, st, update, x, r, pp, ap, w, part);
+    hipLaunchKernelGGL(k_pcg2_apply<1>, dim3(c->n_agg), dim3(256), 0, s, *c, st, r, dinv, w, y, z, p_init, part);
+  }
+}
+
+int pf_pcg2_begin(const pf_problem* p, const pf_coarse* c, const double* b, double* x, double* ws, double rtol,
+                  void* stream) {
+  if (!p || !coarse_ok(c, true) || !b || !x || !ws || !(rtol >= 0.0)) {
+    pf_set_error("pf_pcg2_begin: bad argument");
+    return PF_ERR_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)p->mesh.n_dofs;
+  double* st = ws + 5 * n + 2 * PF_NODE_SLOTS;
+  if (hipMemsetAsync(st, 0, (ST_COUNT + 2 * PF_COARSE_MAX) * sizeof(double), s) != hipSuccess) {
+    pf_set_error("pf_pcg2_begin: state setup failed");
+    return PF_ERR_HIP;
+  }
+  // the Jacobi start (x = 0, r = b, dinv, |b|^2, the b = 0 exit), then z = M^-1 r, p = z and r.z over it
+  const int rc = pf_pcg_begin(p, b, x, ws, rtol, stream);
+  if (rc != PF_OK) return rc;
+  pcg2_precondition(p, c, x, ws, 0, ws + 2 * n, s);
+  hipLaunchKernelGGL(k_pcg2_rz0, dim3(1), dim3(256), 0, s, st, ws + 5 * n, c->n_agg);
+  PCG_CHECK("pf_pcg2_begin");
+  return PF_OK;
+}
+
+static int pcg2_enqueue(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, hipStream_t s) {
+  const int n = p->mesh.n_dofs, nb = pf_node_blocks(p->mesh.n_nodes);
+  double *z = ws + n, *pp = ws + 2 * (size_t)n, *ap = ws + 3 * (size_t)n;
+  double* part = ws + 5 * (size_t)n;
+  double* st = part + 2 * PF_NODE_SLOTS;
+  int nbv = (n + 255) / 256;
+  if (nbv > PF_MAX_NODE_BLOCKS) nbv = PF_MAX_NODE_BLOCKS;
+  for (int it = 0; it < n_iter; ++it) {
+    if (p->mesh.dim == 2) hipLaunchKernelGGL(k_pcg_ap<2>, dim3(nb), dim3(256), 0, s, *p, st, pp, ap, part);
+    else hipLaunchKernelGGL(k_pcg_ap<1>, dim3(nb), dim3(256), 0, s, *p, st, pp, ap, part);
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nb, 1, 0.0);
+    pcg2_precondition(p, c, x, ws, 1, nullptr, s);
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, c->n_agg, 2, 0.0);
+    hipLaunchKernelGGL(k_pcg_dir, dim3(nbv), dim3(256), 0, s, st, n, z, pp);
+  }
+  PCG_CHECK("pf_pcg2_iterations");
+  return PF_OK;
+}
+
+int pf_pcg2_iterations(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, double* state_out,
+                       void* stream) {
+  if (!p || !coarse_ok(c, true) || !x || !ws || n_iter < 0) {
+    pf_set_error("pf_pcg2_iterations: bad argument");
+    return PF_ERR_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int rc = pcg2_enqueue(p, c, x, ws, n_iter, s);
+  if (rc != PF_OK) return rc;
+  return state_out ? pcg_read_state(ws, p->mesh.n_dofs, state_out, s) : PF_OK;
+}
+
+// n_iter iterations as ONE hipGraph: a single chain of 6 * n_iter kernel nodes, no parallel branches
+int pf_pcg2_graph_create(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, void* stream,
+                         void** graph_out) {
+  if (!p || !coarse_ok(c, true) || !x || !ws || n_iter < 1 || !graph_out) {
+    pf_set_error("pf_pcg2_graph_create: bad argument");
+    return PF_ERR_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+    pf_set_error("pf_pcg2_graph_create: hipStreamBeginCapture failed");
+    return PF_ERR_HIP;
+  }
+  const int rc = pcg2_enqueue(p, c, x, ws, n_iter, s);
+  const hipError_t e = hipStreamEndCapture(s, &graph);
+  if (rc != PF_OK || e != hipSuccess || !graph) {
+    if (graph) hipGraphDestroy(graph);
+    if (rc == PF_OK) pf_set_error("pf_pcg2_graph_create: capture failed");
+    return rc != PF_OK ? rc : PF_ERR_HIP;
+  }
+  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+    hipGraphDestroy(graph);
+    pf_set_error("pf_pcg2_graph_create: hipGraphInstantiate failed");
+    return PF_ERR_HIP;
+  }
+  hipGraphDestroy(graph);
+  *graph_out = (void*)exec;
+  return PF_OK;
+}
+
+int pf_pcg2_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
+  if (!p || !ws || !state_out) { pf_set_error("pf_pcg2_state: bad argument"); return PF_ERR_ARG; }
   return pcg_read_state(ws, p->mesh.n_dofs, state_out, (hipStream_t)stream);
 }
 

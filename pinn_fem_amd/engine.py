@@ -10,12 +10,14 @@ import contextlib
 import ctypes as C
 import functools
 import os
+import warnings
 from typing import List, Optional
 
 import numpy as np
 import torch
 
 from . import _capi
+from . import coarse as _coarse
 from ._capi import PfProblem, PfState, PinnFemHipError
 from .nets import FlatTheta, NetSpec, describe_module
 from .plan import HostPlan, build_host_plan
@@ -37,6 +39,28 @@ def _on_engine_stream(fn):
         with self.on_stream():
             return fn(self, *a, **k)
     return wrapper
+
+
+class DeviceCoarse:
+    """A coarse.CoarseSpace on the device and the pf_coarse record that points at it."""
+
+    def __init__(self, cs, device):
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        self.space = cs
+        self.node_agg, self.agg_off, self.zcoef = t(cs.node_agg), t(cs.agg_off), t(cs.zcoef)
+        self.agg_ptr, self.agg_nodes = t(cs.agg_ptr), t(cs.agg_nodes)
+        self.a_c = None                 # host copy of Z^T K Z as the device formed it
+        self.a_inv_host = None
+        self.a_inv = torch.zeros(max(cs.n_coarse, 1) ** 2, dtype=torch.float64, device=device)
+        R = self.record = _capi.PfCoarse()
+        R.n_agg, R.n_coarse = cs.n_agg, cs.n_coarse
+        R.node_agg, R.agg_off, R.zcoef = self.node_agg.data_ptr(), self.agg_off.data_ptr(), self.zcoef.data_ptr()
+        R.agg_ptr, R.agg_nodes, R.a_inv = self.agg_ptr.data_ptr(), self.agg_nodes.data_ptr(), self.a_inv.data_ptr()
+
+    def set_inverse(self, a_inv):
+        self.a_inv_host = np.ascontiguousarray(a_inv, dtype=np.float64)
+        if self.a_inv_host.size:
+            self.a_inv[: self.a_inv_host.size].copy_(torch.from_numpy(self.a_inv_host.reshape(-1)))
 
 
 class HipEngine:
@@ -179,6 +203,8 @@ class HipEngine:
         self.hist_rows = 0
         self.P = PfProblem()
         self._graph = None
+        self.pcg_iterations = 0         # CG iterations of every pcg_solve so far (tools/nr_scale.py reports them)
+        self._coarse_cache = None       # (key, DeviceCoarse | None): coarse space of the two-level CG preconditioner
         self._configured = False
         env_k = os.environ.get("PINNFEM_GRAPH_ITERS")
         self.GRAPH_ITERS = int(env_k) if env_k else (self.GRAPH_ITERS_LARGE if hp.n_elems >= 200_000 else self.GRAPH_ITERS)
@@ -505,16 +531,24 @@ class HipEngine:
         return out
 
     @_on_engine_stream
-    def pcg_solve(self, b: torch.Tensor, rtol: float = 1e-13, max_iter: Optional[int] = None, poll: int = 64):
-        """K_ff x = b by conjugate gradients with the diag(K_ff) preconditioner, float64, on the device.
-        Returns (x with zeros on fixed dofs, iterations, converged)."""
+    def pcg_solve(self, b: torch.Tensor, rtol: float = 1e-13, max_iter: Optional[int] = None, poll: int = 64,
+                  preconditioner: str = "jacobi", n_aggregates: Optional[int] = None, aggregates=None):
+        """K_ff x = b by conjugate gradients, float64, on the device.  preconditioner: "jacobi" (diag(K_ff), the
+        default) or "two-level" (Jacobi plus a coarse space of per-aggregate rigid-body modes, coarse.py;
+        n_aggregates strips along the longest axis, or the caller's own node -> aggregate map).
+        Returns (x with zeros on fixed dofs, iterations, converged, |r|^2, |b|^2)."""
+        coarse = None
+        if _coarse.check_preconditioner(preconditioner) == "two-level":
+            coarse = self.coarse_space(n_aggregates, aggregates)        # None: the coarse matrix could not be factored
+        fam = "pf_pcg" if coarse is None else "pf_pcg2"
+        lib, ref, s = self.lib, self._ref(), self._stream()
+        head = (ref,) if coarse is None else (ref, C.byref(coarse.record))
         n = self.plan.n_dofs
         bb = b.to(device=self.device, dtype=torch.float64).contiguous()
         x = torch.zeros(n, dtype=torch.float64, device=self.device)
-        ws = torch.zeros(int(self.lib.pf_pcg_workspace_count(self._ref())), dtype=torch.float64, device=self.device)
-        s = self._stream()
-        _capi.check(self.lib.pf_pcg_begin(self._ref(), bb.data_ptr(), x.data_ptr(), ws.data_ptr(), float(rtol), s),
-                    "pf_pcg_begin")
+        ws = torch.zeros(int(getattr(lib, fam + "_workspace_count")(ref)), dtype=torch.float64, device=self.device)
+        _capi.check(getattr(lib, fam + "_begin")(*head, bb.data_ptr(), x.data_ptr(), ws.data_ptr(), float(rtol), s),
+                    fam + "_begin")
         if max_iter is None:
             max_iter = 40 * n + 2000            # slender trusses are beam-like: CG needs far more than n steps
         st = (C.c_double * 4)()
@@ -522,25 +556,64 @@ class HipEngine:
         graph = C.c_void_p()
         use_graph = os.environ.get("PINNFEM_GRAPH", "1") != "0" and max_iter >= poll
         if use_graph:
-            _capi.check(self.lib.pf_pcg_graph_create(self._ref(), x.data_ptr(), ws.data_ptr(), int(poll), s,
-                                                     C.byref(graph)), "pf_pcg_graph_create")
+            _capi.check(getattr(lib, fam + "_graph_create")(*head, x.data_ptr(), ws.data_ptr(), int(poll), s,
+                                                            C.byref(graph)), fam + "_graph_create")
         try:
             while True:
                 k = min(poll, max_iter - done_it)
                 if use_graph and k == poll:
-                    _capi.check(self.lib.pf_graph_launch(graph, s), "pf_graph_launch")
-                    _capi.check(self.lib.pf_pcg_state(self._ref(), ws.data_ptr(), st, s), "pf_pcg_state")
+                    _capi.check(lib.pf_graph_launch(graph, s), "pf_graph_launch")
+                    _capi.check(getattr(lib, fam + "_state")(ref, ws.data_ptr(), st, s), fam + "_state")
                 else:
-                    _capi.check(self.lib.pf_pcg_iterations(self._ref(), x.data_ptr(), ws.data_ptr(), int(max(k, 0)), st, s),
-                                "pf_pcg_iterations")
+                    _capi.check(getattr(lib, fam + "_iterations")(*head, x.data_ptr(), ws.data_ptr(), int(max(k, 0)), st, s),
+                                fam + "_iterations")
                 done_it += max(k, 0)
                 if st[1] != 0.0 or done_it >= max_iter:
                     break
         finally:
             if graph:
-                self.lib.pf_graph_destroy(graph)
+                lib.pf_graph_destroy(graph)
+        self.pcg_iterations += int(st[0])
         converged = st[2] <= (rtol * rtol) * st[3] * 4.0 or st[3] == 0.0     # |r| <= 2 rtol |b|
         return x, int(st[0]), bool(converged), float(st[2]), float(st[3])
+
+    def _stiffness_signature(self):
+        """What the coarse matrix Z^T K Z was built from: the E and A that elem_s64 reads."""
+        sig = []
+        ne = max(self.plan.n_elems, 0)
+        for spec, buf in zip(self.specs, (self.prop_e, self.prop_a)):
+            sig.append(buf[:ne].cpu().numpy().tobytes() if spec.enabled else float(np.float32(spec.scale)))
+        return tuple(sig)
+
+    @_on_engine_stream
+    def coarse_space(self, n_aggregates: Optional[int] = None, aggregates=None):
+        """The two-level preconditioner's coarse space on the device (a DeviceCoarse), cached per engine and rebuilt
+        when the aggregation asked for or the element stiffness changes.  The device forms A_c = Z^T K Z
+        (pf_coarse_setup); the host factors it (Cholesky, float64) and uploads the explicit inverse.  Returns None,
+        with a RuntimeWarning, when A_c is not positive definite: the solve then runs with Jacobi alone."""
+        agg_key = None if aggregates is None else np.asarray(aggregates).astype(np.int64).tobytes()
+        key = (None if n_aggregates is None else int(n_aggregates), agg_key, self._stiffness_signature())
+        if self._coarse_cache is not None and self._coarse_cache[0] == key:
+            return self._coarse_cache[1]
+        hp = self.plan
+        if len(self.model.nodes) != hp.n_nodes:
+            raise NotImplementedError("the two-level preconditioner needs the engine's mesh to be the model's "
+                                      "(no sharded form)")
+        cs = _coarse.build_coarse_space(np.asarray(self.model.nodes, dtype=np.float64), hp.dim,
+                                        (hp.dof_flags & _capi.PF_DOF_FIXED) != 0, n_aggregates, aggregates)
+        dc = DeviceCoarse(cs, self.device)
+        a_c = torch.zeros(max(cs.n_coarse, 1) ** 2, dtype=torch.float64, device=self.device)
+        _capi.check(self.lib.pf_coarse_setup(self._ref(), C.byref(dc.record), a_c.data_ptr(), self._stream()),
+                    "pf_coarse_setup")
+        dc.a_c = a_c[: cs.n_coarse ** 2].cpu().numpy().reshape(cs.n_coarse, cs.n_coarse)
+        try:
+            dc.set_inverse(_coarse.coarse_inverse(dc.a_c))
+        except np.linalg.LinAlgError as e:
+            warnings.warn(f"two-level preconditioner: the coarse matrix Z^T K Z ({cs.n_coarse} x {cs.n_coarse}) could "
+                          f"not be factored ({e}); falling back to the Jacobi preconditioner", RuntimeWarning)
+            dc = None
+        self._coarse_cache = (key, dc)
+        return dc
 
     @_on_engine_stream
     def diag_k(self, lam: Optional[float] = None) -> torch.Tensor:

@@ -45,6 +45,10 @@ class SolverConfig:
     alpha_data: float = 100.0
     method: str = "auto"
     preconditioning: bool = False
+    # preconditioner of the CG solve inside solve_nr: "jacobi" (diag(K_ff)) or "two-level" (Jacobi plus a coarse space
+    # of per-aggregate rigid-body modes, pinn_fem_amd/coarse.py); nr_aggregates: number of aggregates (None: default)
+    nr_preconditioner: str = "jacobi"
+    nr_aggregates: Optional[int] = None
 
 
 @dataclass
@@ -316,7 +320,8 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     The reference assembles the dense float64 tangent (fem/assembly.py:16-75) and calls
     np.linalg.solve on K_ff; here K is applied matrix-free in float64 on the device (pf_kv_f64) and
     K_ff du = rhs is solved by conjugate gradients with the diag(K_ff) (Jacobi) preconditioner
-    (pf_pcg_*), so the solver no longer stops at the ~2*10^4 dofs a dense K allows.  Same loop, same
+    (pf_pcg_*) or, with config.nr_preconditioner = "two-level", Jacobi plus a coarse space of per-aggregate
+    rigid-body modes (pf_pcg2_*), so the solver no longer stops at the ~2*10^4 dofs a dense K allows.  Same loop, same
     stopping rule (|du| / max(|u|, min_denominator) <= tolerance), same history record; like the
     reference, u starts from zero whatever u_initial says (:443)."""
     config = config or SolverConfig()
@@ -337,7 +342,8 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     for ite in range(config.max_iterations):
         max_e = _max_abs_strain(model, u)
         rhs = f_ext - eng.kv_f64(u)
-        du, _, ok, rr, bb = eng.pcg_solve(rhs)
+        du, _, ok, rr, bb = eng.pcg_solve(rhs, preconditioner=config.nr_preconditioner,
+                                         n_aggregates=config.nr_aggregates)
         # np.linalg.solve either succeeds or raises on a singular matrix; CG shows singularity (or a hopeless
         # condition number for the Jacobi preconditioner) as a residual that does not come down at all.  An
         # inner solve that merely stops short of 1e-13 is fine: the Newton loop then acts as iterative refinement.
