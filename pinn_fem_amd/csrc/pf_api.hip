@@ -4,6 +4,7 @@
 #include <string.h>
 #include <stdio.h>
 #include "pf_common.h"
+#include "pf_graph.h"
 #include "pf_net32.h"
 
 // launchers from pf_mesh.hip
@@ -520,11 +521,7 @@ int pf_gd_iterations(const pf_problem* p, int n_iter, void* stream) {
 // The stop flag is read by every kernel at its start; a kernel of t+1 that misses a stop raised by finalize(t) only
 // rewrites scratch (properties, g_f, partial sums): everything that changes solver state (both Adam kernels, the next
 // finalize) is ordered behind finalize(t) and returns at once, so the final state is the reference's `break`.
-#define PF_CAP_EV 2
-struct pf_capture {
-  hipStream_t s, a;   // the captured stream and the side branch
-  hipEvent_t* ev;     // PF_CAP_EV per iteration: the last reader of u is done | gradu done
-};
+#define PF_CAP_EV 2   /* pf_capture.ev per iteration: the last reader of u is done | gradu done */
 
 // Does pf_problem.pad_index hold exactly what pf_pad_index_of computes (the layout pinn_fem_amd builds and INTEGRATION.md
 // describes: nets in order, pf_net_pad_index + pad_off)?  Then the forward launch's update prologue computes the index
@@ -623,51 +620,6 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
   PF_TRY(pf_launch_finalize(&q, 0, 0, s, tn_ready), "finalize");
   return PF_OK;
 }
-
-}  // extern "C"
-// capture fn(capture streams/events) on `s` (+ a side stream) and instantiate the graph
-template <class F>
-static int capture_graph(hipStream_t s, int nev, hipStreamCaptureMode mode, void** graph_out, F&& fn) {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  hipStream_t side = nullptr;
-  hipEvent_t* ev = new hipEvent_t[nev];
-  int made = 0;
-  bool ok = hipStreamCreateWithFlags(&side, hipStreamNonBlocking) == hipSuccess;
-  for (; ok && made < nev; ++made)
-    if (hipEventCreateWithFlags(&ev[made], hipEventDisableTiming) != hipSuccess) break;
-  ok = ok && made == nev;
-  auto cleanup = [&]() {
-    for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
-    delete[] ev;
-    if (side) (void)hipStreamDestroy(side);
-  };
-  if (!ok) {
-    cleanup();
-    return fail(PF_ERR_HIP, "graph capture: stream/event creation failed");
-  }
-  if (hipStreamBeginCapture(s, mode) != hipSuccess) {
-    cleanup();
-    return fail(PF_ERR_HIP, "hipStreamBeginCapture failed");
-  }
-  pf_capture cap{s, side, ev};
-  const int rc = fn(cap);
-  const hipError_t e = hipStreamEndCapture(s, &graph);
-  cleanup();
-  if (rc != PF_OK) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return rc;
-  }
-  if (e != hipSuccess || !graph) return fail(PF_ERR_HIP, "hipStreamEndCapture failed");
-  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-    (void)hipGraphDestroy(graph);
-    return fail(PF_ERR_HIP, "hipGraphInstantiate failed");
-  }
-  (void)hipGraphDestroy(graph);
-  *graph_out = (void*)exec;
-  return PF_OK;
-}
-extern "C" {
 
 int pf_graph_create(const pf_problem* p, int iters_per_graph, void* stream, void** graph_out) {
   return pf_graph_create_ex(p, iters_per_graph, 0, stream, graph_out);

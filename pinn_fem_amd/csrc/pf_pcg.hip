@@ -9,7 +9,9 @@
 // and columns dropped).  The element stiffness is ((double)E*(double)A)/(double)l0 with E, A from the
 // per-element property arrays when a net is enabled, else the scalar value.  Sums over a node's elements
 // run in ascending element id (no atomics: the same owner-computes gather as pf_mesh.hip).
+#include <stdio.h>
 #include "pf_common.h"
+#include "pf_graph.h"
 
 namespace {
 
@@ -373,121 +375,134 @@ __global__ __launch_bounds__(256) void k_pcg2_rz0(double* st, const double* __re
 
 }  // namespace
 
-#define PCG_CHECK(what)                                                      \
-  if (hipGetLastError() != hipSuccess) { pf_set_error(what ": HIP launch failed"); return PF_ERR_HIP; }
+// ---- host side ------------------------------------------------------------------------------------------------------
+// One implementation behind two exported families: pf_pcg_* (Jacobi) and pf_pcg2_* (two-level) are argument checks in
+// front of pcg_begin_impl / pcg_iterations_impl / pcg_graph_impl / pcg_state_impl, which take the coarse space as a
+// nullable `c` (NULL = Jacobi) and the exported function's name as `who`, the prefix of every error message.  The
+// workspace layout is stated once, in pcg_layout; the iteration's launch sequence once, in pcg_enqueue; the CG graphs
+// are captured by the library's capture_graph (pf_graph.h) as a single chain.
+#define PCG_CHECK(who) \
+  if (hipGetLastError() != hipSuccess) return pcg_fail(PF_ERR_HIP, who, "HIP launch failed");
+
+// `launches` once for the mesh's dimension, with DIM a compile-time constant
+#define PCG_FOR_DIM(p, launches)                                 \
+  do {                                                           \
+    if ((p)->mesh.dim == 2) { constexpr int DIM = 2; launches; } \
+    else { constexpr int DIM = 1; launches; }                    \
+  } while (0)
+
+static int pcg_fail(int code, const char* who, const char* what) {
+  char buf[160];
+  snprintf(buf, sizeof(buf), "%s: %s", who, what);
+  pf_set_error(buf);
+  return code;
+}
+
+// The CG workspace, in doubles: r | z | p | ap | dinv (n_dofs each) | partials (2 * PF_NODE_SLOTS) | state (ST_COUNT) |
+// w = Z^T r | y = A^-1 w (PF_COARSE_MAX each).  The Jacobi solve's workspace ends at w, the two-level solve's at end.
+// T = double*: the parts of a workspace; T = long long: their offsets, i.e. the counts
+template <class T>
+struct PcgLayout { T r, z, p, ap, dinv, part, st, w, y, end; };
+using PcgWs = PcgLayout<double*>;
+
+template <class T>
+static PcgLayout<T> pcg_layout(T base, int n_dofs) {
+  const long long n = n_dofs;
+  PcgLayout<T> L;
+  L.r = base; L.z = L.r + n; L.p = L.z + n; L.ap = L.p + n; L.dinv = L.ap + n; L.part = L.dinv + n;
+  L.st = L.part + 2 * PF_NODE_SLOTS; L.w = L.st + ST_COUNT; L.y = L.w + PF_COARSE_MAX; L.end = L.y + PF_COARSE_MAX;
+  return L;
+}
+
+static long long pcg_ws_count(const pf_problem* p, bool two_level) {
+  if (!p) return PF_ERR_ARG;
+  const PcgLayout<long long> L = pcg_layout(0LL, p->mesh.n_dofs);
+  return two_level ? L.end : L.w;
+}
 
 extern "C" {
 
-long long pf_pcg_workspace_count(const pf_problem* p) {
-  if (!p) return PF_ERR_ARG;
-  return 5LL * p->mesh.n_dofs + 2LL * PF_NODE_SLOTS + ST_COUNT;   // r, z, p, ap, dinv | partials | state
-}
-
 int pf_kv_f64(const pf_problem* p, const double* v, double* out, int zero_fixed, void* stream) {
-  if (!p || !v || !out) { pf_set_error("pf_kv_f64: null argument"); return PF_ERR_ARG; }
+  if (!p || !v || !out) return pcg_fail(PF_ERR_ARG, "pf_kv_f64", "null argument");
   const int nb = pf_node_blocks(p->mesh.n_nodes);
-  hipStream_t s = (hipStream_t)stream;
-  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_kv64<2>, dim3(nb), dim3(256), 0, s, *p, v, out, zero_fixed);
-  else hipLaunchKernelGGL(k_kv64<1>, dim3(nb), dim3(256), 0, s, *p, v, out, zero_fixed);
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_kv64<DIM>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, v, out, zero_fixed));
   PCG_CHECK("pf_kv_f64");
   return PF_OK;
 }
 
-// ws layout (doubles): r | z | p | ap | dinv (n_dofs each) | partials (2*PF_NODE_SLOTS) | state (16)
-int pf_pcg_begin(const pf_problem* p, const double* b, double* x, double* ws, double rtol, void* stream) {
-  if (!p || !b || !x || !ws || !(rtol >= 0.0)) { pf_set_error("pf_pcg_begin: bad argument"); return PF_ERR_ARG; }
-  const int n = p->mesh.n_dofs, nb = pf_node_blocks(p->mesh.n_nodes);
-  double *r = ws, *z = ws + n, *pp = ws + 2 * (size_t)n, *dinv = ws + 4 * (size_t)n;
-  double* part = ws + 5 * (size_t)n;
-  double* st = part + 2 * PF_NODE_SLOTS;
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(st, 0, ST_COUNT * sizeof(double), s) != hipSuccess) {
-    pf_set_error("pf_pcg_begin: state setup failed");
-    return PF_ERR_HIP;
+static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x, const PcgWs& L, int update, double* p_init,
+                              hipStream_t s);   // (with the two-level preconditioner's own code, below)
+
+// x = 0, r = b, dinv, |b|^2 and the b = 0 exit; two-level: then z = M^-1 r, p = z and r.z over the Jacobi start
+static int pcg_begin_impl(const pf_problem* p, const pf_coarse* c, const double* b, double* x, double* ws, double rtol,
+                          hipStream_t s, const char* who) {
+  if (!p || !b || !x || !ws || !(rtol >= 0.0)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
+  const PcgWs L = pcg_layout(ws, p->mesh.n_dofs);
+  const int nb = pf_node_blocks(p->mesh.n_nodes);
+  if (hipMemsetAsync(L.st, 0, ((c ? L.end : L.w) - L.st) * sizeof(double), s) != hipSuccess)
+    return pcg_fail(PF_ERR_HIP, who, "state setup failed");
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_init<DIM>, dim3(nb), dim3(256), 0, s, *p, b, x, L.r, L.z, L.p, L.dinv, L.part));
+  PCG_CHECK(who);
+  hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, L.st, L.part, nb, 0, rtol * rtol);   // by value: no copy, no sync
+  if (c) {
+    pcg2_precondition(p, c, x, L, 0, L.p, s);
+    hipLaunchKernelGGL(k_pcg2_rz0, dim3(1), dim3(256), 0, s, L.st, L.part, c->n_agg);
   }
-  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_pcg_init<2>, dim3(nb), dim3(256), 0, s, *p, b, x, r, z, pp, dinv, part);
-  else hipLaunchKernelGGL(k_pcg_init<1>, dim3(nb), dim3(256), 0, s, *p, b, x, r, z, pp, dinv, part);
-  PCG_CHECK("pf_pcg_begin");
-  hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nb, 0, rtol * rtol);   // by value: no copy, no sync
-  PCG_CHECK("pf_pcg_begin");
+  PCG_CHECK(who);
   return PF_OK;
 }
 
-static int pcg_enqueue(const pf_problem* p, double* x, double* ws, int n_iter, hipStream_t s) {
+// n_iter CG iterations (no-ops once the stop test |r| <= rtol |b| fired).  The preconditioner step is k_pcg_update
+// (one block per 256 dofs) or restrict + apply (one block per aggregate); phase 2 sums that step's partials
+static int pcg_enqueue(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, hipStream_t s,
+                       const char* who) {
   const int n = p->mesh.n_dofs, nb = pf_node_blocks(p->mesh.n_nodes);
-  double *r = ws, *z = ws + n, *pp = ws + 2 * (size_t)n, *ap = ws + 3 * (size_t)n, *dinv = ws + 4 * (size_t)n;
-  double* part = ws + 5 * (size_t)n;
-  double* st = part + 2 * PF_NODE_SLOTS;
+  const PcgWs L = pcg_layout(ws, n);
   int nbv = (n + 255) / 256;
   if (nbv > PF_MAX_NODE_BLOCKS) nbv = PF_MAX_NODE_BLOCKS;
   for (int it = 0; it < n_iter; ++it) {
-    if (p->mesh.dim == 2) hipLaunchKernelGGL(k_pcg_ap<2>, dim3(nb), dim3(256), 0, s, *p, st, pp, ap, part);
-    else hipLaunchKernelGGL(k_pcg_ap<1>, dim3(nb), dim3(256), 0, s, *p, st, pp, ap, part);
-    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nb, 1, 0.0);
-    hipLaunchKernelGGL(k_pcg_update, dim3(nbv), dim3(256), 0, s, st, n, x, r, z, pp, ap, dinv, part);
-    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nbv, 2, 0.0);
-    hipLaunchKernelGGL(k_pcg_dir, dim3(nbv), dim3(256), 0, s, st, n, z, pp);
+    PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_ap<DIM>, dim3(nb), dim3(256), 0, s, *p, L.st, L.p, L.ap, L.part));
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, L.st, L.part, nb, 1, 0.0);
+    if (c) pcg2_precondition(p, c, x, L, 1, nullptr, s);
+    else hipLaunchKernelGGL(k_pcg_update, dim3(nbv), dim3(256), 0, s, L.st, n, x, L.r, L.z, L.p, L.ap, L.dinv, L.part);
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, L.st, L.part, c ? c->n_agg : nbv, 2, 0.0);
+    hipLaunchKernelGGL(k_pcg_dir, dim3(nbv), dim3(256), 0, s, L.st, n, L.z, L.p);
   }
-  PCG_CHECK("pf_pcg_iterations");
-  return PF_OK;
-}
-
-static int pcg_read_state(double* ws, int n, double* state_out, hipStream_t s) {
-  double* st = ws + 5 * (size_t)n + 2 * PF_NODE_SLOTS;
-  double h[ST_COUNT];
-  if (hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-    pf_set_error("pf_pcg: state read-back failed");
-    return PF_ERR_HIP;
-  }
-  state_out[0] = h[ST_ITERS]; state_out[1] = h[ST_DONE]; state_out[2] = h[ST_RR]; state_out[3] = h[ST_BB];
-  return PF_OK;
-}
-
-// n_iter CG iterations (no-ops once the stop test |r| <= rtol |b| fired); state_out (host, may be NULL)
-// receives [iterations, done, |r|^2, |b|^2] after a stream synchronisation
-int pf_pcg_iterations(const pf_problem* p, double* x, double* ws, int n_iter, double* state_out, void* stream) {
-  if (!p || !x || !ws || n_iter < 0) { pf_set_error("pf_pcg_iterations: bad argument"); return PF_ERR_ARG; }
-  hipStream_t s = (hipStream_t)stream;
-  int rc = pcg_enqueue(p, x, ws, n_iter, s);
-  if (rc != PF_OK) return rc;
-  return state_out ? pcg_read_state(ws, p->mesh.n_dofs, state_out, s) : PF_OK;
-}
-
-// the same n_iter iterations as ONE hipGraph (record and pointers baked in; handle for pf_graph_launch /
-// pf_graph_destroy): 5 tiny launches per CG iteration are launch bound when issued one by one
-int pf_pcg_graph_create(const pf_problem* p, double* x, double* ws, int n_iter, void* stream, void** graph_out) {
-  if (!p || !x || !ws || n_iter < 1 || !graph_out) { pf_set_error("pf_pcg_graph_create: bad argument"); return PF_ERR_ARG; }
-  hipStream_t s = (hipStream_t)stream;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    pf_set_error("pf_pcg_graph_create: hipStreamBeginCapture failed");
-    return PF_ERR_HIP;
-  }
-  const int rc = pcg_enqueue(p, x, ws, n_iter, s);
-  const hipError_t e = hipStreamEndCapture(s, &graph);
-  if (rc != PF_OK || e != hipSuccess || !graph) {
-    if (graph) hipGraphDestroy(graph);
-    if (rc == PF_OK) pf_set_error("pf_pcg_graph_create: capture failed");
-    return rc != PF_OK ? rc : PF_ERR_HIP;
-  }
-  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-    hipGraphDestroy(graph);
-    pf_set_error("pf_pcg_graph_create: hipGraphInstantiate failed");
-    return PF_ERR_HIP;
-  }
-  hipGraphDestroy(graph);
-  *graph_out = (void*)exec;
+  PCG_CHECK(who);
   return PF_OK;
 }
 
 // [iterations, stopped, |r|^2, |b|^2] of the running solve (synchronises the stream)
-int pf_pcg_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
-  if (!p || !ws || !state_out) { pf_set_error("pf_pcg_state: bad argument"); return PF_ERR_ARG; }
-  return pcg_read_state(ws, p->mesh.n_dofs, state_out, (hipStream_t)stream);
+static int pcg_state_impl(const pf_problem* p, double* ws, double* state_out, hipStream_t s, const char* who) {
+  if (!p || !ws || !state_out) return pcg_fail(PF_ERR_ARG, who, "bad argument");
+  double h[ST_COUNT];
+  if (hipMemcpyAsync(h, pcg_layout(ws, p->mesh.n_dofs).st, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return pcg_fail(PF_ERR_HIP, who, "state read-back failed");
+  state_out[0] = h[ST_ITERS]; state_out[1] = h[ST_DONE]; state_out[2] = h[ST_RR]; state_out[3] = h[ST_BB];
+  return PF_OK;
 }
 
-// ---- two-level preconditioner ---------------------------------------------------------------------------------------
+// state_out (host, may be NULL) receives the state after a stream synchronisation
+static int pcg_iterations_impl(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter,
+                               double* state_out, hipStream_t s, const char* who) {
+  if (!p || !x || !ws || n_iter < 0) return pcg_fail(PF_ERR_ARG, who, "bad argument");
+  const int rc = pcg_enqueue(p, c, x, ws, n_iter, s, who);
+  if (rc != PF_OK) return rc;
+  return state_out ? pcg_state_impl(p, ws, state_out, s, who) : PF_OK;
+}
+
+// the same n_iter iterations as ONE hipGraph (record and pointers baked in; handle for pf_graph_launch /
+// pf_graph_destroy): 5 or 6 tiny launches per CG iteration are launch bound when issued one by one.  A single chain of
+// kernel nodes, no parallel branches: no events, no side stream
+static int pcg_graph_impl(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, hipStream_t s,
+                          void** graph_out, const char* who) {
+  if (!p || !x || !ws || n_iter < 1 || !graph_out) return pcg_fail(PF_ERR_ARG, who, "bad argument");
+  return capture_graph(s, 0, hipStreamCaptureModeThreadLocal, graph_out,
+                       [&](pf_capture& cap) { return pcg_enqueue(p, c, x, ws, n_iter, cap.s, who); });
+}
+
+// ---- the two-level preconditioner's own code ----------------------------------------------------------------------
 static bool coarse_ok(const pf_coarse* c, bool need_inverse) {
   return c && c->n_agg >= 1 && c->n_agg <= PF_COARSE_MAX_AGG && c->n_coarse >= 0 &&
          c->n_coarse <= PF_COARSE_MODES * c->n_agg && c->node_agg && c->agg_off && c->zcoef && c->agg_ptr &&
@@ -495,128 +510,64 @@ static bool coarse_ok(const pf_coarse* c, bool need_inverse) {
 }
 
 int pf_coarse_setup(const pf_problem* p, const pf_coarse* c, double* a_c_out, void* stream) {
-  if (!p || !coarse_ok(c, false) || !a_c_out) { pf_set_error("pf_coarse_setup: bad argument"); return PF_ERR_ARG; }
+  if (!p || !coarse_ok(c, false) || !a_c_out) return pcg_fail(PF_ERR_ARG, "pf_coarse_setup", "bad argument");
   hipStream_t s = (hipStream_t)stream;
   if (c->n_coarse == 0) return PF_OK;
-  if (hipMemsetAsync(a_c_out, 0, (size_t)c->n_coarse * c->n_coarse * sizeof(double), s) != hipSuccess) {
-    pf_set_error("pf_coarse_setup: clearing the coarse matrix failed");
-    return PF_ERR_HIP;
-  }
-  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_coarse_setup<2>, dim3(c->n_agg), dim3(256), 0, s, *p, *c, a_c_out);
-  else hipLaunchKernelGGL(k_coarse_setup<1>, dim3(c->n_agg), dim3(256), 0, s, *p, *c, a_c_out);
+  if (hipMemsetAsync(a_c_out, 0, (size_t)c->n_coarse * c->n_coarse * sizeof(double), s) != hipSuccess)
+    return pcg_fail(PF_ERR_HIP, "pf_coarse_setup", "clearing the coarse matrix failed");
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_coarse_setup<DIM>, dim3(c->n_agg), dim3(256), 0, s, *p, *c, a_c_out));
   PCG_CHECK("pf_coarse_setup");
   return PF_OK;
 }
 
-long long pf_pcg2_workspace_count(const pf_problem* p) {
-  if (!p) return PF_ERR_ARG;
-  return pf_pcg_workspace_count(p) + 2LL * PF_COARSE_MAX;        // ... | w = Z^T r | y = A^-1 w
-}
-
 // z = M^-1 r and r.z for the r in the workspace: restriction, then coarse solve + prolongation (two launches)
-static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int update, double* p_init,
+static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x, const PcgWs& L, int update, double* p_init,
                               hipStream_t s) {
-  const size_t n = (size_t)p->mesh.n_dofs;
-  double *r = ws, *z = ws + n, *pp = ws + 2 * n, *ap = ws + 3 * n, *dinv = ws + 4 * n;
-  double* part = ws + 5 * n;
-  double* st = part + 2 * PF_NODE_SLOTS;
-  double *w = st + ST_COUNT, *y = w + PF_COARSE_MAX;
-  if (p->mesh.dim == 2) {
-    hipLaunchKernelGGL(k_pcg2_restrict<2>, dim3(c->n_agg), dim3(256), 0, s, *c, st, update, x, r, pp, ap, w, part);
-    hipLaunchKernelGGL(k_pcg2_apply<2>, dim3(c->n_agg), dim3(256), 0, s, *c, st, r, dinv, w, y, z, p_init, part);
-  } else {
-    hipLaunchKernelGGL(k_pcg2_restrict<1>, dim3(c->n_agg), dim3(256), 0, s, *c, st, update, x, r, pp, ap, w, part);
-    hipLaunchKernelGGL(k_pcg2_apply<1>, dim3(c->n_agg), dim3(256), 0, s, *c, st, r, dinv, w, y, z, p_init, part);
-  }
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg2_restrict<DIM>, dim3(c->n_agg), dim3(256), 0, s, *c, L.st, update, x, L.r, L.p,
+                                    L.ap, L.w, L.part);
+              hipLaunchKernelGGL(k_pcg2_apply<DIM>, dim3(c->n_agg), dim3(256), 0, s, *c, L.st, L.r, L.dinv, L.w, L.y, L.z,
+                                 p_init, L.part));
 }
 
+// ---- the exported families -----------------------------------------------------------------------------------------
+long long pf_pcg_workspace_count(const pf_problem* p) { return pcg_ws_count(p, false); }
+long long pf_pcg2_workspace_count(const pf_problem* p) { return pcg_ws_count(p, true); }
+
+int pf_pcg_begin(const pf_problem* p, const double* b, double* x, double* ws, double rtol, void* stream) {
+  return pcg_begin_impl(p, nullptr, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg_begin");
+}
 int pf_pcg2_begin(const pf_problem* p, const pf_coarse* c, const double* b, double* x, double* ws, double rtol,
                   void* stream) {
-  if (!p || !coarse_ok(c, true) || !b || !x || !ws || !(rtol >= 0.0)) {
-    pf_set_error("pf_pcg2_begin: bad argument");
-    return PF_ERR_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n = (size_t)p->mesh.n_dofs;
-  double* st = ws + 5 * n + 2 * PF_NODE_SLOTS;
-  if (hipMemsetAsync(st, 0, (ST_COUNT + 2 * PF_COARSE_MAX) * sizeof(double), s) != hipSuccess) {
-    pf_set_error("pf_pcg2_begin: state setup failed");
-    return PF_ERR_HIP;
-  }
-  // the Jacobi start (x = 0, r = b, dinv, |b|^2, the b = 0 exit), then z = M^-1 r, p = z and r.z over it
-  const int rc = pf_pcg_begin(p, b, x, ws, rtol, stream);
-  if (rc != PF_OK) return rc;
-  pcg2_precondition(p, c, x, ws, 0, ws + 2 * n, s);
-  hipLaunchKernelGGL(k_pcg2_rz0, dim3(1), dim3(256), 0, s, st, ws + 5 * n, c->n_agg);
-  PCG_CHECK("pf_pcg2_begin");
-  return PF_OK;
+  const char* who = "pf_pcg2_begin";
+  if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
+  return pcg_begin_impl(p, c, b, x, ws, rtol, (hipStream_t)stream, who);
 }
 
-static int pcg2_enqueue(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, hipStream_t s) {
-  const int n = p->mesh.n_dofs, nb = pf_node_blocks(p->mesh.n_nodes);
-  double *z = ws + n, *pp = ws + 2 * (size_t)n, *ap = ws + 3 * (size_t)n;
-  double* part = ws + 5 * (size_t)n;
-  double* st = part + 2 * PF_NODE_SLOTS;
-  int nbv = (n + 255) / 256;
-  if (nbv > PF_MAX_NODE_BLOCKS) nbv = PF_MAX_NODE_BLOCKS;
-  for (int it = 0; it < n_iter; ++it) {
-    if (p->mesh.dim == 2) hipLaunchKernelGGL(k_pcg_ap<2>, dim3(nb), dim3(256), 0, s, *p, st, pp, ap, part);
-    else hipLaunchKernelGGL(k_pcg_ap<1>, dim3(nb), dim3(256), 0, s, *p, st, pp, ap, part);
-    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, nb, 1, 0.0);
-    pcg2_precondition(p, c, x, ws, 1, nullptr, s);
-    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, st, part, c->n_agg, 2, 0.0);
-    hipLaunchKernelGGL(k_pcg_dir, dim3(nbv), dim3(256), 0, s, st, n, z, pp);
-  }
-  PCG_CHECK("pf_pcg2_iterations");
-  return PF_OK;
+int pf_pcg_iterations(const pf_problem* p, double* x, double* ws, int n_iter, double* state_out, void* stream) {
+  return pcg_iterations_impl(p, nullptr, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg_iterations");
 }
-
 int pf_pcg2_iterations(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, double* state_out,
                        void* stream) {
-  if (!p || !coarse_ok(c, true) || !x || !ws || n_iter < 0) {
-    pf_set_error("pf_pcg2_iterations: bad argument");
-    return PF_ERR_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  int rc = pcg2_enqueue(p, c, x, ws, n_iter, s);
-  if (rc != PF_OK) return rc;
-  return state_out ? pcg_read_state(ws, p->mesh.n_dofs, state_out, s) : PF_OK;
+  const char* who = "pf_pcg2_iterations";
+  if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
+  return pcg_iterations_impl(p, c, x, ws, n_iter, state_out, (hipStream_t)stream, who);
 }
 
-// n_iter iterations as ONE hipGraph: a single chain of 6 * n_iter kernel nodes, no parallel branches
+int pf_pcg_graph_create(const pf_problem* p, double* x, double* ws, int n_iter, void* stream, void** graph_out) {
+  return pcg_graph_impl(p, nullptr, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg_graph_create");
+}
 int pf_pcg2_graph_create(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, void* stream,
                          void** graph_out) {
-  if (!p || !coarse_ok(c, true) || !x || !ws || n_iter < 1 || !graph_out) {
-    pf_set_error("pf_pcg2_graph_create: bad argument");
-    return PF_ERR_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    pf_set_error("pf_pcg2_graph_create: hipStreamBeginCapture failed");
-    return PF_ERR_HIP;
-  }
-  const int rc = pcg2_enqueue(p, c, x, ws, n_iter, s);
-  const hipError_t e = hipStreamEndCapture(s, &graph);
-  if (rc != PF_OK || e != hipSuccess || !graph) {
-    if (graph) hipGraphDestroy(graph);
-    if (rc == PF_OK) pf_set_error("pf_pcg2_graph_create: capture failed");
-    return rc != PF_OK ? rc : PF_ERR_HIP;
-  }
-  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-    hipGraphDestroy(graph);
-    pf_set_error("pf_pcg2_graph_create: hipGraphInstantiate failed");
-    return PF_ERR_HIP;
-  }
-  hipGraphDestroy(graph);
-  *graph_out = (void*)exec;
-  return PF_OK;
+  const char* who = "pf_pcg2_graph_create";
+  if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
+  return pcg_graph_impl(p, c, x, ws, n_iter, (hipStream_t)stream, graph_out, who);
 }
 
+int pf_pcg_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
+  return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcg_state");
+}
 int pf_pcg2_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
-  if (!p || !ws || !state_out) { pf_set_error("pf_pcg2_state: bad argument"); return PF_ERR_ARG; }
-  return pcg_read_state(ws, p->mesh.n_dofs, state_out, (hipStream_t)stream);
+  return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcg2_state");
 }
 
 }  // extern "C"
