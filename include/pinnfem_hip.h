@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 8
+#define PF_ABI_VERSION 9
 
 /* error codes */
 #define PF_OK 0
@@ -214,7 +214,7 @@ int pf_padded_width(int width);
 int pf_net_pad_count(int in_dim, int width, int n_hidden);
 /* padded-image index (inside the net's image) of the net's `local`-th torch parameter */
 int pf_net_pad_index(int in_dim, int width, int n_hidden, int local);
-/* sizeof of the ABI structs: 0 pf_mesh, 1 pf_net, 2 pf_state, 3 pf_problem, 4 pf_scalar_id, 5 pf_coarse (binding self-check) */
+/* sizeof of the ABI structs: 0 pf_mesh, 1 pf_net, 2 pf_state, 3 pf_problem, 4 pf_scalar_id, 5 pf_coarse, 6 pf_gl (binding self-check) */
 int pf_sizeof(int what);
 /* floats of operand-image workspace (pf_problem.net_op) one net needs with the MFMA32 engine, or <0 */
 int pf_net_op_count(int in_dim, int width, int n_hidden);
@@ -425,6 +425,39 @@ int pf_pcg2_iterations(const pf_problem* p, const pf_coarse* c, double* x, doubl
 int pf_pcg2_graph_create(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, void* stream,
                          void** graph_out);
 int pf_pcg2_state(const pf_problem* p, double* ws, double* state_out, void* stream);
+
+/* ---- large displacements: the Green-Lagrange truss element and its tangent operator (pf_nl.hip, pf_pcg.hip) -----------
+ * Total-Lagrangian element in float64, per element with nodes i, j:  d0 = X_j - X_i,  du = u_j - u_i,  d = d0 + du,
+ *   e  = (2 d0.du + du.du) / (2 l0^2)        (not (l^2 - l0^2) / (2 l0^2): that form cancels at small strain)
+ *   N  = E*A * e                             E*A as pf_kv_f64 forms it (per-element properties if a net is enabled)
+ *   fe = (N / l0) d                          f_int[j] += fe, f_int[i] -= fe
+ *   B  = (E*A / l0^3) d d^T + (N / l0) I     K_t v: row j += B (v_j - v_i), row i -= B (v_j - v_i)
+ * 1-D: d, fe and B are scalars.  At u = 0, B is the linear element block s*(c2, cs; cs, s2).  This is the consistent
+ * element of the virtual-work derivation, not the reference's truss2d_element_state (fem/element.py:105-133), whose force
+ * has the other sign and no 1/l0 and whose stiffness lacks the geometric term.  All arrays dev, caller-owned. */
+typedef struct pf_gl {
+  const double* d0;   /* [n_elems][dim] X_j - X_i in float64, from the model's float64 coordinates (not from the f32 egeo) */
+  double* kt;         /* [n_elems][3] = B11, B12, B22   (1-D: [n_elems]) */
+  double* fe;         /* [n_elems][dim] */
+  double* strain;     /* [n_elems] e */
+} pf_gl;
+/* kt, fe and strain of every element at the displacements u (dev double [n_dofs]); one element per thread */
+int pf_gl_state(const pf_problem* p, const pf_gl* g, const double* u, void* stream);
+/* f_int_out (dev double [n_dofs], every row) = the node gather of +-g->fe, ascending element id, no atomics */
+int pf_gl_fint(const pf_problem* p, const pf_gl* g, double* f_int_out, void* stream);
+/* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */
+int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream);
+/* as pf_pcg_begin / pf_pcg_iterations / pf_pcg_graph_create / pf_pcg_state on K_t: the same kernels, workspace
+ * (pf_pcg_workspace_count), stop test and single-chain graph, the Jacobi preconditioner from kt's diagonal.  kt is read
+ * when the launches RUN, so a graph stays valid while pf_gl_state overwrites kt in place between solves.  A null kt is
+ * PF_ERR_ARG from every one of them, never a silent linear solve.  CG needs K_t positive definite on the free dofs: the
+ * caller checks rhs.du > 0.  There is no two-level form (its coarse matrix would change with every Newton iteration). */
+int pf_pcgt_begin(const pf_problem* p, const double* kt, const double* b, double* x, double* ws, double rtol, void* stream);
+int pf_pcgt_iterations(const pf_problem* p, const double* kt, double* x, double* ws, int n_iter, double* state_out,
+                       void* stream);
+int pf_pcgt_graph_create(const pf_problem* p, const double* kt, double* x, double* ws, int n_iter, void* stream,
+                         void** graph_out);
+int pf_pcgt_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream);
 
 /* ---- scalar (E, A) identification: the device loop of pinn_inverse_problem_gd -------------------------------------
  * FEM/python/api_pinn_gradient_descent.py:102-121 calls pinn_inverse_problem_gd(nodes, elements, f_ext, fixed_dofs,

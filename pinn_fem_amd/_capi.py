@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PINNFEM_LIB: another build of the same library (experiment builds, A/B runs); no fallback of any kind
 LIB_PATH = os.environ.get("PINNFEM_LIB") or os.path.join(_HERE, "lib", "libpinnfem_hip.so")
 
-PF_ABI_VERSION = 8
+PF_ABI_VERSION = 9
 PF_OK, PF_ERR_ARG, PF_ERR_UNSUPPORTED, PF_ERR_HIP = 0, -1, -2, -3
 PF_DOF_FIXED, PF_DOF_MEASURED, PF_DOF_SHARED, PF_DOF_GHOST = 1, 2, 4, 8
 PF_WG_SHUFFLE, PF_WG_MFMA, PF_WG_MFMA44, PF_WG_MFMA32 = 0, 1, 2, 3
@@ -109,9 +109,14 @@ class PfCoarse(C.Structure):
     ]
 
 
+class PfGl(C.Structure):
+    _fields_ = [("d0", C.c_void_p), ("kt", C.c_void_p), ("fe", C.c_void_p), ("strain", C.c_void_p)]
+
+
 # every symbol include/pinnfem_hip.h declares: name -> (restype, argtypes)
 _PP = C.POINTER(PfProblem)
 _PC = C.POINTER(PfCoarse)
+_PG = C.POINTER(PfGl)
 SYMBOLS = {
     "pf_abi_version": (C.c_int, []),
     "pf_last_error": (C.c_char_p, []),
@@ -160,6 +165,13 @@ SYMBOLS = {
     "pf_pcg2_iterations": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "pf_pcg2_graph_create": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "pf_pcg2_state": (C.c_int, [_PP, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "pf_gl_state": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p]),
+    "pf_gl_fint": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p]),
+    "pf_kt_v_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_pcgt_begin": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "pf_pcgt_iterations": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
+    "pf_pcgt_graph_create": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pf_pcgt_state": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "pf_comm_unique_id": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pf_comm_create": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pf_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -221,7 +233,7 @@ def load():
         fn.argtypes = args
     if lib.pf_abi_version() != PF_ABI_VERSION:
         raise PinnFemHipError("libpinnfem_hip.so ABI version mismatch; rebuild the library")
-    for idx, st in enumerate((PfMesh, PfNet, PfState, PfProblem, PfScalarId, PfCoarse)):
+    for idx, st in enumerate((PfMesh, PfNet, PfState, PfProblem, PfScalarId, PfCoarse, PfGl)):
         if lib.pf_sizeof(idx) != C.sizeof(st):
             raise PinnFemHipError(
                 f"struct layout mismatch for {st.__name__}: C {lib.pf_sizeof(idx)} vs ctypes {C.sizeof(st)}")

@@ -21,7 +21,7 @@ import torch
 from ..coarse import check_preconditioner
 from ..fem.model import FEMModel, Material
 from ..fem.properties import NNProperty
-from ..fem.solver import SolverConfig, solve
+from ..fem.solver import SolverConfig, check_kinematics, solve
 from ..nets import SimpleNN
 
 logger = None
@@ -80,7 +80,9 @@ def parse_problem(problem_file):
     #           "fe_mode": "reference"|"delta",       element-force formulation
     #           "mlp_dtype": "f32"|"bf16",            precision of the MLP matrix products (bf16 study)
     #           "nr_preconditioner": "jacobi"|"two-level",  preconditioner of the CG solve inside Newton-Raphson
-    #           "nr_aggregates": N}                   aggregates of the two-level coarse space (default: by mesh size)
+    #           "nr_aggregates": N,                   aggregates of the two-level coarse space (default: by mesh size)
+    #           "kinematics": "linear"|"green-lagrange"}  element of Newton-Raphson: small displacements (default) or the
+    #                                                 total-Lagrangian large-displacement truss (Jacobi only)
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -207,7 +209,8 @@ def _solver_config_from(data):
         preconditioning=pc.get("preconditioning", sc.get("preconditioning", False)),
         method=method,
         nr_preconditioner=check_preconditioner(accel.get("nr_preconditioner", "jacobi")),
-        nr_aggregates=None if accel.get("nr_aggregates") is None else int(accel["nr_aggregates"]))
+        nr_aggregates=None if accel.get("nr_aggregates") is None else int(accel["nr_aggregates"]),
+        kinematics=check_kinematics(accel.get("kinematics", "linear"), accel.get("nr_preconditioner", "jacobi")))
 
 
 def _parse_synthetic_chain(data, accel, chain):

@@ -273,6 +273,7 @@ int pf_sizeof(int what) {
     case 3: return (int)sizeof(pf_problem);
     case 4: return (int)sizeof(pf_scalar_id);
     case 5: return (int)sizeof(pf_coarse);
+    case 6: return (int)sizeof(pf_gl);
   }
   return PF_ERR_ARG;
 }

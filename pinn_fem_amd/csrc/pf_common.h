@@ -227,6 +227,14 @@ __device__ __forceinline__ float elem_stiffness(const pf_problem& P, int e, floa
   return (E * A) / l0;  // nn_assembly.py:74 (2-D), :37 (1-D)
 }
 
+// E*A of an element in float64, for the float64 Newton-Raphson kernels (pf_pcg.hip, pf_nl.hip): the float32 properties
+// widened, one float64 product
+__device__ __forceinline__ double elem_ea64(const pf_problem& P, int e) {
+  const double E = P.net[0].enabled ? (double)P.prop_e[e] : (double)P.net[0].scale;
+  const double A = P.net[1].enabled ? (double)P.prop_a[e] : (double)P.net[1].scale;
+  return E * A;
+}
+
 // The three distinct entries of an element's stiffness matrix ke = s * pattern (nn_assembly.py:74, 84-94): s*c2, s*cs,
 // s*s2 (1-D: s in c2).  The MFMA32 forward pass writes them per element (pf_problem.elem_k: 12 B, or 4 B in 1-D), so the
 // node kernels read ONE record per incidence instead of the geometry (16 B) and the stiffness (4 B); without the record

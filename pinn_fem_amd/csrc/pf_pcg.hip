@@ -9,6 +9,11 @@
 // and columns dropped).  The element stiffness is ((double)E*(double)A)/(double)l0 with E, A from the
 // per-element property arrays when a net is enabled, else the scalar value.  Sums over a node's elements
 // run in ascending element id (no atomics: the same owner-computes gather as pf_mesh.hip).
+//
+// The operator has a second form: with a non-null `kt` (double [n_elems][3] = B11, B12, B22; 1-D [n_elems]) the element
+// block is read from it instead of being formed as s*(c2, cs, s2).  That is the tangent of the Green-Lagrange element
+// (pf_nl.hip: pf_gl_state writes kt), served by the same kernels: pf_kt_v_f64 and pf_pcgt_*.  kt == NULL is the linear
+// operator, arithmetic unchanged.
 #include <stdio.h>
 #include "pf_common.h"
 #include "pf_graph.h"
@@ -18,15 +23,14 @@ namespace {
 enum { ST_RZ = 0, ST_PAP, ST_RR, ST_BB, ST_ALPHA, ST_BETA, ST_DONE, ST_ITERS, ST_RTOL2, ST_RZ_NEW, ST_COUNT = 16 };
 
 __device__ __forceinline__ double elem_s64(const pf_problem& P, int e, float l0) {
-  const double E = P.net[0].enabled ? (double)P.prop_e[e] : (double)P.net[0].scale;
-  const double A = P.net[1].enabled ? (double)P.prop_a[e] : (double)P.net[1].scale;
-  return (E * A) / (double)l0;
+  return elem_ea64(P, e) / (double)l0;
 }
 
-// (K v)[node] and diag(K)[node] in one pass over the node's elements
+// (K v)[node] and diag(K)[node] in one pass over the node's elements; kt != NULL: the element blocks are kt's (the same
+// decision in every thread of the launch)
 template <int DIM>
-__device__ __forceinline__ void gather64(const pf_problem& P, const double* __restrict__ v, int node,
-                                         double* kv, double* diag) {
+__device__ __forceinline__ void gather64(const pf_problem& P, const double* __restrict__ kt, const double* __restrict__ v,
+                                         int node, double* kv, double* diag) {
   const pf_mesh& M = P.mesh;
 #pragma unroll
   for (int c = 0; c < DIM; ++c) { kv[c] = 0.0; diag[c] = 0.0; }
@@ -34,9 +38,24 @@ __device__ __forceinline__ void gather64(const pf_problem& P, const double* __re
     const int code = M.adj[idx];
     const int e = code >> 1, end = code & 1;
     const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
+    const double sg = end ? -1.0 : 1.0;
+    if (kt) {
+      if (DIM == 2) {
+        const double dx = v ? v[2 * nn.y] - v[2 * nn.x] : 0.0, dy = v ? v[2 * nn.y + 1] - v[2 * nn.x + 1] : 0.0;
+        const double b11 = kt[3 * (size_t)e], b12 = kt[3 * (size_t)e + 1], b22 = kt[3 * (size_t)e + 2];
+        kv[0] += -sg * (b11 * dx + b12 * dy);
+        kv[1] += -sg * (b12 * dx + b22 * dy);
+        diag[0] += b11;
+        diag[1] += b22;
+      } else {
+        const double dx = v ? v[nn.y] - v[nn.x] : 0.0;
+        kv[0] += -sg * (kt[e] * dx);
+        diag[0] += kt[e];
+      }
+      continue;
+    }
     const ElemGeo g = load_geo(M.egeo, e);
     const double s = elem_s64(P, e, g.l0);
-    const double sg = end ? -1.0 : 1.0;
     if (DIM == 2) {
       const double dx = v ? v[2 * nn.y] - v[2 * nn.x] : 0.0, dy = v ? v[2 * nn.y + 1] - v[2 * nn.x + 1] : 0.0;
       // rows of s*pattern @ [v_i; v_j] for this end: -(sg*s) * (c2*dx + cs*dy), -(sg*s) * (cs*dx + s2*dy)
@@ -53,12 +72,12 @@ __device__ __forceinline__ void gather64(const pf_problem& P, const double* __re
 }
 
 template <int DIM>
-__global__ __launch_bounds__(256) void k_kv64(pf_problem P, const double* __restrict__ v, double* __restrict__ out,
-                                              int zero_fixed) {
+__global__ __launch_bounds__(256) void k_kv64(pf_problem P, const double* __restrict__ kt, const double* __restrict__ v,
+                                              double* __restrict__ out, int zero_fixed) {
   const pf_mesh& M = P.mesh;
   for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < M.n_nodes; node += gridDim.x * blockDim.x) {
     double kv[2], dg[2];
-    gather64<DIM>(P, v, node, kv, dg);
+    gather64<DIM>(P, kt, v, node, kv, dg);
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
       const int dof = node * DIM + c;
@@ -81,14 +100,14 @@ __device__ __forceinline__ double block_sum64(double v, double* smem) {
 
 // x = 0, r = b (free dofs), dinv = 1/diag(K_ff), z = dinv*r, p = z; partials of r.z and b.b
 template <int DIM>
-__global__ __launch_bounds__(256) void k_pcg_init(pf_problem P, const double* __restrict__ b, double* x, double* r,
-                                                  double* z, double* p, double* dinv, double* part) {
+__global__ __launch_bounds__(256) void k_pcg_init(pf_problem P, const double* __restrict__ kt, const double* __restrict__ b,
+                                                  double* x, double* r, double* z, double* p, double* dinv, double* part) {
   __shared__ double red[8];
   const pf_mesh& M = P.mesh;
   double rz = 0.0, bb = 0.0;
   for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < M.n_nodes; node += gridDim.x * blockDim.x) {
     double kv[2], dg[2];
-    gather64<DIM>(P, nullptr, node, kv, dg);
+    gather64<DIM>(P, kt, nullptr, node, kv, dg);
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
       const int dof = node * DIM + c;
@@ -107,15 +126,15 @@ __global__ __launch_bounds__(256) void k_pcg_init(pf_problem P, const double* __
 
 // ap = K p (fixed rows zero); partial p.ap
 template <int DIM>
-__global__ __launch_bounds__(256) void k_pcg_ap(pf_problem P, const double* __restrict__ st, const double* __restrict__ p,
-                                                double* __restrict__ ap, double* part) {
+__global__ __launch_bounds__(256) void k_pcg_ap(pf_problem P, const double* __restrict__ kt, const double* __restrict__ st,
+                                                const double* __restrict__ p, double* __restrict__ ap, double* part) {
   if (st[ST_DONE] != 0.0) return;
   __shared__ double red[8];
   const pf_mesh& M = P.mesh;
   double pap = 0.0;
   for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < M.n_nodes; node += gridDim.x * blockDim.x) {
     double kv[2], dg[2];
-    gather64<DIM>(P, p, node, kv, dg);
+    gather64<DIM>(P, kt, p, node, kv, dg);
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
       const int dof = node * DIM + c;
@@ -376,9 +395,10 @@ __global__ __launch_bounds__(256) void k_pcg2_rz0(double* st, const double* __re
 }  // namespace
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// One implementation behind two exported families: pf_pcg_* (Jacobi) and pf_pcg2_* (two-level) are argument checks in
-// front of pcg_begin_impl / pcg_iterations_impl / pcg_graph_impl / pcg_state_impl, which take the coarse space as a
-// nullable `c` (NULL = Jacobi) and the exported function's name as `who`, the prefix of every error message.  The
+// One implementation behind three exported families: pf_pcg_* (Jacobi), pf_pcg2_* (two-level) and pf_pcgt_* (Jacobi on
+// the tangent operator) are argument checks in front of pcg_begin_impl / pcg_iterations_impl / pcg_graph_impl /
+// pcg_state_impl, which take the coarse space as a nullable `c` (NULL = Jacobi), the tangent blocks as a nullable `kt`
+// (NULL = the linear operator) and the exported function's name as `who`, the prefix of every error message.  The
 // workspace layout is stated once, in pcg_layout; the iteration's launch sequence once, in pcg_enqueue; the CG graphs
 // are captured by the library's capture_graph (pf_graph.h) as a single chain.
 #define PCG_CHECK(who) \
@@ -422,11 +442,12 @@ static long long pcg_ws_count(const pf_problem* p, bool two_level) {
 
 extern "C" {
 
-int pf_kv_f64(const pf_problem* p, const double* v, double* out, int zero_fixed, void* stream) {
-  if (!p || !v || !out) return pcg_fail(PF_ERR_ARG, "pf_kv_f64", "null argument");
+static int kv_impl(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, hipStream_t s,
+                   const char* who) {
+  if (!p || !v || !out) return pcg_fail(PF_ERR_ARG, who, "null argument");
   const int nb = pf_node_blocks(p->mesh.n_nodes);
-  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_kv64<DIM>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, v, out, zero_fixed));
-  PCG_CHECK("pf_kv_f64");
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_kv64<DIM>, dim3(nb), dim3(256), 0, s, *p, kt, v, out, zero_fixed));
+  PCG_CHECK(who);
   return PF_OK;
 }
 
@@ -434,14 +455,14 @@ static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x
                               hipStream_t s);   // (with the two-level preconditioner's own code, below)
 
 // x = 0, r = b, dinv, |b|^2 and the b = 0 exit; two-level: then z = M^-1 r, p = z and r.z over the Jacobi start
-static int pcg_begin_impl(const pf_problem* p, const pf_coarse* c, const double* b, double* x, double* ws, double rtol,
-                          hipStream_t s, const char* who) {
+static int pcg_begin_impl(const pf_problem* p, const pf_coarse* c, const double* kt, const double* b, double* x, double* ws,
+                          double rtol, hipStream_t s, const char* who) {
   if (!p || !b || !x || !ws || !(rtol >= 0.0)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
   const PcgWs L = pcg_layout(ws, p->mesh.n_dofs);
   const int nb = pf_node_blocks(p->mesh.n_nodes);
   if (hipMemsetAsync(L.st, 0, ((c ? L.end : L.w) - L.st) * sizeof(double), s) != hipSuccess)
     return pcg_fail(PF_ERR_HIP, who, "state setup failed");
-  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_init<DIM>, dim3(nb), dim3(256), 0, s, *p, b, x, L.r, L.z, L.p, L.dinv, L.part));
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_init<DIM>, dim3(nb), dim3(256), 0, s, *p, kt, b, x, L.r, L.z, L.p, L.dinv, L.part));
   PCG_CHECK(who);
   hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, L.st, L.part, nb, 0, rtol * rtol);   // by value: no copy, no sync
   if (c) {
@@ -454,14 +475,14 @@ static int pcg_begin_impl(const pf_problem* p, const pf_coarse* c, const double*
 
 // n_iter CG iterations (no-ops once the stop test |r| <= rtol |b| fired).  The preconditioner step is k_pcg_update
 // (one block per 256 dofs) or restrict + apply (one block per aggregate); phase 2 sums that step's partials
-static int pcg_enqueue(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, hipStream_t s,
-                       const char* who) {
+static int pcg_enqueue(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
+                       hipStream_t s, const char* who) {
   const int n = p->mesh.n_dofs, nb = pf_node_blocks(p->mesh.n_nodes);
   const PcgWs L = pcg_layout(ws, n);
   int nbv = (n + 255) / 256;
   if (nbv > PF_MAX_NODE_BLOCKS) nbv = PF_MAX_NODE_BLOCKS;
   for (int it = 0; it < n_iter; ++it) {
-    PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_ap<DIM>, dim3(nb), dim3(256), 0, s, *p, L.st, L.p, L.ap, L.part));
+    PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_ap<DIM>, dim3(nb), dim3(256), 0, s, *p, kt, L.st, L.p, L.ap, L.part));
     hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, L.st, L.part, nb, 1, 0.0);
     if (c) pcg2_precondition(p, c, x, L, 1, nullptr, s);
     else hipLaunchKernelGGL(k_pcg_update, dim3(nbv), dim3(256), 0, s, L.st, n, x, L.r, L.z, L.p, L.ap, L.dinv, L.part);
@@ -484,10 +505,10 @@ static int pcg_state_impl(const pf_problem* p, double* ws, double* state_out, hi
 }
 
 // state_out (host, may be NULL) receives the state after a stream synchronisation
-static int pcg_iterations_impl(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter,
+static int pcg_iterations_impl(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
                                double* state_out, hipStream_t s, const char* who) {
   if (!p || !x || !ws || n_iter < 0) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  const int rc = pcg_enqueue(p, c, x, ws, n_iter, s, who);
+  const int rc = pcg_enqueue(p, c, kt, x, ws, n_iter, s, who);
   if (rc != PF_OK) return rc;
   return state_out ? pcg_state_impl(p, ws, state_out, s, who) : PF_OK;
 }
@@ -495,11 +516,11 @@ static int pcg_iterations_impl(const pf_problem* p, const pf_coarse* c, double* 
 // the same n_iter iterations as ONE hipGraph (record and pointers baked in; handle for pf_graph_launch /
 // pf_graph_destroy): 5 or 6 tiny launches per CG iteration are launch bound when issued one by one.  A single chain of
 // kernel nodes, no parallel branches: no events, no side stream
-static int pcg_graph_impl(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, hipStream_t s,
-                          void** graph_out, const char* who) {
+static int pcg_graph_impl(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
+                          hipStream_t s, void** graph_out, const char* who) {
   if (!p || !x || !ws || n_iter < 1 || !graph_out) return pcg_fail(PF_ERR_ARG, who, "bad argument");
   return capture_graph(s, 0, hipStreamCaptureModeThreadLocal, graph_out,
-                       [&](pf_capture& cap) { return pcg_enqueue(p, c, x, ws, n_iter, cap.s, who); });
+                       [&](pf_capture& cap) { return pcg_enqueue(p, c, kt, x, ws, n_iter, cap.s, who); });
 }
 
 // ---- the two-level preconditioner's own code ----------------------------------------------------------------------
@@ -530,37 +551,64 @@ static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x
 }
 
 // ---- the exported families -----------------------------------------------------------------------------------------
+// pf_pcgt_*: a null kt is an error here, never a silent linear solve
+#define PCGT_NEED_KT(who) \
+  if (!kt) return pcg_fail(PF_ERR_ARG, who, "null tangent (kt)");
+
 long long pf_pcg_workspace_count(const pf_problem* p) { return pcg_ws_count(p, false); }
 long long pf_pcg2_workspace_count(const pf_problem* p) { return pcg_ws_count(p, true); }
 
+int pf_kv_f64(const pf_problem* p, const double* v, double* out, int zero_fixed, void* stream) {
+  return kv_impl(p, nullptr, v, out, zero_fixed, (hipStream_t)stream, "pf_kv_f64");
+}
+int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream) {
+  PCGT_NEED_KT("pf_kt_v_f64");
+  return kv_impl(p, kt, v, out, zero_fixed, (hipStream_t)stream, "pf_kt_v_f64");
+}
+
 int pf_pcg_begin(const pf_problem* p, const double* b, double* x, double* ws, double rtol, void* stream) {
-  return pcg_begin_impl(p, nullptr, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg_begin");
+  return pcg_begin_impl(p, nullptr, nullptr, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg_begin");
 }
 int pf_pcg2_begin(const pf_problem* p, const pf_coarse* c, const double* b, double* x, double* ws, double rtol,
                   void* stream) {
   const char* who = "pf_pcg2_begin";
   if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  return pcg_begin_impl(p, c, b, x, ws, rtol, (hipStream_t)stream, who);
+  return pcg_begin_impl(p, c, nullptr, b, x, ws, rtol, (hipStream_t)stream, who);
+}
+int pf_pcgt_begin(const pf_problem* p, const double* kt, const double* b, double* x, double* ws, double rtol,
+                  void* stream) {
+  PCGT_NEED_KT("pf_pcgt_begin");
+  return pcg_begin_impl(p, nullptr, kt, b, x, ws, rtol, (hipStream_t)stream, "pf_pcgt_begin");
 }
 
 int pf_pcg_iterations(const pf_problem* p, double* x, double* ws, int n_iter, double* state_out, void* stream) {
-  return pcg_iterations_impl(p, nullptr, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg_iterations");
+  return pcg_iterations_impl(p, nullptr, nullptr, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg_iterations");
 }
 int pf_pcg2_iterations(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, double* state_out,
                        void* stream) {
   const char* who = "pf_pcg2_iterations";
   if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  return pcg_iterations_impl(p, c, x, ws, n_iter, state_out, (hipStream_t)stream, who);
+  return pcg_iterations_impl(p, c, nullptr, x, ws, n_iter, state_out, (hipStream_t)stream, who);
+}
+int pf_pcgt_iterations(const pf_problem* p, const double* kt, double* x, double* ws, int n_iter, double* state_out,
+                       void* stream) {
+  PCGT_NEED_KT("pf_pcgt_iterations");
+  return pcg_iterations_impl(p, nullptr, kt, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcgt_iterations");
 }
 
 int pf_pcg_graph_create(const pf_problem* p, double* x, double* ws, int n_iter, void* stream, void** graph_out) {
-  return pcg_graph_impl(p, nullptr, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg_graph_create");
+  return pcg_graph_impl(p, nullptr, nullptr, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg_graph_create");
 }
 int pf_pcg2_graph_create(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, void* stream,
                          void** graph_out) {
   const char* who = "pf_pcg2_graph_create";
   if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  return pcg_graph_impl(p, c, x, ws, n_iter, (hipStream_t)stream, graph_out, who);
+  return pcg_graph_impl(p, c, nullptr, x, ws, n_iter, (hipStream_t)stream, graph_out, who);
+}
+int pf_pcgt_graph_create(const pf_problem* p, const double* kt, double* x, double* ws, int n_iter, void* stream,
+                         void** graph_out) {
+  PCGT_NEED_KT("pf_pcgt_graph_create");
+  return pcg_graph_impl(p, nullptr, kt, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcgt_graph_create");
 }
 
 int pf_pcg_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
@@ -568,6 +616,10 @@ int pf_pcg_state(const pf_problem* p, double* ws, double* state_out, void* strea
 }
 int pf_pcg2_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
   return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcg2_state");
+}
+int pf_pcgt_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream) {
+  PCGT_NEED_KT("pf_pcgt_state");
+  return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcgt_state");
 }
 
 }  // extern "C"

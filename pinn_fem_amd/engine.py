@@ -205,6 +205,7 @@ class HipEngine:
         self._graph = None
         self.pcg_iterations = 0         # CG iterations of every pcg_solve so far (tools/nr_scale.py reports them)
         self._coarse_cache = None       # (key, DeviceCoarse | None): coarse space of the two-level CG preconditioner
+        self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
         self._configured = False
         env_k = os.environ.get("PINNFEM_GRAPH_ITERS")
         self.GRAPH_ITERS = int(env_k) if env_k else (self.GRAPH_ITERS_LARGE if hp.n_elems >= 200_000 else self.GRAPH_ITERS)
@@ -530,23 +531,90 @@ class HipEngine:
                     "pf_kv_f64")
         return out
 
+    # ---- large displacements: the Green-Lagrange element (pf_nl.hip) and its tangent operator --------------------
+    def _gl_buffers(self):
+        """(d0, kt, fe, strain, pf_gl record), allocated on first use.  d0 = X_j - X_i comes from the model's float64
+        coordinates, not from the plan's float32 geometry."""
+        if self._gl is None:
+            hp = self.plan
+            if len(self.model.nodes) != hp.n_nodes:
+                raise ValueError("the Green-Lagrange element needs the engine's mesh to be the model's "
+                                 "(no sharded form)")
+            nodes = np.asarray(self.model.nodes, dtype=np.float64).reshape(hp.n_nodes, hp.dim)
+            conn = np.asarray(hp.conn, dtype=np.int64).reshape(-1, 2)
+            ne = max(hp.n_elems, 1)
+            d0 = torch.zeros(ne * hp.dim, dtype=torch.float64, device=self.device)
+            if hp.n_elems:
+                d0[: hp.n_elems * hp.dim] = torch.from_numpy(
+                    np.ascontiguousarray(nodes[conn[:, 1]] - nodes[conn[:, 0]]).reshape(-1)).to(self.device)
+            f64 = dict(dtype=torch.float64, device=self.device)
+            kt = torch.zeros(ne * (3 if hp.dim == 2 else 1), **f64)
+            fe, strain = torch.zeros(ne * hp.dim, **f64), torch.zeros(ne, **f64)
+            rec = _capi.PfGl()
+            rec.d0, rec.kt, rec.fe, rec.strain = d0.data_ptr(), kt.data_ptr(), fe.data_ptr(), strain.data_ptr()
+            self._gl = (d0, kt, fe, strain, rec)
+        return self._gl
+
+    @_on_engine_stream
+    def gl_state(self, u: torch.Tensor) -> torch.Tensor:
+        """Green-Lagrange strain, element force and tangent block of every element at the displacements u (float64,
+        pf_gl_state); they stay on the device for gl_fint, kt_v_f64 and pcg_solve(tangent=True).  Returns the strains
+        [n_elems] (the engine's buffer: the next gl_state overwrites it)."""
+        uu = u.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)
+        if uu.numel() != self.plan.n_dofs:
+            raise ValueError(f"gl_state: u has {uu.numel()} entries, the mesh has {self.plan.n_dofs} dofs")
+        rec = self._gl_buffers()[4]
+        _capi.check(self.lib.pf_gl_state(self._ref(), C.byref(rec), uu.data_ptr(), self._stream()), "pf_gl_state")
+        return self._gl[3][: self.plan.n_elems]
+
+    def _gl_ready(self, who):
+        if self._gl is None:
+            raise RuntimeError(f"{who}: no Green-Lagrange state yet; call gl_state(u) first")
+        return self._gl
+
+    @_on_engine_stream
+    def gl_fint(self) -> torch.Tensor:
+        """f_int(u) [n_dofs, every row] of the last gl_state (pf_gl_fint)."""
+        rec = self._gl_ready("gl_fint")[4]
+        out = torch.empty(self.plan.n_dofs, dtype=torch.float64, device=self.device)
+        _capi.check(self.lib.pf_gl_fint(self._ref(), C.byref(rec), out.data_ptr(), self._stream()), "pf_gl_fint")
+        return out
+
+    @_on_engine_stream
+    def kt_v_f64(self, v: torch.Tensor, zero_fixed: bool = False) -> torch.Tensor:
+        """K_t(u) v in float64 with the tangent blocks of the last gl_state (pf_kt_v_f64)."""
+        kt = self._gl_ready("kt_v_f64")[1]
+        vv = v.to(device=self.device, dtype=torch.float64).contiguous()
+        out = torch.empty(self.plan.n_dofs, dtype=torch.float64, device=self.device)
+        _capi.check(self.lib.pf_kt_v_f64(self._ref(), kt.data_ptr(), vv.data_ptr(), out.data_ptr(), int(zero_fixed),
+                                         self._stream()), "pf_kt_v_f64")
+        return out
+
     @_on_engine_stream
     def pcg_solve(self, b: torch.Tensor, rtol: float = 1e-13, max_iter: Optional[int] = None, poll: int = 64,
-                  preconditioner: str = "jacobi", n_aggregates: Optional[int] = None, aggregates=None):
+                  preconditioner: str = "jacobi", n_aggregates: Optional[int] = None, aggregates=None,
+                  tangent: bool = False):
         """K_ff x = b by conjugate gradients, float64, on the device.  preconditioner: "jacobi" (diag(K_ff), the
         default) or "two-level" (Jacobi plus a coarse space of per-aggregate rigid-body modes, coarse.py;
-        n_aggregates strips along the longest axis, or the caller's own node -> aggregate map).
+        n_aggregates strips along the longest axis, or the caller's own node -> aggregate map).  tangent: K is the
+        tangent K_t(u) of the last gl_state (pf_pcgt_*; Jacobi only, and K_t must be positive definite).
         Returns (x with zeros on fixed dofs, iterations, converged, |r|^2, |b|^2)."""
         coarse = None
         if _coarse.check_preconditioner(preconditioner) == "two-level":
+            if tangent:
+                raise ValueError("the two-level preconditioner has no tangent-operator form; use preconditioner='jacobi' "
+                                 "with tangent=True")
             coarse = self.coarse_space(n_aggregates, aggregates)        # None: the coarse matrix could not be factored
-        fam = "pf_pcg" if coarse is None else "pf_pcg2"
+        fam = "pf_pcgt" if tangent else ("pf_pcg" if coarse is None else "pf_pcg2")
         lib, ref, s = self.lib, self._ref(), self._stream()
         head = (ref,) if coarse is None else (ref, C.byref(coarse.record))
+        if tangent:
+            head = (ref, self._gl_ready("pcg_solve(tangent=True)")[1].data_ptr())
         n = self.plan.n_dofs
         bb = b.to(device=self.device, dtype=torch.float64).contiguous()
         x = torch.zeros(n, dtype=torch.float64, device=self.device)
-        ws = torch.zeros(int(getattr(lib, fam + "_workspace_count")(ref)), dtype=torch.float64, device=self.device)
+        ws_count = lib.pf_pcg2_workspace_count if fam == "pf_pcg2" else lib.pf_pcg_workspace_count
+        ws = torch.zeros(int(ws_count(ref)), dtype=torch.float64, device=self.device)
         _capi.check(getattr(lib, fam + "_begin")(*head, bb.data_ptr(), x.data_ptr(), ws.data_ptr(), float(rtol), s),
                     fam + "_begin")
         if max_iter is None:
@@ -563,7 +631,8 @@ class HipEngine:
                 k = min(poll, max_iter - done_it)
                 if use_graph and k == poll:
                     _capi.check(lib.pf_graph_launch(graph, s), "pf_graph_launch")
-                    _capi.check(getattr(lib, fam + "_state")(ref, ws.data_ptr(), st, s), fam + "_state")
+                    _capi.check(getattr(lib, fam + "_state")(*(head if tangent else (ref,)), ws.data_ptr(), st, s),
+                                fam + "_state")
                 else:
                     _capi.check(getattr(lib, fam + "_iterations")(*head, x.data_ptr(), ws.data_ptr(), int(max(k, 0)), st, s),
                                 fam + "_iterations")

@@ -2,9 +2,11 @@
 """solve_nr (matrix-free float64 K v + preconditioned CG on the device) on Warren girders of growing size; for the
 smaller ones also the oracle's dense float64 restatement of the reference (np.linalg.solve) on the host.
 
-    nr_scale.py [--preconditioner jacobi|two-level] [--aggregates N] [panels ...]
+    nr_scale.py [--preconditioner jacobi|two-level] [--aggregates N] [--kinematics linear|green-lagrange] [panels ...]
 
-The timed solve includes the two-level preconditioner's setup (coarse space, Z^T K Z, its inverse)."""
+The timed solve includes the two-level preconditioner's setup (coarse space, Z^T K Z, its inverse).  With
+--kinematics green-lagrange the same girders run the large-displacement element (Jacobi only; the dense comparison is
+of the linear problem and is left out)."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,23 +19,32 @@ import torch
 ap = argparse.ArgumentParser()
 ap.add_argument("--preconditioner", default="jacobi", choices=["jacobi", "two-level"])
 ap.add_argument("--aggregates", type=int, default=None)
+ap.add_argument("--kinematics", default="linear", choices=["linear", "green-lagrange"])
 ap.add_argument("panels", nargs="*", type=int)
 args = ap.parse_args()
 rows = []
 for panels in args.panels or [100, 1000, 5000]:
     nodes, el, loads, fixed, mv, md = warren_mesh(panels)
     model = FEMModel(nodes=nodes, elements=el, material=Material(2.0, 0.5, 1.0), loads=loads, fixed_dofs=fixed, dimension=2)
-    cfg = SolverConfig(max_iterations=10, tolerance=1e-10, nr_preconditioner=args.preconditioner, nr_aggregates=args.aggregates)
+    # green-lagrange: the unit loads would fold a girder of E*A = 1 up; scale them so that the midspan sags about a
+    # hundredth of the span (beam theory: 5 q L^4 / (384 EI), EI = E*A*height^2 / 2 = 0.5).  An estimate: that this load
+    # keeps the tangent positive definite and the Newton loop inside 25 iterations is what the run itself shows (the row
+    # reports `converged`; a non-SPD state raises)
+    green_lagrange = args.kinematics == "green-lagrange"
+    lam = (panels / 100.0) * 384.0 * 0.5 / (5.0 * float(panels) ** 4) if green_lagrange else 1.0
+    cfg = SolverConfig(max_iterations=25 if green_lagrange else 10, tolerance=1e-10,
+                       nr_preconditioner=args.preconditioner, nr_aggregates=args.aggregates, kinematics=args.kinematics)
     if panels <= 100:                                        # warm-up (library load, allocator) on a model of its own
         solve_nr(FEMModel(nodes=nodes, elements=el, material=Material(2.0, 0.5, 1.0), loads=loads, fixed_dofs=fixed, dimension=2),
-                 cfg, 1.0)
+                 cfg, lam)
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    res = solve_nr(model, cfg, 1.0)
+    res = solve_nr(model, cfg, lam)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     row = {"panels": panels, "elements": len(el), "dofs": 2 * len(nodes), "preconditioner": args.preconditioner,
+           "kinematics": args.kinematics, "load_factor": lam,
            "hip_seconds": dt, "converged": bool(res.converged), "nr_iterations": res.history[-1]["iterations"],
            "cg_iterations": model._pf_engine_cache[1].pcg_iterations}
-    if 2 * len(nodes) <= 4100:
+    if 2 * len(nodes) <= 4100 and args.kinematics == "linear":
         from oracle import pinn_oracle as orc
         pb = orc.Problem(nodes=nodes, elements=el, loads=loads, fixed_dofs=fixed, dimension=2, young=2.0, area=0.5, density=1.0)
         t0 = time.perf_counter(); ref = orc.solve_nr(pb, orc.SolverConfig(max_iterations=10, tolerance=1e-10), 1.0)
