@@ -188,7 +188,10 @@ typedef struct pf_problem {
    * iteration t (pf_node_gradu + Adam) WRITE the other vector than the one the residual and the element adjoint of t
    * read, so the update runs beside the whole backward launch instead of behind the adjoint's last read of u; the
    * vectors swap roles every iteration, an even number of iterations per replay ends in p->u, and a replay cut short by
-   * the stop test copies the result home (state->u_half). */
+   * the stop test copies the result home (state->u_half).
+   * In the path form of the graph (pf_graph_form_info: PF_GRAPH_FORM_FOLDED_RESIDUAL; it needs u_alt) the vector is
+   * SCRATCH instead: every iteration of a replay overwrites it with the residual r (0 at fixed dofs), which the
+   * theta-stage-1 launch re-sums.  Do not keep anything in it across a replay. */
   float* u_alt;
   /* per CSR entry of mesh.adj: the node at the OTHER end of that element ([adj_ptr[n_nodes]] int32).  With it the node
    * kernels fetch a neighbour's values one dependent load earlier (adj -> value instead of adj -> conn -> value) and
@@ -232,6 +235,18 @@ long long pf_partials_count(const pf_problem* p);
 #define PF_FUSED_U_PINGPONG 8
 #define PF_FUSED_U_UPDATE 16
 int pf_fusion_info(const pf_problem* p);
+/* the form of this problem's iteration graph beyond pf_fusion_info (bit mask).  PF_GRAPH_FORM_FOLDED_RESIDUAL: the mesh is an
+ * open path in element order (every node touches at most element e-1 at its j end and element e at its i end; node ids
+ * arbitrary — a bar, a synthetic chain) on a problem of the PF_FUSED_U_UPDATE one-chain form with PF_FUSED_BACKWARD and
+ * PF_FUSED_THETA_UPDATE and u_alt present: the graph then has no residual launch.  The fused backward launch forms r and g_f
+ * itself, the loss sums and the previous iteration's bookkeeping ride in the theta-stage-1 launch: three launches per
+ * iteration, same bits.  Further conditions: both nets at most 24 wide (the register buckets whose fused backward runs its
+ * phases without a barrier), mesh.dim == in_dim - 1, no interface dofs; with mesh.dim == 2 mesh.dof_flags must be 2-byte
+ * aligned (a node's two flags are read as one 16-bit load).  Wider nets keep the four-launch chain.  u_alt is scratch in this
+ * form (see pf_problem.u_alt).  Eager launches and the building blocks are not affected.  The query inspects the mesh on the
+ * device (one small launch and a 4-byte copy; synchronous), as pf_graph_create does. */
+#define PF_GRAPH_FORM_FOLDED_RESIDUAL 1
+int pf_graph_form_info(const pf_problem* p);
 
 /* ---- building blocks (each replaces the cited reference lines) ------------------------ */
 /* torch-layout theta -> padded image (no reference analogue; internal layout change) */
@@ -277,8 +292,9 @@ int pf_gd_iterations(const pf_problem* p, int n_iter, void* stream);
  * pf_problem record by value: create it after the record is final (one per solve_gd call) and destroy
  * it before changing any field.  *graph_out is an opaque handle owned by the caller.  iters_per_graph >= 1.
  * In every form the bookkeeping of iteration t (pf_finalize's work) runs as one extra block of the residual launch of
- * t+1, reading the other half of the residual's partial sums (part_half); the last iteration of a replay gets a
- * stand-alone pf_finalize.  The form (pf_fusion_info reports it):
+ * t+1 (on a path mesh, pf_graph_form_info: of the theta-stage-1 launch of t+1), reading the other half of the residual's
+ * partial sums (part_half); the last iteration of a replay gets a stand-alone pf_finalize.  The form (pf_fusion_info
+ * reports it):
  *  - ONE CHAIN where the forward launch carries the displacement update of the previous iteration (PF_FUSED_U_UPDATE:
  *    MFMA32 engine, both nets enabled with equal depths, elem_k, adj_other and prop_double present, one GPU), at any
  *    size; and below 2e5 elements otherwise, with grad_u + Adam(u) as a stand-alone launch on the chain.
@@ -286,9 +302,9 @@ int pf_gd_iterations(const pf_problem* p, int n_iter, void* stream);
  *    runs on a side branch beside the backward launches.  With u_alt and an even iters_per_graph it ping-pongs the
  *    displacements between u and u_alt (PF_FUSED_U_PINGPONG; a replay always ends with them in u) and starts right
  *    behind the residual; otherwise it starts behind the last reader of u.
- * u, theta, both Adam moments, the state and every history column are bit-identical to pf_gd_iterations, with one
- * exception: in the PF_FUSED_U_UPDATE form the u-norm monitor (history column 3, pf_state.u_norm) sums the same block
- * partials in another grouping and may differ in the last bits. */
+ * The state (u, theta), both optimisers' moments and every history column except the u_norm monitor are bit-identical to
+ * pf_gd_iterations.  The u_norm monitor (history column 3, pf_state.u_norm) is the exception: in the PF_FUSED_U_UPDATE form it
+ * sums the same block partials in another grouping and may differ in the last bits. */
 int pf_graph_create(const pf_problem* p, int iters_per_graph, void* stream, void** graph_out);
 /* Replays that hand their last iteration's tail to the next replay (one-chain form of the graph only, even
  * iters_per_graph; PF_ERR_UNSUPPORTED otherwise).  A plain replay ends with three stand-alone launches — the parameter

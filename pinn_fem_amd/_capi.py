@@ -28,6 +28,7 @@ PF_KERNEL_SLOTS = 9
 PF_COARSE_MAX_AGG, PF_COARSE_MODES = 256, 3
 PF_COARSE_MAX = PF_COARSE_MAX_AGG * PF_COARSE_MODES
 PF_GRAPH_CONT_HEAD, PF_GRAPH_NO_TAIL = 1, 2
+PF_GRAPH_FORM_FOLDED_RESIDUAL = 1
 PF_FUSED_FORWARD, PF_FUSED_BACKWARD, PF_FUSED_THETA_UPDATE, PF_FUSED_U_PINGPONG, PF_FUSED_U_UPDATE = 1, 2, 4, 8, 16
 KERNEL_SLOT_NAMES = ("net_forward_young", "net_forward_area", "node_residual", "elem_adjoint",
                      "net_backward_young", "net_backward_area", "node_gradu_adam", "theta_reduce_adam",
@@ -128,6 +129,7 @@ SYMBOLS = {
     "pf_net_op_count": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "pf_partials_count": (C.c_longlong, [_PP]),
     "pf_fusion_info": (C.c_int, [_PP]),
+    "pf_graph_form_info": (C.c_int, [_PP]),
     "pf_pack_theta": (C.c_int, [_PP, C.c_void_p]),
     "pf_net_forward": (C.c_int, [_PP, C.c_int, C.c_void_p]),
     "pf_net_forward_all": (C.c_int, [_PP, C.c_void_p]),

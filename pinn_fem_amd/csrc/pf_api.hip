@@ -21,6 +21,8 @@ int pf_launch_theta_reduce(const pf_problem* p, int fuse_adam, hipStream_t s);
 int pf_launch_pack_theta(const pf_problem* p, hipStream_t s);
 int pf_launch_finalize(const pf_problem* p, int mode, int with_theta, hipStream_t s, int tn_ready = 0);
 int pf_launch_theta_stage1(const pf_problem* p, hipStream_t s);
+int pf_launch_theta_stage1_path(const pf_problem* p, hipStream_t s, int fin_prev);
+int pf_launch_path_check(const pf_problem* p, int* bad, hipStream_t s);
 int pf_launch_theta_stage2(const pf_problem* p, int fuse_adam, hipStream_t s);
 int pf_launch_reset(const pf_problem* p, hipStream_t s);
 int pf_launch_adam(float* param, const float* grad, float* m, float* v, int n, int step, double lr,
@@ -215,16 +217,17 @@ static int net_backward_gea(const pf_problem* p, int which, hipStream_t s) {
 static bool can_fuse_backward(const pf_problem* p) {
   return can_fuse_forward(p) && p->net[0].n_hidden == 2 && fuse_gea_for(p);
 }
-static int net_backward2(const pf_problem* p, hipStream_t s) {
+// path: the launch also forms r and g_f (the iteration graph's path form: can_fold_residual)
+static int net_backward2(const pf_problem* p, hipStream_t s, int path = 0) {
 #define PF_NR0_SWITCH_B(PREFIX)                                   \
   switch (pf_net32_bucket(p->net[0].width)) {                     \
-    case 2: return PREFIX##2(p, s);                               \
-    case 4: return PREFIX##4(p, s);                               \
-    case 6: return PREFIX##6(p, s);                               \
-    case 8: return PREFIX##8(p, s);                               \
-    case 10: return PREFIX##10(p, s);                             \
-    case 12: return PREFIX##12(p, s);                             \
-    case 15: return PREFIX##15(p, s);                             \
+    case 2: return PREFIX##2(p, s, path);                         \
+    case 4: return PREFIX##4(p, s, path);                         \
+    case 6: return PREFIX##6(p, s, path);                         \
+    case 8: return PREFIX##8(p, s, path);                         \
+    case 10: return PREFIX##10(p, s, path);                       \
+    case 12: return PREFIX##12(p, s, path);                       \
+    case 15: return PREFIX##15(p, s, path);                       \
   }                                                               \
   return fail(PF_ERR_UNSUPPORTED, "MFMA32 engine: net width outside 1..30");
   if (p->mlp_dtype == PF_MLP_BF16) { PF_NR0_SWITCH_B(pf_launch_net32b_backward2_) }
@@ -538,6 +541,38 @@ static bool pad_index_is_canonical(const pf_problem* p) {
   return same;
 }
 
+// Is the mesh an open path in element order: every node touches at most element e-1 at its j end and element e at its i end
+// (node ids arbitrary)?  A ring, a shuffled element order, a girder, a hub or a mesh with dofs shared between ranks is not.
+// Decided on the device (pf_mesh.hip: k_path_check; one flag, a 4-byte copy), at graph creation only: once per captured
+// graph (a solve captures up to three), on the null stream — the mesh arrays are uploaded long before, and the synchronous
+// copy orders the answer.  A failed allocation, launch or copy answers "not a path": the graph then keeps its residual launch,
+// which is always correct; pf_last_error says so and pf_graph_form_info shows the form that was chosen.
+static bool mesh_is_path(const pf_problem* p) {
+  const pf_mesh& M = p->mesh;
+  if (M.n_elems < 1 || M.n_nodes != M.n_elems + 1 || !M.conn || !M.adj_ptr || !M.adj || !M.dof_flags) return false;
+  int* bad = nullptr;
+  if (hipMalloc(&bad, sizeof(int)) != hipSuccess) {
+    pf_set_error("path check of the mesh failed (hipMalloc): the iteration graph keeps its residual launch");
+    return false;
+  }
+  int h = 1;
+  bool ok = hipMemset(bad, 0, sizeof(int)) == hipSuccess && pf_launch_path_check(p, bad, nullptr) == PF_OK &&
+            hipMemcpy(&h, bad, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+  (void)hipFree(bad);
+  if (!ok) pf_set_error("path check of the mesh failed (HIP error): the iteration graph keeps its residual launch");
+  return ok && h == 0;
+}
+
+// Can the iteration graph drop the residual launch (the PATH form)?  Wherever the forward launch carries the displacement
+// update today (one chain: can_fuse_gradu with elem_k and prop_double), the backward is the fused two-phase launch and the
+// parameter update rides in the forward launch (so theta stage 1 is a launch of every iteration), on one GPU, with the second
+// displacement vector free to hold r — and the mesh is a path.
+static bool can_fold_residual_static(const pf_problem* p) {
+  return p->prop_double != 0 && p->elem_k != nullptr && p->u_alt != nullptr && can_fuse_gradu(p) && can_fuse_backward(p) &&
+         can_fuse_theta_update(p) && pf_n32_bwd2_has_path(p) && p->n_iface == 0 && p->mesh.dim == p->net[0].in_dim - 1;
+}
+static bool can_fold_residual(const pf_problem* p) { return can_fold_residual_static(p) && mesh_is_path(p); }
+
 // The buffers iteration i of the graph works on.  Properties and stiffness records ping-pong between iterations
 // (prop_double), so the forwards of iteration i do not wait for gradu(i-1), the last reader of the other half.  The
 // residual's partial sums always do (part_half).
@@ -555,8 +590,17 @@ static pf_problem graph_iteration_view(const pf_problem& p, int i) {
 // head_cont: iteration 0 also carries the updates and the bookkeeping of the iteration BEFORE the replay (left pending by a
 // no_tail replay); no_tail: the replay ends behind the last iteration's gradient-row reduction, its parameter update,
 // displacement update and bookkeeping stay pending (pf_graph_create_ex).  Both only in the one-chain form.
+//
+// PATH form (fold; can_fold_residual, decided at graph creation): THREE launches per iteration, forward -> backward -> theta
+// stage 1.  The backward launch forms r and g_f of its elements' nodes itself (pf_net32.hip: backward_phase, PATH); the
+// residual's loss sums and the bookkeeping of i-1 ride in the theta-stage-1 launch of i (pf_mesh.hip: k_theta_stage1_path),
+// with the same partition and order of the sums, so nothing changes a bit.  The stop is then raised one launch later than
+// above, behind backward(i) instead of beside residual(i): what backward(i) and stage 1(i) write before the flag is seen is
+// scratch all the same (g_f, r in u_alt, g_ea, gradient rows, partial sums of the half nobody will read), and every
+// state-changing step — the updates inside forward(i+1), or the replay's stand-alone tail — still starts behind stage 1(i),
+// reads the flag first and returns at once.
 static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_capture& c, bool calc_index = false,
-                                    bool head_cont = false, bool no_tail = false) {
+                                    bool head_cont = false, bool no_tail = false, bool fold = false) {
   hipStream_t s = c.s;
   if (!(p->net[0].enabled || p->net[1].enabled)) {
     for (int i = 0; i < iters; ++i) {
@@ -594,6 +638,15 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
     // (both nets in one launch where the engine has it; else one after the other: side by side on two branches they
     // measured slower, the same issue pipe, and the second one writes the stiffness records from both)
     PF_TRY(net_forward_all(&q, s, fo), "net_forward");
+    if (fold) {
+      PF_TRY(net_backward2(&q, s, 1), "net_backward2");
+      PF_TRY(pf_launch_theta_stage1_path(&q, s, carries ? (tn_ready ? 2 : 1) : 0), "theta_stage1");
+      if (i == iters - 1 && !no_tail) {
+        PF_TRY(pf_launch_theta_stage2(&q, 1, s), "theta_stage2");
+        PF_TRY(pf_launch_node_gradu(&q, 1, s, 0, nullptr), "node_gradu");
+      }
+      continue;
+    }
     // residual(i) reads u(i) [gradu(i-1)]; its block 0 is finalize(i-1): behind the theta update of i-1 (this chain:
     // the forward launch above, or the stand-alone kernel) and gradu(i-1)
     if (dag && i > 0 && hipStreamWaitEvent(s, ep[1], 0) != hipSuccess) return fail(PF_ERR_HIP, "graph edge failed");
@@ -622,6 +675,11 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
   return PF_OK;
 }
 
+int pf_graph_form_info(const pf_problem* p) {
+  if (check_problem(p) != PF_OK) return PF_ERR_ARG;
+  return can_fold_residual(p) ? PF_GRAPH_FORM_FOLDED_RESIDUAL : 0;
+}
+
 int pf_graph_create(const pf_problem* p, int iters_per_graph, void* stream, void** graph_out) {
   return pf_graph_create_ex(p, iters_per_graph, 0, stream, graph_out);
 }
@@ -638,9 +696,10 @@ int pf_graph_create_ex(const pf_problem* p, int iters_per_graph, int flags, void
   if ((flags & (PF_GRAPH_CONT_HEAD | PF_GRAPH_NO_TAIL)) && !can_chain_replays(p, iters_per_graph))
     return fail(PF_ERR_UNSUPPORTED, "pf_graph_create_ex: replays of this problem's graph cannot hand over their tail");
   const bool calc_index = can_fuse_theta_update(p) && pad_index_is_canonical(p);
+  const bool fold = can_fold_residual(p);
   const bool head = (flags & PF_GRAPH_CONT_HEAD) != 0, no_tail = (flags & PF_GRAPH_NO_TAIL) != 0;
   return capture_graph((hipStream_t)stream, PF_CAP_EV * iters_per_graph, hipStreamCaptureModeThreadLocal, graph_out,
-                       [&](pf_capture& cap) { return enqueue_graph_iterations(p, iters_per_graph, cap, calc_index, head, no_tail); });
+                       [&](pf_capture& cap) { return enqueue_graph_iterations(p, iters_per_graph, cap, calc_index, head, no_tail, fold); });
 }
 
 // the pending tail of a PF_GRAPH_NO_TAIL replay: what the last iteration of a plain replay ends with

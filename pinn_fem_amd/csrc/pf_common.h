@@ -308,6 +308,11 @@ __device__ __forceinline__ void ke_rows_times(const ElemK& k, int end, const flo
 }
 
 template <int DIM>
+__device__ __forceinline__ void store_vec(float* __restrict__ v, int node, const float* in) {
+  if (DIM == 2) reinterpret_cast<float2*>(v)[node] = make_float2(in[0], in[1]);
+  else v[node] = in[0];
+}
+template <int DIM>
 __device__ __forceinline__ void load_vec(const float* __restrict__ v, int node, float* out) {
   if (DIM == 2) {
     const float2 t = reinterpret_cast<const float2*>(v)[node];
@@ -422,8 +427,8 @@ struct pf_fwd2_opts {
   int pf_launch_net32b_backward_gea_##NRB(const pf_problem* p, int which, hipStream_t s); \
   int pf_launch_net32_forward2_##NRB(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o);    \
   int pf_launch_net32b_forward2_##NRB(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o);   \
-  int pf_launch_net32_backward2_##NRB(const pf_problem* p, hipStream_t s);                \
-  int pf_launch_net32b_backward2_##NRB(const pf_problem* p, hipStream_t s);
+  int pf_launch_net32_backward2_##NRB(const pf_problem* p, hipStream_t s, int path);      \
+  int pf_launch_net32b_backward2_##NRB(const pf_problem* p, hipStream_t s, int path);
 PF_DECL_NET32_LAUNCHERS(2)
 PF_DECL_NET32_LAUNCHERS(4)
 PF_DECL_NET32_LAUNCHERS(6)

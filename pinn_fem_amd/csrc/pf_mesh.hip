@@ -112,20 +112,12 @@ __global__ __launch_bounds__(PF_NODE_THREADS) __attribute__((amdgpu_num_sgpr(72)
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
       const int dof = node * DIM + c;
-      const bool mine = !(fl[c] & PF_DOF_GHOST);
       if (f_int_out) f_int_out[dof] = f[c];
       if (!compute_loss) continue;
-      float gf = 0.f;
-      if (!(fl[c] & PF_DOF_FIXED)) {
-        const float r = f[c] - P.lam * fx[c];           // solver.py:267-269
-        if (mine) sum_r2 += r * r;
-        gf = P.alpha_physics * r;                       // d(alpha_p * 0.5*sum r^2)/dr
-      }
+      float r, gf;
+      dof_residual(f[c], fl[c], fx[c], P.lam, P.alpha_physics, r, gf);        // (pf_node.h)
       P.g_f[dof] = gf;
-      if (mine && P.use_data && (fl[c] & PF_DOF_MEASURED)) {
-        const float d = mv[c] - un[c];                  // solver.py:274
-        sum_d2 += d * d;
-      }
+      dof_loss_terms(fl[c], r, P.use_data, mv[c], un[c], sum_r2, sum_d2);
     }
   };
   const int stride = nblk * (int)blockDim.x;
@@ -262,13 +254,14 @@ __global__ __launch_bounds__(PF_NODE_THREADS) __attribute__((amdgpu_num_sgpr(72)
 // ---- parameter gradient: sum block partials (fixed order) -> torch layout (+ Adam on theta) --------
 // stage 1: [nb_rows][pad_total] -> [PF_RG][pad_total]; grid (ceil(pad_total/64), PF_RG), 256 threads =
 // 64 columns x 4 row lanes, every thread a short strided row sum, then a fixed-order LDS combine.
-__global__ __launch_bounds__(256) void k_theta_stage1(pf_problem P, int nb_rows) {
+// (bx, by: the block's place in that grid)
+__device__ __forceinline__ void theta_stage1_body(const pf_problem& P, int nb_rows, int bx, int by) {
   const int done = P.state->done;   // checked before the store: the row loads are issued beside this load, not behind it
   __shared__ float red[4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + cl;
+  const int col = bx * 64 + cl;
   const int rpg = (nb_rows + PF_RG - 1) / PF_RG;
-  const int r0 = blockIdx.y * rpg, r1 = min(r0 + rpg, nb_rows);
+  const int r0 = by * rpg, r1 = min(r0 + rpg, nb_rows);
   float a = 0.f;
   if (col < P.pad_total) {
     const float* __restrict__ rows = P.partials + PF_PART_WG + col;
@@ -279,8 +272,103 @@ __global__ __launch_bounds__(256) void k_theta_stage1(pf_problem P, int nb_rows)
   if (done) return;
   if (rl == 0 && col < P.pad_total) {
     const float t = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
-    P.partials[PF_PART_WG + (size_t)P.n_part_blocks * P.pad_total + (size_t)blockIdx.y * P.pad_total + col] = t;
+    P.partials[PF_PART_WG + (size_t)P.n_part_blocks * P.pad_total + (size_t)by * P.pad_total + col] = t;
   }
+}
+__global__ __launch_bounds__(256) void k_theta_stage1(pf_problem P, int nb_rows) {
+  theta_stage1_body(P, nb_rows, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// ---- stage 1 of the iteration graph's PATH form (pf_api.hip: can_fold_residual) ------------------------------------------
+// There the fused backward launch has formed r and g_f itself (pf_node.h: path_residual) and no residual launch exists; what
+// that launch did besides rides here, as further blocks beside the nb_s1 = nb_cols * PF_RG reduction blocks:
+//   block 0 (fin_prev != 0 only)   the bookkeeping of the PREVIOUS iteration from the other half of the residual sums,
+//                                  as block 0 of k_node_residual does it (fin_prev: 1, or 2 = with tn_ready)
+//   nb_s1 blocks                   theta_stage1_body
+//   nb_node blocks                 the residual's loss sums from the stored r (pf_problem.u_alt, which the one-chain form
+//                                  leaves unused): k_node_residual's partition exactly — the same grid-stride walk two
+//                                  nodes at a time over the same number of blocks, the same per-dof terms in the same order
+//                                  (dof_loss_terms), the same block tree — so PF_PART_R2H / D2H receive the same bits.
+static_assert(PF_NODE_THREADS == 256,
+              "k_theta_stage1_path runs theta_stage1_body (laid out for 256 threads) and finalize_body in blocks of PF_NODE_THREADS");
+template <int DIM>
+__global__ __launch_bounds__(PF_NODE_THREADS) void k_theta_stage1_path(pf_problem P, int nb_rows, int nb_cols, int nb_node, int fin_prev) {
+  int b = (int)blockIdx.x;
+  if (fin_prev) {
+    if (b == 0) {
+      finalize_body(P, nb_node, 0, 0, nullptr, nullptr, 0, P.part_half ^ 1, nullptr, fin_prev == 2);
+      return;
+    }
+    b -= 1;
+  }
+  const int nb_s1 = nb_cols * PF_RG;
+  if (b < nb_s1) {
+    theta_stage1_body(P, nb_rows, b % nb_cols, b / nb_cols);
+    return;
+  }
+  const int bid = b - nb_s1;
+  __shared__ float red[16];
+  // the stop flag, ONE read per block (block 0 of this very launch may be raising it; see k_node_residual)
+  __shared__ int s_done;
+  if (threadIdx.x == 0) s_done = P.state->done;
+  __syncthreads();
+  if (s_done) return;
+  const pf_mesh& M = P.mesh;
+  const float* __restrict__ rres = P.u_alt;
+  const float* __restrict__ mvals = P.use_data ? M.meas_val : P.u;
+  float sum_r2 = 0.f, sum_d2 = 0.f;
+  const int stride = nb_node * (int)blockDim.x;
+  constexpr int NW = PF_RESIDUAL_NODES;
+  for (int node = bid * (int)blockDim.x + (int)threadIdx.x; node < M.n_nodes; node += NW * stride) {
+    bool ok[NW];
+    unsigned fl[NW][2];
+    float r[NW][2], un[NW][2], mv[NW][2];
+#pragma unroll
+    for (int m = 0; m < NW; ++m) {
+      ok[m] = node + m * stride < M.n_nodes;
+      const int nd = ok[m] ? node + m * stride : node;
+      load_vec<DIM>(rres, nd, r[m]);
+      load_vec<DIM>(P.u, nd, un[m]);
+      load_vec<DIM>(mvals, nd, mv[m]);
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) fl[m][c] = M.dof_flags[nd * DIM + c];
+    }
+#pragma unroll
+    for (int m = 0; m < NW; ++m)
+      if (ok[m]) {
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) dof_loss_terms(fl[m][c], r[m][c], P.use_data, mv[m][c], un[m][c], sum_r2, sum_d2);
+      }
+  }
+  const float t0 = pf_block_sum(sum_r2, red);
+  const float t1 = pf_block_sum(sum_d2, red);
+  if (threadIdx.x == 0) {
+    P.partials[PF_PART_R2H(P.part_half) + bid] = t0;
+    P.partials[PF_PART_D2H(P.part_half) + bid] = t1;
+  }
+}
+
+// ---- is the mesh an open path in element order? --------------------------------------------------------------------------
+// Every node has at most two incident elements: element e-1 at its j end and element e at its i end (node ids arbitrary).
+// One thread per element checks the CSR rows of its two nodes; any violation raises *bad.  Together with
+// n_nodes == n_elems + 1 (host) that is the whole property: the i nodes of the elements and the last j node are then
+// n_elems + 1 different nodes.  A dof that is shared between ranks disqualifies the mesh as well.
+__global__ __launch_bounds__(256) void k_path_check(pf_mesh M, int* bad) {
+  const int n = M.n_elems;
+  bool wrong = false;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
+    const int i = M.conn[2 * e], j = M.conn[2 * e + 1];
+    if (i < 0 || i >= M.n_nodes || j < 0 || j >= M.n_nodes) { wrong = true; continue; }
+    const int bi = M.adj_ptr[i], di = M.adj_ptr[i + 1] - bi;
+    const int bj = M.adj_ptr[j], dj = M.adj_ptr[j + 1] - bj;
+    if (e == 0) wrong |= di != 1 || M.adj[bi] != 0;
+    else wrong |= di != 2 || M.adj[bi] != (((e - 1) << 1) | 1) || M.adj[bi + 1] != (e << 1);
+    if (e == n - 1) wrong |= dj != 1 || M.adj[bj] != ((e << 1) | 1);
+    else wrong |= dj != 2 || M.adj[bj] != ((e << 1) | 1) || M.adj[bj + 1] != ((e + 1) << 1);
+    for (int c = 0; c < M.dim; ++c)
+      wrong |= ((M.dof_flags[i * M.dim + c] | M.dof_flags[j * M.dim + c]) & (PF_DOF_SHARED | PF_DOF_GHOST)) != 0;
+  }
+  if (wrong) *bad = 1;
 }
 
 // MFMA32 engine: rebuild the split-f16 operand images of the enabled nets from `th` (the flat active
@@ -352,6 +440,7 @@ __global__ __launch_bounds__(256) void k_pack_theta(pf_problem P) {
 // it completes the previous history row; this iteration's u_norm is filled in by the next call (or by k_shard_flush).
 // `half`: which half of the residual's partial sums to read.  One block of PF_FIN_THREADS threads or more.
 #define PF_FIN_THREADS PF_NODE_THREADS
+static_assert(PF_FIN_THREADS == PF_NODE_THREADS, "finalize_body also runs as a block of k_node_residual and of k_theta_stage1_path");
 // tn_ready: state->theta_norm already holds this iteration's value (k_theta_stage2).
 __device__ void finalize_body(const pf_problem& P, int nb_node, int mode, int with_theta, const float* __restrict__ ext_rd,
                               const float* __restrict__ ext_u2, int u2_lag, int half, float* new_theta, int tn_ready) {
@@ -850,6 +939,27 @@ int pf_launch_theta_stage1(const pf_problem* p, hipStream_t s) {
   if (p->n_theta_active <= 0) return PF_OK;
   const int nb_rows = pf_net_blocks(p);
   hipLaunchKernelGGL(k_theta_stage1, dim3((p->pad_total + 63) / 64, PF_RG), dim3(256), 0, s, *p, nb_rows);
+  return PF_CHECK_LAUNCH();
+}
+
+// stage 1 of the iteration graph's path form (k_theta_stage1_path); fin_prev as in pf_launch_node_residual
+int pf_launch_theta_stage1_path(const pf_problem* p, hipStream_t s, int fin_prev) {
+  if (p->n_theta_active <= 0 || !p->u_alt) { pf_set_error("path form of theta stage 1: no parameters / no u_alt"); return PF_ERR_ARG; }
+  const int nb_rows = pf_net_blocks(p), nb_cols = (p->pad_total + 63) / 64, nb_node = pf_node_blocks(p->mesh.n_nodes);
+  const int nb = (fin_prev ? 1 : 0) + nb_cols * PF_RG + nb_node;
+  if (p->mesh.dim == 2)
+    hipLaunchKernelGGL(k_theta_stage1_path<2>, dim3(nb), dim3(PF_NODE_THREADS), 0, s, *p, nb_rows, nb_cols, nb_node, fin_prev);
+  else
+    hipLaunchKernelGGL(k_theta_stage1_path<1>, dim3(nb), dim3(PF_NODE_THREADS), 0, s, *p, nb_rows, nb_cols, nb_node, fin_prev);
+  return PF_CHECK_LAUNCH();
+}
+
+// *bad (device, zeroed by the caller) becomes 1 unless the mesh is an open path in element order (k_path_check)
+int pf_launch_path_check(const pf_problem* p, int* bad, hipStream_t s) {
+  int nb = (p->mesh.n_elems + 255) / 256;
+  if (nb > 1024) nb = 1024;
+  if (nb < 1) nb = 1;
+  hipLaunchKernelGGL(k_path_check, dim3(nb), dim3(256), 0, s, p->mesh, bad);
   return PF_CHECK_LAUNCH();
 }
 

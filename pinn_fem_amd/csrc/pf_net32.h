@@ -154,6 +154,12 @@ inline int pf_n32_fwd2_blocks(int n_elems) {
 // Can the fused forward launch also run the displacement update of the previous iteration (gu_nb = entries of the
 // u-norm partial sums the bookkeeping reads)?  It needs the other-end adjacency, a single-GPU mesh (no ghost elements, no
 // shared dofs), every block's partial inside what the bookkeeping sums, and its node tasks inside the block's LDS table.
+// Has the fused backward launch a path form for this problem's nets (pf_net32.hip: launch_bwd2_t)?  Both register buckets
+// in the compact LDS layout (widths <= 24).
+inline bool pf_n32_bwd2_has_path(const pf_problem* p) {
+  const int be = pf_net32_bucket(p->net[0].width), ba = pf_net32_bucket(p->net[1].width);
+  return be > 0 && ba > 0 && be <= 12 && ba <= 12;
+}
 inline bool pf_n32_fwd2_can_update_u(const pf_problem* p, int gu_nb) {
   if (!p->adj_other || !p->m_u || !p->v_u || p->mesh.n_elems <= 0) return false;
   if (p->n_shared != 0 || p->own_lo != 0 || p->own_hi != 0) return false;

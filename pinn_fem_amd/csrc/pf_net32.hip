@@ -214,6 +214,11 @@ struct TaskIn {
   int2 nn;
   ElemGeo g;
   float ui[2], uj[2], gi[2], gj[2];
+  // path form (backward_phase, PATH) instead of gi, gj: f_ext and dof flags at the element's i node, and what the wave's
+  // edge lanes need of the elements beside the task (pf_node.h: path_residual)
+  float fxi[2];
+  unsigned fli;
+  PathEdge<DIM> edge;
 };
 
 // 1 - e^(-s) for s >= 0 (softplus'(z) = sigmoid(z) from s = softplus(z)) to ~3 ulp in 11 instructions: the hardware exp2
@@ -261,18 +266,59 @@ __device__ __forceinline__ void task_fetch_b(TaskIn<IN - 1>& t, const pf_problem
   load_vec<DIM>(P.g_f, t.nn.y, t.gj);
 }
 
+// Path form: which element beside its own a lane of a task reads (lane 0: e-1, lane 63: e+1; -1: none), and whether it
+// needs f_ext / dof flags at its j node (lane 63, and the mesh's last element, whose j node no other element owns)
+__device__ __forceinline__ int path_edge_elem(int e, int n, int lane) {
+  if (lane == 0 && e > 0) return e - 1;
+  if (lane == 63 && e < n - 1) return e + 1;
+  return -1;
+}
+// the far node of that element (lane 0: i(e-1), lane 63: j(e+1)): fetched two tasks ahead with the element's own node ids
+__device__ __forceinline__ int path_edge_node(const pf_problem& P, int e, int n, int lane) {
+  const int ee = path_edge_elem(e, n, lane);
+  int nd = 0;
+  if (ee >= 0) nd = P.mesh.conn[2 * ee + (lane == 0 ? 0 : 1)];
+  return nd;
+}
+// the nodal part of a path task's inputs: no gather of g_f (the task forms it), but f_ext and the dof flags at the i node,
+// and the edge lanes' extras (loads under the lanes' own predicate: two lanes of 64).  The element's own stiffness record is
+// not fetched: the task forms it from the properties and the geometry it holds anyway, by the float operations the forward
+// launch wrote it with (k_net32_forward2; the kernel runs at its register budget, and a record is three registers held over
+// both tiles).
+template <int IN>
+__device__ __forceinline__ void task_fetch_b_path(TaskIn<IN - 1>& t, const pf_problem& P, int e, int n, int lane, int edge_node) {
+  constexpr int DIM = IN - 1;
+  load_vec<DIM>(P.u, t.nn.x, t.ui);
+  load_vec<DIM>(P.u, t.nn.y, t.uj);
+  load_vec<DIM>(P.mesh.f_ext, t.nn.x, t.fxi);
+  t.fli = load_node_flags<DIM>(P.mesh.dof_flags, t.nn.x);
+  t.edge.k = ElemK{0.f, 0.f, 0.f};
+  t.edge.u[0] = t.edge.u[1] = 0.f;
+  t.edge.fx[0] = t.edge.fx[1] = 0.f;
+  t.edge.fl = 0u;
+  const int ee = path_edge_elem(e, n, lane);
+  if (ee >= 0) {
+    t.edge.k = load_k_record<DIM>(P.elem_k, ee);
+    load_vec<DIM>(P.u, edge_node, t.edge.u);
+  }
+  if (lane == 63 || e >= n - 1) {
+    load_vec<DIM>(P.mesh.f_ext, t.nn.y, t.edge.fx);
+    t.edge.fl = load_node_flags<DIM>(P.mesh.dof_flags, t.nn.y);
+  }
+}
+
 // dL/d(E*A) from the fetched operands: the arithmetic of pf_elem_gea (pf_common.h), op for op
 template <int DIM>
-__device__ __forceinline__ float task_gea(const TaskIn<DIM>& t, int fe_mode) {
+__device__ __forceinline__ float task_gea(const TaskIn<DIM>& t, const float* gi, const float* gj, int fe_mode) {
   float pu0[2], pu1[2];
   const ElemK k1 = elem_k_unit<DIM>(t.g);
   ke_rows_times<DIM>(k1, 0, t.ui, t.uj, pu0, fe_mode);
   ke_rows_times<DIM>(k1, 1, t.ui, t.uj, pu1, fe_mode);
   float gs = 0.f;
 #pragma unroll
-  for (int c = 0; c < DIM; ++c) gs = fmaf(t.gi[c], pu0[c], gs);
+  for (int c = 0; c < DIM; ++c) gs = fmaf(gi[c], pu0[c], gs);
 #pragma unroll
-  for (int c = 0; c < DIM; ++c) gs = fmaf(t.gj[c], pu1[c], gs);
+  for (int c = 0; c < DIM; ++c) gs = fmaf(gj[c], pu1[c], gs);
   return gs / t.g.l0;
 }
 
@@ -1191,7 +1237,16 @@ __device__ __forceinline__ void bw_row_from_parked(const pf_problem& P, int whic
 // of the write-out; 2 = second phase entered WITHOUT a block barrier (constant blocks and images are in place since phase
 // 1; the wave's scratch is its own), at its end: block barrier, `first_row()` (the first phase's row from the parked tiles),
 // block barrier, park, block barrier, own row.
-template <int NR, int L, int IN, bool GEA, int MODE = 0, class FirstRow = int>
+// PATH (GEA phases of the iteration graph's path form only; pf_api.hip: can_fold_residual): no residual launch has run.  The
+// task forms r and g_f at its elements' nodes itself (pf_node.h: path_residual), stores g_f and r (into pf_problem.u_alt,
+// for the loss sums: pf_mesh.hip, k_theta_stage1_path) for node i(e) — the mesh's last element also for its j node — and
+// takes the adjoint's g_f from registers.  Tasks, waves and sums are those of the plain form.
+// FRESH (second phase behind a PATH phase): the phase derives its lane-dependent addresses from a thread id the compiler
+// cannot connect with the first phase's — shared with phase 1 they stay live over its task loop, which in the path form has
+// no register left for them (they were spilled to scratch in front of the loop and reloaded behind it).  The empty asm is a
+// hint that this compiler's register allocator took: profiles/r04_bwd2_registers.txt records what it gave (252 VGPRs, no
+// spill, for <10,8,2,3,true>); re-read .vgpr_spill_count in the code-object metadata after a toolchain change.
+template <int NR, int L, int IN, bool GEA, int MODE = 0, class FirstRow = int, bool PATH = false, bool FRESH = false>
 __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, int hp, int dbg, const unsigned char* smem,
                                                unsigned char* cst, unsigned char* wscr,
                                                unsigned long long* stamps = nullptr, float* park = nullptr,
@@ -1206,7 +1261,9 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
   const float* __restrict__ other = which == 0 ? P.prop_a : P.prop_e;
   const float* __restrict__ mine = which == 0 ? P.prop_e : P.prop_a;   // this net's forward values (pf_net_forward)
   const int n = P.mesh.n_elems;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  int tid = (int)threadIdx.x;
+  if constexpr (FRESH) asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wv = tid >> 6, waves = blockDim.x >> 6;
   const int h = lane >> 5;
   unsigned char* scratch = wscr + wv * WAVE_SCRATCH;
   if constexpr (MODE != 2)
@@ -1244,14 +1301,22 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     if (elder && k < n_mine) return ((c_par - sh + (k - c_own)) * per_round + partner) * 64;
     return n - 1;
   };
+  static_assert(!PATH || GEA, "the path form belongs to the phase that computes the element adjoint");
   TaskIn<DIM> nxt;
   int2 nn_ahead = int2{0, 0};                    // node ids of the task after next (GEA only)
+  int en_ahead = 0, en_next = 0;                 // PATH: the edge lanes' far node of the task after next / of the next task
   if (n > 0) {
-    task_fetch_a<IN, GEA>(nxt, P, onet, other, mine, min(task_base(0) + lane, n - 1));
-    if (GEA) nn_ahead = reinterpret_cast<const int2*>(P.mesh.conn)[min(task_base(1) + lane, n - 1)];
+    const int e0 = min(task_base(0) + lane, n - 1), e1 = min(task_base(1) + lane, n - 1);
+    task_fetch_a<IN, GEA>(nxt, P, onet, other, mine, e0);
+    if (GEA) nn_ahead = reinterpret_cast<const int2*>(P.mesh.conn)[e1];
+    if constexpr (PATH) {
+      en_next = path_edge_node(P, e0, n, lane);
+      en_ahead = path_edge_node(P, e1, n, lane);
+    }
   }
   if constexpr (MODE != 2) __syncthreads();      // (image, constant blocks and scratch are in place)
-  task_fetch_b<IN, GEA>(nxt, P);
+  if constexpr (PATH) task_fetch_b_path<IN>(nxt, P, min(task_base(0) + lane, n - 1), n, lane, en_next);
+  else task_fetch_b<IN, GEA>(nxt, P);
 
   // block-uniform scalars: keep them in SGPRs (the kernel runs at its register budget)
   const float bound = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, reinterpret_cast<const float*>(smem)[0])));
@@ -1278,10 +1343,31 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     // softplus'(z) = sigmoid(z) = 1 - exp(-softplus(z)) from the forward's stored value (= softplus(z) * scale), so the
     // output unit need not be recomputed (torch: z > 20 ? 1 : e^z / (e^z + 1), the same number to float round-off)
     float gz = 0.f;
+    float gi[2] = {0.f, 0.f}, gj[2] = {0.f, 0.f};      // g_f at the element's nodes (GEA): gathered, or formed here (PATH)
+    if constexpr (GEA && !PATH) {
+      gi[0] = cur.gi[0]; gi[1] = cur.gi[1];
+      gj[0] = cur.gj[0]; gj[1] = cur.gj[1];
+    }
+    if constexpr (PATH) {
+      // every lane (lane shifts inside); a lane past the mesh's end holds the last element again and stores nothing
+      float ri[2], rj[2];
+      const int ec = min(e, n - 1);
+      const ElemK k_own = elem_k_from<DIM>(cur.g, (cur.own * cur.oth) / cur.g.l0);      // = the forward launch's record of e
+      path_residual<DIM>(k_own, cur.edge, cur.ui, cur.uj, cur.fxi, cur.fli, ec, n, lane, P.lam, P.alpha_physics, P.fe_mode,
+                         ri, gi, rj, gj);
+      if (live) {
+        store_vec<DIM>(P.g_f, cur.nn.x, gi);
+        store_vec<DIM>(P.u_alt, cur.nn.x, ri);
+        if (e == n - 1) {
+          store_vec<DIM>(P.g_f, cur.nn.y, gj);
+          store_vec<DIM>(P.u_alt, cur.nn.y, rj);
+        }
+      }
+    }
     if (live) {
       float gea;
       if (GEA) {
-        gea = task_gea<DIM>(cur, P.fe_mode);
+        gea = task_gea<DIM>(cur, gi, gj, P.fe_mode);
         P.g_ea[e] = gea;
       } else {
         gea = cur.gea;
@@ -1329,8 +1415,14 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
       task_fetch_a<IN, GEA>(nxt, P, onet, other, mine, min(task_base(k + 1) + lane, n - 1), false);
       if (GEA) {
         nxt.nn = nn_ahead;
-        task_fetch_b<IN, GEA>(nxt, P);
-        nn_ahead = reinterpret_cast<const int2*>(P.mesh.conn)[min(task_base(k + 2) + lane, n - 1)];
+        const int e2 = min(task_base(k + 2) + lane, n - 1);
+        if constexpr (PATH) {
+          task_fetch_b_path<IN>(nxt, P, min(task_base(k + 1) + lane, n - 1), n, lane, en_ahead);
+          en_ahead = path_edge_node(P, e2, n, lane);
+        } else {
+          task_fetch_b<IN, GEA>(nxt, P);
+        }
+        nn_ahead = reinterpret_cast<const int2*>(P.mesh.conn)[e2];
       }
     }
     // ---- the two tiles ------------------------------------------------------------------------------------------
@@ -1501,7 +1593,7 @@ constexpr size_t bw2_lds_bytes() {
 // eighths of the younger wave's tasks the older wave of its SIMD takes over (backward_phase, shift8), measured on MI355X
 // (profiles/r03_ab.txt): 0 / 1 / 2 / 3 -> backward launch 72.2 / 69.7 / 68.0 / 71.1 us
 constexpr int PF_BW_SHIFT = 2;
-template <int NRE, int NRA, int L, int IN>
+template <int NRE, int NRA, int L, int IN, bool PATH = false>
 __global__ __launch_bounds__((bw2_threads<NRE, NRA, L, IN>())) void k_net32_backward2(pf_problem P, int hp_e, int hp_a, int dbg_arg) {
   const int dbg = PF_N32_DBG_ENABLE ? dbg_arg : 0;
   const unsigned long long t_entry = PF_N32_DBG_ENABLE ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -1527,11 +1619,11 @@ __global__ __launch_bounds__((bw2_threads<NRE, NRA, L, IN>())) void k_net32_back
     float* park = reinterpret_cast<float*>(wscr + (size_t)(blockDim.x >> 6) * bw2_wave_scratch<NRE, NRA>());
     const float kl_e = pf_n32_lam_scale(P.lam), kx_e = __builtin_ldexpf(1.0f, P.coord_exp);
     auto first_row = [&]() { bw_row_from_parked<NRE, L, IN>(P, 0, hp_e, park, kl_e, kx_e); };
-    backward_phase<NRE, L, IN, true, 1>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, park, 0, PF_BW_SHIFT);
-    backward_phase<NRA, L, IN, false, 2>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr, st ? st + 4 : nullptr, park, first_row,
-                                         PF_BW_SHIFT);
+    backward_phase<NRE, L, IN, true, 1, int, PATH>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, park, 0, PF_BW_SHIFT);
+    backward_phase<NRA, L, IN, false, 2, decltype(first_row), false, PATH>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr,
+                                                                           st ? st + 4 : nullptr, park, first_row, PF_BW_SHIFT);
   } else {
-    backward_phase<NRE, L, IN, true>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, nullptr, 0, PF_BW_SHIFT);
+    backward_phase<NRE, L, IN, true, 0, int, PATH>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, nullptr, 0, PF_BW_SHIFT);
     __syncthreads();                             // the write-out staging of phase 1 is read; scratch and constants are re-initialised
     backward_phase<NRA, L, IN, false>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr, st ? st + 4 : nullptr, nullptr, 0, PF_BW_SHIFT);
   }
@@ -1599,7 +1691,7 @@ int launch_fwd2(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o) {
 
 // fused backward of both nets (two phases): E net of this translation unit's bucket, A net's bucket dispatched here
 template <int NRA, int L, int IN>
-int launch_bwd2_t(const pf_problem* p, hipStream_t s) {
+int launch_bwd2_t(const pf_problem* p, hipStream_t s, int path) {
   constexpr int NRE = PF_NR;
   const int nb = pf_net_blocks(p);
   const int hp_e = ((p->net[0].width + 3) / 4) * 4, hp_a = ((p->net[1].width + 3) / 4) * 4;
@@ -1607,19 +1699,31 @@ int launch_bwd2_t(const pf_problem* p, hipStream_t s) {
   const size_t lds = bw2_lds_bytes<NRE, NRA, L, IN>();
   static_assert(bw2_lds_bytes<NRE, NRA, L, IN>() <= 160 * 1024, "fused backward: LDS budget");
   static const int dbg = getenv("PF_N32_DBG") ? atoi(getenv("PF_N32_DBG")) : 0;
-  hipLaunchKernelGGL((k_net32_backward2<NRE, NRA, L, IN>), dim3(nb), dim3(THREADS), lds, s, *p, hp_e, hp_a, dbg);
+  if (path) {
+    // (only with the parked phases: the buckets past 12 registers run the two phases with a barrier between them and have
+    //  no register left for the path task's inputs; pf_api.hip: can_fold_residual asks pf_n32_bwd2_has_path)
+    if constexpr (bw2_parked<NRE, NRA>()) {
+      if (!p->elem_k || !p->u_alt) { pf_set_error("fused backward, path form: elem_k and u_alt are needed"); return PF_ERR_ARG; }
+      hipLaunchKernelGGL((k_net32_backward2<NRE, NRA, L, IN, true>), dim3(nb), dim3(THREADS), lds, s, *p, hp_e, hp_a, dbg);
+    } else {
+      pf_set_error("fused backward: no path form for nets wider than 24");
+      return PF_ERR_UNSUPPORTED;
+    }
+  } else {
+    hipLaunchKernelGGL((k_net32_backward2<NRE, NRA, L, IN>), dim3(nb), dim3(THREADS), lds, s, *p, hp_e, hp_a, dbg);
+  }
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_HIP;
 }
 template <int L, int IN>
-int launch_bwd2(const pf_problem* p, hipStream_t s) {
+int launch_bwd2(const pf_problem* p, hipStream_t s, int path) {
   switch (pf_net32_bucket(p->net[1].width)) {
-    case 2: return launch_bwd2_t<2, L, IN>(p, s);
-    case 4: return launch_bwd2_t<4, L, IN>(p, s);
-    case 6: return launch_bwd2_t<6, L, IN>(p, s);
-    case 8: return launch_bwd2_t<8, L, IN>(p, s);
-    case 10: return launch_bwd2_t<10, L, IN>(p, s);
-    case 12: return launch_bwd2_t<12, L, IN>(p, s);
-    case 15: return launch_bwd2_t<15, L, IN>(p, s);
+    case 2: return launch_bwd2_t<2, L, IN>(p, s, path);
+    case 4: return launch_bwd2_t<4, L, IN>(p, s, path);
+    case 6: return launch_bwd2_t<6, L, IN>(p, s, path);
+    case 8: return launch_bwd2_t<8, L, IN>(p, s, path);
+    case 10: return launch_bwd2_t<10, L, IN>(p, s, path);
+    case 12: return launch_bwd2_t<12, L, IN>(p, s, path);
+    case 15: return launch_bwd2_t<15, L, IN>(p, s, path);
   }
   pf_set_error("MFMA32 engine: area net width outside 1..30");
   return PF_ERR_UNSUPPORTED;
@@ -1695,10 +1799,11 @@ int PF_N32_SYM(forward2_)(const pf_problem* p, hipStream_t s, const pf_fwd2_opts
 // Two hidden layers only (the reference's SimpleNN default and every example): with one or three the two phases in one
 // kernel no longer fit the register budget of their block shapes without spilling (checked in the compiler's asm), and
 // a spill reload in the task loop costs more than a launch boundary — those shapes keep the two launches.
-int PF_N32_SYM(backward2_)(const pf_problem* p, hipStream_t s) {
+// path: the iteration graph's path form (backward_phase, PATH)
+int PF_N32_SYM(backward2_)(const pf_problem* p, hipStream_t s, int path) {
   const int L = p->net[0].n_hidden, IN = p->net[0].in_dim;
-  if (L == 2 && IN == 3) return launch_bwd2<2, 3>(p, s);
-  if (L == 2 && IN == 2) return launch_bwd2<2, 2>(p, s);
+  if (L == 2 && IN == 3) return launch_bwd2<2, 3>(p, s, path);
+  if (L == 2 && IN == 2) return launch_bwd2<2, 2>(p, s, path);
   pf_set_error("fused backward: two hidden layers only");
   return PF_ERR_UNSUPPORTED;
 }

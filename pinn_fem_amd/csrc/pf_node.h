@@ -263,3 +263,79 @@ __device__ __forceinline__ void gather_kv_multi(const pf_problem& P, const float
     }
   }
 }
+
+// ---- residual, dL/df_int and the loss terms of one dof (fem/solver.py:267-283) -----------------------------------------
+// Shared by k_node_residual (pf_mesh.hip), by the path form of the fused backward launch, which forms r and g_f of its
+// elements' nodes itself (pf_net32.hip: backward_phase, PATH), and by the blocks that re-sum that form's stored residuals
+// (pf_mesh.hip: k_theta_stage1_path).  ONE copy of each expression: under the compiler's default contraction two copies
+// of one expression have drifted apart before (pf_common.h: PF_NO_CONTRACT).
+// f = the dof's internal force; r comes back as 0 for a fixed dof.
+__device__ __forceinline__ void dof_residual(float f, unsigned fl, float fx, float lam, float alpha_physics, float& r, float& gf) {
+  r = 0.f;
+  gf = 0.f;
+  if (!(fl & PF_DOF_FIXED)) {
+    r = f - lam * fx;                               // solver.py:267-269
+    gf = alpha_physics * r;                         // d(alpha_p * 0.5*sum r^2)/dr
+  }
+}
+// the dof's terms of sum r^2 and sum d^2 (mv, un: measured and current displacement; read only where the dof is measured)
+__device__ __forceinline__ void dof_loss_terms(unsigned fl, float r, int use_data, float mv, float un, float& sum_r2, float& sum_d2) {
+  const bool mine = !(fl & PF_DOF_GHOST);
+  if (!(fl & PF_DOF_FIXED) && mine) sum_r2 += r * r;
+  if (mine && use_data && (fl & PF_DOF_MEASURED)) {
+    const float d = mv - un;                        // solver.py:274
+    sum_d2 += d * d;
+  }
+}
+
+// ---- the residual on a PATH mesh, from the element side -----------------------------------------------------------------
+// On a mesh whose elements form an open path in element order (element e joins node i(e) to j(e) = i(e+1); pf_api.hip:
+// mesh_is_path) node i(e) touches only elements e-1 (at its j end) and e (at its i end), so a wave that holds 64 consecutive
+// elements, one per lane, can form the internal force of every node it touches without the node adjacency: lane e computes
+// its element's two end forces, takes the j-end force of e-1 from the lane below and adds in ascending element id like
+// gather_kv_multi above (same ke_rows_times, same 0 + fe0 + fe1 sequence: same bits).  Only the wave's two edge lanes need
+// values of an element outside the task (PathEdge).  Every lane of the wave must call this (lane shifts).
+template <int DIM>
+struct PathEdge {
+  ElemK k;          // lane 0: record of e-1; lane 63: record of e+1
+  float u[2];       // lane 0: u at i(e-1); lane 63: u at j(e+1)
+  float fx[2];      // f_ext and dof flags at j(e): lane 63 and the mesh's last element
+  unsigned fl;
+};
+// dof flags of a node, both dofs in one register
+template <int DIM>
+__device__ __forceinline__ unsigned load_node_flags(const uint8_t* __restrict__ dof_flags, int node) {
+  if (DIM == 2) return reinterpret_cast<const uint16_t*>(dof_flags)[node];
+  return dof_flags[node];
+}
+// k: the element's own record; fxi, fli: f_ext and flags at i(e); e < n.  Out: r and g_f at i(e) (what the lane stores), and
+// at j(e) (r_j only valid for the mesh's last element, which stores it).
+template <int DIM>
+__device__ __forceinline__ void path_residual(const ElemK& k, const PathEdge<DIM>& x, const float* ui, const float* uj,
+                                              const float* fxi, unsigned fli, int e, int n, int lane, float lam,
+                                              float alpha_physics, int fe_mode, float* ri, float* gi, float* rj, float* gj) {
+  float A[2], B[2], Bl[2], Ar[2];
+  ke_rows_times<DIM>(k, 0, ui, uj, A, fe_mode);        // element e at its i end -> node i(e)
+  ke_rows_times<DIM>(k, 1, ui, uj, B, fe_mode);        // element e at its j end -> node j(e)
+  ke_rows_times<DIM>(x.k, 1, x.u, ui, Bl, fe_mode);    // lane 0: element e-1 = (i(e-1), i(e)) at its j end
+  ke_rows_times<DIM>(x.k, 0, uj, x.u, Ar, fe_mode);    // lane 63: element e+1 = (j(e), j(e+1)) at its i end
+  const bool first = e == 0, last = e >= n - 1, right = lane == 63 || last;
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) {
+    const float below = __shfl_up(B[c], 1, 64);
+    const float Bp = lane == 0 ? Bl[c] : below;
+    float acc = 0.f;
+    acc = acc + (first ? A[c] : Bp);                   // the node's first incidence: e-1, or e itself at the path's start
+    const float t = acc + A[c];
+    acc = first ? acc : t;
+    dof_residual(acc, (fli >> (8 * c)) & 0xffu, fxi[c], lam, alpha_physics, ri[c], gi[c]);
+    float accj = 0.f;
+    accj = accj + B[c];
+    const float tj = accj + Ar[c];
+    accj = last ? accj : tj;                           // the path's end node has one incidence
+    float gje;
+    dof_residual(accj, (x.fl >> (8 * c)) & 0xffu, x.fx[c], lam, alpha_physics, rj[c], gje);
+    const float above = __shfl_down(gi[c], 1, 64);
+    gj[c] = right ? gje : above;
+  }
+}

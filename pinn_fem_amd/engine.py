@@ -295,6 +295,12 @@ class HipEngine:
         """Bit mask of the fused launches of this problem (_capi.PF_FUSED_*)."""
         return int(self.lib.pf_fusion_info(self._ref()))
 
+    @_on_engine_stream
+    def graph_form_info(self) -> int:
+        """Bit mask of the iteration graph's form beyond fusion_info() (_capi.PF_GRAPH_FORM_*): 1 = the residual launch is
+        folded into the fused backward and theta-stage-1 launches (path meshes).  Inspects the mesh on the device."""
+        return int(self.lib.pf_graph_form_info(self._ref()))
+
     # ---- solve_gd support ------------------------------------------------------------------------
     @_on_engine_stream
     def begin(self, u_initial, lam, config, max_iter: Optional[int] = None, want_history=True):
