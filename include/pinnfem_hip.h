@@ -26,6 +26,8 @@
 extern "C" {
 #endif
 
+/* 9 still covers pf_coarse_setup_t and pf_pcg2t_*: they are additive (new symbols only, no struct or signature changed), so
+ * a binding built against the earlier 9 keeps working; a binding that needs them finds them by name */
 #define PF_ABI_VERSION 9
 
 /* error codes */
@@ -467,13 +469,29 @@ int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* 
  * (pf_pcg_workspace_count), stop test and single-chain graph, the Jacobi preconditioner from kt's diagonal.  kt is read
  * when the launches RUN, so a graph stays valid while pf_gl_state overwrites kt in place between solves.  A null kt is
  * PF_ERR_ARG from every one of them, never a silent linear solve.  CG needs K_t positive definite on the free dofs: the
- * caller checks rhs.du > 0.  There is no two-level form (its coarse matrix would change with every Newton iteration). */
+ * caller checks rhs.du > 0.  The two-level form is pf_pcg2t_*, below. */
 int pf_pcgt_begin(const pf_problem* p, const double* kt, const double* b, double* x, double* ws, double rtol, void* stream);
 int pf_pcgt_iterations(const pf_problem* p, const double* kt, double* x, double* ws, int n_iter, double* state_out,
                        void* stream);
 int pf_pcgt_graph_create(const pf_problem* p, const double* kt, double* x, double* ws, int n_iter, void* stream,
                          void** graph_out);
 int pf_pcgt_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream);
+/* the two-level preconditioner on K_t.  The near-null space of K_t(u) is the rigid motions of the DEFORMED body, so the
+ * host rebuilds the columns on X + u and Z^T K_t Z is formed and factored again at every Newton iteration; the
+ * aggregation stays that of the reference configuration, and every buffer of the pf_coarse record is refreshed in place
+ * (n_coarse and agg_off may change with the configuration).
+ * pf_coarse_setup_t: pf_coarse_setup with the element blocks of kt, the same workgroup-per-aggregate sums.
+ * pf_pcg2t_*: pf_pcg2_* on K_t: the same kernels, workspace (pf_pcg2_workspace_count), stop test and single-chain graph.
+ * kt, zcoef and a_inv are read when the launches RUN.  A null kt, or a null or inconsistent coarse space (a_inv
+ * included), is PF_ERR_ARG before anything is enqueued: never a silent linear solve, never a silent Jacobi solve. */
+int pf_coarse_setup_t(const pf_problem* p, const pf_coarse* c, const double* kt, double* a_c_out, void* stream);
+int pf_pcg2t_begin(const pf_problem* p, const pf_coarse* c, const double* kt, const double* b, double* x, double* ws,
+                   double rtol, void* stream);
+int pf_pcg2t_iterations(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
+                        double* state_out, void* stream);
+int pf_pcg2t_graph_create(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
+                          void* stream, void** graph_out);
+int pf_pcg2t_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream);
 
 /* ---- scalar (E, A) identification: the device loop of pinn_inverse_problem_gd -------------------------------------
  * FEM/python/api_pinn_gradient_descent.py:102-121 calls pinn_inverse_problem_gd(nodes, elements, f_ext, fixed_dofs,

@@ -174,6 +174,13 @@ SYMBOLS = {
     "pf_pcgt_iterations": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "pf_pcgt_graph_create": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "pf_pcgt_state": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "pf_coarse_setup_t": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_pcg2t_begin": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "pf_pcg2t_iterations": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double),
+                                      C.c_void_p]),
+    "pf_pcg2t_graph_create": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.POINTER(C.c_void_p)]),
+    "pf_pcg2t_state": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "pf_comm_unique_id": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pf_comm_create": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pf_comm_destroy": (C.c_int, [C.c_void_p]),

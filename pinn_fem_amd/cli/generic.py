@@ -79,10 +79,12 @@ def parse_problem(problem_file):
     #           "compact_output": true|false|"auto",  big arrays -> <stem>.res.npz instead of JSON lists
     #           "fe_mode": "reference"|"delta",       element-force formulation
     #           "mlp_dtype": "f32"|"bf16",            precision of the MLP matrix products (bf16 study)
-    #           "nr_preconditioner": "jacobi"|"two-level",  preconditioner of the CG solve inside Newton-Raphson
+    #           "nr_preconditioner": "jacobi"|"two-level"|"two-level-updated",  preconditioner of the CG solve inside
+    #                                                 Newton-Raphson ("two-level": linear kinematics; "two-level-updated":
+    #                                                 green-lagrange, rebuilt on the current configuration every iteration)
     #           "nr_aggregates": N,                   aggregates of the two-level coarse space (default: by mesh size)
     #           "kinematics": "linear"|"green-lagrange"}  element of Newton-Raphson: small displacements (default) or the
-    #                                                 total-Lagrangian large-displacement truss (Jacobi only)
+    #                                                 total-Lagrangian large-displacement truss
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):

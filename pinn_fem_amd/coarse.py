@@ -17,7 +17,9 @@ import numpy as np
 MAX_AGGREGATES = 256           # coarse dimension <= 768: the device kernels size their LDS by it
 MODES = 3                      # coarse columns per aggregate at most (pf_coarse.zcoef is [n_dofs][3])
 GRAM_DROP = 1e-12              # directions below this fraction of the aggregate's largest Gram eigenvalue are dropped
-PRECONDITIONERS = ("jacobi", "two-level")
+# "two-level-updated": the two-level preconditioner of the Green-Lagrange tangent solve, its columns rebuilt on the current
+# configuration X + u and Z^T K_t Z re-formed and re-factored at every Newton iteration (update_coarse_space)
+PRECONDITIONERS = ("jacobi", "two-level", "two-level-updated")
 
 
 @dataclass
@@ -138,6 +140,19 @@ def build_coarse_space(nodes, dim: int, fixed_mask, n_aggregates: Optional[int] 
     zcoef[fixed.reshape(-1)] = 0.0
     return CoarseSpace(dim=dim, n_nodes=n, n_agg=n_agg, n_coarse=int(agg_off[-1]), node_agg=node_agg,
                        agg_off=agg_off, zcoef=np.ascontiguousarray(zcoef), agg_ptr=agg_ptr, agg_nodes=agg_nodes)
+
+
+def update_coarse_space(coords, dim: int, fixed_mask, node_agg) -> CoarseSpace:
+    """The coarse space on other coordinates with a FIXED node -> aggregate map: the rigid-body modes of every
+    aggregate as it lies at `coords` (the current configuration X + u of a large-displacement solve, where the
+    near-null space of the tangent is the rigid motions of the deformed body, not of the reference one).
+
+    node_agg comes from the reference configuration, once per solve (strip_aggregates(X, ...) or the node_agg of the
+    CoarseSpace built on X): the aggregates, and with them agg_ptr and agg_nodes, then stay what they are while the
+    columns follow the body.  The per-aggregate column count may still differ between configurations, because the
+    Gram drop is decided on the masked columns at the coordinates given (an aggregate whose free nodes line up under
+    a centroid shift, for one): agg_off and n_coarse are therefore refreshed together with zcoef, never carried over."""
+    return build_coarse_space(coords, dim, fixed_mask, aggregates=np.asarray(node_agg))
 
 
 def coarse_inverse(a_c: np.ndarray) -> np.ndarray:

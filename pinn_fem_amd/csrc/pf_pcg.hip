@@ -12,8 +12,8 @@
 //
 // The operator has a second form: with a non-null `kt` (double [n_elems][3] = B11, B12, B22; 1-D [n_elems]) the element
 // block is read from it instead of being formed as s*(c2, cs, s2).  That is the tangent of the Green-Lagrange element
-// (pf_nl.hip: pf_gl_state writes kt), served by the same kernels: pf_kt_v_f64 and pf_pcgt_*.  kt == NULL is the linear
-// operator, arithmetic unchanged.
+// (pf_nl.hip: pf_gl_state writes kt), served by the same kernels: pf_kt_v_f64, pf_pcgt_* and, with the two-level
+// preconditioner, pf_coarse_setup_t and pf_pcg2t_*.  kt == NULL is the linear operator, arithmetic unchanged.
 #include <stdio.h>
 #include "pf_common.h"
 #include "pf_graph.h"
@@ -213,10 +213,11 @@ __device__ __forceinline__ void coarse_cols(const pf_coarse& C, int node, int J,
       z[c][k] = in ? C.zcoef[((size_t)node * DIM + c) * PF_COARSE_MODES + k] : 0.0;
 }
 
-// (K z_j)[node] for the (up to 3) columns j of aggregate J: gather64 with z_j evaluated from the coefficients
+// (K z_j)[node] for the (up to 3) columns j of aggregate J: gather64 with z_j evaluated from the coefficients; kt != NULL:
+// the element blocks are kt's, as in gather64 (the same decision in every thread of the launch)
 template <int DIM>
-__device__ __forceinline__ void gather_kz(const pf_problem& P, const pf_coarse& C, int J, int node,
-                                          double (*kz)[PF_COARSE_MODES]) {
+__device__ __forceinline__ void gather_kz(const pf_problem& P, const double* __restrict__ kt, const pf_coarse& C, int J,
+                                          int node, double (*kz)[PF_COARSE_MODES]) {
   const pf_mesh& M = P.mesh;
 #pragma unroll
   for (int c = 0; c < DIM; ++c)
@@ -226,12 +227,27 @@ __device__ __forceinline__ void gather_kz(const pf_problem& P, const pf_coarse& 
     const int code = M.adj[idx];
     const int e = code >> 1, end = code & 1;
     const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
-    const ElemGeo g = load_geo(M.egeo, e);
-    const double s = elem_s64(P, e, g.l0);
     const double sg = end ? -1.0 : 1.0;
     double zi[DIM][PF_COARSE_MODES], zj[DIM][PF_COARSE_MODES];
     coarse_cols<DIM>(C, nn.x, J, zi);
     coarse_cols<DIM>(C, nn.y, J, zj);
+    if (kt) {
+      if (DIM == 2) {
+        const double b11 = kt[3 * (size_t)e], b12 = kt[3 * (size_t)e + 1], b22 = kt[3 * (size_t)e + 2];
+#pragma unroll
+        for (int k = 0; k < PF_COARSE_MODES; ++k) {
+          const double dx = zj[0][k] - zi[0][k], dy = zj[1][k] - zi[1][k];
+          kz[0][k] += -sg * (b11 * dx + b12 * dy);
+          kz[1][k] += -sg * (b12 * dx + b22 * dy);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < PF_COARSE_MODES; ++k) kz[0][k] += -sg * (kt[e] * (zj[0][k] - zi[0][k]));
+      }
+      continue;
+    }
+    const ElemGeo g = load_geo(M.egeo, e);
+    const double s = elem_s64(P, e, g.l0);
 #pragma unroll
     for (int k = 0; k < PF_COARSE_MODES; ++k) {
       if (DIM == 2) {
@@ -247,9 +263,10 @@ __device__ __forceinline__ void gather_kz(const pf_problem& P, const pf_coarse& 
 
 // A_c = Z^T K Z.  Block I owns the rows of aggregate I: entry (I,ki | J,kj) = sum over the nodes of I of
 // z_(I,ki)[node] . (K z_(J,kj))[node], which is non-zero only when J is I or holds a neighbour of a node of I
-// (nbr[] marks those).  The caller zeroed ac.
+// (nbr[] marks those).  The caller zeroed ac.  kt != NULL: K is the tangent K_t of those element blocks (pf_coarse_setup_t).
 template <int DIM>
-__global__ __launch_bounds__(256) void k_coarse_setup(pf_problem P, pf_coarse C, double* __restrict__ ac) {
+__global__ __launch_bounds__(256) void k_coarse_setup(pf_problem P, const double* __restrict__ kt, pf_coarse C,
+                                                      double* __restrict__ ac) {
   __shared__ int nbr[PF_COARSE_MAX_AGG];
   __shared__ double red[8];
   const pf_mesh& M = P.mesh;
@@ -279,7 +296,7 @@ __global__ __launch_bounds__(256) void k_coarse_setup(pf_problem P, pf_coarse C,
     for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
       const int node = C.agg_nodes[i];
       double kz[DIM][PF_COARSE_MODES];
-      gather_kz<DIM>(P, C, J, node, kz);
+      gather_kz<DIM>(P, kt, C, J, node, kz);
 #pragma unroll
       for (int c = 0; c < DIM; ++c)
 #pragma unroll
@@ -395,12 +412,12 @@ __global__ __launch_bounds__(256) void k_pcg2_rz0(double* st, const double* __re
 }  // namespace
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// One implementation behind three exported families: pf_pcg_* (Jacobi), pf_pcg2_* (two-level) and pf_pcgt_* (Jacobi on
-// the tangent operator) are argument checks in front of pcg_begin_impl / pcg_iterations_impl / pcg_graph_impl /
-// pcg_state_impl, which take the coarse space as a nullable `c` (NULL = Jacobi), the tangent blocks as a nullable `kt`
-// (NULL = the linear operator) and the exported function's name as `who`, the prefix of every error message.  The
-// workspace layout is stated once, in pcg_layout; the iteration's launch sequence once, in pcg_enqueue; the CG graphs
-// are captured by the library's capture_graph (pf_graph.h) as a single chain.
+// One implementation behind four exported families: pf_pcg_* (Jacobi), pf_pcg2_* (two-level), pf_pcgt_* (Jacobi on the
+// tangent operator) and pf_pcg2t_* (two-level on the tangent operator) are argument checks in front of pcg_begin_impl /
+// pcg_iterations_impl / pcg_graph_impl / pcg_state_impl, which take the coarse space as a nullable `c` (NULL = Jacobi),
+// the tangent blocks as a nullable `kt` (NULL = the linear operator) and the exported function's name as `who`, the
+// prefix of every error message.  The workspace layout is stated once, in pcg_layout; the iteration's launch sequence
+// once, in pcg_enqueue; the CG graphs are captured by the library's capture_graph (pf_graph.h) as a single chain.
 #define PCG_CHECK(who) \
   if (hipGetLastError() != hipSuccess) return pcg_fail(PF_ERR_HIP, who, "HIP launch failed");
 
@@ -530,14 +547,15 @@ static bool coarse_ok(const pf_coarse* c, bool need_inverse) {
          c->agg_nodes && (!need_inverse || c->a_inv);
 }
 
-int pf_coarse_setup(const pf_problem* p, const pf_coarse* c, double* a_c_out, void* stream) {
-  if (!p || !coarse_ok(c, false) || !a_c_out) return pcg_fail(PF_ERR_ARG, "pf_coarse_setup", "bad argument");
-  hipStream_t s = (hipStream_t)stream;
+// A_c = Z^T K Z, K the linear operator (kt == NULL) or the tangent of the element blocks kt
+static int coarse_setup_impl(const pf_problem* p, const pf_coarse* c, const double* kt, double* a_c_out, hipStream_t s,
+                             const char* who) {
+  if (!p || !coarse_ok(c, false) || !a_c_out) return pcg_fail(PF_ERR_ARG, who, "bad argument");
   if (c->n_coarse == 0) return PF_OK;
   if (hipMemsetAsync(a_c_out, 0, (size_t)c->n_coarse * c->n_coarse * sizeof(double), s) != hipSuccess)
-    return pcg_fail(PF_ERR_HIP, "pf_coarse_setup", "clearing the coarse matrix failed");
-  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_coarse_setup<DIM>, dim3(c->n_agg), dim3(256), 0, s, *p, *c, a_c_out));
-  PCG_CHECK("pf_coarse_setup");
+    return pcg_fail(PF_ERR_HIP, who, "clearing the coarse matrix failed");
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_coarse_setup<DIM>, dim3(c->n_agg), dim3(256), 0, s, *p, kt, *c, a_c_out));
+  PCG_CHECK(who);
   return PF_OK;
 }
 
@@ -551,9 +569,21 @@ static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x
 }
 
 // ---- the exported families -----------------------------------------------------------------------------------------
-// pf_pcgt_*: a null kt is an error here, never a silent linear solve
+// pf_pcgt_*, pf_pcg2t_*, pf_coarse_setup_t: a null kt is an error here, never a silent linear solve
 #define PCGT_NEED_KT(who) \
   if (!kt) return pcg_fail(PF_ERR_ARG, who, "null tangent (kt)");
+// pf_pcg2t_*: nor does a null or inconsistent coarse space become a silent Jacobi solve
+#define PCG2T_NEED(who)                                                         \
+  PCGT_NEED_KT(who);                                                            \
+  if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad coarse space");
+
+int pf_coarse_setup(const pf_problem* p, const pf_coarse* c, double* a_c_out, void* stream) {
+  return coarse_setup_impl(p, c, nullptr, a_c_out, (hipStream_t)stream, "pf_coarse_setup");
+}
+int pf_coarse_setup_t(const pf_problem* p, const pf_coarse* c, const double* kt, double* a_c_out, void* stream) {
+  PCGT_NEED_KT("pf_coarse_setup_t");
+  return coarse_setup_impl(p, c, kt, a_c_out, (hipStream_t)stream, "pf_coarse_setup_t");
+}
 
 long long pf_pcg_workspace_count(const pf_problem* p) { return pcg_ws_count(p, false); }
 long long pf_pcg2_workspace_count(const pf_problem* p) { return pcg_ws_count(p, true); }
@@ -581,6 +611,12 @@ int pf_pcgt_begin(const pf_problem* p, const double* kt, const double* b, double
   return pcg_begin_impl(p, nullptr, kt, b, x, ws, rtol, (hipStream_t)stream, "pf_pcgt_begin");
 }
 
+int pf_pcg2t_begin(const pf_problem* p, const pf_coarse* c, const double* kt, const double* b, double* x, double* ws,
+                   double rtol, void* stream) {
+  PCG2T_NEED("pf_pcg2t_begin");
+  return pcg_begin_impl(p, c, kt, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg2t_begin");
+}
+
 int pf_pcg_iterations(const pf_problem* p, double* x, double* ws, int n_iter, double* state_out, void* stream) {
   return pcg_iterations_impl(p, nullptr, nullptr, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg_iterations");
 }
@@ -594,6 +630,12 @@ int pf_pcgt_iterations(const pf_problem* p, const double* kt, double* x, double*
                        void* stream) {
   PCGT_NEED_KT("pf_pcgt_iterations");
   return pcg_iterations_impl(p, nullptr, kt, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcgt_iterations");
+}
+
+int pf_pcg2t_iterations(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
+                        double* state_out, void* stream) {
+  PCG2T_NEED("pf_pcg2t_iterations");
+  return pcg_iterations_impl(p, c, kt, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg2t_iterations");
 }
 
 int pf_pcg_graph_create(const pf_problem* p, double* x, double* ws, int n_iter, void* stream, void** graph_out) {
@@ -611,6 +653,12 @@ int pf_pcgt_graph_create(const pf_problem* p, const double* kt, double* x, doubl
   return pcg_graph_impl(p, nullptr, kt, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcgt_graph_create");
 }
 
+int pf_pcg2t_graph_create(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
+                          void* stream, void** graph_out) {
+  PCG2T_NEED("pf_pcg2t_graph_create");
+  return pcg_graph_impl(p, c, kt, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg2t_graph_create");
+}
+
 int pf_pcg_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
   return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcg_state");
 }
@@ -620,6 +668,10 @@ int pf_pcg2_state(const pf_problem* p, double* ws, double* state_out, void* stre
 int pf_pcgt_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream) {
   PCGT_NEED_KT("pf_pcgt_state");
   return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcgt_state");
+}
+int pf_pcg2t_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream) {
+  PCGT_NEED_KT("pf_pcg2t_state");
+  return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcg2t_state");
 }
 
 }  // extern "C"

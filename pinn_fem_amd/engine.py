@@ -10,6 +10,7 @@ import contextlib
 import ctypes as C
 import functools
 import os
+import time
 import warnings
 from typing import List, Optional
 
@@ -44,18 +45,31 @@ def _on_engine_stream(fn):
 class DeviceCoarse:
     """A coarse.CoarseSpace on the device and the pf_coarse record that points at it."""
 
-    def __init__(self, cs, device):
+    def __init__(self, cs, device, max_coarse=None):
+        """max_coarse: size a_inv for this many columns instead of cs.n_coarse (a space that refresh() will replace by
+        one with another column count)."""
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
         self.space = cs
         self.node_agg, self.agg_off, self.zcoef = t(cs.node_agg), t(cs.agg_off), t(cs.zcoef)
         self.agg_ptr, self.agg_nodes = t(cs.agg_ptr), t(cs.agg_nodes)
         self.a_c = None                 # host copy of Z^T K Z as the device formed it
         self.a_inv_host = None
-        self.a_inv = torch.zeros(max(cs.n_coarse, 1) ** 2, dtype=torch.float64, device=device)
+        self.max_coarse = max(cs.n_coarse, 1) if max_coarse is None else max(int(max_coarse), cs.n_coarse, 1)
+        self.a_inv = torch.zeros(self.max_coarse ** 2, dtype=torch.float64, device=device)
         R = self.record = _capi.PfCoarse()
         R.n_agg, R.n_coarse = cs.n_agg, cs.n_coarse
         R.node_agg, R.agg_off, R.zcoef = self.node_agg.data_ptr(), self.agg_off.data_ptr(), self.zcoef.data_ptr()
         R.agg_ptr, R.agg_nodes, R.a_inv = self.agg_ptr.data_ptr(), self.agg_nodes.data_ptr(), self.a_inv.data_ptr()
+
+    def refresh(self, cs):
+        """Another space on the same aggregation, in place: the record keeps its pointers; zcoef, agg_off and n_coarse
+        follow cs (the column count of an aggregate may change with the configuration, coarse.update_coarse_space)."""
+        if not np.array_equal(cs.node_agg, self.space.node_agg) or cs.n_coarse > self.max_coarse:
+            raise ValueError("DeviceCoarse.refresh: the new space is not one on the same node -> aggregate map")
+        self.zcoef.copy_(torch.from_numpy(cs.zcoef))
+        self.agg_off.copy_(torch.from_numpy(cs.agg_off))
+        self.space, self.record.n_coarse = cs, cs.n_coarse
+        self.a_c = self.a_inv_host = None
 
     def set_inverse(self, a_inv):
         self.a_inv_host = np.ascontiguousarray(a_inv, dtype=np.float64)
@@ -205,6 +219,9 @@ class HipEngine:
         self._graph = None
         self.pcg_iterations = 0         # CG iterations of every pcg_solve so far (tools/nr_scale.py reports them)
         self._coarse_cache = None       # (key, DeviceCoarse | None): coarse space of the two-level CG preconditioner
+        self._coarse_updated = None     # (aggregation key, DeviceCoarse, A_c buffer) of preconditioner "two-level-updated"
+        self.coarse_refresh_seconds = 0.0   # host seconds in the refreshes of that space so far, and their parts
+        self.coarse_refresh_parts = dict(columns=0.0, setup=0.0, factor=0.0, upload=0.0)
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
         self._configured = False
         env_k = os.environ.get("PINNFEM_GRAPH_ITERS")
@@ -599,27 +616,42 @@ class HipEngine:
     @_on_engine_stream
     def pcg_solve(self, b: torch.Tensor, rtol: float = 1e-13, max_iter: Optional[int] = None, poll: int = 64,
                   preconditioner: str = "jacobi", n_aggregates: Optional[int] = None, aggregates=None,
-                  tangent: bool = False):
+                  tangent: bool = False, u=None):
         """K_ff x = b by conjugate gradients, float64, on the device.  preconditioner: "jacobi" (diag(K_ff), the
         default) or "two-level" (Jacobi plus a coarse space of per-aggregate rigid-body modes, coarse.py;
         n_aggregates strips along the longest axis, or the caller's own node -> aggregate map).  tangent: K is the
-        tangent K_t(u) of the last gl_state (pf_pcgt_*; Jacobi only, and K_t must be positive definite).
+        tangent K_t(u) of the last gl_state, which must be positive definite: pf_pcgt_* with "jacobi", pf_pcg2t_* with
+        "two-level-updated", whose coarse space is rebuilt on X + u at every call (updated_coarse_space; u: the
+        displacements the last gl_state was given).
         Returns (x with zeros on fixed dofs, iterations, converged, |r|^2, |b|^2)."""
         coarse = None
-        if _coarse.check_preconditioner(preconditioner) == "two-level":
+        name = _coarse.check_preconditioner(preconditioner)
+        if name == "two-level":
             if tangent:
-                raise ValueError("the two-level preconditioner has no tangent-operator form; use preconditioner='jacobi' "
-                                 "with tangent=True")
+                raise ValueError("the two-level preconditioner of the linear operator has no tangent form: with "
+                                 "tangent=True use preconditioner='two-level-updated' (or 'jacobi')")
             coarse = self.coarse_space(n_aggregates, aggregates)        # None: the coarse matrix could not be factored
-        fam = "pf_pcgt" if tangent else ("pf_pcg" if coarse is None else "pf_pcg2")
+        elif name == "two-level-updated":
+            if not tangent:
+                raise ValueError("preconditioner='two-level-updated' belongs to the tangent solve (tangent=True): the "
+                                 "linear operator has nothing to update; use 'two-level'")
+            if u is None:
+                raise ValueError("preconditioner='two-level-updated' needs u, the displacements of the last gl_state")
+            coarse = self.updated_coarse_space(u, n_aggregates, aggregates)     # None: Jacobi on the tangent
         lib, ref, s = self.lib, self._ref(), self._stream()
-        head = (ref,) if coarse is None else (ref, C.byref(coarse.record))
         if tangent:
-            head = (ref, self._gl_ready("pcg_solve(tangent=True)")[1].data_ptr())
+            kt = self._gl_ready("pcg_solve(tangent=True)")[1].data_ptr()
+            fam = "pf_pcgt" if coarse is None else "pf_pcg2t"
+            head = (ref, kt) if coarse is None else (ref, C.byref(coarse.record), kt)
+            state_head = (ref, kt)
+        else:
+            fam = "pf_pcg" if coarse is None else "pf_pcg2"
+            head = (ref,) if coarse is None else (ref, C.byref(coarse.record))
+            state_head = (ref,)
         n = self.plan.n_dofs
         bb = b.to(device=self.device, dtype=torch.float64).contiguous()
         x = torch.zeros(n, dtype=torch.float64, device=self.device)
-        ws_count = lib.pf_pcg2_workspace_count if fam == "pf_pcg2" else lib.pf_pcg_workspace_count
+        ws_count = lib.pf_pcg_workspace_count if coarse is None else lib.pf_pcg2_workspace_count
         ws = torch.zeros(int(ws_count(ref)), dtype=torch.float64, device=self.device)
         _capi.check(getattr(lib, fam + "_begin")(*head, bb.data_ptr(), x.data_ptr(), ws.data_ptr(), float(rtol), s),
                     fam + "_begin")
@@ -637,7 +669,7 @@ class HipEngine:
                 k = min(poll, max_iter - done_it)
                 if use_graph and k == poll:
                     _capi.check(lib.pf_graph_launch(graph, s), "pf_graph_launch")
-                    _capi.check(getattr(lib, fam + "_state")(*(head if tangent else (ref,)), ws.data_ptr(), st, s),
+                    _capi.check(getattr(lib, fam + "_state")(*state_head, ws.data_ptr(), st, s),
                                 fam + "_state")
                 else:
                     _capi.check(getattr(lib, fam + "_iterations")(*head, x.data_ptr(), ws.data_ptr(), int(max(k, 0)), st, s),
@@ -689,6 +721,58 @@ class HipEngine:
             dc = None
         self._coarse_cache = (key, dc)
         return dc
+
+    @_on_engine_stream
+    def updated_coarse_space(self, u, n_aggregates: Optional[int] = None, aggregates=None):
+        """The coarse space of preconditioner "two-level-updated" for the tangent of the last gl_state: the rigid-body
+        modes of every aggregate at the current configuration X + u (X: the model's float64 coordinates), on the
+        aggregation of the reference configuration.  One engine-owned DeviceCoarse is refreshed in place at every call:
+        host columns, pf_coarse_setup_t with the engine's kt, read-back, host Cholesky, upload.  There is no cache: K_t
+        and X + u change with every Newton iteration.  Returns None, with a RuntimeWarning, when Z^T K_t Z is not positive
+        definite: the caller then runs Jacobi on the tangent."""
+        t0 = time.perf_counter()
+        hp = self.plan
+        if len(self.model.nodes) != hp.n_nodes:
+            raise NotImplementedError("the two-level preconditioner needs the engine's mesh to be the model's "
+                                      "(no sharded form)")
+        kt = self._gl_ready("updated_coarse_space")[1]
+        X = np.asarray(self.model.nodes, dtype=np.float64).reshape(hp.n_nodes, hp.dim)
+        uu = u.detach().cpu().numpy() if isinstance(u, torch.Tensor) else np.asarray(u)
+        uu = np.asarray(uu, dtype=np.float64).reshape(-1)
+        if uu.size != hp.n_dofs:
+            raise ValueError(f"updated_coarse_space: u has {uu.size} entries, the mesh has {hp.n_dofs} dofs")
+        fixed = (hp.dof_flags & _capi.PF_DOF_FIXED) != 0
+        agg_key = None if aggregates is None else np.asarray(aggregates).astype(np.int64).tobytes()
+        key = (None if n_aggregates is None else int(n_aggregates), agg_key)
+        if self._coarse_updated is None or self._coarse_updated[0] != key:
+            # the node -> aggregate map: once, on the reference configuration
+            first = _coarse.build_coarse_space(X, hp.dim, fixed, n_aggregates, aggregates)
+            cap = _capi.PF_COARSE_MODES * first.n_agg
+            dc = DeviceCoarse(first, self.device, max_coarse=cap)
+            self._coarse_updated = (key, dc, torch.zeros(cap * cap, dtype=torch.float64, device=self.device))
+        _, dc, a_c = self._coarse_updated
+        cs = _coarse.update_coarse_space(X + uu.reshape(hp.n_nodes, hp.dim), hp.dim, fixed, dc.space.node_agg)
+        dc.refresh(cs)
+        t1 = time.perf_counter()
+        _capi.check(self.lib.pf_coarse_setup_t(self._ref(), C.byref(dc.record), kt.data_ptr(), a_c.data_ptr(),
+                                               self._stream()), "pf_coarse_setup_t")
+        dc.a_c = a_c[: cs.n_coarse ** 2].cpu().numpy().reshape(cs.n_coarse, cs.n_coarse)
+        t2 = time.perf_counter()
+        try:
+            inv = _coarse.coarse_inverse(dc.a_c)
+        except np.linalg.LinAlgError as e:
+            warnings.warn(f"two-level-updated preconditioner: the coarse matrix Z^T K_t Z ({cs.n_coarse} x {cs.n_coarse}) "
+                          f"could not be factored ({e}); this step falls back to the Jacobi preconditioner on the tangent",
+                          RuntimeWarning)
+            inv = None
+        t3 = time.perf_counter()
+        if inv is not None:
+            dc.set_inverse(inv)
+        t4 = time.perf_counter()
+        parts = self.coarse_refresh_parts
+        parts["columns"] += t1 - t0; parts["setup"] += t2 - t1; parts["factor"] += t3 - t2; parts["upload"] += t4 - t3
+        self.coarse_refresh_seconds += t4 - t0
+        return dc if inv is not None else None
 
     @_on_engine_stream
     def diag_k(self, lam: Optional[float] = None) -> torch.Tensor:

@@ -46,8 +46,10 @@ class SolverConfig:
     alpha_data: float = 100.0
     method: str = "auto"
     preconditioning: bool = False
-    # preconditioner of the CG solve inside solve_nr: "jacobi" (diag(K_ff)) or "two-level" (Jacobi plus a coarse space
-    # of per-aggregate rigid-body modes, pinn_fem_amd/coarse.py); nr_aggregates: number of aggregates (None: default)
+    # preconditioner of the CG solve inside solve_nr: "jacobi" (diag(K_ff)), "two-level" (Jacobi plus a coarse space
+    # of per-aggregate rigid-body modes, pinn_fem_amd/coarse.py; linear kinematics) or "two-level-updated" (the same on the
+    # Green-Lagrange tangent, rebuilt on the current configuration at every Newton iteration); nr_aggregates: number of
+    # aggregates (None: default)
     nr_preconditioner: str = "jacobi"
     nr_aggregates: Optional[int] = None
     # kinematics of solve_nr: "linear" (small displacements, the reference's element) or "green-lagrange" (total-Lagrangian
@@ -63,9 +65,13 @@ def check_kinematics(name, nr_preconditioner: str = "jacobi") -> str:
     from ..coarse import check_preconditioner
     if name not in KINEMATICS:
         raise ValueError(f"unknown kinematics {name!r}: accepted values are 'linear' and 'green-lagrange'")
-    if name == "green-lagrange" and check_preconditioner(nr_preconditioner) == "two-level":
-        raise ValueError("kinematics 'green-lagrange' supports nr_preconditioner 'jacobi' only: the two-level "
-                         "preconditioner has no tangent-operator form.")
+    pre = check_preconditioner(nr_preconditioner)
+    if name == "green-lagrange" and pre == "two-level":
+        raise ValueError("kinematics 'green-lagrange' supports nr_preconditioner 'jacobi' and 'two-level-updated': "
+                         "'two-level' keeps the coarse space of the reference configuration, which is not the tangent's.")
+    if name == "linear" and pre == "two-level-updated":
+        raise ValueError("nr_preconditioner 'two-level-updated' belongs to kinematics 'green-lagrange': the linear "
+                         "stiffness does not change, so there is nothing to update; use 'two-level'.")
     return name
 
 
@@ -350,7 +356,8 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
 
     config.kinematics = "green-lagrange" replaces the linear element by the total-Lagrangian one (pf_gl_state,
     pf_gl_fint): u starts from u_initial when given, every iteration re-forms the element state at u and
-    solves K_t(u) du = load_factor f_ext - f_int(u) with the Jacobi-preconditioned CG on the tangent (pf_pcgt_*).  CG needs
+    solves K_t(u) du = load_factor f_ext - f_int(u) with the Jacobi-preconditioned CG on the tangent (pf_pcgt_*) or, with
+    config.nr_preconditioner = "two-level-updated", the two-level one whose coarse space follows X + u (pf_pcg2t_*).  CG needs
     K_t positive definite: a limit point or buckling (rhs.du <= 0) raises RuntimeError; there is no arc-length control."""
     config = config or SolverConfig()
     green_lagrange = check_kinematics(config.kinematics, config.nr_preconditioner) == "green-lagrange"
@@ -382,7 +389,8 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
         if green_lagrange:
             eng.gl_state(u)                 # the history's max |e| is read once, from the state at the final u
             rhs = f_ext - eng.gl_fint()
-            du, _, ok, rr, bb = eng.pcg_solve(rhs, tangent=True)
+            du, _, ok, rr, bb = eng.pcg_solve(rhs, tangent=True, preconditioner=config.nr_preconditioner,
+                                             n_aggregates=config.nr_aggregates, u=u)
         else:
             max_e = _max_abs_strain(model, u)
             rhs = f_ext - eng.kv_f64(u)

@@ -1,0 +1,462 @@
+"""The two-level preconditioner of the Green-Lagrange tangent solve on the device: pf_coarse_setup_t and pf_pcg2t_* called
+through the C ABI, HipEngine.pcg_solve(tangent=True, preconditioner="two-level-updated"), and solve_nr / solve / the CLI
+with nr_preconditioner = "two-level-updated", against the CPU restatements (tests/gl_reference.py,
+tests/two_level_reference.py, tests/two_level_tangent_reference.py).
+
+The yardsticks are those of tests/test_pcg_two_level.py: a float64 round-off bound per entry of the coarse matrix, and
+`iterations <= 1.25 * scipy's`, `error <= 10 * scipy's` against scipy's CG with the restated preconditioner.  The measured
+figures are printed in front of every assertion."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import gl_reference as gl
+import two_level_reference as tl
+import two_level_tangent_reference as tt
+
+pytestmark = pytest.mark.gpu
+
+U53 = 2.0 ** -53
+RTOL = 1e-13
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+class Sys:
+    """One truss on the device (E*A = 1e6) with the engine's own Green-Lagrange buffers."""
+
+    def __init__(self, nodes, el, fixed, dim, loads=None):
+        from pinn_fem_amd import _capi
+        from pinn_fem_amd.engine import HipEngine
+        from pinn_fem_amd.fem.model import FEMModel, Material
+        self.capi, self.dim = _capi, dim
+        self.nodes = np.asarray(nodes, dtype=np.float64).reshape(-1, dim)
+        self.el, self.fixed = np.asarray(el), np.asarray(fixed, dtype=int)
+        self.n_nodes, self.ne = len(self.nodes), len(self.el)
+        self.n = self.n_nodes * dim
+        self.mask = ~gl.free_mask(self.n, self.fixed)
+        self.max_degree = int(np.bincount(self.el.reshape(-1), minlength=self.n_nodes).max())
+        self.model = FEMModel(nodes=self.nodes if dim == 2 else self.nodes.reshape(-1), elements=self.el,
+                              material=Material(tt.YOUNG, tt.AREA, 1.0), loads=np.zeros(self.n) if loads is None else loads,
+                              fixed_dofs=self.fixed, dimension=dim)
+        self.eng = HipEngine(self.model)
+        self.lib = self.eng.lib
+
+    def dev(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.eng.device)
+
+    def tangent(self, u):
+        """pf_gl_state at u; K_t and |K_t| as CSR from the DEVICE's kt read back, and the device pointer of kt."""
+        self.eng.gl_state(self.dev(u))
+        torch.cuda.synchronize()
+        kt_t = self.eng._gl[1]
+        kt = kt_t.cpu().numpy()
+        if self.dim == 2:
+            kt = kt[: 3 * self.ne].reshape(self.ne, 3)
+            B = np.stack([kt[:, [0, 1]], kt[:, [1, 2]]], axis=1)
+        else:
+            B = kt[: self.ne].reshape(self.ne, 1, 1)
+        return (gl.blocks_csr(B, self.el, self.n_nodes, self.dim), gl.blocks_csr(B, self.el, self.n_nodes, self.dim, True),
+                kt_t.data_ptr())
+
+    def columns(self, node_agg, u=None):
+        from pinn_fem_amd.coarse import update_coarse_space
+        X = self.nodes if u is None else self.nodes + np.asarray(u).reshape(-1, self.dim)
+        return update_coarse_space(X if self.dim == 2 else X[:, 0], self.dim, self.mask, node_agg)
+
+    def setup_t(self, dc, kt_ptr):
+        """pf_coarse_setup_t into a buffer the kernel has to overwrite."""
+        nc = dc.space.n_coarse
+        ac = torch.full((max(nc, 1) ** 2,), 7.0, dtype=torch.float64, device=self.eng.device)
+        with self.eng.on_stream():
+            self.capi.check(self.lib.pf_coarse_setup_t(self.eng._ref(), C.byref(dc.record), kt_ptr, ac.data_ptr(),
+                                                       self.eng._stream()), "pf_coarse_setup_t")
+        torch.cuda.synchronize()
+        return ac[: nc * nc].cpu().numpy().reshape(nc, nc)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# A. pf_coarse_setup_t against Z^T K_t Z
+# ---------------------------------------------------------------------------------------------------------------------
+def _truss(n_elems, n_agg, dead=None, per_node=False):
+    from pinn_fem_amd.coarse import strip_aggregates
+    rng = np.random.default_rng(3000 + n_elems)
+    nodes, el = gl.irregular_truss(n_elems, rng)
+    fixed = np.unique(np.concatenate([[0, 1, 2], rng.choice(nodes.size, size=max(1, nodes.size // 10), replace=False)]))
+    agg = np.arange(len(nodes)) if per_node else strip_aggregates(nodes, 2, n_agg)
+    if dead is not None:
+        gone = np.flatnonzero(agg == dead)
+        fixed = np.unique(np.concatenate([fixed, 2 * gone, 2 * gone + 1]))
+    return Sys(nodes, el, fixed, 2), agg
+
+
+def _bar(n_elems, n_agg):
+    from pinn_fem_amd.coarse import strip_aggregates
+    rng = np.random.default_rng(4000 + n_elems)
+    x = np.concatenate([[0.0], np.cumsum(0.5 + rng.random(n_elems))])
+    e = np.arange(n_elems)
+    el = np.stack([e, e + 1], axis=1)
+    flip = rng.random(n_elems) < 0.5
+    el[flip] = el[flip][:, ::-1]
+    return Sys(x, el[rng.permutation(n_elems)], np.array([0]), 1), strip_aggregates(x, 1, n_agg)
+
+
+def _rollers():
+    """Six nodes on a line, pairs as aggregates; node 2 and node 4 roll (uy fixed).  On X the two nodes of a pair share their
+    y, so the masked rotation column of pairs (2, 3) and (4, 5) lies in the span of the translations: 2 columns each.  Once
+    node 3 or 5 has moved in y it does not: 3 columns."""
+    nodes = np.stack([np.arange(6.0), np.zeros(6)], axis=1)
+    el = np.stack([np.arange(5), np.arange(1, 6)], axis=1)
+    return Sys(nodes, el, np.array([0, 1, 5, 9]), 2), np.arange(6) // 2
+
+
+CASES = {
+    "hub257": lambda: _truss(257, 7),                       # the irregular truss with a hub, 7 strips
+    "one_aggregate": lambda: _truss(1700, 1),               # ~600 nodes in one aggregate: the node loop strides past 256 threads
+    "node_per_aggregate": lambda: _truss(63, None, per_node=True),
+    "dead": lambda: _truss(257, 7, dead=3),                 # every dof of strip 3 fixed: an aggregate without columns
+    "bar": lambda: _bar(300, 10),
+    "one_element": lambda: (Sys(np.array([[0.3, -0.2], [1.1, 0.5]]), np.array([[1, 0]]), np.array([0, 1, 3]), 2), np.zeros(2, int)),
+    "rollers": _rollers,
+}
+
+
+def _field(S, rng):
+    """A 5 % dilation plus a random field of |du| / l0 about 0.1: every block of kt differs from the linear one."""
+    d = S.nodes[S.el[:, 1]] - S.nodes[S.el[:, 0]]
+    amp = 0.1 * float(np.mean(np.linalg.norm(d, axis=1))) / np.sqrt(2.0 * S.dim)
+    return np.where(S.mask, 0.0, 0.05 * S.nodes.reshape(-1) + amp * rng.standard_normal(S.n))
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_coarse_matrix_of_the_tangent_from_device(name):
+    from pinn_fem_amd.engine import DeviceCoarse
+    S, agg = CASES[name]()
+    u = _field(S, np.random.default_rng(5))
+    K, Kabs, kt_ptr = S.tangent(u)
+    cs0, cs = S.columns(agg), S.columns(agg, u)
+    # the engine's path: one DeviceCoarse built on X, refreshed in place to X + u
+    dc = DeviceCoarse(cs0, S.eng.device, max_coarse=3 * cs0.n_agg)
+    dc.refresh(cs)
+    assert dc.record.n_coarse == cs.n_coarse and np.array_equal(dc.agg_off.cpu().numpy(), cs.agg_off)
+    got = S.setup_t(dc, kt_ptr)
+    m = int(np.max(np.diff(cs.agg_ptr)))
+    Z = tl.z_matrix(cs)
+    want, scale = (Z.T @ (K @ Z)).toarray(), (abs(Z).T @ (Kabs @ abs(Z))).toarray()
+    # the per-entry bound of test_pcg_two_level.py::test_coarse_matrix_from_device, in units of 2^-53 |Z|^T|K_t||Z|
+    terms = 2 * (16 + 4 * S.max_degree + S.dim * m)
+    err = np.abs(got - want)
+    worst = float(np.max(err / np.maximum(scale, 1e-300))) / U53 if err.size else 0.0
+    counts0, counts = np.diff(cs0.agg_off), np.diff(cs.agg_off)
+    print(f"{name}: {cs.n_agg} aggregates of <= {m} nodes, {cs.n_coarse} columns ({cs0.n_coarse} on X), max degree "
+          f"{S.max_degree}: worst error {worst:.2f} * 2^-53 |Z|^T|K_t||Z| (bound {terms})")
+    assert got.shape == (cs.n_coarse, cs.n_coarse) and np.all(np.isfinite(got))
+    assert np.all(err <= terms * U53 * scale)                      # exact zeros where no element joins two aggregates
+    if name == "one_aggregate":
+        assert cs.n_agg == 1 and m > 2 * 256
+    if name == "node_per_aggregate":
+        assert m == 1 and cs.n_agg == S.n_nodes
+    if name == "dead":
+        assert cs.columns_of(3) == 0 and cs.n_coarse < 3 * cs.n_agg
+    if name == "one_element":
+        assert (cs.n_agg, cs.n_coarse) == (1, 1)
+    # a state at which an aggregate's column count differs from its count on X: "rollers" is built to show it, the
+    # other cases do not
+    assert np.array_equal(counts0, counts) == (name != "rollers")
+    if name == "rollers":
+        assert list(counts0) == [2, 2, 2] and list(counts) == [2, 3, 3]
+
+
+@pytest.mark.parametrize("name", ["hub257", "bar"])
+def test_coarse_matrix_at_zero_displacement_is_the_linear_one(name):
+    """At u = 0 the tangent is the linear stiffness, which pf_coarse_setup forms from float32 geometry (c2, cs, s2, l0:
+    2^-24 each): the two agree to that level only, 1e-6 of |Z|^T|K||Z| and not bitwise."""
+    from pinn_fem_amd.engine import DeviceCoarse
+    S, agg = CASES[name]()
+    K, Kabs, kt_ptr = S.tangent(np.zeros(S.n))
+    cs = S.columns(agg)
+    dc = DeviceCoarse(cs, S.eng.device)
+    got = S.setup_t(dc, kt_ptr)
+    lin = torch.full((cs.n_coarse ** 2,), 7.0, dtype=torch.float64, device=S.eng.device)
+    with S.eng.on_stream():
+        S.capi.check(S.lib.pf_coarse_setup(S.eng._ref(), C.byref(dc.record), lin.data_ptr(), S.eng._stream()), "pf_coarse_setup")
+    torch.cuda.synchronize()
+    lin = lin.cpu().numpy().reshape(got.shape)
+    Za = abs(tl.z_matrix(cs))
+    scale = (Za.T @ (Kabs @ Za)).toarray()
+    print(f"{name}: |A_c,t(0) - A_c| worst {np.max(np.abs(got - lin) / np.maximum(scale, 1e-300)):.2e} of |Z|^T|K||Z|")
+    assert np.all(np.abs(got - lin) <= 1e-6 * scale)
+    assert np.max(np.abs(got - lin)) <= 1e-6 * np.max(np.abs(lin))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the Warren cantilever of the issue, at the final Newton state of its CPU run
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def warren():
+    case = tt.warren_case()
+    S = Sys(case.nodes, case.el, case.fixed, 2, loads=case.loads)
+    u = case.states[-1][0]
+    S.eng.gl_state(S.dev(u))
+    yield case, S, u
+    torch.cuda.empty_cache()
+
+
+class Run2t:
+    """One pf_pcg2t_begin with test-owned x / ws, on the engine's kt and a DeviceCoarse."""
+
+    def __init__(self, S, dc, b, rtol=RTOL):
+        self.S, eng = S, S.eng
+        self.head = (eng._ref(), C.byref(dc.record), eng._gl[1].data_ptr())
+        self.b = S.dev(b)
+        self.x = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
+        self.ws = torch.full((int(S.lib.pf_pcg2_workspace_count(eng._ref())),), 7.0, dtype=torch.float64, device=eng.device)
+        with eng.on_stream():
+            S.capi.check(S.lib.pf_pcg2t_begin(*self.head, self.b.data_ptr(), self.x.data_ptr(), self.ws.data_ptr(), float(rtol),
+                                              eng._stream()), "pf_pcg2t_begin")
+
+    def iterate(self, k):
+        S, st = self.S, (C.c_double * 4)()
+        with S.eng.on_stream():
+            S.capi.check(S.lib.pf_pcg2t_iterations(*self.head, self.x.data_ptr(), self.ws.data_ptr(), int(k), st,
+                                                   S.eng._stream()), "pf_pcg2t_iterations")
+        return tuple(st)
+
+    def state(self):
+        S, st = self.S, (C.c_double * 4)()
+        with S.eng.on_stream():
+            S.capi.check(S.lib.pf_pcg2t_state(self.head[0], self.head[2], self.ws.data_ptr(), st, S.eng._stream()), "pf_pcg2t_state")
+        return tuple(st)
+
+    def graph(self, n_iter):
+        S, g = self.S, C.c_void_p()
+        with S.eng.on_stream():
+            S.capi.check(S.lib.pf_pcg2t_graph_create(*self.head, self.x.data_ptr(), self.ws.data_ptr(), int(n_iter),
+                                                     S.eng._stream(), C.byref(g)), "pf_pcg2t_graph_create")
+        return g
+
+    def replay(self, g):
+        S = self.S
+        with S.eng.on_stream():
+            S.capi.check(S.lib.pf_graph_launch(g, S.eng._stream()), "pf_graph_launch")
+        return self.state()
+
+    def read(self):
+        torch.cuda.synchronize()
+        return self.x.cpu().numpy(), self.ws.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# B. argument errors
+# ---------------------------------------------------------------------------------------------------------------------
+def test_null_tangent_or_coarse_space_is_an_argument_error(warren):
+    case, S, u = warren
+    eng, lib, capi = S.eng, S.lib, S.capi
+    dc = eng.updated_coarse_space(S.dev(u), case.n_agg)
+    assert dc is not None
+    b = S.dev(case.unit)
+    x = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
+    ws = torch.full((int(lib.pf_pcg2_workspace_count(eng._ref())),), 7.0, dtype=torch.float64, device=eng.device)
+    ac = torch.full((dc.space.n_coarse ** 2,), 7.0, dtype=torch.float64, device=eng.device)
+    st, g, s, P = (C.c_double * 4)(), C.c_void_p(), eng._stream(), eng._ref()
+    kt, cc, bp, xp, wp, ap = eng._gl[1].data_ptr(), C.byref(dc.record), b.data_ptr(), x.data_ptr(), ws.data_ptr(), ac.data_ptr()
+    no_inv = capi.PfCoarse.from_buffer_copy(dc.record)
+    no_inv.a_inv = None
+    odd = capi.PfCoarse.from_buffer_copy(dc.record)
+    odd.n_coarse = 3 * dc.record.n_agg + 1
+    calls = {
+        "pf_coarse_setup_t": lambda c, k: lib.pf_coarse_setup_t(P, c, k, ap, s),
+        "pf_pcg2t_begin": lambda c, k: lib.pf_pcg2t_begin(P, c, k, bp, xp, wp, RTOL, s),
+        "pf_pcg2t_iterations": lambda c, k: lib.pf_pcg2t_iterations(P, c, k, xp, wp, 1, st, s),
+        "pf_pcg2t_graph_create": lambda c, k: lib.pf_pcg2t_graph_create(P, c, k, xp, wp, 4, s, C.byref(g)),
+    }
+    with eng.on_stream():
+        for name, call in calls.items():
+            bad = [(cc, None), (None, kt), (C.byref(odd), kt)]
+            if name != "pf_coarse_setup_t":                            # which does not read a_inv
+                bad.append((C.byref(no_inv), kt))
+            for i, (c, k) in enumerate(bad):
+                assert call(c, k) == capi.PF_ERR_ARG, (name, i)
+                assert lib.pf_last_error().decode().startswith(name + ":"), (name, i)
+        assert lib.pf_pcg2t_state(P, None, wp, st, s) == capi.PF_ERR_ARG
+        assert lib.pf_last_error().decode().startswith("pf_pcg2t_state:")
+        for call in (lambda: lib.pf_pcg2t_begin(P, cc, kt, None, xp, wp, RTOL, s), lambda: lib.pf_pcg2t_begin(P, cc, kt, bp, xp, wp, -1.0, s),
+                     lambda: lib.pf_pcg2t_iterations(P, cc, kt, xp, wp, -1, st, s),
+                     lambda: lib.pf_pcg2t_graph_create(P, cc, kt, xp, wp, 0, s, C.byref(g)),
+                     lambda: lib.pf_coarse_setup_t(P, cc, kt, None, s), lambda: lib.pf_pcg2t_state(P, kt, None, st, s)):
+            assert call() == capi.PF_ERR_ARG
+    assert not g.value
+    torch.cuda.synchronize()
+    for t in (x, ws, ac):                                              # nothing was enqueued
+        assert bool((t == 7.0).all())
+    with pytest.raises(ValueError, match="two-level-updated"):
+        eng.pcg_solve(b, tangent=True, preconditioner="two-level")
+    with pytest.raises(ValueError, match="tangent"):
+        eng.pcg_solve(b, preconditioner="two-level-updated", u=S.dev(u))
+    with pytest.raises(ValueError, match="needs u"):
+        eng.pcg_solve(b, tangent=True, preconditioner="two-level-updated")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# C. one tangent solve
+# ---------------------------------------------------------------------------------------------------------------------
+def test_two_level_updated_solves_the_tangent_system(warren):
+    """Warren 100 panels / 32 aggregates at the last Newton state of the CPU run, rhs = the unit tip load.  Measured: scipy's
+    CG takes 80 iterations with the restated two-level preconditioner, the device 80, and the device's Jacobi solve of
+    the same tangent 981: the bound of an eighth leaves the 1.25 margin on both."""
+    case, S, u = warren
+    k = len(case.states) - 1
+    y, it_ref, info = tt.cg_state(case, k, "current", b=case.unit)
+    assert info == 0
+    K = case.states[k][1]
+    direct = tl.direct_solve(K, case.mask, case.unit)
+    scale = np.max(np.abs(direct))
+    err_ref = np.max(np.abs(y - direct)) / scale
+    S.eng.gl_state(S.dev(u))
+    b = S.dev(case.unit)
+    x, it, ok, rr, bb = S.eng.pcg_solve(b, rtol=RTOL, tangent=True, preconditioner="two-level-updated",
+                                        n_aggregates=case.n_agg, u=S.dev(u))
+    xj, itj, okj, _, _ = S.eng.pcg_solve(b, rtol=RTOL, tangent=True)
+    torch.cuda.synchronize()
+    x = x.cpu().numpy()
+    err = np.max(np.abs(x - direct)) / scale
+    print(f"two-level-updated: scipy {it_ref} iterations, error {err_ref:.2e} | device {it} iterations, error {err:.2e} | "
+          f"device Jacobi on the tangent {itj} iterations")
+    assert ok and okj and rr <= RTOL ** 2 * bb
+    assert np.all(x[case.mask] == 0.0)
+    assert it <= 1.25 * it_ref
+    assert err <= 10 * err_ref
+    assert it <= itj / 8
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# D. graph replay equals eager launches, bit for bit
+# ---------------------------------------------------------------------------------------------------------------------
+def _same(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])          # x and the whole workspace
+
+
+def test_two_level_tangent_graph_replay_equals_eager_bitwise(warren):
+    case, S, u = warren
+    S.eng.gl_state(S.dev(u))
+    dc = S.eng.updated_coarse_space(S.dev(u), case.n_agg)
+    b = case.unit
+    probe = Run2t(S, dc, b)
+    T = int(probe.iterate(2000)[0])                                 # the stopping iteration
+    assert probe.state()[1] == 1.0
+    poll = next(q for q in (8, 7, 6, 5) if 2 <= T % q <= q - 2)    # the stop fires inside a replay
+    assert T > 4 * poll, T
+    k = -(-T // poll)
+    eager, graphed = Run2t(S, dc, b), Run2t(S, dc, b)
+    g = graphed.graph(poll)
+    try:
+        for i in range(3):
+            st_g = graphed.replay(g)
+        st_e = eager.iterate(3 * poll)
+        assert st_g == st_e == (3.0 * poll, 0.0, st_e[2], st_e[3])
+        assert _same(graphed.read(), eager.read())                  # after 3 polls: x, r, z, p, ap, dinv, partials, state, w, y
+        for i in range(3, k):
+            st_g = graphed.replay(g)
+        st_e = eager.iterate((k - 3) * poll)
+        assert st_g == st_e and st_e[:2] == (float(T), 1.0)         # stopped in mid-replay
+        a, e = graphed.read(), eager.read()
+        assert _same(a, e) and _same(e, probe.read())
+        assert graphed.replay(g) == st_g and eager.iterate(5) == st_e           # after the stop every launch is a no-op
+        assert _same(graphed.read(), a) and _same(eager.read(), e)
+    finally:
+        S.lib.pf_graph_destroy(g)
+    # pcg_solve: the refresh is repeatable to the bit, and the poll size (a graph per poll, or an odd one with an eager
+    # remainder) does not show in the result
+    outs = []
+    for poll_size in (64, 64, 7):
+        x, it, ok, rr, bb = S.eng.pcg_solve(S.dev(b), rtol=RTOL, poll=poll_size, tangent=True, preconditioner="two-level-updated",
+                                            n_aggregates=case.n_agg, u=S.dev(u))
+        outs.append((x.cpu().numpy(), it, ok, rr, bb))
+    for o in outs[1:]:
+        assert np.array_equal(outs[0][0], o[0]) and outs[0][1:] == o[1:]
+    assert np.array_equal(outs[0][0], a[0]) and outs[0][1] == T
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# E. end to end
+# ---------------------------------------------------------------------------------------------------------------------
+def _config(**kw):
+    from pinn_fem_amd.fem.solver import SolverConfig
+    return SolverConfig(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange", nr_preconditioner="two-level-updated",
+                        **kw)
+
+
+def test_solve_warren_cantilever_two_level_updated():
+    """solve() on the Warren 100 case in 4 increments.  The CPU runs: direct-solve Newton [5, 6, 6, 6] iterations; the same
+    loop with scipy's CG and the restated preconditioner 1 577 CG iterations in all."""
+    import pinn_fem_amd.fem.solver as solver
+    from pinn_fem_amd.fem.model import FEMModel, Material
+    case = tt.warren_case()
+    u_cg, its_cg, cg_total = tt.cg_newton()
+    assert case.its == its_cg == [5, 6, 6, 6]
+    model = FEMModel(nodes=case.nodes, elements=case.el, material=Material(tt.YOUNG, tt.AREA, 1.0), loads=case.loads,
+                     fixed_dofs=case.fixed, dimension=2)
+    runs = []
+    inner = solver.solve_nr
+
+    def counting(*a, **k):
+        r = inner(*a, **k)
+        runs.append((int(r.history[-1]["iterations"]), bool(r.converged)))
+        return r
+    solver.solve_nr = counting
+    try:
+        res = solver.solve(model, _config(n_increments=case.n_inc, method="nr", nr_aggregates=case.n_agg))
+    finally:
+        solver.solve_nr = inner
+    eng = model._pf_engine_cache[1]
+    u = res.displacements.reshape(-1)
+    scale = np.max(np.abs(case.u_ref))
+    err_ref, err = np.max(np.abs(u_cg - case.u_ref)) / scale, np.max(np.abs(u - case.u_ref)) / scale
+    print(f"warren cantilever, two-level-updated: tip {u[case.tip]:.6f}, Newton iterations {[r[0] for r in runs]} (CPU "
+          f"{case.its}), CG iterations {eng.pcg_iterations} (scipy {cg_total}), refresh {eng.coarse_refresh_seconds:.3f} s "
+          f"{eng.coarse_refresh_parts}, scipy-CG Newton error {err_ref:.2e}, device error {err:.2e}")
+    assert res.converged and len(runs) == case.n_inc and all(ok for _, ok in runs)
+    assert all(ref <= it <= ref + 1 for (it, _), ref in zip(runs, case.its))
+    assert eng._coarse_updated is not None and eng.coarse_refresh_seconds > 0.0          # the two-level path really ran
+    assert eng.pcg_iterations <= 1.25 * cg_total
+    R = res.reactions.reshape(-1, 2)
+    total = np.sum(case.loads.reshape(-1, 2), axis=0)
+    print(f"reactions {R.sum(axis=0)} against loads {total}")
+    assert np.all(R.reshape(-1)[case.free] == 0.0)
+    assert np.all(np.abs(R.sum(axis=0) + total) <= 1e-9 * np.linalg.norm(total))
+    assert err <= 10 * err_ref
+
+
+def test_cli_two_level_updated_keys(tmp_path):
+    from pinn_fem_amd.cli import generic as g
+    with open(os.path.join(HERE, "nl_inputs", "two_bar_green_lagrange.json")) as f:
+        data = json.load(f)
+    data["accel"] = dict(data["accel"], kinematics="green-lagrange", nr_preconditioner="two-level-updated", nr_aggregates=1)
+    (tmp_path / "two_bar.json").write_text(json.dumps(data))
+    g.main(["generic.py", str(tmp_path / "two_bar.json")])
+    got = np.array(json.loads((tmp_path / "two_bar.res.json").read_text())["displacements"]).reshape(-1)
+    tb = gl.TwoBar(ea=1000.0)
+    p = 0.5 * tb.p_lim
+    print(f"CLI two-level-updated: {got}, P(w)/P - 1 = {tb.load(-got[5]) / p - 1:.3e}")
+    assert 0.0 < -got[5] < tb.w_lim and abs(tb.load(-got[5]) / p - 1.0) <= 1e-9
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# F. fallback
+# ---------------------------------------------------------------------------------------------------------------------
+def test_indefinite_coarse_matrix_warns_and_the_step_is_refused():
+    """The indefinite two-bar state of test_gl_f64.py::test_non_positive_definite_tangent_is_refused (apex at the supports'
+    level, vertical tangent -0.985): the coarse matrix is K_t,ff in another basis, Cholesky refuses it, the step runs with
+    Jacobi on the tangent and solve_nr's rhs.du > 0 test raises as before.  Arithmetic on a 2-dof system."""
+    from pinn_fem_amd.fem.model import FEMModel, Material
+    from pinn_fem_amd.fem.solver import solve_nr
+    tb = gl.TwoBar(ea=1000.0)
+    model = FEMModel(nodes=tb.nodes, elements=tb.el, material=Material(2000.0, 0.5, 1.0), loads=tb.loads(0.1),
+                     fixed_dofs=tb.fixed, dimension=2)
+    u0 = np.zeros(6)
+    u0[5] = -tb.h
+    with pytest.warns(RuntimeWarning, match="Jacobi"), pytest.raises(RuntimeError, match="not positive definite"):
+        solve_nr(model, _config(), 1.0, u_initial=torch.from_numpy(u0))

@@ -2,11 +2,14 @@
 """solve_nr (matrix-free float64 K v + preconditioned CG on the device) on Warren girders of growing size; for the
 smaller ones also the oracle's dense float64 restatement of the reference (np.linalg.solve) on the host.
 
-    nr_scale.py [--preconditioner jacobi|two-level] [--aggregates N] [--kinematics linear|green-lagrange] [panels ...]
+    nr_scale.py [--preconditioner jacobi|two-level|two-level-updated] [--aggregates N]
+                [--kinematics linear|green-lagrange] [panels ...]
 
 The timed solve includes the two-level preconditioner's setup (coarse space, Z^T K Z, its inverse).  With
---kinematics green-lagrange the same girders run the large-displacement element (Jacobi only; the dense comparison is
-of the linear problem and is left out)."""
+--kinematics green-lagrange the same girders run the large-displacement element (jacobi or two-level-updated; the dense
+comparison is of the linear problem and is left out).  two-level-updated refreshes its coarse space at every Newton
+iteration: the row reports the seconds spent there (refresh_seconds) and their parts: host columns, setup launch with
+the read-back, Cholesky and inverse, upload."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,11 +20,13 @@ from pinn_fem_amd.fem.solver import SolverConfig, solve_nr
 from pinn_fem_amd.plan import warren_mesh
 import torch
 ap = argparse.ArgumentParser()
-ap.add_argument("--preconditioner", default="jacobi", choices=["jacobi", "two-level"])
+ap.add_argument("--preconditioner", default="jacobi", choices=["jacobi", "two-level", "two-level-updated"])
 ap.add_argument("--aggregates", type=int, default=None)
 ap.add_argument("--kinematics", default="linear", choices=["linear", "green-lagrange"])
 ap.add_argument("panels", nargs="*", type=int)
 args = ap.parse_args()
+if args.preconditioner == "two-level-updated" and args.kinematics != "green-lagrange":
+    ap.error("--preconditioner two-level-updated goes with --kinematics green-lagrange only")
 rows = []
 for panels in args.panels or [100, 1000, 5000]:
     nodes, el, loads, fixed, mv, md = warren_mesh(panels)
@@ -40,10 +45,14 @@ for panels in args.panels or [100, 1000, 5000]:
     torch.cuda.synchronize(); t0 = time.perf_counter()
     res = solve_nr(model, cfg, lam)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    eng = model._pf_engine_cache[1]
     row = {"panels": panels, "elements": len(el), "dofs": 2 * len(nodes), "preconditioner": args.preconditioner,
            "kinematics": args.kinematics, "load_factor": lam,
            "hip_seconds": dt, "converged": bool(res.converged), "nr_iterations": res.history[-1]["iterations"],
-           "cg_iterations": model._pf_engine_cache[1].pcg_iterations}
+           "cg_iterations": eng.pcg_iterations}
+    if args.preconditioner == "two-level-updated":
+        row["refresh_seconds"] = eng.coarse_refresh_seconds
+        row["refresh_parts"] = dict(eng.coarse_refresh_parts)
     if 2 * len(nodes) <= 4100 and args.kinematics == "linear":
         from oracle import pinn_oracle as orc
         pb = orc.Problem(nodes=nodes, elements=el, loads=loads, fixed_dofs=fixed, dimension=2, young=2.0, area=0.5, density=1.0)
