@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-/* 9 still covers pf_coarse_setup_t and pf_pcg2t_*: they are additive (new symbols only, no struct or signature changed), so
+/* 9 still covers pf_coarse_setup_t, pf_pcg2t_*, pf_pcgtm_* and pf_pcg2tm_*: they are additive (new symbols only, no struct or signature changed), so
  * a binding built against the earlier 9 keeps working; a binding that needs them finds them by name */
 #define PF_ABI_VERSION 9
 
@@ -492,6 +492,30 @@ int pf_pcg2t_iterations(const pf_problem* p, const pf_coarse* c, const double* k
 int pf_pcg2t_graph_create(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
                           void* stream, void** graph_out);
 int pf_pcg2t_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream);
+/* m right-hand sides through the same launches: pf_pcgt_* / pf_pcg2t_* with every launch given grid (blocks, m), right-hand
+ * side k = blockIdx.y.  b and x are dev double [m][n_dofs]; ws is m complete workspaces, one after the other
+ * (pf_pcg_workspace_count doubles each for pf_pcgtm_*, pf_pcg2_workspace_count for pf_pcg2tm_*), so every right-hand side
+ * has its own vectors, partial sums and state; kt, the coarse space and a_inv are shared.  Each right-hand side runs the
+ * arithmetic of its own single solve in the same order (bit for bit), stops by its own test and from then on returns at
+ * kernel entry while the others go on; state_out is host double [m][4].  The graph is still one chain of kernel nodes.
+ * 1 <= m <= PF_PCG_MAX_RHS; a bad m, a null kt or (pf_pcg2tm_*) a bad coarse space is PF_ERR_ARG before anything is
+ * enqueued.  The caller is displacement control in the Newton solve: K' a = f' and K' b = -R' - ... per iteration cost
+ * the launches of one solve.  There is no batch of the linear operator (nothing calls one). */
+#define PF_PCG_MAX_RHS 2
+int pf_pcgtm_begin(const pf_problem* p, const double* kt, int m, const double* b, double* x, double* ws, double rtol,
+                   void* stream);
+int pf_pcgtm_iterations(const pf_problem* p, const double* kt, int m, double* x, double* ws, int n_iter, double* state_out,
+                        void* stream);
+int pf_pcgtm_graph_create(const pf_problem* p, const double* kt, int m, double* x, double* ws, int n_iter, void* stream,
+                          void** graph_out);
+int pf_pcgtm_state(const pf_problem* p, const double* kt, int m, double* ws, double* state_out, void* stream);
+int pf_pcg2tm_begin(const pf_problem* p, const pf_coarse* c, const double* kt, int m, const double* b, double* x, double* ws,
+                    double rtol, void* stream);
+int pf_pcg2tm_iterations(const pf_problem* p, const pf_coarse* c, const double* kt, int m, double* x, double* ws, int n_iter,
+                         double* state_out, void* stream);
+int pf_pcg2tm_graph_create(const pf_problem* p, const pf_coarse* c, const double* kt, int m, double* x, double* ws, int n_iter,
+                           void* stream, void** graph_out);
+int pf_pcg2tm_state(const pf_problem* p, const double* kt, int m, double* ws, double* state_out, void* stream);
 
 /* ---- scalar (E, A) identification: the device loop of pinn_inverse_problem_gd -------------------------------------
  * FEM/python/api_pinn_gradient_descent.py:102-121 calls pinn_inverse_problem_gd(nodes, elements, f_ext, fixed_dofs,

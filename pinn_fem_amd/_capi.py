@@ -27,6 +27,7 @@ PF_NODE_SLOTS = PF_MAX_NODE_BLOCKS + 8
 PF_KERNEL_SLOTS = 9
 PF_COARSE_MAX_AGG, PF_COARSE_MODES = 256, 3
 PF_COARSE_MAX = PF_COARSE_MAX_AGG * PF_COARSE_MODES
+PF_PCG_MAX_RHS = 2
 PF_GRAPH_CONT_HEAD, PF_GRAPH_NO_TAIL = 1, 2
 PF_GRAPH_FORM_FOLDED_RESIDUAL = 1
 PF_FUSED_FORWARD, PF_FUSED_BACKWARD, PF_FUSED_THETA_UPDATE, PF_FUSED_U_PINGPONG, PF_FUSED_U_UPDATE = 1, 2, 4, 8, 16
@@ -181,6 +182,19 @@ SYMBOLS = {
     "pf_pcg2t_graph_create": (C.c_int, [_PP, _PC, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                         C.POINTER(C.c_void_p)]),
     "pf_pcg2t_state": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "pf_pcgtm_begin": (C.c_int, [_PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "pf_pcgtm_iterations": (C.c_int, [_PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double),
+                                      C.c_void_p]),
+    "pf_pcgtm_graph_create": (C.c_int, [_PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.POINTER(C.c_void_p)]),
+    "pf_pcgtm_state": (C.c_int, [_PP, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "pf_pcg2tm_begin": (C.c_int, [_PP, _PC, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                  C.c_void_p]),
+    "pf_pcg2tm_iterations": (C.c_int, [_PP, _PC, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.POINTER(C.c_double), C.c_void_p]),
+    "pf_pcg2tm_graph_create": (C.c_int, [_PP, _PC, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.POINTER(C.c_void_p)]),
+    "pf_pcg2tm_state": (C.c_int, [_PP, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "pf_comm_unique_id": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pf_comm_create": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pf_comm_destroy": (C.c_int, [C.c_void_p]),

@@ -85,6 +85,9 @@ def parse_problem(problem_file):
     #           "nr_aggregates": N,                   aggregates of the two-level coarse space (default: by mesh size)
     #           "kinematics": "linear"|"green-lagrange"}  element of Newton-Raphson: small displacements (default) or the
     #                                                 total-Lagrangian large-displacement truss
+    #           "nr_control": {"dof": g, "displacement": d}}  displacement control of the green-lagrange Newton solve: the
+    #                                                 global dof g goes to d over the increments and the load factor is
+    #                                                 solved for (the .res.json gains "equilibrium_path"); absent: load control
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -198,7 +201,13 @@ def _solver_config_from(data):
         method = "hybrid"
     else:
         method = "auto"
+    control = accel.get("nr_control")
+    if control is not None and not (isinstance(control, dict) and set(control) == {"dof", "displacement"}):
+        raise ValueError('accel.nr_control must be {"dof": <global dof>, "displacement": <value at the last increment>}')
     return SolverConfig(
+        nr_control="load" if control is None else "displacement",
+        nr_control_dof=None if control is None else int(control["dof"]),
+        nr_control_displacement=0.0 if control is None else float(control["displacement"]),
         max_iterations=pc.get("max_iterations", sc.get("max_iterations", 1000)),
         tolerance=pc.get("tolerance", sc.get("tolerance", 1e-6)),
         print_every=pc.get("print_every", 10),
@@ -326,6 +335,8 @@ def solve_problem(parsed_data):
         "iterations": len(result.history),
         "history": result.history,
     }
+    if result.path is not None:             # displacement control: (control displacement, load factor) per increment
+        output["equilibrium_path"] = result.path
     if compact:
         # §8(f) rank 1: at 10^6 nodes the reference's JSON lists (every coordinate three times per
         # property) would be hundreds of MB; arrays go to a side file, the JSON keeps the small fields

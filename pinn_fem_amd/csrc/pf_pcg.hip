@@ -98,12 +98,25 @@ __device__ __forceinline__ double block_sum64(double v, double* smem) {
   return t;
 }
 
+// ---- several right-hand sides per launch ----------------------------------------------------------------------------
+// Every CG kernel below serves right-hand side k = blockIdx.y of a launch with grid (blocks, m): its b and x are rows k of
+// [m][n_dofs] arrays (stride xs = n_dofs) and every part of its workspace lies wss doubles behind the same part of
+// right-hand side 0 (wss = the family's workspace count, so state and partial sums are its own).  kt, the coarse space
+// and a_inv are shared.  m = 1 (the four single families): blockIdx.y = 0 and every pointer is the caller's.
+template <class T>
+__device__ __forceinline__ T* rhs_of(T* base, long long stride) {
+  return base + (size_t)blockIdx.y * (size_t)stride;
+}
+
 // x = 0, r = b (free dofs), dinv = 1/diag(K_ff), z = dinv*r, p = z; partials of r.z and b.b
 template <int DIM>
 __global__ __launch_bounds__(256) void k_pcg_init(pf_problem P, const double* __restrict__ kt, const double* __restrict__ b,
-                                                  double* x, double* r, double* z, double* p, double* dinv, double* part) {
+                                                  double* x, double* r, double* z, double* p, double* dinv, double* part,
+                                                  long long wss) {
   __shared__ double red[8];
   const pf_mesh& M = P.mesh;
+  b = rhs_of(b, M.n_dofs); x = rhs_of(x, M.n_dofs);
+  r = rhs_of(r, wss); z = rhs_of(z, wss); p = rhs_of(p, wss); dinv = rhs_of(dinv, wss); part = rhs_of(part, wss);
   double rz = 0.0, bb = 0.0;
   for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < M.n_nodes; node += gridDim.x * blockDim.x) {
     double kv[2], dg[2];
@@ -127,8 +140,11 @@ __global__ __launch_bounds__(256) void k_pcg_init(pf_problem P, const double* __
 // ap = K p (fixed rows zero); partial p.ap
 template <int DIM>
 __global__ __launch_bounds__(256) void k_pcg_ap(pf_problem P, const double* __restrict__ kt, const double* __restrict__ st,
-                                                const double* __restrict__ p, double* __restrict__ ap, double* part) {
+                                                const double* __restrict__ p, double* __restrict__ ap, double* part,
+                                                long long wss) {
+  st = rhs_of(st, wss);
   if (st[ST_DONE] != 0.0) return;
+  p = rhs_of(p, wss); ap = rhs_of(ap, wss); part = rhs_of(part, wss);
   __shared__ double red[8];
   const pf_mesh& M = P.mesh;
   double pap = 0.0;
@@ -150,7 +166,8 @@ __global__ __launch_bounds__(256) void k_pcg_ap(pf_problem P, const double* __re
 // one block: phase 0 (after init) rz, bb | phase 1 (after ap) pAp -> alpha | phase 2 (after update) rz_new, rr ->
 // beta, stop test.  rtol2 is read in phase 0 only (it is stored in the state for the stop tests that follow)
 __global__ __launch_bounds__(1024) void k_pcg_scalars(double* st, const double* __restrict__ part, int nb, int phase,
-                                                      double rtol2) {
+                                                      double rtol2, long long wss) {
+  st = rhs_of(st, wss); part = rhs_of(part, wss);
   if (phase != 0 && st[ST_DONE] != 0.0) return;
   __shared__ double red[16];
   double a = 0.0, b = 0.0;
@@ -173,8 +190,11 @@ __global__ __launch_bounds__(1024) void k_pcg_scalars(double* st, const double* 
 // x += alpha p; r -= alpha ap; z = dinv r; partials r.z, r.r
 __global__ __launch_bounds__(256) void k_pcg_update(const double* __restrict__ st, int n, double* x, double* r, double* z,
                                                     const double* __restrict__ p, const double* __restrict__ ap,
-                                                    const double* __restrict__ dinv, double* part) {
+                                                    const double* __restrict__ dinv, double* part, long long wss) {
+  st = rhs_of(st, wss);
   if (st[ST_DONE] != 0.0) return;
+  x = rhs_of(x, n); r = rhs_of(r, wss); z = rhs_of(z, wss); p = rhs_of(p, wss); ap = rhs_of(ap, wss);
+  dinv = rhs_of(dinv, wss); part = rhs_of(part, wss);
   __shared__ double red[8];
   const double alpha = st[ST_ALPHA];
   double rz = 0.0, rr = 0.0;
@@ -191,8 +211,11 @@ __global__ __launch_bounds__(256) void k_pcg_update(const double* __restrict__ s
 }
 
 // p = z + beta p
-__global__ __launch_bounds__(256) void k_pcg_dir(const double* __restrict__ st, int n, const double* __restrict__ z, double* p) {
+__global__ __launch_bounds__(256) void k_pcg_dir(const double* __restrict__ st, int n, const double* __restrict__ z, double* p,
+                                                 long long wss) {
+  st = rhs_of(st, wss);
   if (st[ST_DONE] != 0.0) return;
+  z = rhs_of(z, wss); p = rhs_of(p, wss);
   const double beta = st[ST_BETA];
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = z[i] + beta * p[i];
 }
@@ -321,8 +344,12 @@ __global__ __launch_bounds__(256) void k_coarse_setup(pf_problem P, const double
 template <int DIM>
 __global__ __launch_bounds__(256) void k_pcg2_restrict(pf_coarse C, const double* __restrict__ st, int update, double* x,
                                                        double* r, const double* __restrict__ p,
-                                                       const double* __restrict__ ap, double* __restrict__ w, double* part) {
+                                                       const double* __restrict__ ap, double* __restrict__ w, double* part,
+                                                       long long xs, long long wss) {
+  st = rhs_of(st, wss);
   if (st[ST_DONE] != 0.0) return;
+  x = rhs_of(x, xs); r = rhs_of(r, wss); p = rhs_of(p, wss); ap = rhs_of(ap, wss); w = rhs_of(w, wss);
+  part = rhs_of(part, wss);
   __shared__ double red[8];
   const int a = blockIdx.x, lo = C.agg_ptr[a], hi = C.agg_ptr[a + 1];
   const int off = C.agg_off[a], nk = C.agg_off[a + 1] - off;
@@ -359,8 +386,12 @@ template <int DIM>
 __global__ __launch_bounds__(256) void k_pcg2_apply(pf_coarse C, const double* __restrict__ st, const double* __restrict__ r,
                                                     const double* __restrict__ dinv, const double* __restrict__ w,
                                                     double* __restrict__ y, double* __restrict__ z, double* p_init,
-                                                    double* part) {
+                                                    double* part, long long wss) {
+  st = rhs_of(st, wss);
   if (st[ST_DONE] != 0.0) return;
+  r = rhs_of(r, wss); dinv = rhs_of(dinv, wss); w = rhs_of(w, wss); y = rhs_of(y, wss); z = rhs_of(z, wss);
+  if (p_init) p_init = rhs_of(p_init, wss);                  // a null p_init stays null
+  part = rhs_of(part, wss);
   __shared__ double red[8];
   __shared__ double ys[PF_COARSE_MODES];
   const int a = blockIdx.x, lo = C.agg_ptr[a], hi = C.agg_ptr[a + 1];
@@ -400,7 +431,8 @@ __global__ __launch_bounds__(256) void k_pcg2_apply(pf_coarse C, const double* _
 }
 
 // r.z of the start (pf_pcg2_begin): k_pcg_scalars' phase 0 stored the Jacobi value
-__global__ __launch_bounds__(256) void k_pcg2_rz0(double* st, const double* __restrict__ part, int nb) {
+__global__ __launch_bounds__(256) void k_pcg2_rz0(double* st, const double* __restrict__ part, int nb, long long wss) {
+  st = rhs_of(st, wss); part = rhs_of(part, wss);
   if (st[ST_DONE] != 0.0) return;
   __shared__ double red[8];
   double a = 0.0;
@@ -412,11 +444,12 @@ __global__ __launch_bounds__(256) void k_pcg2_rz0(double* st, const double* __re
 }  // namespace
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// One implementation behind four exported families: pf_pcg_* (Jacobi), pf_pcg2_* (two-level), pf_pcgt_* (Jacobi on the
-// tangent operator) and pf_pcg2t_* (two-level on the tangent operator) are argument checks in front of pcg_begin_impl /
-// pcg_iterations_impl / pcg_graph_impl / pcg_state_impl, which take the coarse space as a nullable `c` (NULL = Jacobi),
-// the tangent blocks as a nullable `kt` (NULL = the linear operator) and the exported function's name as `who`, the
-// prefix of every error message.  The workspace layout is stated once, in pcg_layout; the iteration's launch sequence
+// One implementation behind six exported families: pf_pcg_* (Jacobi), pf_pcg2_* (two-level), pf_pcgt_* (Jacobi on the
+// tangent operator), pf_pcg2t_* (two-level on the tangent operator) and their forms for m right-hand sides per launch,
+// pf_pcgtm_* and pf_pcg2tm_*, are argument checks in front of pcg_begin_impl / pcg_iterations_impl / pcg_graph_impl /
+// pcg_state_impl, which take the coarse space as a nullable `c` (NULL = Jacobi), the tangent blocks as a nullable `kt`
+// (NULL = the linear operator), the number of right-hand sides `m` (1 for the four single families: grid (blocks, 1)) and
+// the exported function's name as `who`, the prefix of every error message.  The workspace layout is stated once, in pcg_layout; the iteration's launch sequence
 // once, in pcg_enqueue; the CG graphs are captured by the library's capture_graph (pf_graph.h) as a single chain.
 #define PCG_CHECK(who) \
   if (hipGetLastError() != hipSuccess) return pcg_fail(PF_ERR_HIP, who, "HIP launch failed");
@@ -457,6 +490,12 @@ static long long pcg_ws_count(const pf_problem* p, bool two_level) {
   return two_level ? L.end : L.w;
 }
 
+// doubles from one right-hand side's workspace to the next (the family's workspace count)
+static long long pcg_ws_stride(const pf_problem* p, bool two_level) {
+  const PcgLayout<long long> L = pcg_layout(0LL, p->mesh.n_dofs);
+  return two_level ? L.end : L.w;
+}
+
 extern "C" {
 
 static int kv_impl(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, hipStream_t s,
@@ -468,76 +507,89 @@ static int kv_impl(const pf_problem* p, const double* kt, const double* v, doubl
   return PF_OK;
 }
 
-static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x, const PcgWs& L, int update, double* p_init,
-                              hipStream_t s);   // (with the two-level preconditioner's own code, below)
+static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, int m, double* x, const PcgWs& L, int update,
+                              double* p_init, hipStream_t s);   // (with the two-level preconditioner's own code, below)
 
 // x = 0, r = b, dinv, |b|^2 and the b = 0 exit; two-level: then z = M^-1 r, p = z and r.z over the Jacobi start
-static int pcg_begin_impl(const pf_problem* p, const pf_coarse* c, const double* kt, const double* b, double* x, double* ws,
-                          double rtol, hipStream_t s, const char* who) {
+static int pcg_begin_impl(const pf_problem* p, const pf_coarse* c, const double* kt, int m, const double* b, double* x,
+                          double* ws, double rtol, hipStream_t s, const char* who) {
   if (!p || !b || !x || !ws || !(rtol >= 0.0)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
   const PcgWs L = pcg_layout(ws, p->mesh.n_dofs);
+  const long long wss = pcg_ws_stride(p, c != nullptr);
   const int nb = pf_node_blocks(p->mesh.n_nodes);
-  if (hipMemsetAsync(L.st, 0, ((c ? L.end : L.w) - L.st) * sizeof(double), s) != hipSuccess)
-    return pcg_fail(PF_ERR_HIP, who, "state setup failed");
-  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_init<DIM>, dim3(nb), dim3(256), 0, s, *p, kt, b, x, L.r, L.z, L.p, L.dinv, L.part));
+  for (int k = 0; k < m; ++k)
+    if (hipMemsetAsync(L.st + k * wss, 0, ((c ? L.end : L.w) - L.st) * sizeof(double), s) != hipSuccess)
+      return pcg_fail(PF_ERR_HIP, who, "state setup failed");
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_init<DIM>, dim3(nb, m), dim3(256), 0, s, *p, kt, b, x, L.r, L.z, L.p, L.dinv,
+                                    L.part, wss));
   PCG_CHECK(who);
-  hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, L.st, L.part, nb, 0, rtol * rtol);   // by value: no copy, no sync
+  hipLaunchKernelGGL(k_pcg_scalars, dim3(1, m), dim3(1024), 0, s, L.st, L.part, nb, 0, rtol * rtol, wss);   // by value: no copy, no sync
   if (c) {
-    pcg2_precondition(p, c, x, L, 0, L.p, s);
-    hipLaunchKernelGGL(k_pcg2_rz0, dim3(1), dim3(256), 0, s, L.st, L.part, c->n_agg);
+    pcg2_precondition(p, c, m, x, L, 0, L.p, s);
+    hipLaunchKernelGGL(k_pcg2_rz0, dim3(1, m), dim3(256), 0, s, L.st, L.part, c->n_agg, wss);
   }
   PCG_CHECK(who);
   return PF_OK;
 }
 
 // n_iter CG iterations (no-ops once the stop test |r| <= rtol |b| fired).  The preconditioner step is k_pcg_update
-// (one block per 256 dofs) or restrict + apply (one block per aggregate); phase 2 sums that step's partials
-static int pcg_enqueue(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
+// (one block per 256 dofs) or restrict + apply (one block per aggregate); phase 2 sums that step's partials.  Every launch
+// carries the m right-hand sides in grid.y; one that has stopped returns at kernel entry and the others go on
+static int pcg_enqueue(const pf_problem* p, const pf_coarse* c, const double* kt, int m, double* x, double* ws, int n_iter,
                        hipStream_t s, const char* who) {
   const int n = p->mesh.n_dofs, nb = pf_node_blocks(p->mesh.n_nodes);
   const PcgWs L = pcg_layout(ws, n);
+  const long long wss = pcg_ws_stride(p, c != nullptr);
   int nbv = (n + 255) / 256;
   if (nbv > PF_MAX_NODE_BLOCKS) nbv = PF_MAX_NODE_BLOCKS;
   for (int it = 0; it < n_iter; ++it) {
-    PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_ap<DIM>, dim3(nb), dim3(256), 0, s, *p, kt, L.st, L.p, L.ap, L.part));
-    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, L.st, L.part, nb, 1, 0.0);
-    if (c) pcg2_precondition(p, c, x, L, 1, nullptr, s);
-    else hipLaunchKernelGGL(k_pcg_update, dim3(nbv), dim3(256), 0, s, L.st, n, x, L.r, L.z, L.p, L.ap, L.dinv, L.part);
-    hipLaunchKernelGGL(k_pcg_scalars, dim3(1), dim3(1024), 0, s, L.st, L.part, c ? c->n_agg : nbv, 2, 0.0);
-    hipLaunchKernelGGL(k_pcg_dir, dim3(nbv), dim3(256), 0, s, L.st, n, L.z, L.p);
+    PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg_ap<DIM>, dim3(nb, m), dim3(256), 0, s, *p, kt, L.st, L.p, L.ap, L.part, wss));
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1, m), dim3(1024), 0, s, L.st, L.part, nb, 1, 0.0, wss);
+    if (c) pcg2_precondition(p, c, m, x, L, 1, nullptr, s);
+    else hipLaunchKernelGGL(k_pcg_update, dim3(nbv, m), dim3(256), 0, s, L.st, n, x, L.r, L.z, L.p, L.ap, L.dinv, L.part,
+                            wss);
+    hipLaunchKernelGGL(k_pcg_scalars, dim3(1, m), dim3(1024), 0, s, L.st, L.part, c ? c->n_agg : nbv, 2, 0.0, wss);
+    hipLaunchKernelGGL(k_pcg_dir, dim3(nbv, m), dim3(256), 0, s, L.st, n, L.z, L.p, wss);
   }
   PCG_CHECK(who);
   return PF_OK;
 }
 
-// [iterations, stopped, |r|^2, |b|^2] of the running solve (synchronises the stream)
-static int pcg_state_impl(const pf_problem* p, double* ws, double* state_out, hipStream_t s, const char* who) {
+// [iterations, stopped, |r|^2, |b|^2] of the running solve, one row per right-hand side (synchronises the stream once)
+static int pcg_state_impl(const pf_problem* p, bool two_level, int m, double* ws, double* state_out, hipStream_t s,
+                          const char* who) {
   if (!p || !ws || !state_out) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  double h[ST_COUNT];
-  if (hipMemcpyAsync(h, pcg_layout(ws, p->mesh.n_dofs).st, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return pcg_fail(PF_ERR_HIP, who, "state read-back failed");
-  state_out[0] = h[ST_ITERS]; state_out[1] = h[ST_DONE]; state_out[2] = h[ST_RR]; state_out[3] = h[ST_BB];
+  double h[PF_PCG_MAX_RHS][ST_COUNT];
+  const double* st = pcg_layout(ws, p->mesh.n_dofs).st;
+  const long long wss = pcg_ws_stride(p, two_level);
+  for (int k = 0; k < m; ++k)
+    if (hipMemcpyAsync(h[k], st + k * wss, sizeof(h[k]), hipMemcpyDeviceToHost, s) != hipSuccess)
+      return pcg_fail(PF_ERR_HIP, who, "state read-back failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return pcg_fail(PF_ERR_HIP, who, "state read-back failed");
+  for (int k = 0; k < m; ++k) {
+    double* o = state_out + 4 * k;
+    o[0] = h[k][ST_ITERS]; o[1] = h[k][ST_DONE]; o[2] = h[k][ST_RR]; o[3] = h[k][ST_BB];
+  }
   return PF_OK;
 }
 
 // state_out (host, may be NULL) receives the state after a stream synchronisation
-static int pcg_iterations_impl(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
-                               double* state_out, hipStream_t s, const char* who) {
+static int pcg_iterations_impl(const pf_problem* p, const pf_coarse* c, const double* kt, int m, double* x, double* ws,
+                               int n_iter, double* state_out, hipStream_t s, const char* who) {
   if (!p || !x || !ws || n_iter < 0) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  const int rc = pcg_enqueue(p, c, kt, x, ws, n_iter, s, who);
+  const int rc = pcg_enqueue(p, c, kt, m, x, ws, n_iter, s, who);
   if (rc != PF_OK) return rc;
-  return state_out ? pcg_state_impl(p, ws, state_out, s, who) : PF_OK;
+  return state_out ? pcg_state_impl(p, c != nullptr, m, ws, state_out, s, who) : PF_OK;
 }
 
 // the same n_iter iterations as ONE hipGraph (record and pointers baked in; handle for pf_graph_launch /
 // pf_graph_destroy): 5 or 6 tiny launches per CG iteration are launch bound when issued one by one.  A single chain of
 // kernel nodes, no parallel branches: no events, no side stream
-static int pcg_graph_impl(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
+static int pcg_graph_impl(const pf_problem* p, const pf_coarse* c, const double* kt, int m, double* x, double* ws, int n_iter,
                           hipStream_t s, void** graph_out, const char* who) {
   if (!p || !x || !ws || n_iter < 1 || !graph_out) return pcg_fail(PF_ERR_ARG, who, "bad argument");
   return capture_graph(s, 0, hipStreamCaptureModeThreadLocal, graph_out,
-                       [&](pf_capture& cap) { return pcg_enqueue(p, c, kt, x, ws, n_iter, cap.s, who); });
+                       [&](pf_capture& cap) { return pcg_enqueue(p, c, kt, m, x, ws, n_iter, cap.s, who); });
 }
 
 // ---- the two-level preconditioner's own code ----------------------------------------------------------------------
@@ -560,12 +612,13 @@ static int coarse_setup_impl(const pf_problem* p, const pf_coarse* c, const doub
 }
 
 // z = M^-1 r and r.z for the r in the workspace: restriction, then coarse solve + prolongation (two launches)
-static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, double* x, const PcgWs& L, int update, double* p_init,
-                              hipStream_t s) {
-  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg2_restrict<DIM>, dim3(c->n_agg), dim3(256), 0, s, *c, L.st, update, x, L.r, L.p,
-                                    L.ap, L.w, L.part);
-              hipLaunchKernelGGL(k_pcg2_apply<DIM>, dim3(c->n_agg), dim3(256), 0, s, *c, L.st, L.r, L.dinv, L.w, L.y, L.z,
-                                 p_init, L.part));
+static void pcg2_precondition(const pf_problem* p, const pf_coarse* c, int m, double* x, const PcgWs& L, int update,
+                              double* p_init, hipStream_t s) {
+  const long long xs = p->mesh.n_dofs, wss = pcg_ws_stride(p, true);
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_pcg2_restrict<DIM>, dim3(c->n_agg, m), dim3(256), 0, s, *c, L.st, update, x, L.r, L.p,
+                                    L.ap, L.w, L.part, xs, wss);
+              hipLaunchKernelGGL(k_pcg2_apply<DIM>, dim3(c->n_agg, m), dim3(256), 0, s, *c, L.st, L.r, L.dinv, L.w, L.y, L.z,
+                                 p_init, L.part, wss));
 }
 
 // ---- the exported families -----------------------------------------------------------------------------------------
@@ -597,81 +650,130 @@ int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* 
 }
 
 int pf_pcg_begin(const pf_problem* p, const double* b, double* x, double* ws, double rtol, void* stream) {
-  return pcg_begin_impl(p, nullptr, nullptr, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg_begin");
+  return pcg_begin_impl(p, nullptr, nullptr, 1, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg_begin");
 }
 int pf_pcg2_begin(const pf_problem* p, const pf_coarse* c, const double* b, double* x, double* ws, double rtol,
                   void* stream) {
   const char* who = "pf_pcg2_begin";
   if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  return pcg_begin_impl(p, c, nullptr, b, x, ws, rtol, (hipStream_t)stream, who);
+  return pcg_begin_impl(p, c, nullptr, 1, b, x, ws, rtol, (hipStream_t)stream, who);
 }
 int pf_pcgt_begin(const pf_problem* p, const double* kt, const double* b, double* x, double* ws, double rtol,
                   void* stream) {
   PCGT_NEED_KT("pf_pcgt_begin");
-  return pcg_begin_impl(p, nullptr, kt, b, x, ws, rtol, (hipStream_t)stream, "pf_pcgt_begin");
+  return pcg_begin_impl(p, nullptr, kt, 1, b, x, ws, rtol, (hipStream_t)stream, "pf_pcgt_begin");
 }
 
 int pf_pcg2t_begin(const pf_problem* p, const pf_coarse* c, const double* kt, const double* b, double* x, double* ws,
                    double rtol, void* stream) {
   PCG2T_NEED("pf_pcg2t_begin");
-  return pcg_begin_impl(p, c, kt, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg2t_begin");
+  return pcg_begin_impl(p, c, kt, 1, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg2t_begin");
 }
 
 int pf_pcg_iterations(const pf_problem* p, double* x, double* ws, int n_iter, double* state_out, void* stream) {
-  return pcg_iterations_impl(p, nullptr, nullptr, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg_iterations");
+  return pcg_iterations_impl(p, nullptr, nullptr, 1, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg_iterations");
 }
 int pf_pcg2_iterations(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, double* state_out,
                        void* stream) {
   const char* who = "pf_pcg2_iterations";
   if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  return pcg_iterations_impl(p, c, nullptr, x, ws, n_iter, state_out, (hipStream_t)stream, who);
+  return pcg_iterations_impl(p, c, nullptr, 1, x, ws, n_iter, state_out, (hipStream_t)stream, who);
 }
 int pf_pcgt_iterations(const pf_problem* p, const double* kt, double* x, double* ws, int n_iter, double* state_out,
                        void* stream) {
   PCGT_NEED_KT("pf_pcgt_iterations");
-  return pcg_iterations_impl(p, nullptr, kt, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcgt_iterations");
+  return pcg_iterations_impl(p, nullptr, kt, 1, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcgt_iterations");
 }
 
 int pf_pcg2t_iterations(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
                         double* state_out, void* stream) {
   PCG2T_NEED("pf_pcg2t_iterations");
-  return pcg_iterations_impl(p, c, kt, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg2t_iterations");
+  return pcg_iterations_impl(p, c, kt, 1, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg2t_iterations");
 }
 
 int pf_pcg_graph_create(const pf_problem* p, double* x, double* ws, int n_iter, void* stream, void** graph_out) {
-  return pcg_graph_impl(p, nullptr, nullptr, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg_graph_create");
+  return pcg_graph_impl(p, nullptr, nullptr, 1, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg_graph_create");
 }
 int pf_pcg2_graph_create(const pf_problem* p, const pf_coarse* c, double* x, double* ws, int n_iter, void* stream,
                          void** graph_out) {
   const char* who = "pf_pcg2_graph_create";
   if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad argument");
-  return pcg_graph_impl(p, c, nullptr, x, ws, n_iter, (hipStream_t)stream, graph_out, who);
+  return pcg_graph_impl(p, c, nullptr, 1, x, ws, n_iter, (hipStream_t)stream, graph_out, who);
 }
 int pf_pcgt_graph_create(const pf_problem* p, const double* kt, double* x, double* ws, int n_iter, void* stream,
                          void** graph_out) {
   PCGT_NEED_KT("pf_pcgt_graph_create");
-  return pcg_graph_impl(p, nullptr, kt, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcgt_graph_create");
+  return pcg_graph_impl(p, nullptr, kt, 1, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcgt_graph_create");
 }
 
 int pf_pcg2t_graph_create(const pf_problem* p, const pf_coarse* c, const double* kt, double* x, double* ws, int n_iter,
                           void* stream, void** graph_out) {
   PCG2T_NEED("pf_pcg2t_graph_create");
-  return pcg_graph_impl(p, c, kt, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg2t_graph_create");
+  return pcg_graph_impl(p, c, kt, 1, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg2t_graph_create");
 }
 
 int pf_pcg_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
-  return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcg_state");
+  return pcg_state_impl(p, false, 1, ws, state_out, (hipStream_t)stream, "pf_pcg_state");
 }
 int pf_pcg2_state(const pf_problem* p, double* ws, double* state_out, void* stream) {
-  return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcg2_state");
+  return pcg_state_impl(p, true, 1, ws, state_out, (hipStream_t)stream, "pf_pcg2_state");
 }
 int pf_pcgt_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream) {
   PCGT_NEED_KT("pf_pcgt_state");
-  return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcgt_state");
+  return pcg_state_impl(p, false, 1, ws, state_out, (hipStream_t)stream, "pf_pcgt_state");
 }
 int pf_pcg2t_state(const pf_problem* p, const double* kt, double* ws, double* state_out, void* stream) {
   PCGT_NEED_KT("pf_pcg2t_state");
-  return pcg_state_impl(p, ws, state_out, (hipStream_t)stream, "pf_pcg2t_state");
+  return pcg_state_impl(p, true, 1, ws, state_out, (hipStream_t)stream, "pf_pcg2t_state");
+}
+
+// ---- m right-hand sides per launch on the tangent: pf_pcgtm_* (Jacobi), pf_pcg2tm_* (two-level) -----------------------
+// b and x are [m][n_dofs], ws is m workspaces of the family's count, state_out is [m][4]
+#define PCGTM_NEED(who)                                                                                \
+  PCGT_NEED_KT(who);                                                                                   \
+  if (m < 1 || m > PF_PCG_MAX_RHS) return pcg_fail(PF_ERR_ARG, who, "bad right-hand-side count (m)");
+#define PCG2TM_NEED(who)                                                        \
+  PCGTM_NEED(who);                                                              \
+  if (!coarse_ok(c, true)) return pcg_fail(PF_ERR_ARG, who, "bad coarse space");
+
+int pf_pcgtm_begin(const pf_problem* p, const double* kt, int m, const double* b, double* x, double* ws, double rtol,
+                   void* stream) {
+  PCGTM_NEED("pf_pcgtm_begin");
+  return pcg_begin_impl(p, nullptr, kt, m, b, x, ws, rtol, (hipStream_t)stream, "pf_pcgtm_begin");
+}
+int pf_pcgtm_iterations(const pf_problem* p, const double* kt, int m, double* x, double* ws, int n_iter, double* state_out,
+                        void* stream) {
+  PCGTM_NEED("pf_pcgtm_iterations");
+  return pcg_iterations_impl(p, nullptr, kt, m, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcgtm_iterations");
+}
+int pf_pcgtm_graph_create(const pf_problem* p, const double* kt, int m, double* x, double* ws, int n_iter, void* stream,
+                          void** graph_out) {
+  PCGTM_NEED("pf_pcgtm_graph_create");
+  return pcg_graph_impl(p, nullptr, kt, m, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcgtm_graph_create");
+}
+int pf_pcgtm_state(const pf_problem* p, const double* kt, int m, double* ws, double* state_out, void* stream) {
+  PCGTM_NEED("pf_pcgtm_state");
+  return pcg_state_impl(p, false, m, ws, state_out, (hipStream_t)stream, "pf_pcgtm_state");
+}
+
+int pf_pcg2tm_begin(const pf_problem* p, const pf_coarse* c, const double* kt, int m, const double* b, double* x, double* ws,
+                    double rtol, void* stream) {
+  PCG2TM_NEED("pf_pcg2tm_begin");
+  return pcg_begin_impl(p, c, kt, m, b, x, ws, rtol, (hipStream_t)stream, "pf_pcg2tm_begin");
+}
+int pf_pcg2tm_iterations(const pf_problem* p, const pf_coarse* c, const double* kt, int m, double* x, double* ws, int n_iter,
+                         double* state_out, void* stream) {
+  PCG2TM_NEED("pf_pcg2tm_iterations");
+  return pcg_iterations_impl(p, c, kt, m, x, ws, n_iter, state_out, (hipStream_t)stream, "pf_pcg2tm_iterations");
+}
+int pf_pcg2tm_graph_create(const pf_problem* p, const pf_coarse* c, const double* kt, int m, double* x, double* ws, int n_iter,
+                           void* stream, void** graph_out) {
+  PCG2TM_NEED("pf_pcg2tm_graph_create");
+  return pcg_graph_impl(p, c, kt, m, x, ws, n_iter, (hipStream_t)stream, graph_out, "pf_pcg2tm_graph_create");
+}
+int pf_pcg2tm_state(const pf_problem* p, const double* kt, int m, double* ws, double* state_out, void* stream) {
+  PCGTM_NEED("pf_pcg2tm_state");
+  return pcg_state_impl(p, true, m, ws, state_out, (hipStream_t)stream, "pf_pcg2tm_state");
 }
 
 }  // extern "C"

@@ -222,6 +222,8 @@ class HipEngine:
         self._coarse_updated = None     # (aggregation key, DeviceCoarse, A_c buffer) of preconditioner "two-level-updated"
         self.coarse_refresh_seconds = 0.0   # host seconds in the refreshes of that space so far, and their parts
         self.coarse_refresh_parts = dict(columns=0.0, setup=0.0, factor=0.0, upload=0.0)
+        self.pcg_batch_solves = 0       # pcg_solve_batch calls so far
+        self._fixed_views = {}          # extra fixed dofs (tuple) -> (device dof_flags copy, PfProblem view, host fixed mask)
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
         self._configured = False
         env_k = os.environ.get("PINNFEM_GRAPH_ITERS")
@@ -307,6 +309,28 @@ class HipEngine:
 
     def _ref(self):
         return C.byref(self.P)
+
+    def _fixed_view(self, extra_fixed):
+        """(pf_problem reference, host mask of the fixed dofs, key) with the dofs of extra_fixed constrained on top of the
+        model's: a second device copy of dof_flags with PF_DOF_FIXED set on them and a PfProblem record that points at it,
+        cached per dof tuple.  The plan, the engine's own flags and its record are never modified.  None or empty: the
+        engine's own record."""
+        hp = self.plan
+        fixed = (hp.dof_flags & _capi.PF_DOF_FIXED) != 0
+        if extra_fixed is None or len(extra_fixed) == 0:
+            return self._ref(), fixed, ()
+        key = tuple(sorted({int(d) for d in extra_fixed}))
+        if key[0] < 0 or key[-1] >= hp.n_dofs:
+            raise ValueError(f"extra_fixed: dofs {key} are not all in 0..{hp.n_dofs - 1}")
+        if key not in self._fixed_views:
+            flags = np.array(hp.dof_flags, copy=True)
+            flags[list(key)] |= _capi.PF_DOF_FIXED
+            mask = (flags & _capi.PF_DOF_FIXED) != 0
+            self._fixed_views[key] = (torch.from_numpy(np.ascontiguousarray(flags)).to(self.device), PfProblem(), mask)
+        flags_t, view, mask = self._fixed_views[key]
+        C.memmove(C.byref(view), C.byref(self.P), C.sizeof(PfProblem))      # the record as configured now
+        view.mesh.dof_flags = flags_t.data_ptr()
+        return C.byref(view), mask, key
 
     def fusion_info(self) -> int:
         """Bit mask of the fused launches of this problem (_capi.PF_FUSED_*)."""
@@ -604,28 +628,24 @@ class HipEngine:
         return out
 
     @_on_engine_stream
-    def kt_v_f64(self, v: torch.Tensor, zero_fixed: bool = False) -> torch.Tensor:
-        """K_t(u) v in float64 with the tangent blocks of the last gl_state (pf_kt_v_f64)."""
+    def kt_v_f64(self, v: torch.Tensor, zero_fixed: bool = False, extra_fixed=None) -> torch.Tensor:
+        """K_t(u) v in float64 with the tangent blocks of the last gl_state (pf_kt_v_f64).  extra_fixed: dofs that
+        zero_fixed treats as fixed on top of the model's (_fixed_view)."""
         kt = self._gl_ready("kt_v_f64")[1]
         vv = v.to(device=self.device, dtype=torch.float64).contiguous()
         out = torch.empty(self.plan.n_dofs, dtype=torch.float64, device=self.device)
-        _capi.check(self.lib.pf_kt_v_f64(self._ref(), kt.data_ptr(), vv.data_ptr(), out.data_ptr(), int(zero_fixed),
+        _capi.check(self.lib.pf_kt_v_f64(self._fixed_view(extra_fixed)[0], kt.data_ptr(), vv.data_ptr(), out.data_ptr(), int(zero_fixed),
                                          self._stream()), "pf_kt_v_f64")
         return out
 
-    @_on_engine_stream
-    def pcg_solve(self, b: torch.Tensor, rtol: float = 1e-13, max_iter: Optional[int] = None, poll: int = 64,
-                  preconditioner: str = "jacobi", n_aggregates: Optional[int] = None, aggregates=None,
-                  tangent: bool = False, u=None):
-        """K_ff x = b by conjugate gradients, float64, on the device.  preconditioner: "jacobi" (diag(K_ff), the
-        default) or "two-level" (Jacobi plus a coarse space of per-aggregate rigid-body modes, coarse.py;
-        n_aggregates strips along the longest axis, or the caller's own node -> aggregate map).  tangent: K is the
-        tangent K_t(u) of the last gl_state, which must be positive definite: pf_pcgt_* with "jacobi", pf_pcg2t_* with
-        "two-level-updated", whose coarse space is rebuilt on X + u at every call (updated_coarse_space; u: the
-        displacements the last gl_state was given).
-        Returns (x with zeros on fixed dofs, iterations, converged, |r|^2, |b|^2)."""
+    def _pcg_setup(self, who, tangent, preconditioner, n_aggregates, aggregates, u, extra_fixed):
+        """What pcg_solve and pcg_solve_batch share before the solve: the preconditioner's checks and coarse space (one
+        refresh per call), the pf_problem reference (the view of extra_fixed) and the tangent blocks.
+        Returns (ref, coarse | None, kt pointer | None)."""
         coarse = None
         name = _coarse.check_preconditioner(preconditioner)
+        if extra_fixed is not None and len(extra_fixed) and not tangent:
+            raise ValueError(f"{who}: extra_fixed belongs to the tangent solve (tangent=True)")
         if name == "two-level":
             if tangent:
                 raise ValueError("the two-level preconditioner of the linear operator has no tangent form: with "
@@ -637,27 +657,22 @@ class HipEngine:
                                  "linear operator has nothing to update; use 'two-level'")
             if u is None:
                 raise ValueError("preconditioner='two-level-updated' needs u, the displacements of the last gl_state")
-            coarse = self.updated_coarse_space(u, n_aggregates, aggregates)     # None: Jacobi on the tangent
-        lib, ref, s = self.lib, self._ref(), self._stream()
-        if tangent:
-            kt = self._gl_ready("pcg_solve(tangent=True)")[1].data_ptr()
-            fam = "pf_pcgt" if coarse is None else "pf_pcg2t"
-            head = (ref, kt) if coarse is None else (ref, C.byref(coarse.record), kt)
-            state_head = (ref, kt)
-        else:
-            fam = "pf_pcg" if coarse is None else "pf_pcg2"
-            head = (ref,) if coarse is None else (ref, C.byref(coarse.record))
-            state_head = (ref,)
-        n = self.plan.n_dofs
-        bb = b.to(device=self.device, dtype=torch.float64).contiguous()
-        x = torch.zeros(n, dtype=torch.float64, device=self.device)
-        ws_count = lib.pf_pcg_workspace_count if coarse is None else lib.pf_pcg2_workspace_count
-        ws = torch.zeros(int(ws_count(ref)), dtype=torch.float64, device=self.device)
+            coarse = self.updated_coarse_space(u, n_aggregates, aggregates, extra_fixed)    # None: Jacobi on the tangent
+        kt = self._gl_ready(f"{who}(tangent=True)")[1].data_ptr() if tangent else None
+        return self._fixed_view(extra_fixed)[0], coarse, kt
+
+    def _pcg_run(self, fam, head, state_head, m, bb, two_level, rtol, max_iter, poll):
+        """begin, then `poll` iterations at a time (one graph replay, or eager launches for a shorter tail) until every
+        one of the m right-hand sides has stopped or max_iter is reached.  Returns (x [m * n_dofs], state [m][4])."""
+        lib, s, n = self.lib, self._stream(), self.plan.n_dofs
+        x = torch.zeros(m * n, dtype=torch.float64, device=self.device)
+        ws_count = lib.pf_pcg2_workspace_count if two_level else lib.pf_pcg_workspace_count
+        ws = torch.zeros(m * int(ws_count(self._ref())), dtype=torch.float64, device=self.device)
         _capi.check(getattr(lib, fam + "_begin")(*head, bb.data_ptr(), x.data_ptr(), ws.data_ptr(), float(rtol), s),
                     fam + "_begin")
         if max_iter is None:
             max_iter = 40 * n + 2000            # slender trusses are beam-like: CG needs far more than n steps
-        st = (C.c_double * 4)()
+        st = (C.c_double * (4 * m))()
         done_it = 0
         graph = C.c_void_p()
         use_graph = os.environ.get("PINNFEM_GRAPH", "1") != "0" and max_iter >= poll
@@ -675,14 +690,68 @@ class HipEngine:
                     _capi.check(getattr(lib, fam + "_iterations")(*head, x.data_ptr(), ws.data_ptr(), int(max(k, 0)), st, s),
                                 fam + "_iterations")
                 done_it += max(k, 0)
-                if st[1] != 0.0 or done_it >= max_iter:
+                if all(st[4 * j + 1] != 0.0 for j in range(m)) or done_it >= max_iter:
                     break
         finally:
             if graph:
                 lib.pf_graph_destroy(graph)
-        self.pcg_iterations += int(st[0])
+        return x, [tuple(st[4 * j: 4 * j + 4]) for j in range(m)]
+
+    @staticmethod
+    def _pcg_report(st, rtol):
         converged = st[2] <= (rtol * rtol) * st[3] * 4.0 or st[3] == 0.0     # |r| <= 2 rtol |b|
-        return x, int(st[0]), bool(converged), float(st[2]), float(st[3])
+        return int(st[0]), bool(converged), float(st[2]), float(st[3])
+
+    @_on_engine_stream
+    def pcg_solve(self, b: torch.Tensor, rtol: float = 1e-13, max_iter: Optional[int] = None, poll: int = 64,
+                  preconditioner: str = "jacobi", n_aggregates: Optional[int] = None, aggregates=None,
+                  tangent: bool = False, u=None, extra_fixed=None):
+        """K_ff x = b by conjugate gradients, float64, on the device.  preconditioner: "jacobi" (diag(K_ff), the
+        default) or "two-level" (Jacobi plus a coarse space of per-aggregate rigid-body modes, coarse.py;
+        n_aggregates strips along the longest axis, or the caller's own node -> aggregate map).  tangent: K is the
+        tangent K_t(u) of the last gl_state, which must be positive definite: pf_pcgt_* with "jacobi", pf_pcg2t_* with
+        "two-level-updated", whose coarse space is rebuilt on X + u at every call (updated_coarse_space; u: the
+        displacements the last gl_state was given).  extra_fixed (tangent only): dofs constrained on top of the model's
+        for this solve, so K_ff loses their rows and columns as well (_fixed_view).
+        Returns (x with zeros on fixed dofs, iterations, converged, |r|^2, |b|^2)."""
+        ref, coarse, kt = self._pcg_setup("pcg_solve", tangent, preconditioner, n_aggregates, aggregates, u, extra_fixed)
+        if tangent:
+            fam = "pf_pcgt" if coarse is None else "pf_pcg2t"
+            head = (ref, kt) if coarse is None else (ref, C.byref(coarse.record), kt)
+            state_head = (ref, kt)
+        else:
+            fam = "pf_pcg" if coarse is None else "pf_pcg2"
+            head = (ref,) if coarse is None else (ref, C.byref(coarse.record))
+            state_head = (ref,)
+        bb = b.to(device=self.device, dtype=torch.float64).contiguous()
+        x, (st,) = self._pcg_run(fam, head, state_head, 1, bb, coarse is not None, rtol, max_iter, poll)
+        self.pcg_iterations += int(st[0])
+        return (x,) + self._pcg_report(st, rtol)
+
+    @_on_engine_stream
+    def pcg_solve_batch(self, B: torch.Tensor, tangent: bool = True, preconditioner: str = "jacobi",
+                        n_aggregates: Optional[int] = None, aggregates=None, u=None, extra_fixed=None,
+                        rtol: float = 1e-13, max_iter: Optional[int] = None, poll: int = 64):
+        """K_t x_k = B[k] for the m rows of B [m, n_dofs] through the launches of ONE solve (pf_pcgtm_* with "jacobi",
+        pf_pcg2tm_* with "two-level-updated"): every launch carries the m right-hand sides, each with its own workspace,
+        stop test and iteration count, and each computes what its own pcg_solve would, bit for bit.  The coarse space is
+        refreshed once per call and shared.  Polls until every right-hand side has stopped.  The tangent operator only.
+        Returns (x [m, n_dofs], [(iterations, converged, |r|^2, |b|^2) per right-hand side])."""
+        if not tangent:
+            raise ValueError("pcg_solve_batch: only the tangent operator has a batched solve (tangent=True)")
+        if B.dim() != 2 or B.shape[1] != self.plan.n_dofs or not 1 <= B.shape[0] <= _capi.PF_PCG_MAX_RHS:
+            raise ValueError(f"pcg_solve_batch: B must be [m, {self.plan.n_dofs}] with 1 <= m <= {_capi.PF_PCG_MAX_RHS}, "
+                             f"got {tuple(B.shape)}")
+        m = int(B.shape[0])
+        ref, coarse, kt = self._pcg_setup("pcg_solve_batch", True, preconditioner, n_aggregates, aggregates, u,
+                                          extra_fixed)
+        fam = "pf_pcgtm" if coarse is None else "pf_pcg2tm"
+        head = (ref, kt, m) if coarse is None else (ref, C.byref(coarse.record), kt, m)
+        bb = B.to(device=self.device, dtype=torch.float64).contiguous()
+        x, states = self._pcg_run(fam, head, (ref, kt, m), m, bb, coarse is not None, rtol, max_iter, poll)
+        self.pcg_iterations += sum(int(st[0]) for st in states)
+        self.pcg_batch_solves += 1
+        return x.reshape(m, -1), [self._pcg_report(st, rtol) for st in states]
 
     def _stiffness_signature(self):
         """What the coarse matrix Z^T K Z was built from: the E and A that elem_s64 reads."""
@@ -723,13 +792,14 @@ class HipEngine:
         return dc
 
     @_on_engine_stream
-    def updated_coarse_space(self, u, n_aggregates: Optional[int] = None, aggregates=None):
+    def updated_coarse_space(self, u, n_aggregates: Optional[int] = None, aggregates=None, extra_fixed=None):
         """The coarse space of preconditioner "two-level-updated" for the tangent of the last gl_state: the rigid-body
         modes of every aggregate at the current configuration X + u (X: the model's float64 coordinates), on the
         aggregation of the reference configuration.  One engine-owned DeviceCoarse is refreshed in place at every call:
         host columns, pf_coarse_setup_t with the engine's kt, read-back, host Cholesky, upload.  There is no cache: K_t
         and X + u change with every Newton iteration.  Returns None, with a RuntimeWarning, when Z^T K_t Z is not positive
-        definite: the caller then runs Jacobi on the tangent."""
+        definite: the caller then runs Jacobi on the tangent.  extra_fixed: dofs constrained on top of the model's
+        (_fixed_view): the columns are zero on them too, so Z^T K_t Z is that of the smaller K_ff."""
         t0 = time.perf_counter()
         hp = self.plan
         if len(self.model.nodes) != hp.n_nodes:
@@ -741,9 +811,9 @@ class HipEngine:
         uu = np.asarray(uu, dtype=np.float64).reshape(-1)
         if uu.size != hp.n_dofs:
             raise ValueError(f"updated_coarse_space: u has {uu.size} entries, the mesh has {hp.n_dofs} dofs")
-        fixed = (hp.dof_flags & _capi.PF_DOF_FIXED) != 0
+        ref, fixed, fixed_key = self._fixed_view(extra_fixed)
         agg_key = None if aggregates is None else np.asarray(aggregates).astype(np.int64).tobytes()
-        key = (None if n_aggregates is None else int(n_aggregates), agg_key)
+        key = (None if n_aggregates is None else int(n_aggregates), agg_key, fixed_key)
         if self._coarse_updated is None or self._coarse_updated[0] != key:
             # the node -> aggregate map: once, on the reference configuration
             first = _coarse.build_coarse_space(X, hp.dim, fixed, n_aggregates, aggregates)
@@ -754,7 +824,7 @@ class HipEngine:
         cs = _coarse.update_coarse_space(X + uu.reshape(hp.n_nodes, hp.dim), hp.dim, fixed, dc.space.node_agg)
         dc.refresh(cs)
         t1 = time.perf_counter()
-        _capi.check(self.lib.pf_coarse_setup_t(self._ref(), C.byref(dc.record), kt.data_ptr(), a_c.data_ptr(),
+        _capi.check(self.lib.pf_coarse_setup_t(ref, C.byref(dc.record), kt.data_ptr(), a_c.data_ptr(),
                                                self._stream()), "pf_coarse_setup_t")
         dc.a_c = a_c[: cs.n_coarse ** 2].cpu().numpy().reshape(cs.n_coarse, cs.n_coarse)
         t2 = time.perf_counter()

@@ -55,9 +55,16 @@ class SolverConfig:
     # kinematics of solve_nr: "linear" (small displacements, the reference's element) or "green-lagrange" (total-Lagrangian
     # truss element for large displacements: the tangent depends on u and the Newton loop really iterates)
     kinematics: str = "linear"
+    # what solve_nr prescribes: "load" (the load factor; the default) or "displacement" (Green-Lagrange only: the global
+    # dof nr_control_dof is held at factor * nr_control_displacement and the load factor is solved for, which carries the
+    # solve through a limit point of the load)
+    nr_control: str = "load"
+    nr_control_dof: Optional[int] = None
+    nr_control_displacement: float = 0.0
 
 
 KINEMATICS = ("linear", "green-lagrange")
+NR_CONTROLS = ("load", "displacement")
 
 
 def check_kinematics(name, nr_preconditioner: str = "jacobi") -> str:
@@ -75,6 +82,44 @@ def check_kinematics(name, nr_preconditioner: str = "jacobi") -> str:
     return name
 
 
+def check_control(config, model=None, method: str = "nr") -> str:
+    """The control name of solve_nr, checked.  Displacement control needs the Green-Lagrange kinematics, the Newton solve
+    and, when a model is given, scalar materials, one GPU, a free control dof, a non-zero control displacement and loads
+    that are not all zero on the free dofs: every violation is a ValueError before an engine is built."""
+    name = getattr(config, "nr_control", "load")
+    if name not in NR_CONTROLS:
+        raise ValueError(f"unknown nr_control {name!r}: accepted values are 'load' and 'displacement'")
+    if name == "load":
+        return name
+    if method != "nr":
+        raise ValueError(f"nr_control 'displacement' belongs to the Newton-Raphson solve (solve_nr, method 'nr'): "
+                         f"method {method!r} does not support it.")
+    if config.kinematics != "green-lagrange":
+        raise ValueError("nr_control 'displacement' needs kinematics 'green-lagrange': the linear solve has no limit "
+                         "point to pass.")
+    if model is None:
+        return name
+    if model.material.has_trainable_params():
+        raise ValueError("nr_control 'displacement' needs scalar materials (no NN parameters).")
+    if _world_size() > 1:
+        raise ValueError("nr_control 'displacement' does not support a sharded (multi-GPU) run.")
+    c = config.nr_control_dof
+    if c is None or isinstance(c, bool) or int(c) != c or not 0 <= int(c) < model.ndof:
+        raise ValueError(f"nr_control 'displacement' needs nr_control_dof, a global dof in 0..{model.ndof - 1}: got {c!r}")
+    free = np.ones(model.ndof, dtype=bool)
+    free[np.asarray(model.fixed_dofs, dtype=int)] = False
+    if not free[int(c)]:
+        raise ValueError(f"nr_control_dof {int(c)} is a fixed dof: the control dof must be free.")
+    d = float(config.nr_control_displacement)
+    if not np.isfinite(d) or d == 0.0:
+        raise ValueError("nr_control 'displacement' needs a non-zero nr_control_displacement (the control dof's value at "
+                         "factor 1).")
+    if not np.any(np.asarray(model.loads, dtype=float).reshape(-1)[free] != 0.0):
+        raise ValueError("nr_control 'displacement' needs loads that are not all zero on the free dofs: the load factor "
+                         "is the unknown.")
+    return name
+
+
 @dataclass
 class SolverResult:
     """Unified result from any solver (solver.py:65-75)."""
@@ -83,6 +128,9 @@ class SolverResult:
     converged: bool
     history: List[Dict[str, float]] = field(default_factory=list)
     nn_parameters: Optional[Dict[str, np.ndarray]] = None
+    # displacement control (solve() with nr_control = "displacement"): one {control_displacement, load_factor,
+    # iterations} per increment, the equilibrium path; None otherwise
+    path: Optional[list] = None
 
 
 # host polls the device state every CHECK_EVERY iterations (launches after the stop are no-ops)
@@ -134,6 +182,7 @@ def solve_gd(
 ) -> SolverResult:
     """Gradient Descent solver for FEM/PINN problems (solver.py:83-400)."""
     config = config or SolverConfig()
+    check_control(config, method="gd")
     if check_kinematics(config.kinematics) == "green-lagrange":
         # the GD path assembles the small-displacement element only (solve_hybrid runs it as phase 1 of a
         # Green-Lagrange Newton solve, which then starts from this linear answer)
@@ -358,9 +407,15 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     pf_gl_fint): u starts from u_initial when given, every iteration re-forms the element state at u and
     solves K_t(u) du = load_factor f_ext - f_int(u) with the Jacobi-preconditioned CG on the tangent (pf_pcgt_*) or, with
     config.nr_preconditioner = "two-level-updated", the two-level one whose coarse space follows X + u (pf_pcg2t_*).  CG needs
-    K_t positive definite: a limit point or buckling (rhs.du <= 0) raises RuntimeError; there is no arc-length control."""
+    K_t positive definite: under load control a limit point or buckling (rhs.du <= 0) raises RuntimeError.
+
+    config.nr_control = "displacement" (Green-Lagrange only) passes a limit point of the load: target_load_factor is then
+    the fraction of config.nr_control_displacement the control dof is held at and the load factor is solved for
+    (_solve_nr_displacement).  There is no arc-length control."""
     config = config or SolverConfig()
     green_lagrange = check_kinematics(config.kinematics, config.nr_preconditioner) == "green-lagrange"
+    if check_control(config, model) == "displacement":
+        return _solve_nr_displacement(model, config, target_load_factor, u_initial)
     if model.material.has_trainable_params():
         raise ValueError("Newton-Raphson solver with NN materials not fully supported yet. "
                          "Use solve_gd() for problems with NN parameters.")
@@ -425,6 +480,106 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
                         converged=has_converged, history=history)
 
 
+def _solve_nr_displacement(model, config, control_factor, u_initial) -> SolverResult:
+    """solve_nr under displacement control (Batoz-Dhatt), Green-Lagrange kinematics; DESIGN.md §7.
+
+    The free dof c = config.nr_control_dof is held at ubar = control_factor * config.nr_control_displacement and the load
+    factor lam is an unknown.  With F' the free dofs without c, K' = K_t[F', F'] and k_c = K_t[:, c], an iteration is
+      R = f_int(u) - lam f,  du_c = ubar - u_c            (non-zero in the first iteration only)
+      K' a = f[F'],   K' b = -R[F'] - k_c[F'] du_c        (one batched CG solve: two right-hand sides per launch)
+      dlam = -(R_c + k_c[F'].b + K_cc du_c) / (k_c[F'].a - f_c)
+      u[F'] += b + dlam a,  u_c = ubar,  lam += dlam
+    until |du| / max(|u|, min_denominator) and |dlam| / max(|lam|, min_denominator) are both <= tolerance.  K' stays
+    positive definite through a limit point of the load, so the CG solves of load control serve; a K' that is not
+    (a turning point of the control displacement, or a bifurcation the right-hand sides excite) is refused.
+    lam starts at f[F].f_int(u)[F] / f[F].f[F]: the previous increment's lam when u is a converged state."""
+    c = int(config.nr_control_dof)
+    ubar = float(control_factor) * float(config.nr_control_displacement)
+    eng = _engine_for(model, None, None)
+    ndof = model.ndof
+    free = np.ones(ndof, dtype=bool)
+    free[np.asarray(model.fixed_dofs, dtype=int)] = False
+    dev, f64 = eng.device, torch.float64
+    f = torch.from_numpy(np.ascontiguousarray(np.asarray(model.loads, dtype=float).reshape(-1))).to(dev)
+    u = torch.zeros(ndof, dtype=f64, device=dev)
+    if u_initial is not None:
+        u0 = u_initial.detach() if isinstance(u_initial, torch.Tensor) else torch.as_tensor(np.asarray(u_initial))
+        u = u0.to(device=dev, dtype=f64).reshape(-1).clone()
+        if u.numel() != ndof:
+            raise ValueError(f"u_initial has {u.numel()} entries, the model has {ndof} dofs")
+        u[torch.from_numpy(~free).to(dev)] = 0.0
+    if bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
+        raise RuntimeError("Tangent stiffness became singular during solve")
+    free_t = torch.from_numpy(free).to(dev)
+    fc_t = free_t.clone()
+    fc_t[c] = False                                     # F'
+    f_fc = torch.where(fc_t, f, torch.zeros_like(f))
+    f_c = float(f[c])
+    have_a = bool((f_fc != 0.0).any())
+    e_c = torch.zeros(ndof, dtype=f64, device=dev)
+    e_c[c] = 1.0
+    pcg_args = dict(tangent=True, preconditioner=config.nr_preconditioner, n_aggregates=config.nr_aggregates,
+                    extra_fixed=[c])
+
+    def refuse(why):
+        raise RuntimeError(f"Tangent stiffness with control dof {c} removed is not positive definite ({why}): "
+                           "displacement control needs an SPD K' (a turning point of the control displacement or a "
+                           "bifurcation is not passed); choose another control dof or a smaller step")
+
+    def checked(x, rhs, report):
+        _, ok, rr, bb = report
+        if not np.isfinite(rr) or (not ok and rr > 1e-4 * bb):
+            refuse("the CG residual does not come down")
+        if bb > 0.0 and not float(torch.dot(rhs, x)) > 0.0:
+            refuse("rhs.x <= 0")
+        return x
+
+    eng.gl_state(u)
+    lam = float(torch.dot(f[free_t], eng.gl_fint()[free_t])) / float(torch.dot(f[free_t], f[free_t]))
+    has_converged, residual_norm, load_residual, ite = False, float("inf"), float("inf"), -1
+    for ite in range(config.max_iterations):
+        if ite > 0:
+            eng.gl_state(u)                 # (the first iterate's state is the one lam was started from)
+        R = eng.gl_fint() - lam * f
+        du_c = ubar - float(u[c])
+        k_c = eng.kt_v_f64(e_c)             # column c of K_t, every row
+        rhs_b = torch.where(fc_t, -R - k_c * du_c, torch.zeros_like(R))
+        if have_a:
+            X, reports = eng.pcg_solve_batch(torch.stack([f_fc, rhs_b]), u=u, **pcg_args)
+            a, b = checked(X[0], f_fc, reports[0]), checked(X[1], rhs_b, reports[1])
+        else:
+            x, *report = eng.pcg_solve(rhs_b, u=u, **pcg_args)
+            a, b = torch.zeros_like(x), checked(x, rhs_b, report)
+        kc_fc = torch.where(fc_t, k_c, torch.zeros_like(k_c))
+        kc_a = float(torch.dot(kc_fc, a))
+        den = kc_a - f_c
+        if abs(den) <= 1e-12 * (float(torch.linalg.norm(kc_fc)) * float(torch.linalg.norm(a)) + abs(f_c)):
+            raise RuntimeError(f"control dof {c} does not respond to the load (k_c.a - f_c = {den:.3e}): displacement "
+                               "control cannot solve for the load factor; choose another control dof")
+        dlam = -(float(R[c]) + float(torch.dot(kc_fc, b)) + float(k_c[c]) * du_c) / den
+        du = b + dlam * a
+        du[c] = du_c
+        u = u + du
+        u[c] = ubar
+        lam += dlam
+        residual_norm = float(torch.linalg.norm(du)) / max(float(torch.linalg.norm(u)), config.min_denominator)
+        load_residual = abs(dlam) / max(abs(lam), config.min_denominator)
+        if residual_norm <= config.tolerance and load_residual <= config.tolerance:
+            has_converged = True
+            break
+    strain = eng.gl_state(u)
+    max_e = float(strain.abs().max()) if model.nelm else 0.0
+    reactions = (eng.gl_fint() - lam * f).cpu().numpy()
+    reactions[free] = 0.0                   # the control dof is free: the load carries it, it has no reaction
+    history = [{"load_factor": float(lam), "iterations": float(ite + 1), "residual": float(residual_norm),
+                "max_strain": float(max_e), "converged": float(1.0 if has_converged else 0.0),
+                "control_factor": float(control_factor), "control_displacement": float(ubar),
+                "load_residual": float(load_residual)}]
+    shape = (-1, 1) if model.dimension == 1 else (model.nnode, model.dimension)
+    return SolverResult(displacements=u.cpu().numpy().reshape(shape), reactions=reactions.reshape(shape),
+                        converged=has_converged, history=history)
+
+
 def _max_abs_strain(model, u) -> float:
     """max |epsilon| over the elements, epsilon = axial stretch / l0 (fem/element.py:27-28, 74-80): a
     monitor of the history record only (host, float64)."""
@@ -462,6 +617,7 @@ def solve_hybrid(
     """Hybrid solver (solver.py:520-692).  With NN materials phase 2 is GD again (:594-651)."""
     config = config or SolverConfig()
     check_kinematics(config.kinematics, config.nr_preconditioner)
+    check_control(config, method="hybrid")
     _say("=== HYBRID SOLVER ===")
     _say(f"Target load factor: {target_load_factor}")
     gd_result = None
@@ -559,6 +715,8 @@ def solve(
             _say("[AUTO] Selecting: Gradient Descent (inverse problem)")
             method = "gd"
 
+    displacement_control = check_control(config, model, method) == "displacement"
+    path = [] if displacement_control else None
     _say(f"\n{'Inc':>4} | {'Load Factor':>12} | {'Status':>10}")
     _say("-" * 40)
     result = None
@@ -590,6 +748,10 @@ def solve(
         else:
             raise ValueError(f"Unknown solver method: {method}")
         u_current = result.displacements.flatten()
+        if displacement_control:
+            # load_factor above is the control factor; the record's is the solved one
+            path.append({key: result.history[-1][key] for key in ("control_displacement", "load_factor", "iterations")})
+            result.path = path
         status = "CONVERGED" if result.converged else "FAILED"
         _say(f"{iinc:4d} | {load_factor:12.6f} | {status:>10}")
         if not result.converged:

@@ -1,0 +1,162 @@
+"""Displacement control in the Green-Lagrange Newton solve on the device: solve_nr and solve() through the limit point of
+the two-bar truss (closed form) and of a shallow Warren arch (tests/dc_reference.py with direct solves), the refusal of
+a K' that is not positive definite, and the CLI."""
+import json
+import os
+import shutil
+
+import numpy as np
+import pytest
+import torch
+
+import dc_reference as dc
+import gl_reference as gl
+
+pytestmark = pytest.mark.gpu
+
+YOUNG, AREA = 2000.0, 0.5                       # E*A = 1000, exact in float32
+EA = YOUNG * AREA
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _model(nodes, el, loads, fixed):
+    from pinn_fem_amd.fem.model import FEMModel, Material
+    return FEMModel(nodes=nodes, elements=el, material=Material(YOUNG, AREA, 1.0), loads=loads, fixed_dofs=fixed,
+                    dimension=2)
+
+
+def _two_bar():
+    tb = gl.TwoBar(ea=EA)
+    return tb, _model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
+
+
+def _config(**kw):
+    from pinn_fem_amd.fem.solver import SolverConfig
+    base = dict(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange", nr_control="displacement", method="nr")
+    base.update(kw)
+    return SolverConfig(**base)
+
+
+# ---- 8. solve_nr, one step past the limit point ------------------------------------------------------------------------
+def test_solve_nr_two_bar_one_step_past_the_limit_point():
+    """From zero to w = 0.6 > w_lim = 0.423 in one step: the vertical tangent there is -0.512.  The CPU loop takes 3
+    iterations.  |lam P_lim / P(w) - 1| <= 1e-9 as in tests/test_gl_f64.py's _check_two_bar."""
+    from pinn_fem_amd.fem.solver import solve_nr
+    tb, model = _two_bar()
+    w = 0.6
+    assert w > tb.w_lim and abs(tb.tangent(w) + 0.512) < 1e-3
+    res = solve_nr(model, _config(nr_control_dof=5, nr_control_displacement=-w), 1.0)
+    h = res.history[-1]
+    u = res.displacements.reshape(-1)
+    lam = h["load_factor"]
+    print(f"two-bar to w = 0.6: lam P_lim / P(w) - 1 = {lam * tb.p_lim / tb.load(w) - 1:.3e}, ux = {u[4]:.1e}, history {h}")
+    assert res.converged and h["converged"] == 1.0 and 2 <= h["iterations"] <= 6
+    assert u[5] == -w and h["control_displacement"] == -w and h["control_factor"] == 1.0
+    assert abs(lam * tb.p_lim / tb.load(w) - 1.0) <= 1e-9
+    assert abs(u[4]) <= 1e-14 * w                                      # symmetry
+    assert abs(h["max_strain"] - abs(tb.strain(w))) <= 1e-12 * abs(tb.strain(w))
+    assert h["residual"] <= 1e-10 and h["load_residual"] <= 1e-10
+    R = res.reactions.reshape(-1, 2)
+    p = lam * tb.p_lim
+    assert np.all(R[2] == 0.0) and abs(R[:2, 1].sum() - p) <= 1e-9 * p and abs(R[:2, 0].sum()) <= 1e-9 * p
+    assert res.path is None                                            # solve() fills it, solve_nr does not
+    # from that state load control still meets the indefinite tangent
+    load = _config(nr_control="load")
+    with pytest.raises(RuntimeError, match="not positive definite"):
+        solve_nr(model, load, 1.01 * lam, u_initial=torch.from_numpy(u.copy()))
+
+
+# ---- 9. solve(), the whole path ------------------------------------------------------------------------------------------
+def test_solve_two_bar_path_to_beyond_snap_through():
+    from pinn_fem_amd.fem.solver import solve
+    tb, model = _two_bar()
+    res = solve(model, _config(nr_control_dof=5, nr_control_displacement=-2.2 * tb.h, n_increments=11))
+    assert res.converged and res.path is not None and len(res.path) == 11
+    lam_seen = []
+    for k, rec in enumerate(res.path, start=1):
+        w = -rec["control_displacement"]
+        assert abs(w - k * 0.2 * tb.h) <= 1e-15
+        want = tb.load(w) / tb.p_lim
+        lam_seen.append(rec["load_factor"])
+        print(f"two-bar path {k}: w = {w:.3f}, lam = {rec['load_factor']:+.12e}, closed form {want:+.12e}, "
+              f"iterations {rec['iterations']}")
+        if abs(want) > 0.1:
+            assert abs(rec["load_factor"] / want - 1.0) <= 1e-9, k
+        else:
+            assert k in (5, 10) and abs(rec["load_factor"] - want) <= 1e-9, k        # w = h and 2 h: P = 0
+    assert lam_seen[4 - 1] > 0 > lam_seen[6 - 1] and lam_seen[9 - 1] < 0 < lam_seen[11 - 1]
+    assert res.history[-1]["load_factor"] == res.path[-1]["load_factor"]
+    assert res.displacements.reshape(-1)[5] == -2.2 * tb.h
+
+
+# ---- 10. the arch: batched solves ---------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def arch_reference():
+    nodes, el, loads, fixed, c = dc.arch_warren(8, 8.0, 0.5, 0.5)
+    cond = []
+
+    def watch(u, K, free, fc):
+        lam = np.linalg.eigvalsh(gl.restrict(K, fc).toarray())
+        assert lam[0] > 0.0
+        cond.append(lam[-1] / lam[0])
+    u, lams, its = dc.control_path(nodes, el, loads, fixed, EA, 2, c, -1.1, 11, on_iterate=watch)
+    return nodes, el, loads, fixed, c, u, lams, its, max(cond)
+
+
+@pytest.mark.parametrize("pre", ["jacobi", "two-level-updated"])
+def test_solve_arch_through_its_limit_point(arch_reference, pre):
+    """Arch B against the restatement with direct solves.  Tolerance 30 * 1e-13 * kappa of max |lam| and max |u|: the CG
+    rtol times the largest condition number of K' along the reference path (456 .. 947), times the margin 30 of
+    _check_two_bar."""
+    from pinn_fem_amd.fem import solver
+    nodes, el, loads, fixed, c, u_ref, lam_ref, its_ref, kappa = arch_reference
+    model = _model(nodes, el, loads, fixed)
+    eng = solver._engine_for(model, None, None)
+    batches = eng.pcg_batch_solves
+    res = solver.solve(model, _config(nr_control_dof=c, nr_control_displacement=-1.1, n_increments=11,
+                                      nr_preconditioner=pre, nr_aggregates=4 if pre != "jacobi" else None))
+    assert res.converged and len(res.path) == 11
+    lam = np.array([rec["load_factor"] for rec in res.path])
+    its = [int(rec["iterations"]) for rec in res.path]
+    u = res.displacements.reshape(-1)
+    tol = 30 * 1e-13 * kappa
+    e_lam, e_u = np.abs(lam - lam_ref).max() / np.abs(lam_ref).max(), np.abs(u - u_ref).max() / np.abs(u_ref).max()
+    print(f"arch B, {pre}: kappa {kappa:.0f}, tolerance {tol:.2e}, lam error {e_lam:.2e}, u error {e_u:.2e}, "
+          f"iterations {its} (CPU {its_ref}), lam {lam}")
+    assert e_lam <= tol and e_u <= tol
+    assert all(3 <= k <= 8 for k in its)
+    assert int(np.argmax(lam)) == 4                                     # the limit point lies in increment 5
+    assert u[c] == -1.1
+    # six of the seven loaded dofs lie in F': every Newton iteration was one batched solve of two right-hand sides
+    assert eng.pcg_batch_solves - batches == sum(its)
+
+
+# ---- 11. refusal --------------------------------------------------------------------------------------------------------
+def test_indefinite_reduced_tangent_is_refused():
+    """Control dof 4 (horizontal) at w = h: K' is the vertical tangent 2 N / l0 = -0.985."""
+    from pinn_fem_amd.fem.solver import solve_nr
+    tb, model = _two_bar()
+    u0 = np.zeros(6)
+    u0[5] = -tb.h
+    with pytest.raises(RuntimeError, match="not positive definite") as info:
+        solve_nr(model, _config(nr_control_dof=4, nr_control_displacement=0.01), 1.0, u_initial=torch.from_numpy(u0))
+    assert "control dof 4" in str(info.value)
+
+
+# ---- 12. CLI ------------------------------------------------------------------------------------------------------------
+def test_cli_displacement_control(tmp_path):
+    from pinn_fem_amd.cli import generic as g
+    tb = gl.TwoBar(ea=EA)
+    shutil.copy(os.path.join(HERE, "nl_inputs", "two_bar_displacement_control.json"), tmp_path / "dc.json")
+    g.main(["generic.py", str(tmp_path / "dc.json")])
+    out = json.loads((tmp_path / "dc.res.json").read_text())
+    path = out["equilibrium_path"]
+    print(f"CLI displacement control: {path[-1]}")
+    assert out["converged"] and len(path) == 11
+    last = path[-1]
+    assert last["control_displacement"] == -2.2 and out["displacements"][5] == -2.2
+    assert abs(last["load_factor"] / (tb.load(2.2) / tb.p_lim) - 1.0) <= 1e-9
+    # load control writes no path
+    shutil.copy(os.path.join(HERE, "nl_inputs", "two_bar_green_lagrange.json"), tmp_path / "lc.json")
+    g.main(["generic.py", str(tmp_path / "lc.json")])
+    assert "equilibrium_path" not in json.loads((tmp_path / "lc.res.json").read_text())
