@@ -461,6 +461,22 @@ typedef struct pf_gl {
 } pf_gl;
 /* kt, fe and strain of every element at the displacements u (dev double [n_dofs]); one element per thread */
 int pf_gl_state(const pf_problem* p, const pf_gl* g, const double* u, void* stream);
+/* pf_gl_state with E*A of every element from ea (dev double [n_elems]) in place of the problem's own: the same kernel,
+ * so with ea filled with the problem's E*A it gives pf_gl_state's bits.  kt is what every tangent family reads
+ * (pf_kt_v_f64, pf_pcgt_*, pf_pcg2t_*, pf_pcgtm_*, pf_pcg2tm_*, pf_coarse_setup_t), so they all follow.  A null ea is
+ * PF_ERR_ARG, never a silent solve with the problem's E*A.  The three entry points below are additive: the version stays 9. */
+int pf_gl_state_ea(const pf_problem* p, const pf_gl* g, const double* ea, const double* u, void* stream);
+/* Sensitivity of a misfit J(u) to every element's E*A through the adjoint a (K_t(u) a = dJ/du on the free dofs, zero on
+ * the fixed ones): s_e = -(e / l0) d.(a_j - a_i) with d = d0 + u_j - u_i and e the strain as pf_gl_state forms it.  It
+ * does not contain E*A and reads g->d0 only.  out (dev double [n_elems]) = s (accumulate 0) or out + s (accumulate 1:
+ * load levels sum in call order).  One element per thread, no atomics. */
+int pf_gl_sens(const pf_problem* p, const pf_gl* g, const double* u, const double* a, int accumulate, double* out,
+               void* stream);
+/* out[g] (dev double [n_groups]) = sum of values[e] * weights[e] (weights null: of values[e]) over e = group_elems[k],
+ * group_ptr[g] <= k < group_ptr[g + 1] (dev int CSR; ids outside 0..n_elems-1 add nothing).  One workgroup per group, a
+ * fixed summation order, no atomics: the same bits on every run.  An empty group gives 0.0. */
+int pf_group_sum_f64(int n_elems, const double* values, const double* weights, const int* group_ptr, const int* group_elems,
+                     int n_groups, double* out, void* stream);
 /* f_int_out (dev double [n_dofs], every row) = the node gather of +-g->fe, ascending element id, no atomics */
 int pf_gl_fint(const pf_problem* p, const pf_gl* g, double* f_int_out, void* stream);
 /* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */

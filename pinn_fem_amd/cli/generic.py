@@ -88,6 +88,12 @@ def parse_problem(problem_file):
     #           "nr_control": {"dof": g, "displacement": d}}  displacement control of the green-lagrange Newton solve: the
     #                                                 global dof g goes to d over the increments and the load factor is
     #                                                 solved for (the .res.json gains "equilibrium_path"); absent: load control
+    #           "identify_nr": {"groups": [...]|null, "levels": [{"load_factor": l, "dofs": [...], "u": [...]}, ...],
+    #                           "max_evaluations": N}  identify one factor on E*A per group of elements (null: per element)
+    #                                                 from displacements measured at several load levels, through the
+    #                                                 green-lagrange Newton solve (method "nr"; fem/identify.py); the
+    #                                                 .res.json gains "identified_factors", "identified_ea", "misfit" and
+    #                                                 "evaluations", and holds the last level's displacements and reactions
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -182,8 +188,30 @@ def parse_problem(problem_file):
         model._pf_fe_mode = 1
     if accel.get("mlp_dtype"):
         model._pf_mlp_dtype = str(accel["mlp_dtype"])
-    return {"model": model, "solver_config": solver_config, "measured_data": measured_data,
-            "accel": accel}
+    parsed = {"model": model, "solver_config": solver_config, "measured_data": measured_data,
+              "accel": accel}
+    if accel.get("identify_nr") is not None:
+        parsed["identify_nr"] = _identify_block(accel["identify_nr"], solver_config)
+    return parsed
+
+
+def _identify_block(block, solver_config):
+    """accel.identify_nr, checked for its shape (what it holds is checked by fem.identify.check_identify)."""
+    shape = ('accel.identify_nr must be {"groups": [...] | null, "levels": [{"load_factor": .., "dofs": [..], "u": [..]}, ..]'
+             ', "max_evaluations": N}')
+    if not isinstance(block, dict) or "levels" not in block or not set(block) <= {"groups", "levels", "max_evaluations"}:
+        raise ValueError(shape)
+    levels = block["levels"]
+    if not isinstance(levels, list) or not all(isinstance(lv, dict) and set(lv) == {"load_factor", "dofs", "u"}
+                                               for lv in levels):
+        raise ValueError(shape)
+    if solver_config.method != "nr":
+        raise ValueError(f'accel.identify_nr belongs to the Newton-Raphson solve (method "nr"): method '
+                         f'{solver_config.method!r} does not support it.')
+    out = {"groups": block.get("groups"), "levels": levels}
+    if block.get("max_evaluations") is not None:
+        out["max_evaluations"] = int(block["max_evaluations"])
+    return out
 
 
 def _solver_config_from(data):
@@ -323,6 +351,8 @@ def solve_problem(parsed_data):
     log_print(f"Has NN: {model.material.has_trainable_params()}")
     log_print(f"Has measurements: {len(measured_data.get('dofs', [])) > 0}")
     log_print(f"Solver method: {solver_config.method}")
+    if parsed_data.get("identify_nr") is not None:
+        return _identify_problem(model, solver_config, parsed_data["identify_nr"])
     result = solve(model=model, config=solver_config,
                    measured_disp=measured_data.get("values", None),
                    measured_dofs=measured_data.get("dofs", None))
@@ -361,6 +391,27 @@ def solve_problem(parsed_data):
         output["nn_parameters"] = {k: v.tolist() for k, v in result.nn_parameters.items()}
         output["identified_properties"] = extract_nn_properties(model)
     return output
+
+
+def _identify_problem(model, solver_config, block):
+    """accel.identify_nr: the factors on E*A and the state of the last load level at them."""
+    from ..fem.identify import identify_nr
+    kw = {"max_evaluations": block["max_evaluations"]} if "max_evaluations" in block else {}
+    res = identify_nr(model, solver_config, block["levels"], groups=block["groups"], **kw)
+    log_print(f"Identification: {res.evaluations} evaluations, misfit {res.misfit:.3e}, factors {res.factors.tolist()}")
+    return {
+        "success": res.converged,
+        "converged": res.converged,
+        "iterations": res.evaluations,
+        "history": [{"misfit": h["misfit"], "gradient_norm": h["gradient_norm"], "factors": h["factors"].tolist()}
+                    for h in res.history],
+        "identified_factors": res.factors.tolist(),
+        "identified_ea": res.ea.tolist(),
+        "misfit": res.misfit,
+        "evaluations": res.evaluations,
+        "displacements": res.displacements[-1].tolist(),
+        "reactions": res.reactions.tolist(),
+    }
 
 
 def _init_distributed():

@@ -9,17 +9,24 @@
 // B is what pf_pcg.hip's gather64 reads as `kt`.  The reference's truss2d_element_state (fem/element.py:105-133) is NOT
 // this element: its force has the other sign and lacks 1/l0, and its "nonlinear" stiffness is e d d^T, not (N/l0) I.
 //
-// k_gl_state: one element per thread (grid-stride), coalesced records out, two gathered node vectors in.
+// k_gl_state: one element per thread (grid-stride), coalesced records out, two gathered node vectors in.  E*A is
+//             elem_ea64, or the caller's per-element float64 array (pf_gl_state_ea: the identification of DESIGN.md §7).
 // k_gl_fint:  one node per thread, +-fe of the node's elements in ascending element id, no atomics; the adjacency codes
 //             and the records of two incidences are loaded together (selects, not branches), as the node kernels of
 //             pf_node.h issue theirs.
+// k_gl_sens:  dJ/d(E*A) of an element from the state u and an adjoint a: -(e / l0) d.(a_j - a_i); k_gl_state's loads
+//             and its strain, one store (or one load and one store when it accumulates), no atomics.
+// k_group_sum: out[g] = sum of values[e] * weights[e] over the elements of group g (CSR, ascending element id): one
+//             workgroup per group, thread t adds elements t, t + 256, ... in that order, then the fixed-order block
+//             sum of pf_pcg.hip's block_sum64.  No atomics: the same bits on every run.
 #include <stdio.h>
 #include "pf_common.h"
 
 namespace {
 
 template <int DIM>
-__global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const double* __restrict__ u) {
+__global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const double* __restrict__ u,
+                                                  const double* __restrict__ ea_in) {
   const pf_mesh& M = P.mesh;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < M.n_elems; e += gridDim.x * blockDim.x) {
     const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
@@ -33,7 +40,7 @@ __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const d
       d0[0] = G.d0[e];
       du[0] = u[nn.y] - u[nn.x];
     }
-    const double ea = elem_ea64(P, e);
+    const double ea = ea_in ? ea_in[e] : elem_ea64(P, e);
     double l02 = 0.0, d0du = 0.0, dudu = 0.0;
 #pragma unroll
     for (int c = 0; c < DIM; ++c) { l02 += d0[c] * d0[c]; d0du += d0[c] * du[c]; dudu += du[c] * du[c]; }
@@ -55,6 +62,68 @@ __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const d
       G.fe[e] = n_l0 * d[0];
       G.kt[e] = k * (d[0] * d[0]) + n_l0;
     }
+  }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_gl_sens(pf_problem P, const double* __restrict__ d0_in, const double* __restrict__ u,
+                                                 const double* __restrict__ a, int accumulate, double* __restrict__ out) {
+  const pf_mesh& M = P.mesh;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < M.n_elems; e += gridDim.x * blockDim.x) {
+    const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
+    double d0[DIM], du[DIM], da[DIM];
+    if (DIM == 2) {
+      const double2 g = reinterpret_cast<const double2*>(d0_in)[e];
+      const double2 ui = reinterpret_cast<const double2*>(u)[nn.x], uj = reinterpret_cast<const double2*>(u)[nn.y];
+      const double2 ai = reinterpret_cast<const double2*>(a)[nn.x], aj = reinterpret_cast<const double2*>(a)[nn.y];
+      d0[0] = g.x; d0[DIM - 1] = g.y;
+      du[0] = uj.x - ui.x; du[DIM - 1] = uj.y - ui.y;
+      da[0] = aj.x - ai.x; da[DIM - 1] = aj.y - ai.y;
+    } else {
+      d0[0] = d0_in[e];
+      du[0] = u[nn.y] - u[nn.x];
+      da[0] = a[nn.y] - a[nn.x];
+    }
+    double l02 = 0.0, d0du = 0.0, dudu = 0.0;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) { l02 += d0[c] * d0[c]; d0du += d0[c] * du[c]; dudu += du[c] * du[c]; }
+    const double strain = (2.0 * d0du + dudu) / (2.0 * l02);     // as k_gl_state forms it
+    double dda = 0.0;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) dda += (d0[c] + du[c]) * da[c];
+    const double s = -(strain / sqrt(l02)) * dda;
+    out[e] = accumulate ? __dadd_rn(out[e], s) : s;      // s rounded first: the sum of two single calls, to the bit
+  }
+}
+
+// the sum of v over the block's threads, the same on every thread: the order of pf_pcg.hip's block_sum64
+__device__ __forceinline__ double block_sum(double v, double* smem) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if (lane == 0) smem[w] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int i = 0; i < nw; ++i) t += smem[i];
+  return t;
+}
+
+// an element id outside 0..n_elems-1 in group_elems adds nothing (and reads nothing)
+__global__ __launch_bounds__(256) void k_group_sum(int n_elems, const double* __restrict__ values,
+                                                   const double* __restrict__ weights, const int* __restrict__ group_ptr,
+                                                   const int* __restrict__ group_elems, int n_groups,
+                                                   double* __restrict__ out) {
+  __shared__ double red[8];
+  for (int g = blockIdx.x; g < n_groups; g += gridDim.x) {        // uniform over the block: the barriers are safe
+    const int b = group_ptr[g], e_ = group_ptr[g + 1];
+    double acc = 0.0;
+    for (int idx = b + (int)threadIdx.x; idx < e_; idx += (int)blockDim.x) {
+      const int e = group_elems[idx];
+      if ((unsigned)e < (unsigned)n_elems) acc += weights ? values[e] * weights[e] : values[e];
+    }
+    const double t = block_sum(acc, red);
+    if (threadIdx.x == 0) out[g] = t;
   }
 }
 
@@ -106,18 +175,57 @@ int gl_fail(int code, const char* who, const char* what) {
 
 bool mesh_ok(const pf_problem* p) { return p && (p->mesh.dim == 1 || p->mesh.dim == 2) && p->mesh.n_elems >= 0; }
 
+int elem_blocks(int n_elems) {
+  const int nb = (n_elems + 255) / 256;
+  return nb > PF_MAX_NODE_BLOCKS ? PF_MAX_NODE_BLOCKS : nb;
+}
+
+int gl_state(const char* who, const pf_problem* p, const pf_gl* g, const double* ea, const double* u, void* stream) {
+  if (!mesh_ok(p) || !g || !g->d0 || !g->kt || !g->fe || !g->strain || !u) return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (p->mesh.n_elems == 0) return PF_OK;
+  const int nb = elem_blocks(p->mesh.n_elems);
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_state<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, *g, u, ea);
+  else hipLaunchKernelGGL(k_gl_state<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, *g, u, ea);
+  if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
+  return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int pf_gl_state(const pf_problem* p, const pf_gl* g, const double* u, void* stream) {
-  const char* who = "pf_gl_state";
-  if (!mesh_ok(p) || !g || !g->d0 || !g->kt || !g->fe || !g->strain || !u) return gl_fail(PF_ERR_ARG, who, "bad argument");
+  return gl_state("pf_gl_state", p, g, nullptr, u, stream);
+}
+
+int pf_gl_state_ea(const pf_problem* p, const pf_gl* g, const double* ea, const double* u, void* stream) {
+  if (!ea) return gl_fail(PF_ERR_ARG, "pf_gl_state_ea", "null ea (pf_gl_state is the solve with the problem's own E*A)");
+  return gl_state("pf_gl_state_ea", p, g, ea, u, stream);
+}
+
+int pf_gl_sens(const pf_problem* p, const pf_gl* g, const double* u, const double* a, int accumulate, double* out,
+               void* stream) {
+  const char* who = "pf_gl_sens";
+  if (!mesh_ok(p) || !g || !g->d0 || !u || !a || !out || (accumulate != 0 && accumulate != 1))
+    return gl_fail(PF_ERR_ARG, who, "bad argument");
   if (p->mesh.n_elems == 0) return PF_OK;
-  int nb = (p->mesh.n_elems + 255) / 256;
-  if (nb > PF_MAX_NODE_BLOCKS) nb = PF_MAX_NODE_BLOCKS;
-  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_state<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, *g, u);
-  else hipLaunchKernelGGL(k_gl_state<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, *g, u);
+  const int nb = elem_blocks(p->mesh.n_elems);
+  const hipStream_t s = (hipStream_t)stream;
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_sens<2>, dim3(nb), dim3(256), 0, s, *p, g->d0, u, a, accumulate, out);
+  else hipLaunchKernelGGL(k_gl_sens<1>, dim3(nb), dim3(256), 0, s, *p, g->d0, u, a, accumulate, out);
+  if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
+  return PF_OK;
+}
+
+int pf_group_sum_f64(int n_elems, const double* values, const double* weights, const int* group_ptr, const int* group_elems,
+                     int n_groups, double* out, void* stream) {
+  const char* who = "pf_group_sum_f64";
+  if (n_elems < 0 || n_groups < 0 || !values || !group_ptr || !group_elems || !out)
+    return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (n_groups == 0) return PF_OK;
+  const int nb = n_groups < PF_MAX_NODE_BLOCKS ? n_groups : PF_MAX_NODE_BLOCKS;
+  hipLaunchKernelGGL(k_group_sum, dim3(nb), dim3(256), 0, (hipStream_t)stream, n_elems, values, weights, group_ptr,
+                     group_elems, n_groups, out);
   if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
   return PF_OK;
 }

@@ -225,6 +225,7 @@ class HipEngine:
         self.pcg_batch_solves = 0       # pcg_solve_batch calls so far
         self._fixed_views = {}          # extra fixed dofs (tuple) -> (device dof_flags copy, PfProblem view, host fixed mask)
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
+        self._group_csr = None          # group_sum: (key of the group map, n_groups, device CSR pointer, device element ids)
         self._configured = False
         env_k = os.environ.get("PINNFEM_GRAPH_ITERS")
         self.GRAPH_ITERS = int(env_k) if env_k else (self.GRAPH_ITERS_LARGE if hp.n_elems >= 200_000 else self.GRAPH_ITERS)
@@ -602,17 +603,76 @@ class HipEngine:
             self._gl = (d0, kt, fe, strain, rec)
         return self._gl
 
+    def _f64_vector(self, who, name, v, count, what):
+        vv = v.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)
+        if vv.numel() != count:
+            raise ValueError(f"{who}: {name} has {vv.numel()} entries, the mesh has {count} {what}")
+        return vv
+
     @_on_engine_stream
-    def gl_state(self, u: torch.Tensor) -> torch.Tensor:
+    def gl_state(self, u: torch.Tensor, ea: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Green-Lagrange strain, element force and tangent block of every element at the displacements u (float64,
-        pf_gl_state); they stay on the device for gl_fint, kt_v_f64 and pcg_solve(tangent=True).  Returns the strains
-        [n_elems] (the engine's buffer: the next gl_state overwrites it)."""
-        uu = u.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)
-        if uu.numel() != self.plan.n_dofs:
-            raise ValueError(f"gl_state: u has {uu.numel()} entries, the mesh has {self.plan.n_dofs} dofs")
+        pf_gl_state); they stay on the device for gl_fint, kt_v_f64 and pcg_solve(tangent=True).  ea: E*A of every
+        element [n_elems] in float64 in place of the model's (pf_gl_state_ea; the identification of fem/identify.py).
+        Returns the strains [n_elems] (the engine's buffer: the next gl_state overwrites it)."""
+        uu = self._f64_vector("gl_state", "u", u, self.plan.n_dofs, "dofs")
         rec = self._gl_buffers()[4]
-        _capi.check(self.lib.pf_gl_state(self._ref(), C.byref(rec), uu.data_ptr(), self._stream()), "pf_gl_state")
+        if ea is None:
+            _capi.check(self.lib.pf_gl_state(self._ref(), C.byref(rec), uu.data_ptr(), self._stream()), "pf_gl_state")
+        else:
+            ee = self._f64_vector("gl_state", "ea", ea, self.plan.n_elems, "elements")
+            if self.plan.n_elems:
+                _capi.check(self.lib.pf_gl_state_ea(self._ref(), C.byref(rec), ee.data_ptr(), uu.data_ptr(), self._stream()),
+                            "pf_gl_state_ea")
         return self._gl[3][: self.plan.n_elems]
+
+    @_on_engine_stream
+    def gl_sensitivity(self, u: torch.Tensor, a: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dJ/d(E*A) of every element [n_elems] from the displacements u and the adjoint a of a misfit J (K_t(u) a =
+        dJ/du on the free dofs): -(e / l0) d.(a_j - a_i) (pf_gl_sens).  out: a float64 device vector [n_elems] the result
+        is ADDED to (load levels sum in call order); None: a new vector."""
+        uu = self._f64_vector("gl_sensitivity", "u", u, self.plan.n_dofs, "dofs")
+        aa = self._f64_vector("gl_sensitivity", "a", a, self.plan.n_dofs, "dofs")
+        ne = self.plan.n_elems
+        accumulate = out is not None
+        if accumulate:
+            if (out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous() or out.numel() != ne):
+                raise ValueError(f"gl_sensitivity: out must be a contiguous float64 vector of {ne} entries on {self.device}")
+        else:
+            out = torch.empty(ne, dtype=torch.float64, device=self.device)
+        if ne:
+            rec = self._gl_buffers()[4]
+            _capi.check(self.lib.pf_gl_sens(self._ref(), C.byref(rec), uu.data_ptr(), aa.data_ptr(), int(accumulate),
+                                            out.data_ptr(), self._stream()), "pf_gl_sens")
+        return out
+
+    @_on_engine_stream
+    def group_sum(self, values: torch.Tensor, weights: Optional[torch.Tensor], groups) -> torch.Tensor:
+        """out[g] = sum of values[e] * weights[e] (weights None: of values[e]) over the elements e with groups[e] == g, in
+        ascending element id and a fixed order (pf_group_sum_f64: the same bits on every run).  groups: [n_elems]
+        non-negative ints; the result has max(groups) + 1 entries.  The CSR of the last group map is cached."""
+        ne = self.plan.n_elems
+        gm = np.ascontiguousarray(np.asarray(groups).reshape(-1))
+        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < 0)):
+            raise ValueError(f"group_sum: groups must hold one non-negative group id for each of the {ne} elements")
+        gm = gm.astype(np.int64)
+        key = gm.tobytes()
+        if self._group_csr is None or self._group_csr[0] != key:
+            n_groups = int(gm.max()) + 1 if ne else 0
+            ptr = np.zeros(n_groups + 1, dtype=np.int32)
+            np.cumsum(np.bincount(gm, minlength=n_groups), out=ptr[1:])
+            order = np.argsort(gm, kind="stable").astype(np.int32)          # ascending element id inside a group
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            self._group_csr = (key, n_groups, dev(ptr), dev(order if ne else np.zeros(1, dtype=np.int32)))
+        _, n_groups, ptr, order = self._group_csr
+        vv = self._f64_vector("group_sum", "values", values, ne, "elements")
+        ww = None if weights is None else self._f64_vector("group_sum", "weights", weights, ne, "elements")
+        out = torch.empty(n_groups, dtype=torch.float64, device=self.device)
+        if n_groups:
+            _capi.check(self.lib.pf_group_sum_f64(ne, vv.data_ptr(), None if ww is None else ww.data_ptr(), ptr.data_ptr(),
+                                                  order.data_ptr(), n_groups, out.data_ptr(), self._stream()),
+                        "pf_group_sum_f64")
+        return out
 
     def _gl_ready(self, who):
         if self._gl is None:

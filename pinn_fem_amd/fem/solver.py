@@ -392,6 +392,46 @@ def _solve_gd_sharded(model, config, measured_disp, measured_dofs, lam, u_initia
                         converged=converged, history=history, nn_parameters=nn_params)
 
 
+def _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange, ea=None):
+    """The Newton iteration of solve_nr from u at the load f_ext: u += K^-1 (f_ext - f_int(u)) by CG until
+    |du| / max(|u|, min_denominator) <= tolerance.  ea (Green-Lagrange only): E*A of every element in place of the
+    model's (identify.misfit_and_gradient).  Returns (u, converged, |du|/|u|, max strain of the linear branch,
+    index of the last iteration, CG iterations)."""
+    has_converged, residual_norm, max_e, ite = False, float("inf"), 0.0, -1
+    cg0 = eng.pcg_iterations
+    for ite in range(config.max_iterations):
+        if green_lagrange:
+            eng.gl_state(u, ea)             # the history's max |e| is read once, from the state at the final u
+            rhs = f_ext - eng.gl_fint()
+            du, _, ok, rr, bb = eng.pcg_solve(rhs, tangent=True, preconditioner=config.nr_preconditioner,
+                                             n_aggregates=config.nr_aggregates, u=u)
+        else:
+            max_e = _max_abs_strain(model, u)
+            rhs = f_ext - eng.kv_f64(u)
+            du, _, ok, rr, bb = eng.pcg_solve(rhs, preconditioner=config.nr_preconditioner,
+                                             n_aggregates=config.nr_aggregates)
+        _check_cg_step(green_lagrange, rhs, du, ok, rr, bb, free_t)
+        u = u + du
+        residual_norm = float(torch.linalg.norm(du)) / max(float(torch.linalg.norm(u)), config.min_denominator)
+        if residual_norm <= config.tolerance:
+            has_converged = True
+            break
+    return u, has_converged, residual_norm, max_e, ite, eng.pcg_iterations - cg0
+
+
+def _check_cg_step(green_lagrange, rhs, x, ok, rr, bb, free_t):
+    """What solve_nr asks of a CG solve K x = rhs."""
+    # np.linalg.solve either succeeds or raises on a singular matrix; CG shows singularity (or a hopeless
+    # condition number for the Jacobi preconditioner) as a residual that does not come down at all.  An
+    # inner solve that merely stops short of 1e-13 is fine: the Newton loop then acts as iterative refinement.
+    if not np.isfinite(rr) or (not ok and rr > 1e-4 * bb):
+        raise RuntimeError("Tangent stiffness became singular during solve")
+    # CG is only valid for a positive definite operator: x = K_t^-1 rhs must be an ascent direction of rhs
+    if green_lagrange and bb > 0.0 and not float(torch.dot(rhs[free_t], x[free_t])) > 0.0:
+        raise RuntimeError("Tangent stiffness is not positive definite (limit point or buckling): the CG solve of "
+                           "the Green-Lagrange Newton step needs an SPD tangent; reduce the load step")
+
+
 def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> SolverResult:
     """Classical Newton-Raphson for scalar materials (solver.py:408-512), SURVEY.md §8(f) rank 3.
 
@@ -438,33 +478,8 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     # a free dof no element stiffens makes K_ff singular: np.linalg.solve raises there (solver.py:462-467)
     if bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
         raise RuntimeError("Tangent stiffness became singular during solve")
-    has_converged, residual_norm, max_e, ite = False, float("inf"), 0.0, -1
     free_t = torch.from_numpy(free).to(eng.device)
-    for ite in range(config.max_iterations):
-        if green_lagrange:
-            eng.gl_state(u)                 # the history's max |e| is read once, from the state at the final u
-            rhs = f_ext - eng.gl_fint()
-            du, _, ok, rr, bb = eng.pcg_solve(rhs, tangent=True, preconditioner=config.nr_preconditioner,
-                                             n_aggregates=config.nr_aggregates, u=u)
-        else:
-            max_e = _max_abs_strain(model, u)
-            rhs = f_ext - eng.kv_f64(u)
-            du, _, ok, rr, bb = eng.pcg_solve(rhs, preconditioner=config.nr_preconditioner,
-                                             n_aggregates=config.nr_aggregates)
-        # np.linalg.solve either succeeds or raises on a singular matrix; CG shows singularity (or a hopeless
-        # condition number for the Jacobi preconditioner) as a residual that does not come down at all.  An
-        # inner solve that merely stops short of 1e-13 is fine: the Newton loop then acts as iterative refinement.
-        if not np.isfinite(rr) or (not ok and rr > 1e-4 * bb):
-            raise RuntimeError("Tangent stiffness became singular during solve")
-        # CG is only valid for a positive definite operator: du = K_t^-1 rhs must be an ascent direction of rhs
-        if green_lagrange and bb > 0.0 and not float(torch.dot(rhs[free_t], du[free_t])) > 0.0:
-            raise RuntimeError("Tangent stiffness is not positive definite (limit point or buckling): the CG solve of "
-                               "the Green-Lagrange Newton step needs an SPD tangent; reduce the load step")
-        u = u + du
-        residual_norm = float(torch.linalg.norm(du)) / max(float(torch.linalg.norm(u)), config.min_denominator)
-        if residual_norm <= config.tolerance:
-            has_converged = True
-            break
+    u, has_converged, residual_norm, max_e, ite, _ = _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange)
     if green_lagrange:
         strain = eng.gl_state(u)                      # state at the final u: its strain, and f_int for the reactions
         max_e = float(strain.abs().max()) if model.nelm else 0.0

@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""Time identify_nr (fem/identify.py) on the Warren girder of tools/nr_scale.py --kinematics green-lagrange.
+
+    identify_scale.py [--preconditioner jacobi|two-level-updated] [--aggregates N] [--groups 8] [--levels 2]
+                      [--evaluations 5] [panels]
+
+The girder (E*A = 1, the load of nr_scale.py) gets one true factor per span group, alternating 0.8 / 1.25; its states at
+the load levels k / levels, solved on the device, are the measurements (every free dof), which is also the warm-up
+solve.  identify_nr then runs `evaluations` misfit evaluations from all factors 1.  One JSON line: seconds and Newton,
+CG and adjoint CG iterations per evaluation, and the time of single pf_gl_state (model E*A and per-element E*A),
+pf_gl_sens and pf_group_sum_f64 launches (mean of 200 back-to-back launches between two events) with their share of an
+evaluation."""
+import argparse, json, os, sys, time
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("PINNFEM_QUIET", "1")
+from pinn_fem_amd.fem.identify import identify_nr, misfit_and_gradient
+from pinn_fem_amd.fem.model import FEMModel, Material
+from pinn_fem_amd.fem.solver import SolverConfig
+from pinn_fem_amd.plan import warren_mesh
+import torch
+ap = argparse.ArgumentParser()
+ap.add_argument("--preconditioner", default="jacobi", choices=["jacobi", "two-level-updated"])
+ap.add_argument("--aggregates", type=int, default=None)
+ap.add_argument("--groups", type=int, default=8)
+ap.add_argument("--levels", type=int, default=2)
+ap.add_argument("--evaluations", type=int, default=5)
+ap.add_argument("panels", nargs="?", type=int, default=1000)
+args = ap.parse_args()
+panels = args.panels
+nodes, el, loads, fixed, _, _ = warren_mesh(panels)
+lam = (panels / 100.0) * 384.0 * 0.5 / (5.0 * float(panels) ** 4)          # nr_scale.py's: midspan sag about span / 100
+model = FEMModel(nodes=nodes, elements=el, material=Material(2.0, 0.5, 1.0), loads=lam * loads, fixed_dofs=fixed, dimension=2)
+cfg = SolverConfig(max_iterations=25, tolerance=1e-10, kinematics="green-lagrange", nr_preconditioner=args.preconditioner,
+                   nr_aggregates=args.aggregates)
+xc = 0.5 * (nodes[el[:, 0], 0] + nodes[el[:, 1], 0])
+groups = np.minimum((args.groups * xc / float(panels)).astype(int), args.groups - 1)
+true = np.where(np.arange(args.groups) % 2 == 0, 0.8, 1.25)
+free = np.ones(2 * len(nodes), dtype=bool)
+free[fixed] = False
+dofs = np.flatnonzero(free)
+factors = [(k + 1) / args.levels for k in range(args.levels)]
+# measurements: the states of the true structure (the misfit against zeros is not used); the warm-up solve as well
+_, _, states, _ = misfit_and_gradient(model, cfg, [(f, dofs, np.zeros(len(dofs))) for f in factors], true[groups])
+levels = [(f, dofs, s.cpu().numpy()[dofs]) for f, s in zip(factors, states)]
+eng = model._pf_engine_cache[1]
+refresh0 = eng.coarse_refresh_seconds
+torch.cuda.synchronize(); t0 = time.perf_counter()
+res = identify_nr(model, cfg, levels, groups=groups, max_evaluations=args.evaluations)
+torch.cuda.synchronize(); dt = time.perf_counter() - t0
+
+
+def launch_us(fn, n=200):
+    fn(); torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with eng.on_stream():
+        a.record(eng.stream)
+        for _ in range(n):
+            fn()
+        b.record(eng.stream)
+    torch.cuda.synchronize()
+    return 1e3 * a.elapsed_time(b) / n
+
+
+u, ea = states[-1], torch.from_numpy(res.ea).to(eng.device)
+adj, out = torch.ones_like(u), torch.zeros(len(el), dtype=torch.float64, device=eng.device)
+us = {"pf_gl_state": launch_us(lambda: eng.gl_state(u)), "pf_gl_state_ea": launch_us(lambda: eng.gl_state(u, ea)),
+      "pf_gl_sens": launch_us(lambda: eng.gl_sensitivity(u, adj, out=out)),
+      "pf_group_sum_f64": launch_us(lambda: eng.group_sum(out, ea, groups))}
+n = res.evaluations
+per_eval = dt / n
+row = {"panels": panels, "elements": len(el), "dofs": 2 * len(nodes), "preconditioner": args.preconditioner,
+       "groups": args.groups, "levels": args.levels, "evaluations": n, "seconds_per_evaluation": per_eval,
+       "newton_iterations_per_evaluation": res.counters["newton_iterations"] / n,
+       "cg_iterations_per_evaluation": res.counters["cg_iterations"] / n,
+       "adjoint_cg_iterations_per_evaluation": res.counters["adjoint_cg_iterations"] / n,
+       "misfit_first": res.history[0]["misfit"], "misfit_best": res.misfit, "launch_microseconds": us,
+       "share_of_sens_and_group_sum": (args.levels * us["pf_gl_sens"] + us["pf_group_sum_f64"]) * 1e-6 / per_eval}
+if args.preconditioner == "two-level-updated":
+    row["refresh_seconds_per_evaluation"] = (eng.coarse_refresh_seconds - refresh0) / n
+print(json.dumps(row), flush=True)
