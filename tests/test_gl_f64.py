@@ -18,114 +18,17 @@ import scipy.sparse.linalg as spla
 import torch
 
 import gl_reference as gl
+from device_driver import AREA, EA, RTOL, U24, U53, YOUNG, CgRun, gl_field, gl_system, system_cache, wide_vector
+from device_driver import GlTruss as System
 
 pytestmark = pytest.mark.gpu
 
-U53, U24 = 2.0 ** -53, 2.0 ** -24
-RTOL = 1e-13
-ST_COUNT = 16
-YOUNG, AREA = 2000.0, 0.5                       # E*A = 1000, exact in float32
-EA = YOUNG * AREA
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-class System:
-    """One truss on the device with test-owned element buffers (d0, kt, fe, strain) and the raw entry points."""
-
-    def __init__(self, nodes, el, fixed, dim):
-        from pinn_fem_amd import _capi
-        from pinn_fem_amd.engine import HipEngine
-        from pinn_fem_amd.fem.model import FEMModel, Material
-        self.capi = _capi
-        self.nodes = np.asarray(nodes, dtype=np.float64).reshape(-1, dim)
-        self.el, self.dim, self.fixed = np.asarray(el), dim, np.asarray(fixed, dtype=int)
-        self.n_nodes, self.ne = len(self.nodes), len(self.el)
-        self.n = self.n_nodes * dim
-        self.free = gl.free_mask(self.n, self.fixed)
-        self.degree = np.repeat(np.bincount(self.el.reshape(-1), minlength=self.n_nodes), dim)
-        model = FEMModel(nodes=self.nodes if dim == 2 else self.nodes.reshape(-1), elements=self.el,
-                         material=Material(YOUNG, AREA, 1.0), loads=np.zeros(self.n), fixed_dofs=self.fixed, dimension=dim)
-        self.eng = eng = HipEngine(model)
-        self.lib = eng.lib
-        d0 = self.nodes[self.el[:, 1]] - self.nodes[self.el[:, 0]]
-        self.d0 = self.dev(d0.reshape(-1))
-        mk = lambda k: torch.full((k,), 7.0, dtype=torch.float64, device=eng.device)      # the kernel must overwrite it
-        self.kt, self.fe, self.strain = mk(self.ne * (3 if dim == 2 else 1)), mk(self.ne * dim), mk(self.ne)
-        self.rec = _capi.PfGl()
-        self.rec.d0, self.rec.kt, self.rec.fe, self.rec.strain = (t.data_ptr() for t in (self.d0, self.kt, self.fe, self.strain))
-
-    def dev(self, a):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.eng.device)
-
-    def state(self, u):
-        """pf_gl_state at u -> (strain, fe [ne, dim], kt [ne, 3 or 1]) on the host."""
-        eng, uu = self.eng, self.dev(u)
-        with eng.on_stream():
-            self.capi.check(self.lib.pf_gl_state(eng._ref(), C.byref(self.rec), uu.data_ptr(), eng._stream()), "pf_gl_state")
-        torch.cuda.synchronize()
-        return (self.strain.cpu().numpy(), self.fe.cpu().numpy().reshape(self.ne, self.dim),
-                self.kt.cpu().numpy().reshape(self.ne, -1))
-
-    def fint(self):
-        eng = self.eng
-        out = torch.full((self.n,), 7.0, dtype=torch.float64, device=eng.device)
-        with eng.on_stream():
-            self.capi.check(self.lib.pf_gl_fint(eng._ref(), C.byref(self.rec), out.data_ptr(), eng._stream()), "pf_gl_fint")
-        torch.cuda.synchronize()
-        return out.cpu().numpy()
-
-    def kt_v(self, v, zero_fixed=False):
-        eng, vv = self.eng, self.dev(v)
-        out = torch.full((self.n,), 7.0, dtype=torch.float64, device=eng.device)
-        with eng.on_stream():
-            self.capi.check(self.lib.pf_kt_v_f64(eng._ref(), self.kt.data_ptr(), vv.data_ptr(), out.data_ptr(),
-                                                 int(zero_fixed), eng._stream()), "pf_kt_v_f64")
-        torch.cuda.synchronize()
-        return out.cpu().numpy()
-
-    def kv_linear(self, v):
-        out = self.eng.kv_f64(self.dev(v))
-        torch.cuda.synchronize()
-        return out.cpu().numpy()
-
-
-def _field(S, kind, rng):
-    """Displacements with |du| / l0 about 0.3 ("large") or 1e-9 ("tiny": where (l^2 - l0^2) would lose every digit)."""
-    mean_l0 = float(np.mean(np.linalg.norm(S.nodes[S.el[:, 1]] - S.nodes[S.el[:, 0]], axis=1)))
-    amp = {"large": 0.3, "tiny": 1e-9}[kind] * mean_l0 / math.sqrt(2.0 * S.dim)
-    return amp * rng.standard_normal(S.n)
-
-
-def _truss(n_elems, seed=0):
-    rng = np.random.default_rng(1000 + n_elems + seed)
-    nodes, el = gl.irregular_truss(n_elems, rng)
-    fixed = np.unique(np.concatenate([[0, 1, 2], rng.choice(nodes.size, size=max(1, nodes.size // 10), replace=False)]))
-    return System(nodes, el, fixed, 2)
-
-
-def _chain1d(n_elems, seed=0):
-    rng = np.random.default_rng(2000 + n_elems + seed)
-    x = np.concatenate([[0.0], np.cumsum(0.5 + rng.random(n_elems))])
-    e = np.arange(n_elems)
-    el = np.stack([e, e + 1], axis=1)
-    flip = rng.random(n_elems) < 0.5
-    el[flip] = el[flip][:, ::-1]
-    perm = rng.permutation(n_elems)
-    return System(x, el[perm], np.array([0]), 1)
 
 
 @pytest.fixture(scope="module")
 def systems():
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            kind, count = name.split("_")
-            cache[name] = _truss(int(count)) if kind == "truss" else _chain1d(int(count))
-        return cache[name]
-    yield get
-    cache.clear()
-    torch.cuda.empty_cache()
+    yield from system_cache(gl_system)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -165,7 +68,7 @@ def test_gl_state_against_the_restatement(systems, name, kind):
     S = systems(name)
     if S.dim == 2 and S.ne >= 63:
         assert S.degree.max() >= 5
-    u = _field(S, kind, np.random.default_rng(S.ne))
+    u = gl_field(S, kind, np.random.default_rng(S.ne))
     got = S.state(u)
     for label, g, (want, bound, *_) in zip(("strain", "fe", "kt"), got, _state_bounds(S, u)):
         g = g.reshape(want.shape)
@@ -204,7 +107,7 @@ def _check_fint(S, u, label):
 def test_gl_fint_against_the_restatement(systems, name):
     S = systems(name)
     for kind in ("large", "tiny"):
-        _check_fint(S, _field(S, kind, np.random.default_rng(S.ne + 1)), f"{name} {kind}")
+        _check_fint(S, gl_field(S, kind, np.random.default_rng(S.ne + 1)), f"{name} {kind}")
 
 
 def test_gl_fint_rigid_motion_gives_no_force(systems):
@@ -252,18 +155,14 @@ def test_gl_fint_rounded_rigid_motion(systems):
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. pf_kt_v_f64
 # ---------------------------------------------------------------------------------------------------------------------
-def _wide_vector(rng, n):
-    return rng.choice([-1.0, 1.0], n) * np.exp2(rng.uniform(-20.0, 20.0, n))
-
-
 @pytest.mark.parametrize("name", ["truss_1", "truss_257", "truss_1025", "chain_300"])
 def test_kt_v_against_the_csr_product(systems, name):
     S = systems(name)
     rng = np.random.default_rng(S.ne + 2)
-    u = _field(S, "large", rng)
+    u = gl_field(S, "large", rng)
     S.state(u)
     K, Kabs = gl.k_t(S.nodes, S.el, u, EA, S.dim), gl.k_t(S.nodes, S.el, u, EA, S.dim, absolute=True)
-    v, w = _wide_vector(rng, S.n), _wide_vector(rng, S.n)
+    v, w = wide_vector(rng, S.n), wide_vector(rng, S.n)
     got, got_zf = S.kt_v(v), S.kt_v(v, zero_fixed=True)
     scale = Kabs @ np.abs(v)
     # the bound form of tests/test_pcg_f64.py for K v: 8 roundings per incidence and one per accumulated incidence,
@@ -290,7 +189,7 @@ def test_kt_v_at_zero_displacement_is_the_linear_operator(systems, name):
     2^-24 per term, 3 * 2^-24 sum|terms| (the float64 round-off of both is 2^29 times smaller)."""
     S = systems(name)
     S.state(np.zeros(S.n))
-    v = _wide_vector(np.random.default_rng(7), S.n)
+    v = wide_vector(np.random.default_rng(7), S.n)
     scale = gl.k_t(S.nodes, S.el, np.zeros(S.n), EA, S.dim, absolute=True) @ np.abs(v)
     err = np.abs(S.kt_v(v) - S.kv_linear(v))
     print(f"{name}: |K_t(0) v - K v| worst {np.max(err / np.maximum(scale, 1e-300)) / U24:.3f} * 2^-24 sum|terms|")
@@ -331,48 +230,9 @@ def test_null_tangent_is_an_argument_error(systems):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. pf_pcgt_*
 # ---------------------------------------------------------------------------------------------------------------------
-class Run:
-    """One pf_pcgt_begin with test-owned x / ws on S's own kt."""
-
-    def __init__(self, S, b, rtol=RTOL):
-        self.S, eng = S, S.eng
-        self.b = S.dev(b)
-        self.x = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
-        self.ws = torch.full((int(S.lib.pf_pcg_workspace_count(eng._ref())),), 7.0, dtype=torch.float64, device=eng.device)
-        self.args = (eng._ref(), S.kt.data_ptr())
-        with eng.on_stream():
-            S.capi.check(S.lib.pf_pcgt_begin(*self.args, self.b.data_ptr(), self.x.data_ptr(), self.ws.data_ptr(),
-                                             float(rtol), eng._stream()), "pf_pcgt_begin")
-
-    def iterate(self, k):
-        S, st = self.S, (C.c_double * 4)()
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_pcgt_iterations(*self.args, self.x.data_ptr(), self.ws.data_ptr(), int(k), st,
-                                                  S.eng._stream()), "pf_pcgt_iterations")
-        return tuple(st)
-
-    def state(self):
-        S, st = self.S, (C.c_double * 4)()
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_pcgt_state(*self.args, self.ws.data_ptr(), st, S.eng._stream()), "pf_pcgt_state")
-        return tuple(st)
-
-    def graph(self, n_iter):
-        S, g = self.S, C.c_void_p()
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_pcgt_graph_create(*self.args, self.x.data_ptr(), self.ws.data_ptr(), int(n_iter),
-                                                    S.eng._stream(), C.byref(g)), "pf_pcgt_graph_create")
-        return g
-
-    def replay(self, g):
-        S = self.S
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_graph_launch(g, S.eng._stream()), "pf_graph_launch")
-        return self.state()
-
-    def read(self):
-        torch.cuda.synchronize()
-        return self.x.cpu().numpy(), self.ws.cpu().numpy()
+def _run(S, b):
+    """the Jacobi tangent family on S's own kt"""
+    return CgRun(S, b, kt=S.kt.data_ptr())
 
 
 @pytest.fixture(scope="module")
@@ -382,7 +242,7 @@ def spd_case(systems):
     the geometric stiffness N / l0 > 0 also stiffens the dangling bars that linear theory leaves as mechanisms."""
     S = systems("truss_257")
     rng = np.random.default_rng(11)
-    u = 0.05 * S.nodes.reshape(-1) + 0.02 * _field(S, "large", rng)
+    u = 0.05 * S.nodes.reshape(-1) + 0.02 * gl_field(S, "large", rng)
     K = gl.k_t(S.nodes, S.el, u, EA, 2)
     lam = np.linalg.eigvalsh(gl.restrict(K, S.free).toarray())
     print(f"spd case: eigenvalues of K_t,ff in [{lam[0]:.3e}, {lam[-1]:.3e}], condition {lam[-1] / lam[0]:.1f}")
@@ -422,12 +282,12 @@ def test_pcgt_solves_the_tangent_system(spd_case):
 def test_pcgt_graph_replay_equals_eager_bitwise(spd_case):
     S, u, K, xs, b = spd_case
     S.state(u)
-    probe = Run(S, b)
+    probe = _run(S, b)
     T = int(probe.iterate(4000)[0])
     assert probe.state()[1] == 1.0 and T > 16, T
     per = 8 if T % 8 else 7                            # the stop fires inside a replay, not at its end
     k = -(-T // per)
-    eager, graphed = Run(S, b), Run(S, b)
+    eager, graphed = _run(S, b), _run(S, b)
     st_e = eager.iterate(per * k)
     g = graphed.graph(per)
     try:
@@ -450,10 +310,10 @@ def test_pcgt_edge_semantics(spd_case):
     S, u, K, xs, b = spd_case
     S.state(u)
     for rhs in (np.zeros(S.n), np.where(S.free, 0.0, 5.0)):            # b = 0, and load on fixed dofs only
-        run = Run(S, rhs)
+        run = _run(S, rhs)
         assert run.state() == (0.0, 1.0, 0.0, 0.0) and run.iterate(7) == (0.0, 1.0, 0.0, 0.0)
         assert not run.read()[0].any()
-    run = Run(S, b)
+    run = _run(S, b)
     st0, (x0, ws0) = run.state(), run.read()
     assert st0[:2] == (0.0, 0.0) and not x0.any()
     assert run.iterate(0) == st0                                       # n_iter = 0: the state, nothing else

@@ -18,7 +18,7 @@ import torch
 
 import gl_reference as gl
 import identify_reference as ir
-from test_gl_f64 import EA, U53, System, _chain1d, _field, _truss
+from device_driver import EA, U53, gl_field, gl_system, system_cache
 
 pytestmark = pytest.mark.gpu
 
@@ -28,16 +28,7 @@ MESHES = ["truss_1", "truss_255", "truss_256", "truss_257", "truss_1025", "chain
 
 @pytest.fixture(scope="module")
 def systems():
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            kind, count = name.split("_")
-            cache[name] = _truss(int(count)) if kind == "truss" else _chain1d(int(count))
-        return cache[name]
-    yield get
-    cache.clear()
-    torch.cuda.empty_cache()
+    yield from system_cache(gl_system)
 
 
 def _read_state(S):
@@ -114,7 +105,7 @@ def test_gl_state_ea_against_the_restatement(systems, name, kind):
     257; E*A drawn per element from [500, 2000]."""
     S = systems(name)
     rng = np.random.default_rng(S.ne + 5)
-    u, ea = _field(S, kind, rng), rng.uniform(500.0, 2000.0, S.ne)
+    u, ea = gl_field(S, kind, rng), rng.uniform(500.0, 2000.0, S.ne)
     _check_state(_state_ea(S, u, ea), _state_bounds(S, u, ea), f"{name} {kind} per-element ea")
     # pf_gl_state itself: the restatement bound of tests/test_gl_f64.py with the model's scalar E*A ...
     _refill(S)
@@ -142,7 +133,7 @@ def test_gl_sens_against_the_restatement(systems, name):
     S = systems(name)
     rng = np.random.default_rng(S.ne + 6)
     for kind in ("large", "tiny"):
-        u = _field(S, kind, rng)
+        u = gl_field(S, kind, rng)
         a1, a2 = rng.standard_normal(S.n), rng.standard_normal(S.n) * np.exp2(rng.uniform(-8.0, 8.0, S.n))
         one = _sens(S, u, a1).cpu().numpy()
         want, bound = ir.element_sensitivity(S.nodes, S.el, u, a1, S.dim), _sens_bound(S, u, a1)

@@ -14,47 +14,28 @@ import scipy.sparse.linalg as spla
 import torch
 
 import gl_reference as gl
+from device_driver import AREA, EA, RTOL, YOUNG, CgRun, DeviceTruss, irregular_truss_with_supports, same_bits, system_cache
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-13
-YOUNG, AREA = 2000.0, 0.5
-EA = YOUNG * AREA
 
-
-class System:
+class System(DeviceTruss):
     """One truss on the device at a Green-Lagrange state u: the tangent blocks are the engine's (eng.gl_state)."""
 
     def __init__(self, nodes, el, fixed, dim, u):
-        from pinn_fem_amd import _capi
-        from pinn_fem_amd.engine import HipEngine
-        from pinn_fem_amd.fem.model import FEMModel, Material
-        self.capi = _capi
-        self.nodes = np.asarray(nodes, dtype=np.float64).reshape(-1, dim)
-        self.el, self.dim, self.fixed = np.asarray(el), dim, np.asarray(fixed, dtype=int)
-        self.n = self.nodes.size
-        self.free = gl.free_mask(self.n, self.fixed)
-        model = FEMModel(nodes=self.nodes if dim == 2 else self.nodes.reshape(-1), elements=self.el,
-                         material=Material(YOUNG, AREA, 1.0), loads=np.zeros(self.n), fixed_dofs=self.fixed, dimension=dim)
-        self.eng = HipEngine(model)
-        self.lib = self.eng.lib
+        super().__init__(nodes, el, fixed, dim, YOUNG, AREA)
         self.u = np.asarray(u, dtype=np.float64)
         self.K = gl.k_t(self.nodes, self.el, self.u, EA, dim)
         self.eng.gl_state(self.dev(self.u))
         torch.cuda.synchronize()
         self.kt = self.eng._gl[1]
 
-    def dev(self, a):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.eng.device)
-
     def coarse(self, n_agg):
         return self.eng.updated_coarse_space(self.dev(self.u), n_agg)
 
 
 def _truss_1000():
-    rng = np.random.default_rng(2000)
-    nodes, el = gl.irregular_truss(1000, rng)
-    fixed = np.unique(np.concatenate([[0, 1, 2], rng.choice(nodes.size, size=max(1, nodes.size // 10), replace=False)]))
+    nodes, el, fixed = irregular_truss_with_supports(1000, np.random.default_rng(2000))
     rng = np.random.default_rng(11)
     mean_l0 = float(np.mean(np.linalg.norm(nodes[el[:, 1]] - nodes[el[:, 0]], axis=1)))
     u = 0.05 * nodes.reshape(-1) + 0.02 * (0.3 * mean_l0 / math.sqrt(4.0)) * rng.standard_normal(nodes.size)
@@ -91,81 +72,12 @@ def _chain_5():
 
 @pytest.fixture(scope="module")
 def systems():
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = {"truss": _truss_1000, "chain": _chain_5}[name]()
-        return cache[name]
-    yield get
-    cache.clear()
-    torch.cuda.empty_cache()
+    yield from system_cache(lambda name: {"truss": _truss_1000, "chain": _chain_5}[name]())
 
 
-class Run:
-    """One begin with test-owned x / ws (filled with 7.0: what the library does not write stays).  batched: the
-    pf_pcgtm_* / pf_pcg2tm_* family with m = len(B); otherwise the single family (B one row).  dc: a DeviceCoarse for the
-    two-level families."""
-
-    def __init__(self, S, B, dc=None, batched=True, rtol=RTOL):
-        self.S, eng, lib = S, S.eng, S.lib
-        B = np.atleast_2d(np.asarray(B, dtype=np.float64))
-        self.m = m = len(B)
-        assert batched or m == 1
-        self.fam = ("pf_pcg2t" if dc is not None else "pf_pcgt") + ("m" if batched else "")
-        count = lib.pf_pcg2_workspace_count if dc is not None else lib.pf_pcg_workspace_count
-        self.stride = int(count(eng._ref()))
-        self.b = S.dev(B.reshape(-1))
-        self.x = torch.full((m * S.n,), 7.0, dtype=torch.float64, device=eng.device)
-        self.ws = torch.full((m * self.stride,), 7.0, dtype=torch.float64, device=eng.device)
-        tail = (m,) if batched else ()
-        self.head = ((eng._ref(), S.kt.data_ptr()) if dc is None else
-                     (eng._ref(), C.byref(dc.record), S.kt.data_ptr())) + tail
-        self.state_head = (eng._ref(), S.kt.data_ptr()) + tail
-        with eng.on_stream():
-            S.capi.check(getattr(lib, self.fam + "_begin")(*self.head, self.b.data_ptr(), self.x.data_ptr(),
-                                                           self.ws.data_ptr(), float(rtol), eng._stream()), self.fam)
-
-    def _states(self, st):
-        return [tuple(st[4 * k: 4 * k + 4]) for k in range(self.m)]
-
-    def iterate(self, k):
-        S, st = self.S, (C.c_double * (4 * self.m))()
-        with S.eng.on_stream():
-            S.capi.check(getattr(S.lib, self.fam + "_iterations")(*self.head, self.x.data_ptr(), self.ws.data_ptr(), int(k),
-                                                                  st, S.eng._stream()), self.fam)
-        return self._states(st)
-
-    def state(self):
-        S, st = self.S, (C.c_double * (4 * self.m))()
-        with S.eng.on_stream():
-            S.capi.check(getattr(S.lib, self.fam + "_state")(*self.state_head, self.ws.data_ptr(), st, S.eng._stream()),
-                         self.fam)
-        return self._states(st)
-
-    def graph(self, n_iter):
-        S, g = self.S, C.c_void_p()
-        with S.eng.on_stream():
-            S.capi.check(getattr(S.lib, self.fam + "_graph_create")(*self.head, self.x.data_ptr(), self.ws.data_ptr(),
-                                                                    int(n_iter), S.eng._stream(), C.byref(g)), self.fam)
-        return g
-
-    def replay(self, g):
-        S = self.S
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_graph_launch(g, S.eng._stream()), "pf_graph_launch")
-        return self.state()
-
-    def read(self):
-        """[(x, workspace) per right-hand side] on the host."""
-        torch.cuda.synchronize()
-        x, ws = self.x.cpu().numpy().reshape(self.m, -1), self.ws.cpu().numpy().reshape(self.m, -1)
-        return [(x[k], ws[k]) for k in range(self.m)]
-
-
-def _same(a, b):
-    """x and the whole workspace, bit for bit (NaN-safe: compared as bytes)."""
-    return a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+def _run(S, B, dc=None, batched=True):
+    """a tangent family on the engine's kt: pf_pcgtm_* / pf_pcg2tm_* with m = len(B), or the single family (B one row)"""
+    return CgRun(S, B, kt=S.kt.data_ptr(), dc=dc, batched=batched)
 
 
 def _dc(S, two_level):
@@ -178,16 +90,16 @@ def test_one_right_hand_side_equals_the_single_family_bitwise(systems, two_level
     S = systems("truss")
     dc = _dc(S, two_level)
     assert dc is not None or not two_level
-    one, many = Run(S, S.b_dense, dc, batched=False), Run(S, S.b_dense, dc, batched=True)
+    one, many = _run(S, S.b_dense, dc, batched=False), _run(S, S.b_dense, dc, batched=True)
     assert one.stride == many.stride
     done = 0
     for upto in (0, 7, 200):
         st1, stm = one.iterate(upto - done), many.iterate(upto - done)
         done = upto
-        assert st1 == stm, upto
-        assert _same(one.read()[0], many.read()[0]), upto
-    assert st1[0][1] == 1.0 and 16 < st1[0][0] < 200                  # it stopped on its own, inside the last call
-    assert one.state() == many.state() == st1
+        assert [st1] == stm, upto
+        assert same_bits(one.read(), many.read()[0]), upto
+    assert st1[1] == 1.0 and 16 < st1[0] < 200                        # it stopped on its own, inside the last call
+    assert [one.state()] == many.state() == [st1]
 
 
 # ---- 5. m = 2 -----------------------------------------------------------------------------------------------------------
@@ -198,23 +110,23 @@ def test_two_right_hand_sides_equal_their_single_solves_bitwise(systems, name, t
     dc = _dc(S, two_level)
     assert dc is not None or not two_level
     B = np.stack([S.b_dense, S.b_unit])
-    singles = [Run(S, B[k], dc, batched=False) for k in range(2)]
-    pair = Run(S, B, dc)
+    singles = [_run(S, B[k], dc, batched=False) for k in range(2)]
+    pair = _run(S, B, dc)
 
     def check(label):
         st = pair.state()
         got = pair.read()
         for k in range(2):
-            assert singles[k].state()[0] == st[k], (label, k)
-            assert _same(singles[k].read()[0], got[k]), (label, k)
+            assert singles[k].state() == st[k], (label, k)
+            assert same_bits(singles[k].read(), got[k]), (label, k)
         return st, got
 
     check("begin")
     # the iteration counts, from a probe of each
     T = []
     for k in range(2):
-        probe = Run(S, B[k], dc, batched=False)
-        st = probe.iterate(4000)[0]
+        probe = _run(S, B[k], dc, batched=False)
+        st = probe.iterate(4000)
         assert st[1] == 1.0
         T.append(int(st[0]))
     print(f"{name}, {'two-level' if two_level else 'jacobi'}: iterations {T}")
@@ -237,11 +149,11 @@ def test_two_right_hand_sides_equal_their_single_solves_bitwise(systems, name, t
     for r in singles + [pair]:
         r.iterate(T[last] - T[first])
     st2, got2 = check("second stop")
-    assert st2[first] == st[first] and _same(got2[first], got[first])
-    assert st2[last][:2] == (float(T[last]), 1.0) and (T[last] == T[first] or not _same(got2[last], got[last]))
+    assert st2[first] == st[first] and same_bits(got2[first], got[first])
+    assert st2[last][:2] == (float(T[last]), 1.0) and (T[last] == T[first] or not same_bits(got2[last], got[last]))
     # both stopped: further launches change nothing
     assert pair.iterate(10) == st2
-    assert all(_same(a, b) for a, b in zip(pair.read(), got2))
+    assert all(same_bits(a, b) for a, b in zip(pair.read(), got2))
 
 
 @pytest.mark.parametrize("two_level", [False, True], ids=["jacobi", "two-level"])
@@ -250,19 +162,19 @@ def test_batched_graph_of_64_equals_eager_bitwise(systems, name, two_level):
     S = systems(name)
     dc = _dc(S, two_level)
     B = np.stack([S.b_dense, S.b_unit])
-    eager, graphed = Run(S, B, dc), Run(S, B, dc)
+    eager, graphed = _run(S, B, dc), _run(S, B, dc)
     g = graphed.graph(64)
     try:
         for i in range(4):
             st_g, st_e = graphed.replay(g), eager.iterate(64)
             assert st_g == st_e, i
-            assert all(_same(a, b) for a, b in zip(graphed.read(), eager.read())), i
+            assert all(same_bits(a, b) for a, b in zip(graphed.read(), eager.read())), i
             if all(s[1] == 1.0 for s in st_g):
                 break
         assert all(s[1] == 1.0 for s in st_g), st_g
         after = graphed.read()
         assert graphed.replay(g) == st_g                                # after the stop a replay is a no-op
-        assert all(_same(a, b) for a, b in zip(graphed.read(), after))
+        assert all(same_bits(a, b) for a, b in zip(graphed.read(), after))
     finally:
         S.lib.pf_graph_destroy(g)
 
@@ -273,12 +185,12 @@ def test_zero_right_hand_side_is_done_at_begin(systems, name, two_level):
     S = systems(name)
     dc = _dc(S, two_level)
     B = np.stack([S.b_dense, np.zeros(S.n)])
-    single, pair = Run(S, B[0], dc, batched=False), Run(S, B, dc)
+    single, pair = _run(S, B[0], dc, batched=False), _run(S, B, dc)
     assert pair.state()[1] == (0.0, 1.0, 0.0, 0.0) and pair.state()[0][:2] == (0.0, 0.0)
-    st1, st = single.iterate(4000)[0], pair.iterate(4000)
+    st1, st = single.iterate(4000), pair.iterate(4000)
     assert st[0] == st1 and st1[1] == 1.0 and st[1] == (0.0, 1.0, 0.0, 0.0)
     got = pair.read()
-    assert _same(single.read()[0], got[0]) and not got[1][0].any()
+    assert same_bits(single.read(), got[0]) and not got[1][0].any()
 
 
 # ---- 6. argument errors -------------------------------------------------------------------------------------------------

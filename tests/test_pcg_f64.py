@@ -14,147 +14,17 @@ import scipy.sparse.linalg as spla
 import torch
 
 import f64_reference as ref
-from helpers import _random_truss
+from device_driver import RTOL, U24, U53, CgRun, bar1d, hub_truss, manufactured, same_bits, system_cache, wide_vector
+from device_driver import LinearTruss as System
 
 pytestmark = pytest.mark.gpu
 
-U53, U24 = 2.0 ** -53, 2.0 ** -24
-RTOL = 1e-13
-ST_COUNT = 16
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# systems: device engine + CPU matrices of the same truss
-# ---------------------------------------------------------------------------------------------------------------------
-class System:
-    """One truss on the device (HipEngine) and its CPU float64 matrices.  `K`, `Kabs` are built from the plan's
-    own float32 geometry widened to float64 (the inputs the kernel reads) with s = (E*A)/l0 as the kernel forms
-    it; `K64`, `Kabs64` from the float64 node coordinates."""
-
-    def __init__(self, nodes, el, fixed, dim, young=3.0, area=0.25, net_widths=(None, None), seed=0):
-        from pinn_fem_amd.engine import HipEngine
-        from pinn_fem_amd.fem.model import FEMModel, Material
-        from pinn_fem_amd.fem.properties import NNProperty
-        from pinn_fem_amd.nets import SimpleNN
-        torch.manual_seed(seed)
-        props = []
-        for w, scale in zip(net_widths, (young, area)):
-            props.append(scale if w is None else
-                         NNProperty(net=SimpleNN(hidden_layers=2, neurons_per_layer=w, input_dim=dim + 1),
-                                    input_dim=dim + 1, enforce_positive=True, scale=scale))
-        self.nodes, self.el, self.dim = np.asarray(nodes, dtype=np.float64), np.asarray(el), dim
-        self.n_nodes = len(self.nodes)
-        self.n = self.n_nodes * dim
-        model = FEMModel(nodes=self.nodes, elements=self.el, material=Material(props[0], props[1], 1.0),
-                         loads=np.zeros(self.n), fixed_dofs=fixed, dimension=dim)
-        self.eng = HipEngine(model)
-        ne = len(self.el)
-        ea = []
-        if any(w is not None for w in net_widths):
-            self.eng.eval_properties(1.0)
-            torch.cuda.synchronize()
-        for w, scale, buf in zip(net_widths, (young, area), (self.eng.prop_e, self.eng.prop_a)):
-            # the nets are not under test: their float32 outputs are read back and fed to the reference
-            ea.append(np.full(ne, np.float32(scale), dtype=np.float64) if w is None
-                      else buf[:ne].cpu().numpy().astype(np.float64))
-        self.E, self.A = ea
-        assert np.all(np.isfinite(self.E * self.A)) and np.all(self.E * self.A > 0)
-        self.mask = np.zeros(self.n, dtype=bool)
-        self.mask[np.asarray(fixed, dtype=int)] = True
-        self.max_degree = int(np.bincount(self.el.reshape(-1)).max())
-        self._cache = {}
-
-    def _get(self, key, make):
-        if key not in self._cache:
-            self._cache[key] = make()
-        return self._cache[key]
-
-    @property
-    def geo(self):
-        return self.eng.plan.egeo.astype(np.float64)
-
-    @property
-    def s(self):
-        return (self.E * self.A) / self.geo[:, 3]
-
-    K = property(lambda self: self._get("K", lambda: ref.k_csr(self.geo, self.el, self.s, self.dim, self.n_nodes)))
-    Kabs = property(lambda self: self._get("Kabs", lambda: ref.abs_k_csr(self.geo, self.el, self.s, self.dim, self.n_nodes)))
-    Kff = property(lambda self: self._get("Kff", lambda: ref.restrict_ff(self.K, self.mask)))
-    dinv = property(lambda self: self._get("dinv", lambda: ref.jacobi_dinv(self.K, self.mask)))
-
-    def from_f64_coordinates(self):
-        g = ref.geo_f64(self.nodes, self.el, self.dim)
-        s = (self.E * self.A) / g[:, 3]
-        return (ref.k_csr(g, self.el, s, self.dim, self.n_nodes), ref.abs_k_csr(g, self.el, s, self.dim, self.n_nodes))
-
-    # ---- raw C ABI ------------------------------------------------------------------------------------
-    def dev(self, a):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.eng.device)
-
-    def kv(self, v, zero_fixed):
-        out = self.eng.kv_f64(self.dev(v), zero_fixed=zero_fixed)
-        torch.cuda.synchronize()
-        return out.cpu().numpy()
-
-
-class Run:
-    """One pf_pcg_begin with test-owned x / b / ws, so that the workspace can be inspected."""
-
-    def __init__(self, S, b, rtol=RTOL):
-        from pinn_fem_amd import _capi
-        self.S, self.capi, eng = S, _capi, S.eng
-        self.b = S.dev(b)
-        self.x = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)        # begin must overwrite it
-        self.ws = torch.full((int(eng.lib.pf_pcg_workspace_count(eng._ref())),), 7.0, dtype=torch.float64,
-                             device=eng.device)
-        with eng.on_stream():
-            _capi.check(eng.lib.pf_pcg_begin(eng._ref(), self.b.data_ptr(), self.x.data_ptr(), self.ws.data_ptr(),
-                                             float(rtol), eng._stream()), "pf_pcg_begin")
-
-    def iterate(self, k):
-        eng, st = self.S.eng, (C.c_double * 4)()
-        with eng.on_stream():
-            self.capi.check(eng.lib.pf_pcg_iterations(eng._ref(), self.x.data_ptr(), self.ws.data_ptr(), int(k), st,
-                                                      eng._stream()), "pf_pcg_iterations")
-        return tuple(st)
-
-    def state(self):
-        eng, st = self.S.eng, (C.c_double * 4)()
-        with eng.on_stream():
-            self.capi.check(eng.lib.pf_pcg_state(eng._ref(), self.ws.data_ptr(), st, eng._stream()), "pf_pcg_state")
-        return tuple(st)
-
-    def graph(self, n_iter):
-        eng, g = self.S.eng, C.c_void_p()
-        with eng.on_stream():
-            self.capi.check(eng.lib.pf_pcg_graph_create(eng._ref(), self.x.data_ptr(), self.ws.data_ptr(), int(n_iter),
-                                                        eng._stream(), C.byref(g)), "pf_pcg_graph_create")
-        return g
-
-    def replay(self, g):
-        eng = self.S.eng
-        with eng.on_stream():
-            self.capi.check(eng.lib.pf_graph_launch(g, eng._stream()), "pf_graph_launch")
-        return self.state()
-
-    def read(self):
-        """(x, dict of the workspace's parts, the whole workspace) on the host."""
-        torch.cuda.synchronize()
-        n, ws = self.S.n, self.ws.cpu().numpy()
-        parts = {name: ws[i * n:(i + 1) * n] for i, name in enumerate(("r", "z", "p", "ap", "dinv"))}
-        parts["state"] = ws[-ST_COUNT:]
-        return self.x.cpu().numpy(), parts, ws
 
 
 def _mask_of(n, fixed):
     m = np.zeros(n, dtype=bool)
     m[np.asarray(fixed, dtype=int)] = True
     return m
-
-
-def _wide_vector(rng, n):
-    """random signs, magnitudes spread over 2^-20 .. 2^20"""
-    return rng.choice([-1.0, 1.0], n) * np.exp2(rng.uniform(-20.0, 20.0, n))
 
 
 def _chain2d(n_nodes, rng):
@@ -169,51 +39,32 @@ def _chain2d(n_nodes, rng):
     return nodes, el, fixed
 
 
-def _bar1d(n_nodes, rng):
-    x, el, _ = ref.pinned_bar(n_nodes, rng)
-    flip = rng.random(len(el)) < 0.5
-    el[flip] = el[flip][:, ::-1]
-    fixed = np.unique(np.concatenate([[0], rng.choice(n_nodes, size=max(1, n_nodes // 9), replace=False)]))
-    return x, el, fixed
-
-
-def _hub_truss(rng):
-    nodes, el = _random_truss(2500, rng, 300)
-    fixed = np.unique(rng.choice(5000, size=250, replace=False))
-    return nodes, el, fixed
+def _make(name):
+    if name.startswith("grid"):
+        side = int(name.split("_")[0][4:])
+        nets = {"scalar": (None, None), "EA": (20, 15), "E": (20, None)}[name.split("_")[1]]
+        nodes, el, fixed = ref.pinned_grid_truss(side, np.random.default_rng(side))
+        return System(nodes, el, fixed, 2, 2.0, 0.5, nets)
+    if name.startswith("hub"):
+        nets = {"scalar": (None, None), "E": (20, None)}[name.split("_")[1]]
+        return System(*hub_truss(np.random.default_rng(2500)), 2, 2.0, 0.5, nets)
+    if name == "bar300k":
+        x, el, fixed = ref.pinned_bar(300_000, np.random.default_rng(64))
+        return System(x, el, fixed, 1, 3.0, 0.25)
+    raise KeyError(name)
 
 
 @pytest.fixture(scope="module")
 def systems():
     """Every larger system is built once per module (the CPU matrices at side 750 cost some 20 s each)."""
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            if name.startswith("grid"):
-                side = int(name.split("_")[0][4:])
-                nets = {"scalar": (None, None), "EA": (20, 15), "E": (20, None)}[name.split("_")[1]]
-                nodes, el, fixed = ref.pinned_grid_truss(side, np.random.default_rng(side))
-                cache[name] = System(nodes, el, fixed, 2, 2.0, 0.5, nets)
-            elif name.startswith("hub"):
-                nets = {"scalar": (None, None), "E": (20, None)}[name.split("_")[1]]
-                cache[name] = System(*_hub_truss(np.random.default_rng(2500)), 2, 2.0, 0.5, nets)
-            elif name == "bar300k":
-                x, el, fixed = ref.pinned_bar(300_000, np.random.default_rng(64))
-                cache[name] = System(x, el, fixed, 1, 3.0, 0.25)
-            else:
-                raise KeyError(name)
-        return cache[name]
-    yield get
-    cache.clear()
-    torch.cuda.empty_cache()
+    yield from system_cache(_make)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # A. pf_kv_f64 against the CSR product
 # ---------------------------------------------------------------------------------------------------------------------
 def _check_kv(S, rng, symmetry=False):
-    v = _wide_vector(rng, S.n)
+    v = wide_vector(rng, S.n)
     got, got_zf = S.kv(v, False), S.kv(v, True)
     assert np.all(np.isfinite(got))
     want, scale = S.K @ v, S.Kabs @ np.abs(v)
@@ -237,7 +88,7 @@ def _check_kv(S, rng, symmetry=False):
     assert np.all(got_zf[S.mask] == 0.0) and not np.any(np.signbit(got_zf[S.mask]))
     assert np.array_equal(got_zf[~S.mask].view(np.uint64), got[~S.mask].view(np.uint64))
     if symmetry:
-        w = _wide_vector(rng, S.n)
+        w = wide_vector(rng, S.n)
         kw = S.kv(w, False)
         lhs, rhs = math.fsum(w * got), math.fsum(v * kw)                  # one rounding per product, exact sums
         unit = math.fsum(np.abs(w) * scale)
@@ -258,7 +109,7 @@ def test_kv_f64_chain_2d(n_nodes):
 @pytest.mark.parametrize("n_nodes", [2, 257, 262_145])
 def test_kv_f64_bar_1d(n_nodes):
     rng = np.random.default_rng(n_nodes + 1)
-    _check_kv(System(*_bar1d(n_nodes, rng), 1), rng)
+    _check_kv(System(*bar1d(n_nodes, rng), 1), rng)
 
 
 def test_kv_f64_hub_truss(systems):
@@ -286,13 +137,8 @@ def test_kv_f64_net_properties(systems, name):
 # ---------------------------------------------------------------------------------------------------------------------
 # B. state of a running solve
 # ---------------------------------------------------------------------------------------------------------------------
-def _manufactured(S, rng):
-    xs = np.where(S.mask, 0.0, rng.standard_normal(S.n))
-    return xs, S.Kff @ xs
-
-
 def _check_invariants(S, run, b, asked, st):
-    x, w, _ = run.read()
+    x, w = run.read()[0], run.parts()
     free, fixed = ~S.mask, S.mask
     bf = np.where(fixed, 0.0, b)
     # dinv = 1 / diag(K_ff): the diagonal is the same sum of the same products in the same (element) order, and the
@@ -332,16 +178,16 @@ def test_pcg_running_state(systems, name):
     At k <= 20 everything is below 4e-15; the residual drift |r - (b - K x)| / |b| stays below 5e-16."""
     S = systems(name)
     rng = np.random.default_rng(5)
-    xs, b = _manufactured(S, rng)
+    xs, b = manufactured(S, rng)
     b_dirty = b + np.where(S.mask, 3.0, 0.0)                          # entries on fixed dofs are ignored
     ks = (1, 2, 5, 20, 64)
     _, _, _, _, _, snaps = ref.pcg_reference(S.Kff, S.dinv, b, RTOL, 64, snapshots=ks)
     perm = rng.permutation(S.n)
     Kp = S.Kff[perm][:, perm].tocsr()
     _, _, _, _, _, snaps_p = ref.pcg_reference(Kp, S.dinv[perm], b[perm], RTOL, 64, snapshots=ks)
-    run = Run(S, b_dirty)
+    run = CgRun(S, b_dirty)
     _check_invariants(S, run, b_dirty, 0, run.state())
-    x0, w0, _ = run.read()
+    x0, w0 = run.read()[0], run.parts()
     assert not x0.any() and np.array_equal(w0["r"], b) and np.array_equal(w0["p"], w0["z"])
     assert tuple(w0["state"][[7, 6]]) == (0.0, 0.0) and w0["state"][8] == RTOL * RTOL   # ITERS, DONE, RTOL2
     done = 0
@@ -385,7 +231,7 @@ def test_pcg_solve_to_convergence(systems, name):
       grid100_scalar  194  3.25e-12 | 194  3.19e-12  9.83e-14
       bar300k         490  1.40e-10 | 490  1.40e-10  9.98e-14"""
     S = systems(name)
-    xs, b = _manufactured(S, np.random.default_rng(9))
+    xs, b = manufactured(S, np.random.default_rng(9))
     y, it_ref, info = _scipy_cg(S, b, 5000)
     assert info == 0
     err_ref = np.max(np.abs(y - xs)) / np.max(np.abs(xs))
@@ -407,23 +253,19 @@ def test_pcg_solve_to_convergence(systems, name):
 # ---------------------------------------------------------------------------------------------------------------------
 # D. graph replay equals eager launches, bit for bit
 # ---------------------------------------------------------------------------------------------------------------------
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[2], b[2])
-
-
 def test_pcg_graph_replay_equals_eager_bitwise(systems, monkeypatch):
     S = systems("grid200_scalar")
     for seed in range(13, 20):                         # a right-hand side whose stop is not at a replay's very end
-        _, b = _manufactured(S, np.random.default_rng(seed))
-        probe = Run(S, b)
+        _, b = manufactured(S, np.random.default_rng(seed))
+        probe = CgRun(S, b)
         T = int(probe.iterate(4000)[0])                # the stopping iteration
         if 2 <= T % 64 <= 62:
             break
     assert probe.state()[1] == 1.0 and 2 <= T % 64 <= 62 and 64 < T < 400, T
     k = -(-T // 64)                                    # the stop test fires inside the k-th replay
-    eager = Run(S, b)
+    eager = CgRun(S, b)
     st_e = eager.iterate(64 * k)
-    graphed = Run(S, b)
+    graphed = CgRun(S, b)
     g = graphed.graph(64)
     try:
         for i in range(k):
@@ -431,15 +273,15 @@ def test_pcg_graph_replay_equals_eager_bitwise(systems, monkeypatch):
             assert st_g[:2] == ((i + 1) * 64.0, 0.0) if i < k - 1 else st_g[:2] == (float(T), 1.0)
         assert st_g == st_e and st_e[0] == T
         a, e = graphed.read(), eager.read()
-        assert _same(a, e) and _same(e, probe.read())
+        assert same_bits(a, e) and same_bits(e, probe.read())
         # after the stop every launch is a no-op: x, the whole workspace and the counter stay
         assert graphed.replay(g) == st_g and eager.iterate(10) == st_e
-        assert _same(graphed.read(), a) and _same(eager.read(), e)
+        assert same_bits(graphed.read(), a) and same_bits(eager.read(), e)
     finally:
         S.eng.lib.pf_graph_destroy(g)
 
     def plain(n_iter):
-        r = Run(S, b)
+        r = CgRun(S, b)
         st = r.iterate(n_iter)
         return r.read()[0], st
 
@@ -466,8 +308,8 @@ def test_pcg_graph_replay_equals_eager_bitwise(systems, monkeypatch):
 # E. edge semantics
 # ---------------------------------------------------------------------------------------------------------------------
 def _finite_run(run):
-    x, w, ws = run.read()
-    assert np.all(np.isfinite(x)) and np.all(np.isfinite(ws[-ST_COUNT:]))
+    x, w = run.read()[0], run.parts()
+    assert np.all(np.isfinite(x)) and np.all(np.isfinite(w["state"]))
     for name in ("r", "z", "p", "dinv"):
         assert np.all(np.isfinite(w[name])), name
     return x, w
@@ -476,7 +318,7 @@ def _finite_run(run):
 def test_pcg_zero_and_fixed_only_rhs(systems):
     S = systems("grid100_scalar")
     for b in (np.zeros(S.n), np.where(S.mask, 5.0, 0.0)):
-        run = Run(S, b)
+        run = CgRun(S, b)
         assert run.state() == (0.0, 1.0, 0.0, 0.0)
         assert run.iterate(7) == (0.0, 1.0, 0.0, 0.0)
         x, w = _finite_run(run)
@@ -488,7 +330,7 @@ def test_pcg_zero_and_fixed_only_rhs(systems):
 def test_pcg_ignores_rhs_on_fixed_dofs(systems):
     S = systems("grid100_scalar")
     rng = np.random.default_rng(17)
-    _, b = _manufactured(S, rng)
+    _, b = manufactured(S, rng)
     b2 = b + np.where(S.mask, rng.standard_normal(S.n) * 1e6, 0.0)
     outs = []
     for rhs in (b, b2):
@@ -503,7 +345,7 @@ def test_pcg_one_element_mesh():
     nodes = np.array([[0.0, 0.0], [0.75, 0.5]])
     S = System(nodes, np.array([[1, 0]]), np.array([0, 1, 3]), 2)
     b = np.array([9.0, 9.0, 0.3, 9.0])                 # entries on fixed dofs are ignored
-    run = Run(S, b)
+    run = CgRun(S, b)
     assert run.state() == (0.0, 0.0, 0.3 * 0.3, 0.3 * 0.3)
     st = run.iterate(5)
     x, w = _finite_run(run)
@@ -524,7 +366,7 @@ def test_pcg_free_dof_without_stiffness():
     assert S.K.diagonal()[3] == 0.0
     for b3 in (0.0, 0.25):
         b = np.array([0.0, 0.0, 0.4, b3, -1.1, 0.0])
-        run = Run(S, b)
+        run = CgRun(S, b)
         st = run.iterate(50)
         x, w = _finite_run(run)
         assert w["dinv"][3] == 0.0 and x[3] == 0.0 and np.all(x[S.mask] == 0.0)
@@ -540,17 +382,17 @@ def test_pcg_free_dof_without_stiffness():
 
 def test_pcg_rtol_zero_runs_to_max_iter(systems):
     S = systems("grid100_scalar")
-    _, b = _manufactured(S, np.random.default_rng(19))
+    _, b = manufactured(S, np.random.default_rng(19))
     x, it, ok, rr, bb = S.eng.pcg_solve(S.dev(b), rtol=0.0, max_iter=200)
     x = x.cpu().numpy()
     assert np.all(np.isfinite(x)) and math.isfinite(rr) and bb > 0
-    run = Run(S, b, rtol=0.0)
+    run = CgRun(S, b, rtol=0.0)
     st = run.iterate(200)
     assert st[0] == it <= 200 and (st[2], st[3]) == (rr, bb)
     if it < 200:                                       # only an exact zero of |r|^2 or r.z ends it early
-        assert st[1] == 1.0 and (rr == 0.0 or run.read()[1]["state"][0] == 0.0)
+        assert st[1] == 1.0 and (rr == 0.0 or run.parts()["state"][0] == 0.0)
     else:
-        assert st[1] == 0.0 or rr == 0.0 or run.read()[1]["state"][0] == 0.0
+        assert st[1] == 0.0 or rr == 0.0 or run.parts()["state"][0] == 0.0
     assert not ok or rr == 0.0
     assert rr < 1e-12 * bb                             # it did iterate: 200 steps take |r| far below 1e-6 |b|
 

@@ -12,12 +12,11 @@ import pytest
 import torch
 
 import two_level_reference as tl
+from device_driver import RTOL, U53, CgRun, bar1d, hub_truss, manufactured, same_bits, system_cache, wide_vector
+from device_driver import LinearTruss as System
 from helpers import _random_truss, load_run, product_example, rel_err
-from test_pcg_f64 import RTOL, ST_COUNT, U53, System, _bar1d, _hub_truss, _manufactured, _wide_vector
 
 pytestmark = pytest.mark.gpu
-
-COARSE_MAX = 768
 
 
 def _warren(panels):
@@ -40,28 +39,22 @@ def _chain(n):
     return nodes, el, fixed
 
 
+SYSTEMS = {
+    "warren100": lambda: (System(*_warren(100), 2, 2.0, 0.5), 32),
+    "warren300": lambda: (System(*_warren(300), 2, 2.0, 0.5), 64),
+    "warren1000": lambda: (System(*_warren(1000), 2, 2.0, 0.5), 256),
+    "hub": lambda: (System(*hub_truss(np.random.default_rng(2500)), 2, 2.0, 0.5), None),
+    "hub_E": lambda: (System(*hub_truss(np.random.default_rng(2500)), 2, 2.0, 0.5, (20, None)), None),
+    "random": lambda: (System(*_random_truss(611, np.random.default_rng(611)), np.array([0, 1, 41, 700, 1221]), 2), 37),
+    "bar": lambda: (System(*bar1d(2000, np.random.default_rng(7)), 1, 3.0, 0.25), 100),
+    "dead": lambda: (System(*_warren_dead_aggregate(), 2, 2.0, 0.5), 9),
+    "chain": lambda: (System(*_chain(200), 2, 2.0, 0.5), 16),
+}
+
+
 @pytest.fixture(scope="module")
 def systems():
-    cache = {}
-    make = {
-        "warren100": lambda: (System(*_warren(100), 2, 2.0, 0.5), 32),
-        "warren300": lambda: (System(*_warren(300), 2, 2.0, 0.5), 64),
-        "warren1000": lambda: (System(*_warren(1000), 2, 2.0, 0.5), 256),
-        "hub": lambda: (System(*_hub_truss(np.random.default_rng(2500)), 2, 2.0, 0.5), None),
-        "hub_E": lambda: (System(*_hub_truss(np.random.default_rng(2500)), 2, 2.0, 0.5, (20, None)), None),
-        "random": lambda: (System(*_random_truss(611, np.random.default_rng(611)), np.array([0, 1, 41, 700, 1221]), 2), 37),
-        "bar": lambda: (System(*_bar1d(2000, np.random.default_rng(7)), 1, 3.0, 0.25), 100),
-        "dead": lambda: (System(*_warren_dead_aggregate(), 2, 2.0, 0.5), 9),
-        "chain": lambda: (System(*_chain(200), 2, 2.0, 0.5), 16),
-    }
-
-    def get(name):
-        if name not in cache:
-            cache[name] = make[name]()
-        return cache[name]
-    yield get
-    cache.clear()
-    torch.cuda.empty_cache()
+    yield from system_cache(lambda name: SYSTEMS[name]())
 
 
 def _coarse(S, n_agg):
@@ -71,56 +64,8 @@ def _coarse(S, n_agg):
     return dc, cs, int(np.max(np.diff(cs.agg_ptr)))
 
 
-class Run2:
-    """One pf_pcg2_begin with test-owned x / b / ws."""
-
-    def __init__(self, S, n_agg, b, rtol=RTOL):
-        from pinn_fem_amd import _capi
-        self.S, self.capi, eng = S, _capi, S.eng
-        self.dc = eng.coarse_space(n_agg)
-        self.c = C.byref(self.dc.record)
-        self.b = S.dev(b)
-        self.x = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
-        self.ws = torch.full((int(eng.lib.pf_pcg2_workspace_count(eng._ref())),), 7.0, dtype=torch.float64,
-                             device=eng.device)
-        with eng.on_stream():
-            _capi.check(eng.lib.pf_pcg2_begin(eng._ref(), self.c, self.b.data_ptr(), self.x.data_ptr(),
-                                              self.ws.data_ptr(), float(rtol), eng._stream()), "pf_pcg2_begin")
-
-    def iterate(self, k):
-        eng, st = self.S.eng, (C.c_double * 4)()
-        with eng.on_stream():
-            self.capi.check(eng.lib.pf_pcg2_iterations(eng._ref(), self.c, self.x.data_ptr(), self.ws.data_ptr(), int(k),
-                                                       st, eng._stream()), "pf_pcg2_iterations")
-        return tuple(st)
-
-    def state(self):
-        eng, st = self.S.eng, (C.c_double * 4)()
-        with eng.on_stream():
-            self.capi.check(eng.lib.pf_pcg2_state(eng._ref(), self.ws.data_ptr(), st, eng._stream()), "pf_pcg2_state")
-        return tuple(st)
-
-    def graph(self, n_iter):
-        eng, g = self.S.eng, C.c_void_p()
-        with eng.on_stream():
-            self.capi.check(eng.lib.pf_pcg2_graph_create(eng._ref(), self.c, self.x.data_ptr(), self.ws.data_ptr(),
-                                                         int(n_iter), eng._stream(), C.byref(g)), "pf_pcg2_graph_create")
-        return g
-
-    def replay(self, g):
-        eng = self.S.eng
-        with eng.on_stream():
-            self.capi.check(eng.lib.pf_graph_launch(g, eng._stream()), "pf_graph_launch")
-        return self.state()
-
-    def read(self):
-        """(x, named parts of the workspace, the whole workspace) on the host."""
-        torch.cuda.synchronize()
-        n, ws = self.S.n, self.ws.cpu().numpy()
-        parts = {name: ws[i * n:(i + 1) * n] for i, name in enumerate(("r", "z", "p", "ap", "dinv"))}
-        tail = ws[-(ST_COUNT + 2 * COARSE_MAX):]
-        parts["state"], parts["w"], parts["y"] = tail[:ST_COUNT], tail[ST_COUNT:ST_COUNT + COARSE_MAX], tail[ST_COUNT + COARSE_MAX:]
-        return self.x.cpu().numpy(), parts, ws
+def _run(S, n_agg, b):
+    return CgRun(S, b, dc=S.eng.coarse_space(n_agg))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -159,9 +104,9 @@ def test_one_application(systems, name):
     S, n_agg = systems(name)
     dc, cs, m = _coarse(S, n_agg)
     rng = np.random.default_rng(21)
-    b = _wide_vector(rng, S.n)
-    run = Run2(S, n_agg, b)
-    x, w, _ = run.read()
+    b = wide_vector(rng, S.n)
+    run = _run(S, n_agg, b)
+    x, w = run.read()[0], run.parts()
     P = tl.TwoLevel(S.K, S.mask, cs, a_inv=dc.a_inv_host)         # the inverse the device reads: A^-1 is not under test
     r = np.where(S.mask, 0.0, b)
     assert not x.any() and np.array_equal(w["r"], r) and np.array_equal(w["p"], w["z"])
@@ -207,7 +152,7 @@ def _solve_both(S, n_agg, b):
 def test_two_level_solve_to_convergence(systems, name):
     """Manufactured solution at rtol 1e-13; scipy's CG with the restated preconditioner is the yardstick."""
     S, n_agg = systems(name)
-    xs, b = _manufactured(S, np.random.default_rng(9))
+    xs, b = manufactured(S, np.random.default_rng(9))
     y, it_ref, x, it, ok, rr, bb = _solve_both(S, n_agg, b)
     err_ref = np.max(np.abs(y - xs)) / np.max(np.abs(xs))
     err = np.max(np.abs(x - xs)) / np.max(np.abs(xs))
@@ -225,7 +170,7 @@ def test_two_level_solve_warren_1000(systems):
     """4 002 dofs, 256 aggregates: the recursive and the true residual part ways (as for Jacobi), so only the error
     against the direct solve is held against scipy's."""
     S, n_agg = systems("warren1000")
-    xs, b = _manufactured(S, np.random.default_rng(9))
+    xs, b = manufactured(S, np.random.default_rng(9))
     u = tl.direct_solve(S.K, S.mask, b)
     y, it_ref, x, it, ok, rr, bb = _solve_both(S, n_agg, b)
     scale = np.max(np.abs(u))
@@ -251,35 +196,31 @@ def test_two_level_takes_a_tenth_of_the_jacobi_iterations(systems):
 # ---------------------------------------------------------------------------------------------------------------------
 # D. graph replay equals eager launches, bit for bit
 # ---------------------------------------------------------------------------------------------------------------------
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[2], b[2])          # x and the whole workspace
-
-
 def test_two_level_graph_replay_equals_eager_bitwise(systems):
     S, n_agg = systems("warren300")
-    _, b = _manufactured(S, np.random.default_rng(13))
-    probe = Run2(S, n_agg, b)
+    _, b = manufactured(S, np.random.default_rng(13))
+    probe = _run(S, n_agg, b)
     T = int(probe.iterate(2000)[0])                                 # the stopping iteration
     assert probe.state()[1] == 1.0
     poll = next(q for q in (16, 15, 14, 13) if 2 <= T % q <= q - 2)
     assert T > 4 * poll, T
     k = -(-T // poll)
-    eager, graphed = Run2(S, n_agg, b), Run2(S, n_agg, b)
+    eager, graphed = _run(S, n_agg, b), _run(S, n_agg, b)
     g = graphed.graph(poll)
     try:
         for i in range(3):
             st_g = graphed.replay(g)
         st_e = eager.iterate(3 * poll)
         assert st_g == st_e == (3.0 * poll, 0.0, st_e[2], st_e[3])
-        assert _same(graphed.read(), eager.read())                  # after 3 polls: x, r, z, p, ap, dinv, partials, state, w, y
+        assert same_bits(graphed.read(), eager.read())             # after 3 polls: x, r, z, p, ap, dinv, partials, state, w, y
         for i in range(3, k):
             st_g = graphed.replay(g)
         st_e = eager.iterate((k - 3) * poll)
         assert st_g == st_e and st_e[:2] == (float(T), 1.0)         # stopped in mid-replay
         a, e = graphed.read(), eager.read()
-        assert _same(a, e) and _same(e, probe.read())
+        assert same_bits(a, e) and same_bits(e, probe.read())
         assert graphed.replay(g) == st_g and eager.iterate(5) == st_e           # after the stop every launch is a no-op
-        assert _same(graphed.read(), a) and _same(eager.read(), e)
+        assert same_bits(graphed.read(), a) and same_bits(eager.read(), e)
     finally:
         S.eng.lib.pf_graph_destroy(g)
     outs = []
@@ -296,10 +237,10 @@ def test_two_level_graph_replay_equals_eager_bitwise(systems):
 def test_two_level_zero_and_fixed_only_rhs(systems):
     S, n_agg = systems("warren100")
     for b in (np.zeros(S.n), np.where(S.mask, 5.0, 0.0)):
-        run = Run2(S, n_agg, b)
+        run = _run(S, n_agg, b)
         assert run.state() == (0.0, 1.0, 0.0, 0.0)
         assert run.iterate(7) == (0.0, 1.0, 0.0, 0.0)
-        x, w, ws = run.read()
+        x, w = run.read()[0], run.parts()
         assert not x.any() and not w["r"].any() and not w["z"].any() and not w["p"].any()
         assert np.all(np.isfinite(w["state"])) and np.all(np.isfinite(w["dinv"]))
         x, it, ok, rr, bb = S.eng.pcg_solve(S.dev(b), rtol=RTOL, preconditioner="two-level", n_aggregates=n_agg)
@@ -322,13 +263,13 @@ def test_two_level_one_element_mesh():
 
 def test_two_level_aggregate_counts(systems):
     S, _ = systems("warren100")
-    xs, b = _manufactured(S, np.random.default_rng(3))
+    xs, b = manufactured(S, np.random.default_rng(3))
     for n_agg, expect in ((1, 1), (250, 201)):                       # above the node count: clamped to it
         x, it, ok, rr, bb = S.eng.pcg_solve(S.dev(b), rtol=RTOL, preconditioner="two-level", n_aggregates=n_agg)
         assert ok and S.eng.coarse_space(n_agg).space.n_agg == expect
         assert np.max(np.abs(x.cpu().numpy() - xs)) <= 1e-6 * np.max(np.abs(xs))
     small = System(*_warren(20), 2, 2.0, 0.5)                        # 41 nodes
-    xs, b = _manufactured(small, np.random.default_rng(4))
+    xs, b = manufactured(small, np.random.default_rng(4))
     x, it, ok, rr, bb = small.eng.pcg_solve(small.dev(b), rtol=RTOL, preconditioner="two-level", n_aggregates=200)
     assert ok and small.eng.coarse_space(200).space.n_agg == 41
     assert np.max(np.abs(x.cpu().numpy() - xs)) <= 1e-8 * np.max(np.abs(xs))
@@ -414,7 +355,7 @@ def test_two_level_bad_arguments(systems):
         assert msg and msg.decode().startswith("pf_"), (i, msg)
     assert not g.value
     assert lib.pf_pcg2_workspace_count(None) == _capi.PF_ERR_ARG
-    assert lib.pf_pcg2_workspace_count(P) == lib.pf_pcg_workspace_count(P) + 2 * COARSE_MAX
+    assert lib.pf_pcg2_workspace_count(P) == lib.pf_pcg_workspace_count(P) + 2 * _capi.PF_COARSE_MAX
     with pytest.raises(ValueError, match="pf_pcg2_begin"):
         eng.pcg_solve(b, rtol=-1.0, preconditioner="two-level", n_aggregates=n_agg)
 

@@ -17,36 +17,18 @@ import torch
 import gl_reference as gl
 import two_level_reference as tl
 import two_level_tangent_reference as tt
+from device_driver import RTOL, U53, CgRun, DeviceTruss, flipped_chain_1d, irregular_truss_with_supports, same_bits
 
 pytestmark = pytest.mark.gpu
 
-U53 = 2.0 ** -53
-RTOL = 1e-13
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-class Sys:
+class Sys(DeviceTruss):
     """One truss on the device (E*A = 1e6) with the engine's own Green-Lagrange buffers."""
 
     def __init__(self, nodes, el, fixed, dim, loads=None):
-        from pinn_fem_amd import _capi
-        from pinn_fem_amd.engine import HipEngine
-        from pinn_fem_amd.fem.model import FEMModel, Material
-        self.capi, self.dim = _capi, dim
-        self.nodes = np.asarray(nodes, dtype=np.float64).reshape(-1, dim)
-        self.el, self.fixed = np.asarray(el), np.asarray(fixed, dtype=int)
-        self.n_nodes, self.ne = len(self.nodes), len(self.el)
-        self.n = self.n_nodes * dim
-        self.mask = ~gl.free_mask(self.n, self.fixed)
-        self.max_degree = int(np.bincount(self.el.reshape(-1), minlength=self.n_nodes).max())
-        self.model = FEMModel(nodes=self.nodes if dim == 2 else self.nodes.reshape(-1), elements=self.el,
-                              material=Material(tt.YOUNG, tt.AREA, 1.0), loads=np.zeros(self.n) if loads is None else loads,
-                              fixed_dofs=self.fixed, dimension=dim)
-        self.eng = HipEngine(self.model)
-        self.lib = self.eng.lib
-
-    def dev(self, a):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.eng.device)
+        super().__init__(nodes, el, fixed, dim, tt.YOUNG, tt.AREA, loads)
 
     def tangent(self, u):
         """pf_gl_state at u; K_t and |K_t| as CSR from the DEVICE's kt read back, and the device pointer of kt."""
@@ -83,9 +65,7 @@ class Sys:
 # ---------------------------------------------------------------------------------------------------------------------
 def _truss(n_elems, n_agg, dead=None, per_node=False):
     from pinn_fem_amd.coarse import strip_aggregates
-    rng = np.random.default_rng(3000 + n_elems)
-    nodes, el = gl.irregular_truss(n_elems, rng)
-    fixed = np.unique(np.concatenate([[0, 1, 2], rng.choice(nodes.size, size=max(1, nodes.size // 10), replace=False)]))
+    nodes, el, fixed = irregular_truss_with_supports(n_elems, np.random.default_rng(3000 + n_elems))
     agg = np.arange(len(nodes)) if per_node else strip_aggregates(nodes, 2, n_agg)
     if dead is not None:
         gone = np.flatnonzero(agg == dead)
@@ -95,13 +75,8 @@ def _truss(n_elems, n_agg, dead=None, per_node=False):
 
 def _bar(n_elems, n_agg):
     from pinn_fem_amd.coarse import strip_aggregates
-    rng = np.random.default_rng(4000 + n_elems)
-    x = np.concatenate([[0.0], np.cumsum(0.5 + rng.random(n_elems))])
-    e = np.arange(n_elems)
-    el = np.stack([e, e + 1], axis=1)
-    flip = rng.random(n_elems) < 0.5
-    el[flip] = el[flip][:, ::-1]
-    return Sys(x, el[rng.permutation(n_elems)], np.array([0]), 1), strip_aggregates(x, 1, n_agg)
+    x, el, fixed = flipped_chain_1d(n_elems, np.random.default_rng(4000 + n_elems))
+    return Sys(x, el, fixed, 1), strip_aggregates(x, 1, n_agg)
 
 
 def _rollers():
@@ -205,48 +180,9 @@ def warren():
     torch.cuda.empty_cache()
 
 
-class Run2t:
-    """One pf_pcg2t_begin with test-owned x / ws, on the engine's kt and a DeviceCoarse."""
-
-    def __init__(self, S, dc, b, rtol=RTOL):
-        self.S, eng = S, S.eng
-        self.head = (eng._ref(), C.byref(dc.record), eng._gl[1].data_ptr())
-        self.b = S.dev(b)
-        self.x = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
-        self.ws = torch.full((int(S.lib.pf_pcg2_workspace_count(eng._ref())),), 7.0, dtype=torch.float64, device=eng.device)
-        with eng.on_stream():
-            S.capi.check(S.lib.pf_pcg2t_begin(*self.head, self.b.data_ptr(), self.x.data_ptr(), self.ws.data_ptr(), float(rtol),
-                                              eng._stream()), "pf_pcg2t_begin")
-
-    def iterate(self, k):
-        S, st = self.S, (C.c_double * 4)()
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_pcg2t_iterations(*self.head, self.x.data_ptr(), self.ws.data_ptr(), int(k), st,
-                                                   S.eng._stream()), "pf_pcg2t_iterations")
-        return tuple(st)
-
-    def state(self):
-        S, st = self.S, (C.c_double * 4)()
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_pcg2t_state(self.head[0], self.head[2], self.ws.data_ptr(), st, S.eng._stream()), "pf_pcg2t_state")
-        return tuple(st)
-
-    def graph(self, n_iter):
-        S, g = self.S, C.c_void_p()
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_pcg2t_graph_create(*self.head, self.x.data_ptr(), self.ws.data_ptr(), int(n_iter),
-                                                     S.eng._stream(), C.byref(g)), "pf_pcg2t_graph_create")
-        return g
-
-    def replay(self, g):
-        S = self.S
-        with S.eng.on_stream():
-            S.capi.check(S.lib.pf_graph_launch(g, S.eng._stream()), "pf_graph_launch")
-        return self.state()
-
-    def read(self):
-        torch.cuda.synchronize()
-        return self.x.cpu().numpy(), self.ws.cpu().numpy()
+def _run(S, dc, b):
+    """the two-level tangent family on the engine's kt"""
+    return CgRun(S, b, kt=S.eng._gl[1].data_ptr(), dc=dc)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -335,37 +271,33 @@ def test_two_level_updated_solves_the_tangent_system(warren):
 # ---------------------------------------------------------------------------------------------------------------------
 # D. graph replay equals eager launches, bit for bit
 # ---------------------------------------------------------------------------------------------------------------------
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])          # x and the whole workspace
-
-
 def test_two_level_tangent_graph_replay_equals_eager_bitwise(warren):
     case, S, u = warren
     S.eng.gl_state(S.dev(u))
     dc = S.eng.updated_coarse_space(S.dev(u), case.n_agg)
     b = case.unit
-    probe = Run2t(S, dc, b)
+    probe = _run(S, dc, b)
     T = int(probe.iterate(2000)[0])                                 # the stopping iteration
     assert probe.state()[1] == 1.0
     poll = next(q for q in (8, 7, 6, 5) if 2 <= T % q <= q - 2)    # the stop fires inside a replay
     assert T > 4 * poll, T
     k = -(-T // poll)
-    eager, graphed = Run2t(S, dc, b), Run2t(S, dc, b)
+    eager, graphed = _run(S, dc, b), _run(S, dc, b)
     g = graphed.graph(poll)
     try:
         for i in range(3):
             st_g = graphed.replay(g)
         st_e = eager.iterate(3 * poll)
         assert st_g == st_e == (3.0 * poll, 0.0, st_e[2], st_e[3])
-        assert _same(graphed.read(), eager.read())                  # after 3 polls: x, r, z, p, ap, dinv, partials, state, w, y
+        assert same_bits(graphed.read(), eager.read())             # after 3 polls: x, r, z, p, ap, dinv, partials, state, w, y
         for i in range(3, k):
             st_g = graphed.replay(g)
         st_e = eager.iterate((k - 3) * poll)
         assert st_g == st_e and st_e[:2] == (float(T), 1.0)         # stopped in mid-replay
         a, e = graphed.read(), eager.read()
-        assert _same(a, e) and _same(e, probe.read())
+        assert same_bits(a, e) and same_bits(e, probe.read())
         assert graphed.replay(g) == st_g and eager.iterate(5) == st_e           # after the stop every launch is a no-op
-        assert _same(graphed.read(), a) and _same(eager.read(), e)
+        assert same_bits(graphed.read(), a) and same_bits(eager.read(), e)
     finally:
         S.lib.pf_graph_destroy(g)
     # pcg_solve: the refresh is repeatable to the bit, and the poll size (a graph per poll, or an odd one with an eager
