@@ -479,6 +479,16 @@ int pf_group_sum_f64(int n_elems, const double* values, const double* weights, c
                      int n_groups, double* out, void* stream);
 /* f_int_out (dev double [n_dofs], every row) = the node gather of +-g->fe, ascending element id, no atomics */
 int pf_gl_fint(const pf_problem* p, const pf_gl* g, double* f_int_out, void* stream);
+/* Right-hand sides of the sensitivity solves K_t s = -d f_int / d q_g for m groups of elements (q_g: a log-factor on E*A
+ * of group g; f_int is linear in E*A, so the derivative is the internal force of the group's elements alone).  Row k of
+ * out (dev double [m][n_dofs]) belongs to group g0 + k: out[k][dof] = -(sum of +-g->fe over the elements e of the dof's
+ * node with elem_group[e] == g0 + k), pf_gl_fint's signs and ascending element id order, 0.0 on PF_DOF_FIXED dofs.  It
+ * reads the fe of the last pf_gl_state / pf_gl_state_ea.  elem_group: dev int [n_elems]; an id outside g0..g0+m-1
+ * (negative ids included) adds nothing, a node without elements gives zeros.  One node per thread, the group in
+ * blockIdx.y, no atomics: with every element in one group the row is -f_int to the bit on the free dofs.  A null
+ * pointer, m < 1 (or above 65535, the grid's limit), g0 < 0 or a bad mesh is PF_ERR_ARG before anything is enqueued.
+ * Additive: the version stays 9. */
+int pf_gl_group_rhs(const pf_problem* p, const pf_gl* g, const int* elem_group, int g0, int m, double* out, void* stream);
 /* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */
 int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream);
 /* as pf_pcg_begin / pf_pcg_iterations / pf_pcg_graph_create / pf_pcg_state on K_t: the same kernels, workspace

@@ -89,11 +89,14 @@ def parse_problem(problem_file):
     #                                                 global dof g goes to d over the increments and the load factor is
     #                                                 solved for (the .res.json gains "equilibrium_path"); absent: load control
     #           "identify_nr": {"groups": [...]|null, "levels": [{"load_factor": l, "dofs": [...], "u": [...]}, ...],
-    #                           "max_evaluations": N}  identify one factor on E*A per group of elements (null: per element)
+    #                           "max_evaluations": N, "method": "lbfgs"|"gauss-newton", "damping": mu}
+    #                                                 identify one factor on E*A per group of elements (null: per element)
     #                                                 from displacements measured at several load levels, through the
     #                                                 green-lagrange Newton solve (method "nr"; fem/identify.py); the
     #                                                 .res.json gains "identified_factors", "identified_ea", "misfit" and
-    #                                                 "evaluations", and holds the last level's displacements and reactions
+    #                                                 "evaluations", and holds the last level's displacements and reactions;
+    #                                                 with method "gauss-newton" (Levenberg-Marquardt, initial damping mu) also
+    #                                                 "factor_std", "singular_values", "covariance" and "stop"
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -198,8 +201,9 @@ def parse_problem(problem_file):
 def _identify_block(block, solver_config):
     """accel.identify_nr, checked for its shape (what it holds is checked by fem.identify.check_identify)."""
     shape = ('accel.identify_nr must be {"groups": [...] | null, "levels": [{"load_factor": .., "dofs": [..], "u": [..]}, ..]'
-             ', "max_evaluations": N}')
-    if not isinstance(block, dict) or "levels" not in block or not set(block) <= {"groups", "levels", "max_evaluations"}:
+             ', "max_evaluations": N, "method": "lbfgs" | "gauss-newton", "damping": mu}')
+    if (not isinstance(block, dict) or "levels" not in block
+            or not set(block) <= {"groups", "levels", "max_evaluations", "method", "damping"}):
         raise ValueError(shape)
     levels = block["levels"]
     if not isinstance(levels, list) or not all(isinstance(lv, dict) and set(lv) == {"load_factor", "dofs", "u"}
@@ -211,6 +215,10 @@ def _identify_block(block, solver_config):
     out = {"groups": block.get("groups"), "levels": levels}
     if block.get("max_evaluations") is not None:
         out["max_evaluations"] = int(block["max_evaluations"])
+    if block.get("method") is not None:
+        out["method"] = str(block["method"])
+    if block.get("damping") is not None:
+        out["damping"] = float(block["damping"])
     return out
 
 
@@ -396,15 +404,15 @@ def solve_problem(parsed_data):
 def _identify_problem(model, solver_config, block):
     """accel.identify_nr: the factors on E*A and the state of the last load level at them."""
     from ..fem.identify import identify_nr
-    kw = {"max_evaluations": block["max_evaluations"]} if "max_evaluations" in block else {}
+    kw = {key: block[key] for key in ("max_evaluations", "method", "damping") if key in block}
     res = identify_nr(model, solver_config, block["levels"], groups=block["groups"], **kw)
     log_print(f"Identification: {res.evaluations} evaluations, misfit {res.misfit:.3e}, factors {res.factors.tolist()}")
-    return {
+    output = {
         "success": res.converged,
         "converged": res.converged,
         "iterations": res.evaluations,
-        "history": [{"misfit": h["misfit"], "gradient_norm": h["gradient_norm"], "factors": h["factors"].tolist()}
-                    for h in res.history],
+        "history": [{"misfit": h["misfit"], "gradient_norm": h["gradient_norm"], "factors": h["factors"].tolist(),
+                     **{key: h[key] for key in ("accepted", "damping") if key in h}} for h in res.history],
         "identified_factors": res.factors.tolist(),
         "identified_ea": res.ea.tolist(),
         "misfit": res.misfit,
@@ -412,6 +420,11 @@ def _identify_problem(model, solver_config, block):
         "displacements": res.displacements[-1].tolist(),
         "reactions": res.reactions.tolist(),
     }
+    if res.stop is not None:                # method "gauss-newton": how well the factors are determined
+        as_list = lambda a: None if a is None else a.tolist()
+        output.update(factor_std=as_list(res.factor_std), singular_values=as_list(res.singular_values),
+                      covariance=as_list(res.covariance), stop=res.stop)
+    return output
 
 
 def _init_distributed():

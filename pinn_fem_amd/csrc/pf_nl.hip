@@ -19,6 +19,12 @@
 // k_group_sum: out[g] = sum of values[e] * weights[e] over the elements of group g (CSR, ascending element id): one
 //             workgroup per group, thread t adds elements t, t + 256, ... in that order, then the fixed-order block
 //             sum of pf_pcg.hip's block_sum64.  No atomics: the same bits on every run.
+// k_gl_group_rhs: k_gl_fint restricted to the elements of one group and negated: the right-hand side of the sensitivity
+//             solve K_t s = -d f_int / d q_g (f_int is linear in E*A, so that derivative is the group's own internal
+//             force).  One node per thread, the group in blockIdx.y; the group ids of two incidences are loaded with
+//             their codes and records, and an incidence of another group adds +0.0 by a select, so the matching terms
+//             are summed in k_gl_fint's order.  Fixed dofs get 0.0.  No atomics.
+#include <limits.h>
 #include <stdio.h>
 #include "pf_common.h"
 
@@ -166,6 +172,39 @@ __global__ __launch_bounds__(256) void k_gl_fint(pf_problem P, const double* __r
   }
 }
 
+// out[k][dof] = -(sum of +-fe over the node's elements e with elem_group[e] == g0 + k), k = blockIdx.y; 0.0 on fixed dofs
+template <int DIM>
+__global__ __launch_bounds__(256) void k_gl_group_rhs(pf_problem P, const double* __restrict__ fe,
+                                                      const int* __restrict__ elem_group, int g0, double* __restrict__ out) {
+  const pf_mesh& M = P.mesh;
+  const int group = g0 + (int)blockIdx.y;
+  double* __restrict__ row = out + (size_t)blockIdx.y * (size_t)M.n_dofs;
+  for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < M.n_nodes; node += gridDim.x * blockDim.x) {
+    const int b = M.adj_ptr[node], e_ = M.adj_ptr[node + 1];
+    double acc[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) acc[c] = 0.0;
+    for (int idx = b; idx < e_; idx += 2) {
+      const bool two = idx + 1 < e_;
+      const int code0 = M.adj[idx], code1 = M.adj[two ? idx + 1 : idx];
+      const bool in0 = elem_group[code0 >> 1] == group, in1 = two && elem_group[code1 >> 1] == group;
+      double f0[DIM], f1[DIM];
+      load_fe<DIM>(fe, code0, f0);
+      load_fe<DIM>(fe, code1, f1);
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) {
+        acc[c] += in0 ? f0[c] : 0.0;
+        acc[c] += in1 ? f1[c] : 0.0;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const int dof = node * DIM + c;
+      row[dof] = (M.dof_flags[dof] & PF_DOF_FIXED) ? 0.0 : -acc[c];
+    }
+  }
+}
+
 int gl_fail(int code, const char* who, const char* what) {
   char buf[160];
   snprintf(buf, sizeof(buf), "%s: %s", who, what);
@@ -236,6 +275,22 @@ int pf_gl_fint(const pf_problem* p, const pf_gl* g, double* f_int_out, void* str
   const int nb = pf_node_blocks(p->mesh.n_nodes);
   if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_fint<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, g->fe, f_int_out);
   else hipLaunchKernelGGL(k_gl_fint<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, g->fe, f_int_out);
+  if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
+  return PF_OK;
+}
+
+int pf_gl_group_rhs(const pf_problem* p, const pf_gl* g, const int* elem_group, int g0, int m, double* out, void* stream) {
+  const char* who = "pf_gl_group_rhs";
+  if (!mesh_ok(p) || !p->mesh.adj_ptr || !p->mesh.adj || !p->mesh.dof_flags || p->mesh.n_nodes < 0 ||
+      p->mesh.n_dofs != p->mesh.n_nodes * p->mesh.dim || !g || !g->fe || !elem_group || !out)
+    return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (m < 1 || m > 65535) return gl_fail(PF_ERR_ARG, who, "bad group count (m)");
+  if (g0 < 0 || g0 > INT_MAX - m) return gl_fail(PF_ERR_ARG, who, "bad first group (g0)");
+  if (p->mesh.n_nodes == 0) return PF_OK;
+  const dim3 grid(pf_node_blocks(p->mesh.n_nodes), m);
+  const hipStream_t s = (hipStream_t)stream;
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_group_rhs<2>, grid, dim3(256), 0, s, *p, g->fe, elem_group, g0, out);
+  else hipLaunchKernelGGL(k_gl_group_rhs<1>, grid, dim3(256), 0, s, *p, g->fe, elem_group, g0, out);
   if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
   return PF_OK;
 }

@@ -222,10 +222,12 @@ class HipEngine:
         self._coarse_updated = None     # (aggregation key, DeviceCoarse, A_c buffer) of preconditioner "two-level-updated"
         self.coarse_refresh_seconds = 0.0   # host seconds in the refreshes of that space so far, and their parts
         self.coarse_refresh_parts = dict(columns=0.0, setup=0.0, factor=0.0, upload=0.0)
+        self.coarse_refreshes = 0       # updated_coarse_space refreshes so far
         self.pcg_batch_solves = 0       # pcg_solve_batch calls so far
         self._fixed_views = {}          # extra fixed dofs (tuple) -> (device dof_flags copy, PfProblem view, host fixed mask)
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
         self._group_csr = None          # group_sum: (key of the group map, n_groups, device CSR pointer, device element ids)
+        self._group_map = None          # gl_group_rhs: (key of the group map, n_groups, device int32 group ids)
         self._configured = False
         env_k = os.environ.get("PINNFEM_GRAPH_ITERS")
         self.GRAPH_ITERS = int(env_k) if env_k else (self.GRAPH_ITERS_LARGE if hp.n_elems >= 200_000 else self.GRAPH_ITERS)
@@ -674,6 +676,32 @@ class HipEngine:
                         "pf_group_sum_f64")
         return out
 
+    @_on_engine_stream
+    def gl_group_rhs(self, groups, g0: int = 0, m: Optional[int] = None) -> torch.Tensor:
+        """Right-hand sides of the sensitivity solves K_t s_g = -d f_int / d q_g of the last gl_state for the groups g0,
+        ..., g0 + m - 1 (m None: every group from g0 on): row k is minus the internal force of the elements of group
+        g0 + k alone, zero on fixed dofs (pf_gl_group_rhs).  groups: [n_elems] non-negative ints.  The device copy of the
+        last group map is cached.  Returns [m, n_dofs]."""
+        ne = self.plan.n_elems
+        gm = np.ascontiguousarray(np.asarray(groups).reshape(-1))
+        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < 0 or gm.max() >= 2 ** 31)):
+            raise ValueError(f"gl_group_rhs: groups must hold one non-negative group id for each of the {ne} elements")
+        gm = gm.astype(np.int64)
+        key = gm.tobytes()
+        if self._group_map is None or self._group_map[0] != key:
+            ids = gm.astype(np.int32) if ne else np.zeros(1, dtype=np.int32)
+            self._group_map = (key, int(gm.max()) + 1 if ne else 0, torch.from_numpy(ids).to(self.device))
+        _, n_groups, ids = self._group_map
+        g0 = int(g0)
+        m = n_groups - g0 if m is None else int(m)
+        if g0 < 0 or m < 1:
+            raise ValueError(f"gl_group_rhs: no groups in the range asked for (g0 = {g0}, m = {m}, {n_groups} groups)")
+        rec = self._gl_ready("gl_group_rhs")[4]
+        out = torch.empty((m, self.plan.n_dofs), dtype=torch.float64, device=self.device)
+        _capi.check(self.lib.pf_gl_group_rhs(self._ref(), C.byref(rec), ids.data_ptr(), g0, m, out.data_ptr(),
+                                             self._stream()), "pf_gl_group_rhs")
+        return out
+
     def _gl_ready(self, who):
         if self._gl is None:
             raise RuntimeError(f"{who}: no Green-Lagrange state yet; call gl_state(u) first")
@@ -813,6 +841,32 @@ class HipEngine:
         self.pcg_batch_solves += 1
         return x.reshape(m, -1), [self._pcg_report(st, rtol) for st in states]
 
+    @_on_engine_stream
+    def pcg_solve_many(self, B: torch.Tensor, preconditioner: str = "jacobi", n_aggregates: Optional[int] = None,
+                       aggregates=None, u=None, rtol: float = 1e-13, max_iter: Optional[int] = None, poll: int = 64):
+        """K_t x_k = B[k] for the G rows of B [G, n_dofs] on the tangent of the last gl_state, behind ONE setup: the
+        coarse space of "two-level-updated" is refreshed once and serves every row.  The rows go through the batched
+        family (pf_pcgtm_* with "jacobi", pf_pcg2tm_* with "two-level-updated") in row order, PF_PCG_MAX_RHS at a time;
+        a last odd row goes alone through the same family with m = 1.  Each row computes what its own pcg_solve would,
+        bit for bit.  The tangent operator only.
+        Returns (x [G, n_dofs], [(iterations, converged, |r|^2, |b|^2) per row])."""
+        if B.dim() != 2 or B.shape[1] != self.plan.n_dofs or B.shape[0] < 1:
+            raise ValueError(f"pcg_solve_many: B must be [G, {self.plan.n_dofs}] with G >= 1, got {tuple(B.shape)}")
+        ref, coarse, kt = self._pcg_setup("pcg_solve_many", True, preconditioner, n_aggregates, aggregates, u, None)
+        fam = "pf_pcgtm" if coarse is None else "pf_pcg2tm"
+        bb = B.to(device=self.device, dtype=torch.float64).contiguous()
+        G = int(bb.shape[0])
+        x = torch.empty_like(bb)
+        reports = []
+        for r0 in range(0, G, _capi.PF_PCG_MAX_RHS):
+            m = min(_capi.PF_PCG_MAX_RHS, G - r0)
+            head = (ref, kt, m) if coarse is None else (ref, C.byref(coarse.record), kt, m)
+            xm, states = self._pcg_run(fam, head, (ref, kt, m), m, bb[r0:r0 + m], coarse is not None, rtol, max_iter, poll)
+            x[r0:r0 + m] = xm.reshape(m, -1)
+            self.pcg_iterations += sum(int(st[0]) for st in states)
+            reports += [self._pcg_report(st, rtol) for st in states]
+        return x, reports
+
     def _stiffness_signature(self):
         """What the coarse matrix Z^T K Z was built from: the E and A that elem_s64 reads."""
         sig = []
@@ -902,6 +956,7 @@ class HipEngine:
         parts = self.coarse_refresh_parts
         parts["columns"] += t1 - t0; parts["setup"] += t2 - t1; parts["factor"] += t3 - t2; parts["upload"] += t4 - t3
         self.coarse_refresh_seconds += t4 - t0
+        self.coarse_refreshes += 1
         return dc if inv is not None else None
 
     @_on_engine_stream

@@ -12,6 +12,18 @@ f_int(u_k; ea) = lam_k f on the free dofs.  With solve_gd's loss_data summed ove
 and, with an element -> group map and one log-factor per group, ea_e = ea0 exp(q_group(e)) and
 dJ/dq_g = sum_{e in g} ea_e dJ/d ea_e (pf_group_sum_f64).  No finite differences, no dense matrix.
 
+Gauss-Newton (identify_nr(method="gauss-newton")): the problem is a small nonlinear least-squares problem,
+J = rho.rho with rho the residuals r_k / sqrt|m_k| stacked over the levels, and its Jacobian is cheap.  Differentiating the
+equilibrium with respect to the log-factor q_g of a group,
+
+  K_t(u_k) s_kg = - d f_int / d q_g = - f_int of the elements of group g alone     (f_int is linear in E*A)
+
+the right-hand side is the node gather of the fe records gl_state has just written, with a group filter
+(pf_gl_group_rhs), the operator is the tangent the Newton loop has just converged on, and the batched tangent CG carries
+two such right-hand sides per solve (pcg_solve_many: one coarse-space refresh per level).  The rows of s_kg at m_k over
+sqrt|m_k| are the Jacobian A [M, G]; 2 A^T rho is the adjoint gradient.  Levenberg-Marquardt on A needs a handful of
+evaluations where L-BFGS needs fifty, and A gives the covariance of the factors.
+
 Limits: states with a positive definite tangent only (the CG solves), load control only, a scalar base material, no
 regularisation term and no bounds on the factors.
 """
@@ -40,6 +52,12 @@ class IdentifyResult:
     displacements: List[np.ndarray] = field(default_factory=list)   # per level, ascending load factor, at `factors`
     counters: Dict[str, int] = field(default_factory=dict)          # Newton, CG and adjoint CG iterations, all evaluations
     reactions: Optional[np.ndarray] = None                          # of the last level, at `factors`
+    # method "gauss-newton" only, at `factors` (None under L-BFGS)
+    jacobian: Optional[np.ndarray] = None          # A [M, G]: d rho / d q, rho the stacked r_k / sqrt|m_k|
+    singular_values: Optional[np.ndarray] = None   # of A, descending
+    covariance: Optional[np.ndarray] = None        # J / (M - G) (A^T A)^-1 of the log-factors (None when M <= G)
+    factor_std: Optional[np.ndarray] = None        # factors * sqrt(diag(covariance))
+    stop: Optional[str] = None                     # "misfit" | "gradient" | "step" | "cap" | "damping"
 
 
 def _level_parts(level):
@@ -113,18 +131,9 @@ def _base_ea(model) -> float:
     return float(model.material.young.value()) * float(model.material.area.value())
 
 
-def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
-    """J and dJ/d ea at the element stiffnesses ea [n_elems] (float64; host or device).
-
-    Per level, in ascending order of load factor, the Green-Lagrange Newton loop of solve_nr with ea in place of the
-    model's E*A, started from the previous level's state; then the element state at the converged u, ONE tangent CG
-    solve for the adjoint (config.nr_preconditioner / nr_aggregates) and the element sensitivities, accumulated on the
-    device.  The adjoint solve is held to solve_nr's rule: g.a > 0, else the same RuntimeError.  A Newton loop that does
-    not converge in config.max_iterations is a RuntimeError too.
-    Returns (J, dJ/d ea [n_elems] on the device, displacements per level [n_dofs] on the device in that order,
-    {"newton_iterations", "cg_iterations", "adjoint_cg_iterations"})."""
-    config = config or SolverConfig()
-    levels, _, _ = check_identify(model, config, levels)
+def _prepare(model, ea):
+    """What misfit_and_gradient and residuals_and_jacobian share before the first level: ea checked and on the device,
+    the engine, the free mask and the loads at load factor 1.  Returns (engine, ea, free mask, loads)."""
     ea_np = ea.detach().cpu().numpy() if isinstance(ea, torch.Tensor) else np.asarray(ea)
     ea_np = np.asarray(ea_np, dtype=np.float64).reshape(-1)
     if ea_np.size != model.nelm:
@@ -140,16 +149,39 @@ def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
         raise RuntimeError("Tangent stiffness became singular during solve")
     free_t = torch.from_numpy(free).to(dev)
     loads = torch.from_numpy(np.ascontiguousarray(np.asarray(model.loads, dtype=float).reshape(-1))).to(dev)
+    return eng, ea_t, free_t, loads
+
+
+def _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters):
+    """One level's Newton loop from u, as misfit_and_gradient runs it; no convergence is a RuntimeError."""
+    u, ok, residual, _, ite, cg = _solver._newton_loop(eng, model, config, lam * loads, u, free_t, True, ea=ea_t)
+    counters["newton_iterations"] += ite + 1
+    counters["cg_iterations"] += cg
+    if not ok:
+        raise RuntimeError(f"Newton-Raphson did not converge at load factor {lam} in {config.max_iterations} "
+                           f"iterations (|du|/|u| = {residual:.3e}): no misfit at this point")
+    return u
+
+
+def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
+    """J and dJ/d ea at the element stiffnesses ea [n_elems] (float64; host or device).
+
+    Per level, in ascending order of load factor, the Green-Lagrange Newton loop of solve_nr with ea in place of the
+    model's E*A, started from the previous level's state; then the element state at the converged u, ONE tangent CG
+    solve for the adjoint (config.nr_preconditioner / nr_aggregates) and the element sensitivities, accumulated on the
+    device.  The adjoint solve is held to solve_nr's rule: g.a > 0, else the same RuntimeError.  A Newton loop that does
+    not converge in config.max_iterations is a RuntimeError too.
+    Returns (J, dJ/d ea [n_elems] on the device, displacements per level [n_dofs] on the device in that order,
+    {"newton_iterations", "cg_iterations", "adjoint_cg_iterations"})."""
+    config = config or SolverConfig()
+    levels, _, _ = check_identify(model, config, levels)
+    eng, ea_t, free_t, loads = _prepare(model, ea)
+    dev, ndof = eng.device, model.ndof
     u = torch.zeros(ndof, dtype=torch.float64, device=dev)
     J, grad, states = 0.0, None, []
     counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0}
     for lam, dofs, ubar in levels:
-        u, ok, residual, _, ite, cg = _solver._newton_loop(eng, model, config, lam * loads, u, free_t, True, ea=ea_t)
-        counters["newton_iterations"] += ite + 1
-        counters["cg_iterations"] += cg
-        if not ok:
-            raise RuntimeError(f"Newton-Raphson did not converge at load factor {lam} in {config.max_iterations} "
-                               f"iterations (|du|/|u| = {residual:.3e}): no misfit at this point")
+        u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters)
         eng.gl_state(u, ea_t)
         dofs_t = torch.from_numpy(dofs).to(dev)
         r = u[dofs_t] - torch.from_numpy(ubar).to(dev)
@@ -165,13 +197,146 @@ def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
     return J, grad, states, counters
 
 
+def check_gauss_newton(levels, groups, damping):
+    """What method "gauss-newton" needs on top of check_identify (whose levels and groups these are); every violation
+    is a ValueError.  Returns (G, M): groups and measurement rows."""
+    if groups is None:
+        raise ValueError("method 'gauss-newton' needs an element -> group map (groups=None, one factor and so one "
+                         "sensitivity solve per element, is not supported); use method 'lbfgs'.")
+    n_groups = int(groups.max()) + 1 if groups.size else 0
+    empty = np.flatnonzero(np.bincount(groups, minlength=n_groups) == 0)
+    if empty.size:
+        raise ValueError(f"groups {empty.tolist()} have no element: their factors are not determined.")
+    n_rows = sum(len(dofs) for _, dofs, _ in levels)
+    if n_groups > n_rows:
+        raise ValueError(f"{n_groups} groups for {n_rows} measurement rows: the least-squares problem is underdetermined.")
+    damping = float(damping)
+    if not (np.isfinite(damping) and damping > 0.0):
+        raise ValueError("damping must be positive and finite.")
+    return n_groups, n_rows
+
+
+def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, groups, states=None, jacobian: bool = True):
+    """The weighted residuals rho [M] (r_k / sqrt|m_k| stacked over the levels in ascending load factor, so rho.rho is
+    misfit_and_gradient's J) at the element stiffnesses ea [n_elems], and their Jacobian A [M, G] with respect to one
+    log-factor per group (groups [n_elems]).
+
+    Per level the Newton loop of misfit_and_gradient, started from the previous level's state; states (per level
+    [n_dofs], in that order) given: no Newton solves, those are the u_k.  With jacobian, per level: the element state
+    at u_k, the G right-hand sides -f_int of every group alone (gl_group_rhs) and their tangent CG solves behind one
+    preconditioner setup (pcg_solve_many), each held to solve_nr's rule as the adjoint solve is; the solutions' rows at
+    m_k over sqrt|m_k| are the level's rows of A.  A group that moves no measured dof (a zero column) is a RuntimeError.
+    Returns (rho, A or None, displacements per level on the device, misfit_and_gradient's counters plus
+    "sensitivity_cg_iterations" and "jacobians")."""
+    config = config or SolverConfig()
+    levels, groups, _ = check_identify(model, config, levels, groups)
+    if groups is None:
+        raise ValueError("residuals_and_jacobian needs an element -> group map")
+    eng, ea_t, free_t, loads = _prepare(model, ea)
+    dev, ndof = eng.device, model.ndof
+    if states is not None and len(states) != len(levels):
+        raise ValueError(f"states has {len(states)} entries for {len(levels)} levels")
+    counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0, "sensitivity_cg_iterations": 0,
+                "jacobians": int(bool(jacobian))}
+    u = torch.zeros(ndof, dtype=torch.float64, device=dev)
+    rho, rows, out_states = [], [], []
+    for k, (lam, dofs, ubar) in enumerate(levels):
+        if states is None:
+            u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters)
+        else:
+            u = states[k].to(device=dev, dtype=torch.float64).reshape(-1)
+        dofs_t = torch.from_numpy(dofs).to(dev)
+        w = 1.0 / np.sqrt(len(dofs))
+        rho.append((u[dofs_t] - torch.from_numpy(ubar).to(dev)).cpu().numpy() * w)
+        if jacobian:
+            eng.gl_state(u, ea_t)
+            B = eng.gl_group_rhs(groups)
+            S, reports = eng.pcg_solve_many(B, preconditioner=config.nr_preconditioner, n_aggregates=config.nr_aggregates, u=u)
+            for g, (it_s, ok_s, rr, bb) in enumerate(reports):
+                _solver._check_cg_step(True, B[g], S[g], ok_s, rr, bb, free_t)
+                counters["sensitivity_cg_iterations"] += int(it_s)
+            rows.append(S[:, dofs_t].t().cpu().numpy() * w)
+        out_states.append(u)
+    A = None
+    if jacobian:
+        A = np.concatenate(rows, axis=0)
+        dead = np.flatnonzero(~np.any(A != 0.0, axis=0))
+        if dead.size:
+            raise RuntimeError(f"group {int(dead[0])} moves no measured dof (a zero column of the Jacobian): its factor "
+                               "is not determined by these measurements")
+    return np.concatenate(rho), A, out_states, counters
+
+
+def _gauss_newton(model, config, levels, groups, q_start, ea_of, max_evaluations, gtol, misfit_tolerance, damping,
+                  step_tolerance):
+    """Levenberg-Marquardt on the log-factors (identify_nr, method "gauss-newton").
+    Returns (q, rho, A, states, history, counters, stop, evaluations) with q, rho, A and states those of the last accepted
+    point."""
+    counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0, "sensitivity_cg_iterations": 0,
+                "jacobians": 0}
+
+    def evaluate(q_np, **kw):
+        out = residuals_and_jacobian(model, config, levels, ea_of(q_np), groups, **kw)
+        for key in counters:
+            counters[key] += out[3][key]
+        return out[:3]
+
+    q = q_start
+    rho, A, states = evaluate(q)
+    J, mu, evaluations = float(rho @ rho), float(damping), 1
+    history = [{"misfit": J, "gradient_norm": float(np.linalg.norm(2.0 * A.T @ rho)), "factors": np.exp(q),
+                "accepted": True, "damping": mu}]
+    while True:
+        if J <= misfit_tolerance:
+            stop = "misfit"
+            break
+        if np.max(np.abs(2.0 * A.T @ rho)) <= gtol:
+            stop = "gradient"
+            break
+        if evaluations >= int(max_evaluations):
+            stop = "cap"
+            break
+        H = A.T @ A
+        delta = np.linalg.solve(H + mu * np.diag(np.diag(H)), -(A.T @ rho))
+        if np.max(np.abs(delta)) <= step_tolerance:
+            stop = "step"
+            break
+        rho_t, _, states_t = evaluate(q + delta, jacobian=False)
+        evaluations += 1
+        J_t = float(rho_t @ rho_t)
+        entry = {"misfit": J_t, "gradient_norm": None, "factors": np.exp(q + delta), "accepted": J_t < J, "damping": mu}
+        history.append(entry)
+        if J_t < J:
+            q, rho, J, states = q + delta, rho_t, J_t, states_t
+            _, A, _ = evaluate(q, states=states)                # the Jacobian at the trial's own states: no Newton solves
+            entry["gradient_norm"] = float(np.linalg.norm(2.0 * A.T @ rho))
+            mu = max(mu / 10.0, 1e-12)
+        else:
+            mu *= 10.0
+            if mu > 1e12:
+                stop = "damping"
+                break
+    return q, rho, A, states, history, counters, stop, evaluations
+
+
 class _Stop(Exception):
     pass
 
 
+def _reactions(eng, model, lam, u, ea_t):
+    """Reactions of a level at its state: f_int(u; ea) - lam f on the fixed dofs."""
+    eng.gl_state(u, ea_t)
+    reactions = eng.gl_fint().cpu().numpy() - lam * np.asarray(model.loads, dtype=float).reshape(-1)
+    free = np.ones(model.ndof, dtype=bool)
+    free[np.asarray(model.fixed_dofs, dtype=int)] = False
+    reactions[free] = 0.0
+    return reactions
+
+
 def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=None, q0=None, max_evaluations: int = 200,
                 gtol: float = 1e-12, misfit_tolerance: float = 0.0, history_size: int = 10,
-                tolerance_change: float = 1e-18) -> IdentifyResult:
+                tolerance_change: float = 1e-18, method: str = "lbfgs", damping: float = 1e-3,
+                step_tolerance: float = 1e-12) -> IdentifyResult:
     """Factors on the model's scalar E*A, one per group of elements, that make the Green-Lagrange Newton solve match
     the measured displacements of `levels` ([{"load_factor", "dofs", "u"}] or tuples in that order).
 
@@ -180,13 +345,44 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
     [n_elems]; None: one parameter per element (the gradient is then dJ/d ea * ea and the group kernel is skipped).
     It stops when max |dJ/dq| <= gtol, when J <= misfit_tolerance, when L-BFGS can no longer change q
     (tolerance_change) or after max_evaluations evaluations (converged False), and returns the evaluated point with the
-    smallest misfit.  A trial point whose Newton solve raises (a limit point, no convergence) propagates the error."""
+    smallest misfit.  A trial point whose Newton solve raises (a limit point, no convergence) propagates the error.
+
+    method "gauss-newton": Levenberg-Marquardt on the same log-factors with the Jacobian A of residuals_and_jacobian
+    (groups is required, every group needs an element and there must be at least as many measurement rows M as groups
+    G).  From q0 with mu = damping, repeat: stop "misfit" if J <= misfit_tolerance, "gradient" if max |2 A^T rho| <= gtol,
+    "cap" at max_evaluations; delta solves (H + mu diag H) delta = -A^T rho with H = A^T A; stop "step" if max |delta| <=
+    step_tolerance; evaluate rho at q + delta without a Jacobian (one evaluation); if that lowers J accept it, form A
+    at the trial's own states (no Newton solves, not an evaluation) and mu <- max(mu / 10, 1e-12); otherwise mu <- 10 mu
+    and stop "damping" once mu > 1e12.  converged is True for "misfit", "gradient" and "step"; the returned point is the
+    last accepted one.  The result then carries jacobian, singular_values, covariance = J / (M - G) (A^T A)^-1 of the
+    log-factors, factor_std = factors * sqrt(diag covariance) and stop; history entries carry "accepted" and "damping"
+    (a trial that was not accepted has gradient_norm None).  The covariance is that of the WEIGHTED fit (every level's
+    residuals over sqrt|m_k|): it is the covariance of the log-factors for equal noise on all measurements and equal
+    level sizes, and first-order otherwise."""
+    if method not in ("lbfgs", "gauss-newton"):
+        raise ValueError(f"unknown identification method {method!r}: 'lbfgs' or 'gauss-newton'.")
     config = config or SolverConfig()
     levels, groups, q_start = check_identify(model, config, levels, groups, q0)
     if int(max_evaluations) < 1:
         raise ValueError("max_evaluations must be at least 1")
+    if method == "gauss-newton":
+        n_groups, n_rows = check_gauss_newton(levels, groups, damping)
     ea0 = _base_ea(model)
     eng = _solver._engine_for(model, None, None)
+    if method == "gauss-newton":
+        ea_gn = lambda q_np: ea0 * np.exp(q_np)[groups]
+        q, rho, A, states, history, counters, stop, evaluations = _gauss_newton(
+            model, config, levels, groups, q_start, ea_gn, max_evaluations, gtol, misfit_tolerance, damping, step_tolerance)
+        J = float(rho @ rho)
+        covariance = J / (n_rows - n_groups) * np.linalg.inv(A.T @ A) if n_rows > n_groups else None
+        ea_t = torch.from_numpy(ea_gn(q)).to(eng.device)
+        return IdentifyResult(
+            factors=np.exp(q), ea=ea_gn(q), misfit=J, gradient=2.0 * A.T @ rho, evaluations=evaluations,
+            converged=stop in ("misfit", "gradient", "step"), history=history,
+            displacements=[s.cpu().numpy() for s in states], counters=counters,
+            reactions=_reactions(eng, model, levels[-1][0], states[-1], ea_t), jacobian=A,
+            singular_values=np.linalg.svd(A, compute_uv=False), covariance=covariance,
+            factor_std=None if covariance is None else np.exp(q) * np.sqrt(np.diag(covariance)), stop=stop)
     counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0}
     history, best = [], {}
 
@@ -224,13 +420,7 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
         pass
     met = bool(np.max(np.abs(best["g"]), initial=0.0) <= gtol or best["J"] <= misfit_tolerance)
     converged = met or len(history) < int(max_evaluations)          # False: the evaluation cap ended it
-    # reactions of the last level at the returned point: f_int(u; ea) - lam f on the fixed dofs
-    lam_last = levels[-1][0]
-    eng.gl_state(best["states"][-1], best["ea"])
-    reactions = eng.gl_fint().cpu().numpy() - lam_last * np.asarray(model.loads, dtype=float).reshape(-1)
-    free = np.ones(model.ndof, dtype=bool)
-    free[np.asarray(model.fixed_dofs, dtype=int)] = False
-    reactions[free] = 0.0
+    reactions = _reactions(eng, model, levels[-1][0], best["states"][-1], best["ea"])
     return IdentifyResult(factors=np.exp(best["q"]), ea=ea_of(best["q"]), misfit=float(best["J"]), gradient=best["g"],
                           evaluations=len(history), converged=converged, history=history,
                           displacements=[s.cpu().numpy() for s in best["states"]], counters=counters, reactions=reactions)

@@ -2,14 +2,16 @@
 """Time identify_nr (fem/identify.py) on the Warren girder of tools/nr_scale.py --kinematics green-lagrange.
 
     identify_scale.py [--preconditioner jacobi|two-level-updated] [--aggregates N] [--groups 8] [--levels 2]
-                      [--evaluations 5] [panels]
+                      [--method lbfgs|gauss-newton] [--evaluations 200] [--relative-misfit 1e-12] [panels]
 
 The girder (E*A = 1, the load of nr_scale.py) gets one true factor per span group, alternating 0.8 / 1.25; its states at
 the load levels k / levels, solved on the device, are the measurements (every free dof), which is also the warm-up
-solve.  identify_nr then runs `evaluations` misfit evaluations from all factors 1.  One JSON line: seconds and Newton,
-CG and adjoint CG iterations per evaluation, and the time of single pf_gl_state (model E*A and per-element E*A),
-pf_gl_sens and pf_group_sum_f64 launches (mean of 200 back-to-back launches between two events) with their share of an
-evaluation."""
+solve.  identify_nr then runs a whole identification from all factors 1 with the chosen method, to its own stop: the
+misfit tolerance is `relative-misfit` times the sum over the levels of the mean square of the measurements, the same for
+both methods, and `evaluations` is only the cap.  One JSON line: total seconds, evaluations, the stop, the factor error,
+seconds and Newton, CG, adjoint CG and sensitivity CG iterations in total and per evaluation, and the time of single
+pf_gl_state (model E*A and per-element E*A), pf_gl_sens, pf_group_sum_f64 and pf_gl_group_rhs launches (mean of 200
+back-to-back launches between two events) with the share of an evaluation of the L-BFGS path's own two."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,7 +27,9 @@ ap.add_argument("--preconditioner", default="jacobi", choices=["jacobi", "two-le
 ap.add_argument("--aggregates", type=int, default=None)
 ap.add_argument("--groups", type=int, default=8)
 ap.add_argument("--levels", type=int, default=2)
-ap.add_argument("--evaluations", type=int, default=5)
+ap.add_argument("--method", choices=("lbfgs", "gauss-newton"), default="lbfgs")
+ap.add_argument("--evaluations", type=int, default=200)
+ap.add_argument("--relative-misfit", type=float, default=1e-12)
 ap.add_argument("panels", nargs="?", type=int, default=1000)
 args = ap.parse_args()
 panels = args.panels
@@ -45,9 +49,11 @@ factors = [(k + 1) / args.levels for k in range(args.levels)]
 _, _, states, _ = misfit_and_gradient(model, cfg, [(f, dofs, np.zeros(len(dofs))) for f in factors], true[groups])
 levels = [(f, dofs, s.cpu().numpy()[dofs]) for f, s in zip(factors, states)]
 eng = model._pf_engine_cache[1]
-refresh0 = eng.coarse_refresh_seconds
+refresh0, refreshes0 = eng.coarse_refresh_seconds, eng.coarse_refreshes
+misfit_tolerance = args.relative_misfit * sum(float(np.mean(lv[2] ** 2)) for lv in levels)
 torch.cuda.synchronize(); t0 = time.perf_counter()
-res = identify_nr(model, cfg, levels, groups=groups, max_evaluations=args.evaluations)
+res = identify_nr(model, cfg, levels, groups=groups, max_evaluations=args.evaluations, method=args.method,
+                  misfit_tolerance=misfit_tolerance)
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
 
 
@@ -67,16 +73,27 @@ u, ea = states[-1], torch.from_numpy(res.ea).to(eng.device)
 adj, out = torch.ones_like(u), torch.zeros(len(el), dtype=torch.float64, device=eng.device)
 us = {"pf_gl_state": launch_us(lambda: eng.gl_state(u)), "pf_gl_state_ea": launch_us(lambda: eng.gl_state(u, ea)),
       "pf_gl_sens": launch_us(lambda: eng.gl_sensitivity(u, adj, out=out)),
-      "pf_group_sum_f64": launch_us(lambda: eng.group_sum(out, ea, groups))}
+      "pf_group_sum_f64": launch_us(lambda: eng.group_sum(out, ea, groups)),
+      "pf_gl_group_rhs": launch_us(lambda: eng.gl_group_rhs(groups))}
 n = res.evaluations
 per_eval = dt / n
 row = {"panels": panels, "elements": len(el), "dofs": 2 * len(nodes), "preconditioner": args.preconditioner,
-       "groups": args.groups, "levels": args.levels, "evaluations": n, "seconds_per_evaluation": per_eval,
+       "groups": args.groups, "levels": args.levels, "method": args.method, "seconds": dt, "evaluations": n,
+       "stop": res.stop, "converged": res.converged, "misfit_tolerance": misfit_tolerance,
+       "factor_error": float(np.max(np.abs(res.factors - true))), "seconds_per_evaluation": per_eval,
+       "newton_iterations": res.counters["newton_iterations"], "cg_iterations": res.counters["cg_iterations"],
+       "adjoint_cg_iterations": res.counters["adjoint_cg_iterations"],
+       "sensitivity_cg_iterations": res.counters.get("sensitivity_cg_iterations", 0),
+       "jacobians": res.counters.get("jacobians", 0),
        "newton_iterations_per_evaluation": res.counters["newton_iterations"] / n,
        "cg_iterations_per_evaluation": res.counters["cg_iterations"] / n,
        "adjoint_cg_iterations_per_evaluation": res.counters["adjoint_cg_iterations"] / n,
        "misfit_first": res.history[0]["misfit"], "misfit_best": res.misfit, "launch_microseconds": us,
        "share_of_sens_and_group_sum": (args.levels * us["pf_gl_sens"] + us["pf_group_sum_f64"]) * 1e-6 / per_eval}
+if res.factor_std is not None:
+    row["factor_std_max"] = float(np.max(res.factor_std))
 if args.preconditioner == "two-level-updated":
+    row["refresh_seconds"] = eng.coarse_refresh_seconds - refresh0
+    row["refreshes"] = eng.coarse_refreshes - refreshes0
     row["refresh_seconds_per_evaluation"] = (eng.coarse_refresh_seconds - refresh0) / n
 print(json.dumps(row), flush=True)
