@@ -489,6 +489,24 @@ int pf_gl_fint(const pf_problem* p, const pf_gl* g, double* f_int_out, void* str
  * pointer, m < 1 (or above 65535, the grid's limit), g0 < 0 or a bad mesh is PF_ERR_ARG before anything is enqueued.
  * Additive: the version stays 9. */
 int pf_gl_group_rhs(const pf_problem* p, const pf_gl* g, const int* elem_group, int g0, int m, double* out, void* stream);
+/* The derivative of the Green-Lagrange strains with respect to u, B = d e / d u, for strain-gauge data in the
+ * identification:  d e_e / d u_j = +d_e / l0^2,  d e_e / d u_i = -d_e / l0^2  with d = d0 + u_j - u_i formed from g->d0 and u
+ * as pf_gl_sens forms it (e is quadratic in u, so this is exact).  Neither entry point contains E*A or needs a previous
+ * pf_gl_state.  Both are additive: the version stays 9.
+ * pf_gl_strain_rhs: B^T coef, the adjoint right-hand side.  out[dof] (dev double [n_dofs]) = the sum over the node's
+ * incidences, in ascending order, of +-(coef[e] / l0^2) d_e: + at the element's second node, - at its first.  coef: dev
+ * double [n_elems], dense (0.0 where nothing is measured: a dof whose elements all have coef 0.0 gets exactly 0.0).
+ * accumulate 0: out = the sum, 0.0 on PF_DOF_FIXED dofs; accumulate 1: out = out + the sum (rounded first) and fixed dofs
+ * are left untouched.  One node per thread, no atomics.
+ * pf_gl_strain_jvp: B v at n_meas measured elements for m vectors.  out[k * n_meas + i] (dev double [m][n_meas]) =
+ * (d_e / l0^2).(v_k[j] - v_k[i]) for e = elems[i] (dev int [n_meas]) and v_k row k of v (dev double [m][n_dofs]).  An id
+ * outside 0..n_elems-1 writes 0.0 and reads nothing.  One (gauge, row) pair per thread, the row in blockIdx.y:
+ * 1 <= m <= 65535.  n_meas 0 is PF_OK with nothing enqueued.
+ * A null pointer, a bad mesh, accumulate outside {0, 1}, n_meas < 0 or a bad m is PF_ERR_ARG before anything is enqueued. */
+int pf_gl_strain_rhs(const pf_problem* p, const pf_gl* g, const double* u, const double* coef, int accumulate, double* out,
+                     void* stream);
+int pf_gl_strain_jvp(const pf_problem* p, const pf_gl* g, const double* u, const int* elems, int n_meas, const double* v,
+                     int m, double* out, void* stream);
 /* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */
 int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream);
 /* as pf_pcg_begin / pf_pcg_iterations / pf_pcg_graph_create / pf_pcg_state on K_t: the same kernels, workspace

@@ -96,7 +96,14 @@ def parse_problem(problem_file):
     #                                                 .res.json gains "identified_factors", "identified_ea", "misfit" and
     #                                                 "evaluations", and holds the last level's displacements and reactions;
     #                                                 with method "gauss-newton" (Levenberg-Marquardt, initial damping mu) also
-    #                                                 "factor_std", "singular_values", "covariance" and "stop"
+    #                                                 "factor_std", "singular_values", "covariance" and "stop".  A level
+    #                                                 may also hold strain-gauge data: "strain_elements": [...] and
+    #                                                 "strains": [...] (both or neither; GREEN-LAGRANGE strains
+    #                                                 e = (l^2 - l0^2) / (2 l0^2), from an engineering strain eps as
+    #                                                 e = eps + eps^2 / 2) and optionally "strain_scale": L (a length, default
+    #                                                 1; the level adds L^2 mean (e - ebar)^2 to the misfit); "dofs" and "u"
+    #                                                 may then be empty, and the .res.json gains "strains" (every element's
+    #                                                 strain at the last level)
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -201,13 +208,15 @@ def parse_problem(problem_file):
 def _identify_block(block, solver_config):
     """accel.identify_nr, checked for its shape (what it holds is checked by fem.identify.check_identify)."""
     shape = ('accel.identify_nr must be {"groups": [...] | null, "levels": [{"load_factor": .., "dofs": [..], "u": [..]}, ..]'
-             ', "max_evaluations": N, "method": "lbfgs" | "gauss-newton", "damping": mu}')
+             ', "max_evaluations": N, "method": "lbfgs" | "gauss-newton", "damping": mu}; a level may also hold '
+             '"strain_elements": [..] and "strains": [..] (both or neither) and "strain_scale": L')
     if (not isinstance(block, dict) or "levels" not in block
             or not set(block) <= {"groups", "levels", "max_evaluations", "method", "damping"}):
         raise ValueError(shape)
     levels = block["levels"]
-    if not isinstance(levels, list) or not all(isinstance(lv, dict) and set(lv) == {"load_factor", "dofs", "u"}
-                                               for lv in levels):
+    base, gauges = {"load_factor", "dofs", "u"}, {"strain_elements", "strains"}
+    key_sets = (base, base | gauges, base | gauges | {"strain_scale"})
+    if not isinstance(levels, list) or not all(isinstance(lv, dict) and set(lv) in key_sets for lv in levels):
         raise ValueError(shape)
     if solver_config.method != "nr":
         raise ValueError(f'accel.identify_nr belongs to the Newton-Raphson solve (method "nr"): method '
@@ -424,6 +433,8 @@ def _identify_problem(model, solver_config, block):
         as_list = lambda a: None if a is None else a.tolist()
         output.update(factor_std=as_list(res.factor_std), singular_values=as_list(res.singular_values),
                       covariance=as_list(res.covariance), stop=res.stop)
+    if res.strains is not None:             # some level carries strain-gauge data: every element's strain at the last level
+        output["strains"] = res.strains[-1].tolist()
     return output
 
 

@@ -24,6 +24,13 @@
 //             force).  One node per thread, the group in blockIdx.y; the group ids of two incidences are loaded with
 //             their codes and records, and an incidence of another group adds +0.0 by a select, so the matching terms
 //             are summed in k_gl_fint's order.  Fixed dofs get 0.0.  No atomics.
+// k_gl_strain_rhs: B^T c, the transpose of the strain's derivative d e / d u applied to per-element coefficients (the
+//             adjoint right-hand side of a strain misfit): one node per thread, +-(c_e / l0^2) d_e of the node's elements
+//             in ascending incidence order, two incidences per round with selects as k_gl_fint takes them; d is formed
+//             from d0 and u as k_gl_sens forms it.  Fixed dofs get 0.0, or stay untouched when it accumulates.  No atomics.
+// k_gl_strain_jvp: B v, that derivative applied to vectors, at the measured elements only: (d_e / l0^2).(v_j - v_i), one
+//             (gauge, row) pair per thread with the row in blockIdx.y; an element id outside the mesh writes 0.0 and
+//             reads nothing, k_group_sum's rule.
 #include <limits.h>
 #include <stdio.h>
 #include "pf_common.h"
@@ -205,6 +212,103 @@ __global__ __launch_bounds__(256) void k_gl_group_rhs(pf_problem P, const double
   }
 }
 
+// +-(coef[e] / l0^2) d of one incidence: + at the element's second node (end 1), - at its first; d as k_gl_sens forms it
+template <int DIM>
+__device__ __forceinline__ void load_strain_term(const pf_mesh& M, const double* __restrict__ d0_in, const double* __restrict__ u,
+                                                 const double* __restrict__ coef, int code, double* out) {
+  const int e = code >> 1;
+  const double sg = (code & 1) ? 1.0 : -1.0;
+  const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
+  double d0[DIM], du[DIM];
+  if (DIM == 2) {
+    const double2 g = reinterpret_cast<const double2*>(d0_in)[e];
+    const double2 ui = reinterpret_cast<const double2*>(u)[nn.x], uj = reinterpret_cast<const double2*>(u)[nn.y];
+    d0[0] = g.x; d0[DIM - 1] = g.y;
+    du[0] = uj.x - ui.x; du[DIM - 1] = uj.y - ui.y;
+  } else {
+    d0[0] = d0_in[e];
+    du[0] = u[nn.y] - u[nn.x];
+  }
+  double l02 = 0.0;
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) l02 += d0[c] * d0[c];
+  const double w = coef[e] / l02;
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) out[c] = sg * (w * (d0[c] + du[c]));
+}
+
+// out[dof] = sum over the node's incidences of +-(coef[e] / l0^2) d_e; accumulate: out += that sum, rounded first
+template <int DIM>
+__global__ __launch_bounds__(256) void k_gl_strain_rhs(pf_problem P, const double* __restrict__ d0_in,
+                                                       const double* __restrict__ u, const double* __restrict__ coef,
+                                                       int accumulate, double* __restrict__ out) {
+  const pf_mesh& M = P.mesh;
+  for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < M.n_nodes; node += gridDim.x * blockDim.x) {
+    const int b = M.adj_ptr[node], e_ = M.adj_ptr[node + 1];
+    double acc[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) acc[c] = 0.0;
+    for (int idx = b; idx < e_; idx += 2) {
+      const bool two = idx + 1 < e_;
+      const int code0 = M.adj[idx], code1 = M.adj[two ? idx + 1 : idx];
+      double t0[DIM], t1[DIM];
+      load_strain_term<DIM>(M, d0_in, u, coef, code0, t0);
+      load_strain_term<DIM>(M, d0_in, u, coef, code1, t1);
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) {
+        acc[c] += t0[c];
+        const double t = acc[c] + t1[c];
+        acc[c] = two ? t : acc[c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const int dof = node * DIM + c;
+      const bool fixed = M.dof_flags[dof] & PF_DOF_FIXED;
+      if (accumulate) {
+        if (!fixed) out[dof] = __dadd_rn(out[dof], acc[c]);      // acc rounded first: the sum of two single calls, to the bit
+      } else {
+        out[dof] = fixed ? 0.0 : acc[c];
+      }
+    }
+  }
+}
+
+// out[k][i] = (d_e / l0^2).(v_k[j] - v_k[i]) for e = elems[i], k = blockIdx.y; an id outside 0..n_elems-1 gives 0.0
+template <int DIM>
+__global__ __launch_bounds__(256) void k_gl_strain_jvp(pf_problem P, const double* __restrict__ d0_in,
+                                                       const double* __restrict__ u, const int* __restrict__ elems, int n_meas,
+                                                       const double* __restrict__ v, double* __restrict__ out) {
+  const pf_mesh& M = P.mesh;
+  const double* __restrict__ vk = v + (size_t)blockIdx.y * (size_t)M.n_dofs;
+  double* __restrict__ row = out + (size_t)blockIdx.y * (size_t)n_meas;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_meas; i += gridDim.x * blockDim.x) {
+    const int e = elems[i];
+    double r = 0.0;
+    if ((unsigned)e < (unsigned)M.n_elems) {
+      const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
+      double d0[DIM], du[DIM], dv[DIM];
+      if (DIM == 2) {
+        const double2 g = reinterpret_cast<const double2*>(d0_in)[e];
+        const double2 ui = reinterpret_cast<const double2*>(u)[nn.x], uj = reinterpret_cast<const double2*>(u)[nn.y];
+        const double2 vi = reinterpret_cast<const double2*>(vk)[nn.x], vj = reinterpret_cast<const double2*>(vk)[nn.y];
+        d0[0] = g.x; d0[DIM - 1] = g.y;
+        du[0] = uj.x - ui.x; du[DIM - 1] = uj.y - ui.y;
+        dv[0] = vj.x - vi.x; dv[DIM - 1] = vj.y - vi.y;
+      } else {
+        d0[0] = d0_in[e];
+        du[0] = u[nn.y] - u[nn.x];
+        dv[0] = vk[nn.y] - vk[nn.x];
+      }
+      double l02 = 0.0, ddv = 0.0;
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) { l02 += d0[c] * d0[c]; ddv += (d0[c] + du[c]) * dv[c]; }
+      r = ddv / l02;
+    }
+    row[i] = r;
+  }
+}
+
 int gl_fail(int code, const char* who, const char* what) {
   char buf[160];
   snprintf(buf, sizeof(buf), "%s: %s", who, what);
@@ -291,6 +395,38 @@ int pf_gl_group_rhs(const pf_problem* p, const pf_gl* g, const int* elem_group, 
   const hipStream_t s = (hipStream_t)stream;
   if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_group_rhs<2>, grid, dim3(256), 0, s, *p, g->fe, elem_group, g0, out);
   else hipLaunchKernelGGL(k_gl_group_rhs<1>, grid, dim3(256), 0, s, *p, g->fe, elem_group, g0, out);
+  if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
+  return PF_OK;
+}
+
+int pf_gl_strain_rhs(const pf_problem* p, const pf_gl* g, const double* u, const double* coef, int accumulate, double* out,
+                     void* stream) {
+  const char* who = "pf_gl_strain_rhs";
+  if (!mesh_ok(p) || !p->mesh.conn || !p->mesh.adj_ptr || !p->mesh.adj || !p->mesh.dof_flags || p->mesh.n_nodes < 0 ||
+      p->mesh.n_dofs != p->mesh.n_nodes * p->mesh.dim || !g || !g->d0 || !u || !coef || !out ||
+      (accumulate != 0 && accumulate != 1))
+    return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (p->mesh.n_nodes == 0) return PF_OK;
+  const int nb = pf_node_blocks(p->mesh.n_nodes);
+  const hipStream_t s = (hipStream_t)stream;
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_strain_rhs<2>, dim3(nb), dim3(256), 0, s, *p, g->d0, u, coef, accumulate, out);
+  else hipLaunchKernelGGL(k_gl_strain_rhs<1>, dim3(nb), dim3(256), 0, s, *p, g->d0, u, coef, accumulate, out);
+  if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
+  return PF_OK;
+}
+
+int pf_gl_strain_jvp(const pf_problem* p, const pf_gl* g, const double* u, const int* elems, int n_meas, const double* v,
+                     int m, double* out, void* stream) {
+  const char* who = "pf_gl_strain_jvp";
+  if (!mesh_ok(p) || !p->mesh.conn || p->mesh.n_nodes < 0 || p->mesh.n_dofs != p->mesh.n_nodes * p->mesh.dim || !g ||
+      !g->d0 || !u || !elems || !v || !out || n_meas < 0)
+    return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (m < 1 || m > 65535) return gl_fail(PF_ERR_ARG, who, "bad row count (m)");
+  if (n_meas == 0) return PF_OK;
+  const dim3 grid(elem_blocks(n_meas), m);
+  const hipStream_t s = (hipStream_t)stream;
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_strain_jvp<2>, grid, dim3(256), 0, s, *p, g->d0, u, elems, n_meas, v, out);
+  else hipLaunchKernelGGL(k_gl_strain_jvp<1>, grid, dim3(256), 0, s, *p, g->d0, u, elems, n_meas, v, out);
   if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
   return PF_OK;
 }

@@ -702,6 +702,49 @@ class HipEngine:
                                              self._stream()), "pf_gl_group_rhs")
         return out
 
+    @_on_engine_stream
+    def gl_strain_rhs(self, u: torch.Tensor, coef: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """B^T coef [n_dofs] with B = d e / d u the derivative of the Green-Lagrange strains at the displacements u: per dof
+        the sum of +-(coef[e] / l0^2) d_e over the node's elements, zero on fixed dofs (pf_gl_strain_rhs; the adjoint
+        right-hand side of a strain misfit).  coef: [n_elems] float64, 0.0 where nothing is measured.  out: a float64 device
+        vector [n_dofs] the result is ADDED to (fixed dofs stay as they are); None: a new vector.  It reads d0 and u only:
+        no gl_state is needed first."""
+        uu = self._f64_vector("gl_strain_rhs", "u", u, self.plan.n_dofs, "dofs")
+        cc = self._f64_vector("gl_strain_rhs", "coef", coef, self.plan.n_elems, "elements")
+        n = self.plan.n_dofs
+        accumulate = out is not None
+        if accumulate:
+            if (out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous() or out.numel() != n):
+                raise ValueError(f"gl_strain_rhs: out must be a contiguous float64 vector of {n} entries on {self.device}")
+        else:
+            out = torch.zeros(n, dtype=torch.float64, device=self.device)
+        if self.plan.n_elems:
+            rec = self._gl_buffers()[4]
+            _capi.check(self.lib.pf_gl_strain_rhs(self._ref(), C.byref(rec), uu.data_ptr(), cc.data_ptr(), int(accumulate),
+                                                  out.data_ptr(), self._stream()), "pf_gl_strain_rhs")
+        return out
+
+    @_on_engine_stream
+    def gl_strain_jvp(self, u: torch.Tensor, elements, V: torch.Tensor) -> torch.Tensor:
+        """B V^T at the measured elements: [m, n_meas] with entry (k, i) = (d_e / l0^2).(V[k, j] - V[k, i]) for
+        e = elements[i] (pf_gl_strain_jvp; the strain rows of the Gauss-Newton Jacobian from the sensitivity solutions).
+        elements: [n_meas] ints in 0..n_elems-1; V: [m, n_dofs] float64.  It reads d0 and u only."""
+        uu = self._f64_vector("gl_strain_jvp", "u", u, self.plan.n_dofs, "dofs")
+        ids = np.ascontiguousarray(np.asarray(elements.cpu() if isinstance(elements, torch.Tensor) else elements).reshape(-1))
+        if ids.size and (ids.dtype.kind not in "iu" or ids.min() < 0 or ids.max() >= self.plan.n_elems):
+            raise ValueError(f"gl_strain_jvp: elements must be integer ids in 0..{self.plan.n_elems - 1}")
+        if V.dim() != 2 or V.shape[1] != self.plan.n_dofs or not 1 <= V.shape[0] <= 65535:
+            raise ValueError(f"gl_strain_jvp: V must be [m, {self.plan.n_dofs}] with 1 <= m <= 65535, got {tuple(V.shape)}")
+        vv = V.to(device=self.device, dtype=torch.float64).contiguous()
+        m, n_meas = int(vv.shape[0]), int(ids.size)
+        out = torch.empty((m, n_meas), dtype=torch.float64, device=self.device)
+        if n_meas:
+            ids_t = torch.from_numpy(ids.astype(np.int32)).to(self.device)
+            rec = self._gl_buffers()[4]
+            _capi.check(self.lib.pf_gl_strain_jvp(self._ref(), C.byref(rec), uu.data_ptr(), ids_t.data_ptr(), n_meas,
+                                                  vv.data_ptr(), m, out.data_ptr(), self._stream()), "pf_gl_strain_jvp")
+        return out
+
     def _gl_ready(self, who):
         if self._gl is None:
             raise RuntimeError(f"{who}: no Green-Lagrange state yet; call gl_state(u) first")

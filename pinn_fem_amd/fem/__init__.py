@@ -4,9 +4,11 @@ from .properties import Property, ScalarProperty, NNProperty, to_property
 from .boundary import free_and_fixed_dofs
 
 __all__ = ["FEMModel", "Material", "Property", "ScalarProperty", "NNProperty", "to_property",
-           "free_and_fixed_dofs", "IdentifyResult", "check_identify", "identify_nr", "misfit_and_gradient", "residuals_and_jacobian"]
+           "free_and_fixed_dofs", "IdentifyResult", "check_identify", "identify_nr", "misfit_and_gradient", "residuals_and_jacobian",
+           "check_strains"]
 
-_IDENTIFY = ("IdentifyResult", "check_identify", "identify_nr", "misfit_and_gradient", "residuals_and_jacobian")
+_IDENTIFY = ("IdentifyResult", "check_identify", "identify_nr", "misfit_and_gradient", "residuals_and_jacobian",
+             "check_strains")
 
 
 def __getattr__(name):

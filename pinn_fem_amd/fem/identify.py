@@ -24,8 +24,20 @@ two such right-hand sides per solve (pcg_solve_many: one coarse-space refresh pe
 sqrt|m_k| are the Jacobian A [M, G]; 2 A^T rho is the adjoint gradient.  Levenberg-Marquardt on A needs a handful of
 evaluations where L-BFGS needs fifty, and A gives the covariance of the factors.
 
+Strain gauges: a level may carry, beside or in place of its measured dofs, the Green-Lagrange strains ebar of p_k elements
+("strain_elements", "strains") and a length L_k ("strain_scale", default 1) that makes them commensurable with
+displacements.  This is the strain pf_gl_state writes, e = (l^2 - l0^2) / (2 l0^2); an engineering strain eps converts as
+e = eps + eps^2 / 2 (there is no conversion option).  With B = d e / d u,  d e_e / d u_j = +d_e / l0^2 = -d e_e / d u_i
+(e is quadratic in u, so this is exact; it does not contain E*A, so no other term of the derivations changes),
+
+  J   += sum_k L_k^2 mean_{i < p_k} (e_k[elem_i] - ebar_ki)^2
+  g_k += B^T c,   c_e = 2 L_k^2 (e_e - ebar_e) / p_k on the measured elements, 0 elsewhere      (pf_gl_strain_rhs)
+  rho:  per level the displacement rows, then L_k (e - ebar) / sqrt p_k;   A: (L_k / sqrt p_k) B s_kg at the gauges
+                                                                                                  (pf_gl_strain_jvp)
+
 Limits: states with a positive definite tangent only (the CG solves), load control only, a scalar base material, no
-regularisation term and no bounds on the factors.
+regularisation term, no bounds on the factors and no weight per sensor but strain_scale; what a set of gauges
+determines is what the singular values of A say, not more.
 """
 from __future__ import annotations
 
@@ -52,6 +64,8 @@ class IdentifyResult:
     displacements: List[np.ndarray] = field(default_factory=list)   # per level, ascending load factor, at `factors`
     counters: Dict[str, int] = field(default_factory=dict)          # Newton, CG and adjoint CG iterations, all evaluations
     reactions: Optional[np.ndarray] = None                          # of the last level, at `factors`
+    strains: Optional[List[np.ndarray]] = None     # per level, every element's Green-Lagrange strain at `factors` (None
+                                                   # unless some level carries strain data)
     # method "gauss-newton" only, at `factors` (None under L-BFGS)
     jacobian: Optional[np.ndarray] = None          # A [M, G]: d rho / d q, rho the stacked r_k / sqrt|m_k|
     singular_values: Optional[np.ndarray] = None   # of A, descending
@@ -93,14 +107,15 @@ def check_identify(model: FEMModel, config: SolverConfig, levels, groups=None, q
         u = np.asarray(u, dtype=np.float64).reshape(-1)
         if not np.isfinite(lam):
             raise ValueError(f"level {k}: the load factor is not finite.")
-        if dofs.size == 0:
+        gauges = isinstance(level, dict) and ("strain_elements" in level or "strains" in level)
+        if dofs.size == 0 and not gauges:
             raise ValueError(f"level {k}: no measured dofs (an empty level).")
         if dofs.size != u.size:
             raise ValueError(f"level {k}: mismatched lengths: {dofs.size} measured dofs, {u.size} measured values.")
-        if dofs.dtype.kind not in "iu":
+        if dofs.size and dofs.dtype.kind not in "iu":
             raise ValueError(f"level {k}: measured dofs must be integers.")
         dofs = dofs.astype(np.int64)
-        if dofs.min() < 0 or dofs.max() >= model.ndof:
+        if dofs.size and (dofs.min() < 0 or dofs.max() >= model.ndof):
             raise ValueError(f"level {k}: measured dofs out of range 0..{model.ndof - 1}.")
         if not free[dofs].all():
             raise ValueError(f"level {k}: measured dofs {dofs[~free[dofs]].tolist()} are fixed dofs.")
@@ -125,6 +140,66 @@ def check_identify(model: FEMModel, config: SolverConfig, levels, groups=None, q
     if not np.all(np.isfinite(q)):
         raise ValueError("q0 holds non-finite log-factors.")
     return out, groups, q.copy()
+
+
+def check_strains(model: FEMModel, levels):
+    """The strain-gauge data of the levels, checked before an engine is built; every violation is a ValueError.
+    A dict level may carry "strain_elements" (element ids [p]), "strains" (the measured Green-Lagrange strains [p],
+    e = (l^2 - l0^2) / (2 l0^2); an engineering strain eps is e = eps + eps^2 / 2) and optionally "strain_scale" (a
+    length L > 0, default 1.0).  Returns, in check_identify's order (the same stable sort on the load factor), one
+    (elements int64 [p], values float64 [p], scale) per level, or None for a level without strain data."""
+    out = []
+    for k, level in enumerate(list(levels) if levels is not None else []):
+        if not isinstance(level, dict):
+            if len(level) != 3:
+                raise ValueError(f"level {k}: a tuple level is (load factor, dofs, u); only the dict form carries strains.")
+            out.append((float(level[0]), None))
+            continue
+        lam = float(level["load_factor"])
+        has_e, has_v = "strain_elements" in level, "strains" in level
+        if has_e != has_v:
+            raise ValueError(f"level {k}: 'strain_elements' and 'strains' go together: one is given without the other.")
+        if not has_e:
+            if "strain_scale" in level:
+                raise ValueError(f"level {k}: 'strain_scale' without 'strain_elements' and 'strains'.")
+            out.append((lam, None))
+            continue
+        elems = np.asarray(level["strain_elements"]).reshape(-1)
+        values = np.asarray(level["strains"], dtype=np.float64).reshape(-1)
+        if elems.size != values.size:
+            raise ValueError(f"level {k}: mismatched lengths: {elems.size} strain elements, {values.size} strains.")
+        if elems.size == 0:
+            raise ValueError(f"level {k}: no strain elements (leave both keys out for a level without gauges).")
+        if elems.dtype.kind not in "iu":
+            raise ValueError(f"level {k}: strain elements must be integers.")
+        elems = elems.astype(np.int64)
+        if elems.min() < 0 or elems.max() >= model.nelm:
+            raise ValueError(f"level {k}: strain elements out of range 0..{model.nelm - 1}.")
+        if np.unique(elems).size != elems.size:
+            raise ValueError(f"level {k}: a strain element is listed twice.")
+        if not np.all(np.isfinite(values)):
+            raise ValueError(f"level {k}: strains are not all finite.")
+        if np.any(values <= -0.5):
+            raise ValueError(f"level {k}: a strain <= -0.5 is no Green-Lagrange strain (e = (l^2 - l0^2) / (2 l0^2) > -1/2).")
+        scale = float(level.get("strain_scale", 1.0))
+        if not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError(f"level {k}: strain_scale must be positive and finite.")
+        out.append((lam, (elems, values, scale)))
+    out.sort(key=lambda lv: lv[0])
+    return [data for _, data in out]
+
+
+def _with_strains(levels, strains):
+    """check_identify's levels with check_strains' data put back, as the dict levels the two checks accept."""
+    return [lv if st is None else {"load_factor": lv[0], "dofs": lv[1], "u": lv[2], "strain_elements": st[0],
+                                   "strains": st[1], "strain_scale": st[2]} for lv, st in zip(levels, strains)]
+
+
+def _strain_residual(eng, e, strain):
+    """(ids on the device, e[ids] - ebar on the device, L, p) of one level's gauges from the element strains e."""
+    elems, values, scale = strain
+    ids = torch.from_numpy(elems).to(eng.device)
+    return ids, e[ids] - torch.from_numpy(values).to(eng.device), scale, len(elems)
 
 
 def _base_ea(model) -> float:
@@ -170,24 +245,35 @@ def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
     model's E*A, started from the previous level's state; then the element state at the converged u, ONE tangent CG
     solve for the adjoint (config.nr_preconditioner / nr_aggregates) and the element sensitivities, accumulated on the
     device.  The adjoint solve is held to solve_nr's rule: g.a > 0, else the same RuntimeError.  A Newton loop that does
-    not converge in config.max_iterations is a RuntimeError too.
+    not converge in config.max_iterations is a RuntimeError too.  A level with strain data (check_strains) adds
+    L^2 mean (e - ebar)^2 to J and B^T c to the adjoint right-hand side (gl_strain_rhs) before that one solve; the
+    sensitivity kernel is the same.
     Returns (J, dJ/d ea [n_elems] on the device, displacements per level [n_dofs] on the device in that order,
     {"newton_iterations", "cg_iterations", "adjoint_cg_iterations"})."""
     config = config or SolverConfig()
-    levels, _, _ = check_identify(model, config, levels)
+    raw = list(levels) if levels is not None else []
+    levels, _, _ = check_identify(model, config, raw)
+    strains = check_strains(model, raw)
     eng, ea_t, free_t, loads = _prepare(model, ea)
     dev, ndof = eng.device, model.ndof
     u = torch.zeros(ndof, dtype=torch.float64, device=dev)
     J, grad, states = 0.0, None, []
     counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0}
-    for lam, dofs, ubar in levels:
+    for (lam, dofs, ubar), strain in zip(levels, strains):
         u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters)
-        eng.gl_state(u, ea_t)
-        dofs_t = torch.from_numpy(dofs).to(dev)
-        r = u[dofs_t] - torch.from_numpy(ubar).to(dev)
-        J += float(torch.mean(r * r))
+        e = eng.gl_state(u, ea_t)
         g = torch.zeros(ndof, dtype=torch.float64, device=dev)
-        g.index_add_(0, dofs_t, r * (2.0 / len(dofs)))
+        if len(dofs):
+            dofs_t = torch.from_numpy(dofs).to(dev)
+            r = u[dofs_t] - torch.from_numpy(ubar).to(dev)
+            J += float(torch.mean(r * r))
+            g.index_add_(0, dofs_t, r * (2.0 / len(dofs)))
+        if strain is not None:
+            ids, r_e, scale, p = _strain_residual(eng, e, strain)
+            J += scale * scale * float(torch.mean(r_e * r_e))
+            coef = torch.zeros(model.nelm, dtype=torch.float64, device=dev)
+            coef[ids] = r_e * (2.0 * scale * scale / p)
+            eng.gl_strain_rhs(u, coef, out=g)
         a, it_a, ok_a, rr, bb = eng.pcg_solve(g, tangent=True, preconditioner=config.nr_preconditioner,
                                               n_aggregates=config.nr_aggregates, u=u)
         _solver._check_cg_step(True, g, a, ok_a, rr, bb, free_t)
@@ -197,9 +283,10 @@ def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
     return J, grad, states, counters
 
 
-def check_gauss_newton(levels, groups, damping):
+def check_gauss_newton(levels, groups, damping, strains=None):
     """What method "gauss-newton" needs on top of check_identify (whose levels and groups these are); every violation
-    is a ValueError.  Returns (G, M): groups and measurement rows."""
+    is a ValueError.  strains: check_strains' list, whose gauges count as measurement rows (None: no strain data).
+    Returns (G, M): groups and measurement rows."""
     if groups is None:
         raise ValueError("method 'gauss-newton' needs an element -> group map (groups=None, one factor and so one "
                          "sensitivity solve per element, is not supported); use method 'lbfgs'.")
@@ -208,6 +295,8 @@ def check_gauss_newton(levels, groups, damping):
     if empty.size:
         raise ValueError(f"groups {empty.tolist()} have no element: their factors are not determined.")
     n_rows = sum(len(dofs) for _, dofs, _ in levels)
+    if strains is not None:
+        n_rows += sum(len(st[0]) for st in strains if st is not None)
     if n_groups > n_rows:
         raise ValueError(f"{n_groups} groups for {n_rows} measurement rows: the least-squares problem is underdetermined.")
     damping = float(damping)
@@ -225,11 +314,15 @@ def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, gr
     [n_dofs], in that order) given: no Newton solves, those are the u_k.  With jacobian, per level: the element state
     at u_k, the G right-hand sides -f_int of every group alone (gl_group_rhs) and their tangent CG solves behind one
     preconditioner setup (pcg_solve_many), each held to solve_nr's rule as the adjoint solve is; the solutions' rows at
-    m_k over sqrt|m_k| are the level's rows of A.  A group that moves no measured dof (a zero column) is a RuntimeError.
+    m_k over sqrt|m_k| are the level's rows of A.  A level with strain data (check_strains) appends L (e - ebar) / sqrt p to
+    its part of rho and (L / sqrt p) B s_g at its gauges (gl_strain_jvp) to its rows of A.  A group that moves no
+    measured dof and no gauge (a zero column) is a RuntimeError.
     Returns (rho, A or None, displacements per level on the device, misfit_and_gradient's counters plus
     "sensitivity_cg_iterations" and "jacobians")."""
     config = config or SolverConfig()
-    levels, groups, _ = check_identify(model, config, levels, groups)
+    raw = list(levels) if levels is not None else []
+    levels, groups, _ = check_identify(model, config, raw, groups)
+    strains = check_strains(model, raw)
     if groups is None:
         raise ValueError("residuals_and_jacobian needs an element -> group map")
     eng, ea_t, free_t, loads = _prepare(model, ea)
@@ -246,24 +339,32 @@ def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, gr
         else:
             u = states[k].to(device=dev, dtype=torch.float64).reshape(-1)
         dofs_t = torch.from_numpy(dofs).to(dev)
-        w = 1.0 / np.sqrt(len(dofs))
+        w = 1.0 / np.sqrt(len(dofs)) if len(dofs) else 0.0
         rho.append((u[dofs_t] - torch.from_numpy(ubar).to(dev)).cpu().numpy() * w)
+        strain = strains[k]
+        if jacobian or strain is not None:
+            e = eng.gl_state(u, ea_t)
+        if strain is not None:
+            _, r_e, scale, p = _strain_residual(eng, e, strain)
+            w_e = scale / np.sqrt(p)
+            rho.append(r_e.cpu().numpy() * w_e)
         if jacobian:
-            eng.gl_state(u, ea_t)
             B = eng.gl_group_rhs(groups)
             S, reports = eng.pcg_solve_many(B, preconditioner=config.nr_preconditioner, n_aggregates=config.nr_aggregates, u=u)
             for g, (it_s, ok_s, rr, bb) in enumerate(reports):
                 _solver._check_cg_step(True, B[g], S[g], ok_s, rr, bb, free_t)
                 counters["sensitivity_cg_iterations"] += int(it_s)
             rows.append(S[:, dofs_t].t().cpu().numpy() * w)
+            if strain is not None:
+                rows.append(eng.gl_strain_jvp(u, strain[0], S).t().cpu().numpy() * w_e)
         out_states.append(u)
     A = None
     if jacobian:
         A = np.concatenate(rows, axis=0)
         dead = np.flatnonzero(~np.any(A != 0.0, axis=0))
         if dead.size:
-            raise RuntimeError(f"group {int(dead[0])} moves no measured dof (a zero column of the Jacobian): its factor "
-                               "is not determined by these measurements")
+            raise RuntimeError(f"group {int(dead[0])} moves no measured dof and no gauge (a zero column of the Jacobian): its "
+                               "factor is not determined by these measurements")
     return np.concatenate(rho), A, out_states, counters
 
 
@@ -338,7 +439,11 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
                 tolerance_change: float = 1e-18, method: str = "lbfgs", damping: float = 1e-3,
                 step_tolerance: float = 1e-12) -> IdentifyResult:
     """Factors on the model's scalar E*A, one per group of elements, that make the Green-Lagrange Newton solve match
-    the measured displacements of `levels` ([{"load_factor", "dofs", "u"}] or tuples in that order).
+    the measured displacements of `levels` ([{"load_factor", "dofs", "u"}] or tuples in that order).  A dict level may
+    also carry strain-gauge data: "strain_elements" (element ids), "strains" (the measured GREEN-LAGRANGE strains
+    e = (l^2 - l0^2) / (2 l0^2), what pf_gl_state writes; an engineering strain eps converts as e = eps + eps^2 / 2) and
+    "strain_scale" (a length L > 0, default 1.0; the level adds L^2 mean (e - ebar)^2 to the misfit).  Such a level may
+    have empty "dofs".  Both methods take strain data; the result then carries `strains`, every element's strain per level.
 
     torch.optim.LBFGS with the strong-Wolfe line search on float64 log-factors q on the host, from q0 (None: zeros, every
     factor 1); each evaluation is one misfit_and_gradient and one group_sum.  groups: the group id of every element
@@ -362,13 +467,23 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
     if method not in ("lbfgs", "gauss-newton"):
         raise ValueError(f"unknown identification method {method!r}: 'lbfgs' or 'gauss-newton'.")
     config = config or SolverConfig()
-    levels, groups, q_start = check_identify(model, config, levels, groups, q0)
+    raw = list(levels) if levels is not None else []
+    levels, groups, q_start = check_identify(model, config, raw, groups, q0)
+    gauges = check_strains(model, raw)
     if int(max_evaluations) < 1:
         raise ValueError("max_evaluations must be at least 1")
     if method == "gauss-newton":
-        n_groups, n_rows = check_gauss_newton(levels, groups, damping)
+        n_groups, n_rows = check_gauss_newton(levels, groups, damping, gauges)
+    have_gauges = any(st is not None for st in gauges)
+    if have_gauges:
+        levels = _with_strains(levels, gauges)
+    lam_last = float(_level_parts(levels[-1])[0])
     ea0 = _base_ea(model)
     eng = _solver._engine_for(model, None, None)
+
+    def strains_at(states, ea_t):
+        """Every element's strain per level at the returned point (None without strain data)."""
+        return [eng.gl_state(u, ea_t).cpu().numpy() for u in states] if have_gauges else None
     if method == "gauss-newton":
         ea_gn = lambda q_np: ea0 * np.exp(q_np)[groups]
         q, rho, A, states, history, counters, stop, evaluations = _gauss_newton(
@@ -379,8 +494,8 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
         return IdentifyResult(
             factors=np.exp(q), ea=ea_gn(q), misfit=J, gradient=2.0 * A.T @ rho, evaluations=evaluations,
             converged=stop in ("misfit", "gradient", "step"), history=history,
-            displacements=[s.cpu().numpy() for s in states], counters=counters,
-            reactions=_reactions(eng, model, levels[-1][0], states[-1], ea_t), jacobian=A,
+            displacements=[s.cpu().numpy() for s in states], counters=counters, strains=strains_at(states, ea_t),
+            reactions=_reactions(eng, model, lam_last, states[-1], ea_t), jacobian=A,
             singular_values=np.linalg.svd(A, compute_uv=False), covariance=covariance,
             factor_std=None if covariance is None else np.exp(q) * np.sqrt(np.diag(covariance)), stop=stop)
     counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0}
@@ -420,7 +535,8 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
         pass
     met = bool(np.max(np.abs(best["g"]), initial=0.0) <= gtol or best["J"] <= misfit_tolerance)
     converged = met or len(history) < int(max_evaluations)          # False: the evaluation cap ended it
-    reactions = _reactions(eng, model, levels[-1][0], best["states"][-1], best["ea"])
+    reactions = _reactions(eng, model, lam_last, best["states"][-1], best["ea"])
     return IdentifyResult(factors=np.exp(best["q"]), ea=ea_of(best["q"]), misfit=float(best["J"]), gradient=best["g"],
                           evaluations=len(history), converged=converged, history=history,
-                          displacements=[s.cpu().numpy() for s in best["states"]], counters=counters, reactions=reactions)
+                          displacements=[s.cpu().numpy() for s in best["states"]], counters=counters, reactions=reactions,
+                          strains=strains_at(best["states"], best["ea"]))

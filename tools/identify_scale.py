@@ -2,13 +2,18 @@
 """Time identify_nr (fem/identify.py) on the Warren girder of tools/nr_scale.py --kinematics green-lagrange.
 
     identify_scale.py [--preconditioner jacobi|two-level-updated] [--aggregates N] [--groups 8] [--levels 2]
-                      [--method lbfgs|gauss-newton] [--evaluations 200] [--relative-misfit 1e-12] [panels]
+                      [--method lbfgs|gauss-newton] [--data displacements|strains] [--evaluations 200]
+                      [--relative-misfit 1e-12] [panels]
 
 The girder (E*A = 1, the load of nr_scale.py) gets one true factor per span group, alternating 0.8 / 1.25; its states at
 the load levels k / levels, solved on the device, are the measurements (every free dof), which is also the warm-up
 solve.  identify_nr then runs a whole identification from all factors 1 with the chosen method, to its own stop: the
 misfit tolerance is `relative-misfit` times the sum over the levels of the mean square of the measurements, the same for
-both methods, and `evaluations` is only the cap.  One JSON line: total seconds, evaluations, the stop, the factor error,
+both methods, and `evaluations` is only the cap.  --data strains: the measurements are strain gauges and nothing else,
+one per group on the group's lowest-numbered element, with strain_scale L = the span, and the misfit tolerance is
+`relative-misfit` times the sum over the levels of L^2 times the mean square of the measured strains; the row then also
+holds the singular values' ends of the Jacobian (method gauss-newton) and the launch times of pf_gl_strain_rhs and
+pf_gl_strain_jvp.  One JSON line: total seconds, evaluations, the stop, the factor error,
 seconds and Newton, CG, adjoint CG and sensitivity CG iterations in total and per evaluation, and the time of single
 pf_gl_state (model E*A and per-element E*A), pf_gl_sens, pf_group_sum_f64 and pf_gl_group_rhs launches (mean of 200
 back-to-back launches between two events) with the share of an evaluation of the L-BFGS path's own two."""
@@ -28,6 +33,7 @@ ap.add_argument("--aggregates", type=int, default=None)
 ap.add_argument("--groups", type=int, default=8)
 ap.add_argument("--levels", type=int, default=2)
 ap.add_argument("--method", choices=("lbfgs", "gauss-newton"), default="lbfgs")
+ap.add_argument("--data", choices=("displacements", "strains"), default="displacements")
 ap.add_argument("--evaluations", type=int, default=200)
 ap.add_argument("--relative-misfit", type=float, default=1e-12)
 ap.add_argument("panels", nargs="?", type=int, default=1000)
@@ -47,10 +53,18 @@ dofs = np.flatnonzero(free)
 factors = [(k + 1) / args.levels for k in range(args.levels)]
 # measurements: the states of the true structure (the misfit against zeros is not used); the warm-up solve as well
 _, _, states, _ = misfit_and_gradient(model, cfg, [(f, dofs, np.zeros(len(dofs))) for f in factors], true[groups])
-levels = [(f, dofs, s.cpu().numpy()[dofs]) for f, s in zip(factors, states)]
 eng = model._pf_engine_cache[1]
+if args.data == "strains":
+    gauges = np.array([np.flatnonzero(groups == g)[0] for g in range(args.groups)])
+    span = float(panels)
+    ea_true = torch.from_numpy(true[groups]).to(eng.device)
+    levels = [{"load_factor": f, "dofs": [], "u": [], "strain_elements": gauges,
+               "strains": eng.gl_state(s, ea_true).cpu().numpy()[gauges], "strain_scale": span} for f, s in zip(factors, states)]
+    misfit_tolerance = args.relative_misfit * sum(span ** 2 * float(np.mean(lv["strains"] ** 2)) for lv in levels)
+else:
+    levels = [(f, dofs, s.cpu().numpy()[dofs]) for f, s in zip(factors, states)]
+    misfit_tolerance = args.relative_misfit * sum(float(np.mean(lv[2] ** 2)) for lv in levels)
 refresh0, refreshes0 = eng.coarse_refresh_seconds, eng.coarse_refreshes
-misfit_tolerance = args.relative_misfit * sum(float(np.mean(lv[2] ** 2)) for lv in levels)
 torch.cuda.synchronize(); t0 = time.perf_counter()
 res = identify_nr(model, cfg, levels, groups=groups, max_evaluations=args.evaluations, method=args.method,
                   misfit_tolerance=misfit_tolerance)
@@ -75,9 +89,15 @@ us = {"pf_gl_state": launch_us(lambda: eng.gl_state(u)), "pf_gl_state_ea": launc
       "pf_gl_sens": launch_us(lambda: eng.gl_sensitivity(u, adj, out=out)),
       "pf_group_sum_f64": launch_us(lambda: eng.group_sum(out, ea, groups)),
       "pf_gl_group_rhs": launch_us(lambda: eng.gl_group_rhs(groups))}
+if args.data == "strains":
+    coef, V = torch.ones(len(el), dtype=torch.float64, device=eng.device), torch.ones((2, 2 * len(nodes)), dtype=torch.float64,
+                                                                                     device=eng.device)
+    rhs_out = torch.zeros(2 * len(nodes), dtype=torch.float64, device=eng.device)
+    us["pf_gl_strain_rhs"] = launch_us(lambda: eng.gl_strain_rhs(u, coef, out=rhs_out))
+    us["pf_gl_strain_jvp"] = launch_us(lambda: eng.gl_strain_jvp(u, gauges, V))
 n = res.evaluations
 per_eval = dt / n
-row = {"panels": panels, "elements": len(el), "dofs": 2 * len(nodes), "preconditioner": args.preconditioner,
+row = {"panels": panels, "data": args.data, "elements": len(el), "dofs": 2 * len(nodes), "preconditioner": args.preconditioner,
        "groups": args.groups, "levels": args.levels, "method": args.method, "seconds": dt, "evaluations": n,
        "stop": res.stop, "converged": res.converged, "misfit_tolerance": misfit_tolerance,
        "factor_error": float(np.max(np.abs(res.factors - true))), "seconds_per_evaluation": per_eval,
@@ -92,6 +112,8 @@ row = {"panels": panels, "elements": len(el), "dofs": 2 * len(nodes), "precondit
        "share_of_sens_and_group_sum": (args.levels * us["pf_gl_sens"] + us["pf_group_sum_f64"]) * 1e-6 / per_eval}
 if res.factor_std is not None:
     row["factor_std_max"] = float(np.max(res.factor_std))
+if res.singular_values is not None and args.data == "strains":
+    row["singular_value_max"], row["singular_value_min"] = float(res.singular_values[0]), float(res.singular_values[-1])
 if args.preconditioner == "two-level-updated":
     row["refresh_seconds"] = eng.coarse_refresh_seconds - refresh0
     row["refreshes"] = eng.coarse_refreshes - refreshes0
