@@ -466,12 +466,25 @@ int pf_gl_state(const pf_problem* p, const pf_gl* g, const double* u, void* stre
  * (pf_kt_v_f64, pf_pcgt_*, pf_pcg2t_*, pf_pcgtm_*, pf_pcg2tm_*, pf_coarse_setup_t), so they all follow.  A null ea is
  * PF_ERR_ARG, never a silent solve with the problem's E*A.  The three entry points below are additive: the version stays 9. */
 int pf_gl_state_ea(const pf_problem* p, const pf_gl* g, const double* ea, const double* u, void* stream);
+/* pf_gl_state with an initial (eigen-) strain e0 of every element (dev double [n_elems], a Green-Lagrange strain in the
+ * measure of g->strain: prestress e0 = -T / (E*A), thermal e0 = alpha * dT, lack of fit e0 = (L_natural - l0) / l0):
+ *   N = E*A * (e - e0),  fe = (N / l0) d,  B = (E*A / l0^3) d d^T + (N / l0) I,
+ * the derivative chain of sum E*A * l0 * (e - e0)^2 / 2.  g->strain stays the total strain e.  ea: as pf_gl_state_ea, or
+ * null for the problem's own E*A.  The same kernel: e - e0[e] is formed once, after e, so an all-zero e0 gives
+ * pf_gl_state's (pf_gl_state_ea's) bits.  A null e0 is PF_ERR_ARG, never a silent unstrained solve.  Additive: the
+ * version stays 9. */
+int pf_gl_state_e0(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const double* u, void* stream);
 /* Sensitivity of a misfit J(u) to every element's E*A through the adjoint a (K_t(u) a = dJ/du on the free dofs, zero on
  * the fixed ones): s_e = -(e / l0) d.(a_j - a_i) with d = d0 + u_j - u_i and e the strain as pf_gl_state forms it.  It
  * does not contain E*A and reads g->d0 only.  out (dev double [n_elems]) = s (accumulate 0) or out + s (accumulate 1:
  * load levels sum in call order).  One element per thread, no atomics. */
 int pf_gl_sens(const pf_problem* p, const pf_gl* g, const double* u, const double* a, int accumulate, double* out,
                void* stream);
+/* pf_gl_sens for elements with the initial strain e0 of pf_gl_state_e0: s_e = -((e - e0) / l0) d.(a_j - a_i), the same
+ * kernel and accumulate rule; an all-zero e0 gives pf_gl_sens's bits.  A null e0 is PF_ERR_ARG.  Additive: the version
+ * stays 9. */
+int pf_gl_sens_e0(const pf_problem* p, const pf_gl* g, const double* e0, const double* u, const double* a, int accumulate,
+                  double* out, void* stream);
 /* out[g] (dev double [n_groups]) = sum of values[e] * weights[e] (weights null: of values[e]) over e = group_elems[k],
  * group_ptr[g] <= k < group_ptr[g + 1] (dev int CSR; ids outside 0..n_elems-1 add nothing).  One workgroup per group, a
  * fixed summation order, no atomics: the same bits on every run.  An empty group gives 0.0. */
@@ -509,6 +522,11 @@ int pf_gl_strain_jvp(const pf_problem* p, const pf_gl* g, const double* u, const
                      int m, double* out, void* stream);
 /* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */
 int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream);
+/* out (dev double [n_dofs]) = the diagonal of K_t from the element blocks of kt: per dof the sum of the diagonal entries
+ * of the node's elements in ascending incidence order, exactly what pf_pcgt_begin inverts for the Jacobi preconditioner;
+ * 0.0 on PF_DOF_FIXED dofs.  One node per thread, no atomics.  A null kt or out is PF_ERR_ARG.  Additive: the version
+ * stays 9. */
+int pf_kt_diag_f64(const pf_problem* p, const double* kt, double* out, void* stream);
 /* as pf_pcg_begin / pf_pcg_iterations / pf_pcg_graph_create / pf_pcg_state on K_t: the same kernels, workspace
  * (pf_pcg_workspace_count), stop test and single-chain graph, the Jacobi preconditioner from kt's diagonal.  kt is read
  * when the launches RUN, so a graph stays valid while pf_gl_state overwrites kt in place between solves.  A null kt is

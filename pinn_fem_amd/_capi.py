@@ -170,7 +170,9 @@ SYMBOLS = {
     "pf_pcg2_state": (C.c_int, [_PP, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "pf_gl_state": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p]),
     "pf_gl_state_ea": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_gl_state_e0": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_gl_sens": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "pf_gl_sens_e0": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_group_sum_f64": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p]),
     "pf_gl_fint": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p]),
@@ -178,6 +180,7 @@ SYMBOLS = {
     "pf_gl_strain_rhs": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_gl_strain_jvp": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_kt_v_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_kt_diag_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_pcgt_begin": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
     "pf_pcgt_iterations": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "pf_pcgt_graph_create": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -88,6 +88,10 @@ def parse_problem(problem_file):
     #           "nr_control": {"dof": g, "displacement": d}}  displacement control of the green-lagrange Newton solve: the
     #                                                 global dof g goes to d over the increments and the load factor is
     #                                                 solved for (the .res.json gains "equilibrium_path"); absent: load control
+    #           "initial_strain": e0 | [e0_0, ..., e0_{n_elems-1}]  initial (eigen-) strain of the green-lagrange elements:
+    #                                                 N = E*A (e - e0); e0 < 0 pretension, alpha dT thermal, lack of fit
+    #                                                 (L_natural - l0) / l0; in full at every load factor; the
+    #                                                 .res.json gains "axial_forces"
     #           "identify_nr": {"groups": [...]|null, "levels": [{"load_factor": l, "dofs": [...], "u": [...]}, ...],
     #                           "max_evaluations": N, "method": "lbfgs"|"gauss-newton", "damping": mu}
     #                                                 identify one factor on E*A per group of elements (null: per element)
@@ -249,7 +253,12 @@ def _solver_config_from(data):
     control = accel.get("nr_control")
     if control is not None and not (isinstance(control, dict) and set(control) == {"dof", "displacement"}):
         raise ValueError('accel.nr_control must be {"dof": <global dof>, "displacement": <value at the last increment>}')
+    e0 = accel.get("initial_strain")
+    is_number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if e0 is not None and not (is_number(e0) or (isinstance(e0, list) and all(is_number(v) for v in e0))):
+        raise ValueError("accel.initial_strain must be a number or a list of n_elems numbers")
     return SolverConfig(
+        initial_strain=None if e0 is None else (float(e0) if is_number(e0) else [float(v) for v in e0]),
         nr_control="load" if control is None else "displacement",
         nr_control_dof=None if control is None else int(control["dof"]),
         nr_control_displacement=0.0 if control is None else float(control["displacement"]),
@@ -384,11 +393,15 @@ def solve_problem(parsed_data):
     }
     if result.path is not None:             # displacement control: (control displacement, load factor) per increment
         output["equilibrium_path"] = result.path
+    if result.axial_forces is not None and not compact:     # accel.initial_strain: N = E*A (e - e0) of every element
+        output["axial_forces"] = result.axial_forces.tolist()
     if compact:
         # §8(f) rank 1: at 10^6 nodes the reference's JSON lists (every coordinate three times per
         # property) would be hundreds of MB; arrays go to a side file, the JSON keeps the small fields
         arrays = {"displacements": result.displacements.flatten(),
                   "reactions": result.reactions.flatten()}
+        if result.axial_forces is not None:
+            arrays["axial_forces"] = result.axial_forces
         if result.nn_parameters:
             output["nn_parameters"] = {k: v.tolist() for k, v in result.nn_parameters.items()}
             cent = (model.nodes[model.elements[:, 0]] + model.nodes[model.elements[:, 1]]) / 2.0

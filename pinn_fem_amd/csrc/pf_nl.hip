@@ -3,7 +3,8 @@
 //
 // Per element with nodes i, j:  d0 = X_j - X_i (float64, from the caller: pf_gl.d0),  du = u_j - u_i,  d = d0 + du,
 //   e  = (2 d0.du + du.du) / (2 l0^2)          the difference of squares written out: (l^2 - l0^2) cancels at small strain
-//   N  = E*A * e                               E*A as pf_pcg.hip forms it (elem_ea64)
+//   N  = E*A * e                               E*A as pf_pcg.hip forms it (elem_ea64); with an initial strain e0
+//                                              (pf_gl_state_e0: prestress, thermal, lack of fit) N = E*A * (e - e0)
 //   fe = (N / l0) d                            f_int[j] += fe, f_int[i] -= fe
 //   B  = (E*A / l0^3) d d^T + (N / l0) I       K_t v: row j += B (v_j - v_i), row i -= B (v_j - v_i)
 // B is what pf_pcg.hip's gather64 reads as `kt`.  The reference's truss2d_element_state (fem/element.py:105-133) is NOT
@@ -11,11 +12,14 @@
 //
 // k_gl_state: one element per thread (grid-stride), coalesced records out, two gathered node vectors in.  E*A is
 //             elem_ea64, or the caller's per-element float64 array (pf_gl_state_ea: the identification of DESIGN.md §7).
+//             e0 (nullable, the same decision in every thread as ea): e - e0[e] is formed once, after e as above, and
+//             takes e's place in N; the strain written out stays e.  e - 0.0 is e to the bit.
 // k_gl_fint:  one node per thread, +-fe of the node's elements in ascending element id, no atomics; the adjacency codes
 //             and the records of two incidences are loaded together (selects, not branches), as the node kernels of
 //             pf_node.h issue theirs.
 // k_gl_sens:  dJ/d(E*A) of an element from the state u and an adjoint a: -(e / l0) d.(a_j - a_i); k_gl_state's loads
-//             and its strain, one store (or one load and one store when it accumulates), no atomics.
+//             and its strain (less e0[e] when e0 is given, as k_gl_state), one store (or one load and one store when
+//             it accumulates), no atomics.
 // k_group_sum: out[g] = sum of values[e] * weights[e] over the elements of group g (CSR, ascending element id): one
 //             workgroup per group, thread t adds elements t, t + 256, ... in that order, then the fixed-order block
 //             sum of pf_pcg.hip's block_sum64.  No atomics: the same bits on every run.
@@ -39,7 +43,7 @@ namespace {
 
 template <int DIM>
 __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const double* __restrict__ u,
-                                                  const double* __restrict__ ea_in) {
+                                                  const double* __restrict__ ea_in, const double* __restrict__ e0_in) {
   const pf_mesh& M = P.mesh;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < M.n_elems; e += gridDim.x * blockDim.x) {
     const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
@@ -59,7 +63,8 @@ __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const d
     for (int c = 0; c < DIM; ++c) { l02 += d0[c] * d0[c]; d0du += d0[c] * du[c]; dudu += du[c] * du[c]; }
     const double l0 = sqrt(l02);
     const double strain = (2.0 * d0du + dudu) / (2.0 * l02);
-    const double n_l0 = (ea * strain) / l0;          // N / l0
+    const double se = e0_in ? strain - e0_in[e] : strain;     // the strain that carries stress
+    const double n_l0 = (ea * se) / l0;              // N / l0
     const double k = ea / (l02 * l0);                // E*A / l0^3
     double d[DIM];
 #pragma unroll
@@ -80,7 +85,8 @@ __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const d
 
 template <int DIM>
 __global__ __launch_bounds__(256) void k_gl_sens(pf_problem P, const double* __restrict__ d0_in, const double* __restrict__ u,
-                                                 const double* __restrict__ a, int accumulate, double* __restrict__ out) {
+                                                 const double* __restrict__ a, const double* __restrict__ e0_in, int accumulate,
+                                                 double* __restrict__ out) {
   const pf_mesh& M = P.mesh;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < M.n_elems; e += gridDim.x * blockDim.x) {
     const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
@@ -104,7 +110,8 @@ __global__ __launch_bounds__(256) void k_gl_sens(pf_problem P, const double* __r
     double dda = 0.0;
 #pragma unroll
     for (int c = 0; c < DIM; ++c) dda += (d0[c] + du[c]) * da[c];
-    const double s = -(strain / sqrt(l02)) * dda;
+    const double se = e0_in ? strain - e0_in[e] : strain;
+    const double s = -(se / sqrt(l02)) * dda;
     out[e] = accumulate ? __dadd_rn(out[e], s) : s;      // s rounded first: the sum of two single calls, to the bit
   }
 }
@@ -323,12 +330,26 @@ int elem_blocks(int n_elems) {
   return nb > PF_MAX_NODE_BLOCKS ? PF_MAX_NODE_BLOCKS : nb;
 }
 
-int gl_state(const char* who, const pf_problem* p, const pf_gl* g, const double* ea, const double* u, void* stream) {
+int gl_state(const char* who, const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const double* u,
+             void* stream) {
   if (!mesh_ok(p) || !g || !g->d0 || !g->kt || !g->fe || !g->strain || !u) return gl_fail(PF_ERR_ARG, who, "bad argument");
   if (p->mesh.n_elems == 0) return PF_OK;
   const int nb = elem_blocks(p->mesh.n_elems);
-  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_state<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, *g, u, ea);
-  else hipLaunchKernelGGL(k_gl_state<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, *g, u, ea);
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_state<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, *g, u, ea, e0);
+  else hipLaunchKernelGGL(k_gl_state<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, *g, u, ea, e0);
+  if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
+  return PF_OK;
+}
+
+int gl_sens(const char* who, const pf_problem* p, const pf_gl* g, const double* e0, const double* u, const double* a,
+            int accumulate, double* out, void* stream) {
+  if (!mesh_ok(p) || !g || !g->d0 || !u || !a || !out || (accumulate != 0 && accumulate != 1))
+    return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (p->mesh.n_elems == 0) return PF_OK;
+  const int nb = elem_blocks(p->mesh.n_elems);
+  const hipStream_t s = (hipStream_t)stream;
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_sens<2>, dim3(nb), dim3(256), 0, s, *p, g->d0, u, a, e0, accumulate, out);
+  else hipLaunchKernelGGL(k_gl_sens<1>, dim3(nb), dim3(256), 0, s, *p, g->d0, u, a, e0, accumulate, out);
   if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
   return PF_OK;
 }
@@ -338,26 +359,28 @@ int gl_state(const char* who, const pf_problem* p, const pf_gl* g, const double*
 extern "C" {
 
 int pf_gl_state(const pf_problem* p, const pf_gl* g, const double* u, void* stream) {
-  return gl_state("pf_gl_state", p, g, nullptr, u, stream);
+  return gl_state("pf_gl_state", p, g, nullptr, nullptr, u, stream);
 }
 
 int pf_gl_state_ea(const pf_problem* p, const pf_gl* g, const double* ea, const double* u, void* stream) {
   if (!ea) return gl_fail(PF_ERR_ARG, "pf_gl_state_ea", "null ea (pf_gl_state is the solve with the problem's own E*A)");
-  return gl_state("pf_gl_state_ea", p, g, ea, u, stream);
+  return gl_state("pf_gl_state_ea", p, g, ea, nullptr, u, stream);
+}
+
+int pf_gl_state_e0(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const double* u, void* stream) {
+  if (!e0) return gl_fail(PF_ERR_ARG, "pf_gl_state_e0", "null e0 (pf_gl_state / pf_gl_state_ea are the unstrained solves)");
+  return gl_state("pf_gl_state_e0", p, g, ea, e0, u, stream);
 }
 
 int pf_gl_sens(const pf_problem* p, const pf_gl* g, const double* u, const double* a, int accumulate, double* out,
                void* stream) {
-  const char* who = "pf_gl_sens";
-  if (!mesh_ok(p) || !g || !g->d0 || !u || !a || !out || (accumulate != 0 && accumulate != 1))
-    return gl_fail(PF_ERR_ARG, who, "bad argument");
-  if (p->mesh.n_elems == 0) return PF_OK;
-  const int nb = elem_blocks(p->mesh.n_elems);
-  const hipStream_t s = (hipStream_t)stream;
-  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_sens<2>, dim3(nb), dim3(256), 0, s, *p, g->d0, u, a, accumulate, out);
-  else hipLaunchKernelGGL(k_gl_sens<1>, dim3(nb), dim3(256), 0, s, *p, g->d0, u, a, accumulate, out);
-  if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
-  return PF_OK;
+  return gl_sens("pf_gl_sens", p, g, nullptr, u, a, accumulate, out, stream);
+}
+
+int pf_gl_sens_e0(const pf_problem* p, const pf_gl* g, const double* e0, const double* u, const double* a, int accumulate,
+                  double* out, void* stream) {
+  if (!e0) return gl_fail(PF_ERR_ARG, "pf_gl_sens_e0", "null e0 (pf_gl_sens is the unstrained sensitivity)");
+  return gl_sens("pf_gl_sens_e0", p, g, e0, u, a, accumulate, out, stream);
 }
 
 int pf_group_sum_f64(int n_elems, const double* values, const double* weights, const int* group_ptr, const int* group_elems,

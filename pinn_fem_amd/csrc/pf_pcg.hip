@@ -86,6 +86,21 @@ __global__ __launch_bounds__(256) void k_kv64(pf_problem P, const double* __rest
   }
 }
 
+// out = diag(K_t) on the free dofs, 0.0 on the fixed ones: the dg that k_pcg_init inverts (gather64 with a null vector)
+template <int DIM>
+__global__ __launch_bounds__(256) void k_kt_diag64(pf_problem P, const double* __restrict__ kt, double* __restrict__ out) {
+  const pf_mesh& M = P.mesh;
+  for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < M.n_nodes; node += gridDim.x * blockDim.x) {
+    double kv[2], dg[2];
+    gather64<DIM>(P, kt, nullptr, node, kv, dg);
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const int dof = node * DIM + c;
+      out[dof] = (M.dof_flags[dof] & PF_DOF_FIXED) ? 0.0 : dg[c];
+    }
+  }
+}
+
 __device__ __forceinline__ double block_sum64(double v, double* smem) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
 #pragma unroll
@@ -647,6 +662,15 @@ int pf_kv_f64(const pf_problem* p, const double* v, double* out, int zero_fixed,
 int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream) {
   PCGT_NEED_KT("pf_kt_v_f64");
   return kv_impl(p, kt, v, out, zero_fixed, (hipStream_t)stream, "pf_kt_v_f64");
+}
+int pf_kt_diag_f64(const pf_problem* p, const double* kt, double* out, void* stream) {
+  const char* who = "pf_kt_diag_f64";
+  PCGT_NEED_KT(who);
+  if (!p || !out) return pcg_fail(PF_ERR_ARG, who, "null argument");
+  const int nb = pf_node_blocks(p->mesh.n_nodes);
+  PCG_FOR_DIM(p, hipLaunchKernelGGL(k_kt_diag64<DIM>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, kt, out));
+  PCG_CHECK(who);
+  return PF_OK;
 }
 
 int pf_pcg_begin(const pf_problem* p, const double* b, double* x, double* ws, double rtol, void* stream) {

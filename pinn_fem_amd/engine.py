@@ -612,30 +612,39 @@ class HipEngine:
         return vv
 
     @_on_engine_stream
-    def gl_state(self, u: torch.Tensor, ea: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def gl_state(self, u: torch.Tensor, ea: Optional[torch.Tensor] = None, e0: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Green-Lagrange strain, element force and tangent block of every element at the displacements u (float64,
-        pf_gl_state); they stay on the device for gl_fint, kt_v_f64 and pcg_solve(tangent=True).  ea: E*A of every
+        pf_gl_state); they stay on the device for gl_fint, kt_v_f64, kt_diag and pcg_solve(tangent=True).  ea: E*A of every
         element [n_elems] in float64 in place of the model's (pf_gl_state_ea; the identification of fem/identify.py).
-        Returns the strains [n_elems] (the engine's buffer: the next gl_state overwrites it)."""
+        e0: the initial strain of every element [n_elems] in float64 (pf_gl_state_e0: N = E*A (e - e0); prestress, thermal
+        strain, lack of fit).  The engine keeps no e0 of its own: every call that wants it passes it.
+        Returns the total strains e [n_elems] (the engine's buffer: the next gl_state overwrites it)."""
         uu = self._f64_vector("gl_state", "u", u, self.plan.n_dofs, "dofs")
         rec = self._gl_buffers()[4]
-        if ea is None:
-            _capi.check(self.lib.pf_gl_state(self._ref(), C.byref(rec), uu.data_ptr(), self._stream()), "pf_gl_state")
-        else:
-            ee = self._f64_vector("gl_state", "ea", ea, self.plan.n_elems, "elements")
+        ee = None if ea is None else self._f64_vector("gl_state", "ea", ea, self.plan.n_elems, "elements")
+        if e0 is not None:
+            zz = self._f64_vector("gl_state", "e0", e0, self.plan.n_elems, "elements")
             if self.plan.n_elems:
-                _capi.check(self.lib.pf_gl_state_ea(self._ref(), C.byref(rec), ee.data_ptr(), uu.data_ptr(), self._stream()),
-                            "pf_gl_state_ea")
+                _capi.check(self.lib.pf_gl_state_e0(self._ref(), C.byref(rec), None if ee is None else ee.data_ptr(),
+                                                    zz.data_ptr(), uu.data_ptr(), self._stream()), "pf_gl_state_e0")
+        elif ee is None:
+            _capi.check(self.lib.pf_gl_state(self._ref(), C.byref(rec), uu.data_ptr(), self._stream()), "pf_gl_state")
+        elif self.plan.n_elems:
+            _capi.check(self.lib.pf_gl_state_ea(self._ref(), C.byref(rec), ee.data_ptr(), uu.data_ptr(), self._stream()),
+                        "pf_gl_state_ea")
         return self._gl[3][: self.plan.n_elems]
 
     @_on_engine_stream
-    def gl_sensitivity(self, u: torch.Tensor, a: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def gl_sensitivity(self, u: torch.Tensor, a: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       e0: Optional[torch.Tensor] = None) -> torch.Tensor:
         """dJ/d(E*A) of every element [n_elems] from the displacements u and the adjoint a of a misfit J (K_t(u) a =
         dJ/du on the free dofs): -(e / l0) d.(a_j - a_i) (pf_gl_sens).  out: a float64 device vector [n_elems] the result
-        is ADDED to (load levels sum in call order); None: a new vector."""
+        is ADDED to (load levels sum in call order); None: a new vector.  e0: the initial strain of gl_state
+        [n_elems]: e - e0 takes e's place (pf_gl_sens_e0)."""
         uu = self._f64_vector("gl_sensitivity", "u", u, self.plan.n_dofs, "dofs")
         aa = self._f64_vector("gl_sensitivity", "a", a, self.plan.n_dofs, "dofs")
         ne = self.plan.n_elems
+        zz = None if e0 is None else self._f64_vector("gl_sensitivity", "e0", e0, ne, "elements")
         accumulate = out is not None
         if accumulate:
             if (out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous() or out.numel() != ne):
@@ -644,8 +653,12 @@ class HipEngine:
             out = torch.empty(ne, dtype=torch.float64, device=self.device)
         if ne:
             rec = self._gl_buffers()[4]
-            _capi.check(self.lib.pf_gl_sens(self._ref(), C.byref(rec), uu.data_ptr(), aa.data_ptr(), int(accumulate),
-                                            out.data_ptr(), self._stream()), "pf_gl_sens")
+            if zz is None:
+                _capi.check(self.lib.pf_gl_sens(self._ref(), C.byref(rec), uu.data_ptr(), aa.data_ptr(), int(accumulate),
+                                                out.data_ptr(), self._stream()), "pf_gl_sens")
+            else:
+                _capi.check(self.lib.pf_gl_sens_e0(self._ref(), C.byref(rec), zz.data_ptr(), uu.data_ptr(), aa.data_ptr(),
+                                                   int(accumulate), out.data_ptr(), self._stream()), "pf_gl_sens_e0")
         return out
 
     @_on_engine_stream
@@ -767,6 +780,15 @@ class HipEngine:
         out = torch.empty(self.plan.n_dofs, dtype=torch.float64, device=self.device)
         _capi.check(self.lib.pf_kt_v_f64(self._fixed_view(extra_fixed)[0], kt.data_ptr(), vv.data_ptr(), out.data_ptr(), int(zero_fixed),
                                          self._stream()), "pf_kt_v_f64")
+        return out
+
+    @_on_engine_stream
+    def kt_diag(self) -> torch.Tensor:
+        """diag(K_t) [n_dofs] of the last gl_state, 0.0 on fixed dofs (pf_kt_diag_f64): what the Jacobi preconditioner of
+        pcg_solve(tangent=True) inverts."""
+        kt = self._gl_ready("kt_diag")[1]
+        out = torch.empty(self.plan.n_dofs, dtype=torch.float64, device=self.device)
+        _capi.check(self.lib.pf_kt_diag_f64(self._ref(), kt.data_ptr(), out.data_ptr(), self._stream()), "pf_kt_diag_f64")
         return out
 
     def _pcg_setup(self, who, tangent, preconditioner, n_aggregates, aggregates, u, extra_fixed):

@@ -35,9 +35,16 @@ e = eps + eps^2 / 2 (there is no conversion option).  With B = d e / d u,  d e_e
   rho:  per level the displacement rows, then L_k (e - ebar) / sqrt p_k;   A: (L_k / sqrt p_k) B s_kg at the gauges
                                                                                                   (pf_gl_strain_jvp)
 
+Initial strains: config.initial_strain (solver.check_initial_strain) gives every element an eigenstrain e0,
+N = ea (e - e0).  It goes into every gl_state call (the Newton loops, the states the adjoint and the sensitivity solves are
+taken at, the reactions) and into the sensitivity, dJ/d ea_e = - sum_k ((e - e0) / l0) d.(a_j - a_i) (pf_gl_sens_e0).
+f_int stays linear in E*A and the group's own fe records already hold the prestress, so pf_gl_group_rhs needs nothing; the
+strains, measured and computed, stay the total strains e.  A measured structure carries its prestress: fitted without it,
+the error goes into the factors.
+
 Limits: states with a positive definite tangent only (the CG solves), load control only, a scalar base material, no
 regularisation term, no bounds on the factors and no weight per sensor but strain_scale; what a set of gauges
-determines is what the singular values of A say, not more.
+determines is what the singular values of A say, not more.  The initial strain is given, not identified.
 """
 from __future__ import annotations
 
@@ -206,30 +213,37 @@ def _base_ea(model) -> float:
     return float(model.material.young.value()) * float(model.material.area.value())
 
 
-def _prepare(model, ea):
-    """What misfit_and_gradient and residuals_and_jacobian share before the first level: ea checked and on the device,
-    the engine, the free mask and the loads at load factor 1.  Returns (engine, ea, free mask, loads)."""
+def _prepare(model, ea, config):
+    """What misfit_and_gradient and residuals_and_jacobian share before the first level: ea and config.initial_strain
+    checked and on the device, the engine, the free mask and the loads at load factor 1.
+    Returns (engine, ea, free mask, loads, e0 or None)."""
     ea_np = ea.detach().cpu().numpy() if isinstance(ea, torch.Tensor) else np.asarray(ea)
     ea_np = np.asarray(ea_np, dtype=np.float64).reshape(-1)
     if ea_np.size != model.nelm:
         raise ValueError(f"ea has {ea_np.size} entries, the model has {model.nelm} elements")
     if not (np.all(np.isfinite(ea_np)) and np.all(ea_np > 0.0)):
         raise ValueError("ea must be finite and positive in every element")
+    e0_np = _solver.check_initial_strain(config, model)
     eng = _solver._engine_for(model, None, None)
     dev, ndof = eng.device, model.ndof
     ea_t = ea.to(device=dev, dtype=torch.float64).reshape(-1) if isinstance(ea, torch.Tensor) else torch.from_numpy(ea_np).to(dev)
     free = np.ones(ndof, dtype=bool)
     free[np.asarray(model.fixed_dofs, dtype=int)] = False
-    if bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
+    e0_t = None if e0_np is None else torch.from_numpy(e0_np).to(dev)
+    if e0_t is not None:                    # solve_nr's rule: the tangent at the starting state u = 0 decides
+        eng.gl_state(torch.zeros(ndof, dtype=torch.float64, device=dev), ea_t, e0_t)
+        _solver._check_tangent_diagonal(eng, free)
+    elif bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
         raise RuntimeError("Tangent stiffness became singular during solve")
     free_t = torch.from_numpy(free).to(dev)
     loads = torch.from_numpy(np.ascontiguousarray(np.asarray(model.loads, dtype=float).reshape(-1))).to(dev)
-    return eng, ea_t, free_t, loads
+    return eng, ea_t, free_t, loads, e0_t
 
 
-def _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters):
+def _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters, e0_t=None):
     """One level's Newton loop from u, as misfit_and_gradient runs it; no convergence is a RuntimeError."""
-    u, ok, residual, _, ite, cg = _solver._newton_loop(eng, model, config, lam * loads, u, free_t, True, ea=ea_t)
+    u, ok, residual, _, ite, cg = _solver._newton_loop(eng, model, config, lam * loads, u, free_t, True, ea=ea_t,
+                                                      e0=e0_t)
     counters["newton_iterations"] += ite + 1
     counters["cg_iterations"] += cg
     if not ok:
@@ -254,14 +268,14 @@ def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
     raw = list(levels) if levels is not None else []
     levels, _, _ = check_identify(model, config, raw)
     strains = check_strains(model, raw)
-    eng, ea_t, free_t, loads = _prepare(model, ea)
+    eng, ea_t, free_t, loads, e0_t = _prepare(model, ea, config)
     dev, ndof = eng.device, model.ndof
     u = torch.zeros(ndof, dtype=torch.float64, device=dev)
     J, grad, states = 0.0, None, []
     counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0}
     for (lam, dofs, ubar), strain in zip(levels, strains):
-        u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters)
-        e = eng.gl_state(u, ea_t)
+        u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters, e0_t)
+        e = eng.gl_state(u, ea_t, e0_t)
         g = torch.zeros(ndof, dtype=torch.float64, device=dev)
         if len(dofs):
             dofs_t = torch.from_numpy(dofs).to(dev)
@@ -278,7 +292,7 @@ def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
                                               n_aggregates=config.nr_aggregates, u=u)
         _solver._check_cg_step(True, g, a, ok_a, rr, bb, free_t)
         counters["adjoint_cg_iterations"] += int(it_a)
-        grad = eng.gl_sensitivity(u, a, out=grad)
+        grad = eng.gl_sensitivity(u, a, out=grad, e0=e0_t)
         states.append(u)
     return J, grad, states, counters
 
@@ -325,7 +339,7 @@ def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, gr
     strains = check_strains(model, raw)
     if groups is None:
         raise ValueError("residuals_and_jacobian needs an element -> group map")
-    eng, ea_t, free_t, loads = _prepare(model, ea)
+    eng, ea_t, free_t, loads, e0_t = _prepare(model, ea, config)
     dev, ndof = eng.device, model.ndof
     if states is not None and len(states) != len(levels):
         raise ValueError(f"states has {len(states)} entries for {len(levels)} levels")
@@ -335,7 +349,7 @@ def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, gr
     rho, rows, out_states = [], [], []
     for k, (lam, dofs, ubar) in enumerate(levels):
         if states is None:
-            u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters)
+            u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters, e0_t)
         else:
             u = states[k].to(device=dev, dtype=torch.float64).reshape(-1)
         dofs_t = torch.from_numpy(dofs).to(dev)
@@ -343,7 +357,7 @@ def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, gr
         rho.append((u[dofs_t] - torch.from_numpy(ubar).to(dev)).cpu().numpy() * w)
         strain = strains[k]
         if jacobian or strain is not None:
-            e = eng.gl_state(u, ea_t)
+            e = eng.gl_state(u, ea_t, e0_t)
         if strain is not None:
             _, r_e, scale, p = _strain_residual(eng, e, strain)
             w_e = scale / np.sqrt(p)
@@ -424,9 +438,9 @@ class _Stop(Exception):
     pass
 
 
-def _reactions(eng, model, lam, u, ea_t):
-    """Reactions of a level at its state: f_int(u; ea) - lam f on the fixed dofs."""
-    eng.gl_state(u, ea_t)
+def _reactions(eng, model, lam, u, ea_t, e0_t=None):
+    """Reactions of a level at its state: f_int(u; ea, e0) - lam f on the fixed dofs."""
+    eng.gl_state(u, ea_t, e0_t)
     reactions = eng.gl_fint().cpu().numpy() - lam * np.asarray(model.loads, dtype=float).reshape(-1)
     free = np.ones(model.ndof, dtype=bool)
     free[np.asarray(model.fixed_dofs, dtype=int)] = False
@@ -479,11 +493,13 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
         levels = _with_strains(levels, gauges)
     lam_last = float(_level_parts(levels[-1])[0])
     ea0 = _base_ea(model)
+    e0_np = _solver.check_initial_strain(config, model)
     eng = _solver._engine_for(model, None, None)
+    e0_t = None if e0_np is None else torch.from_numpy(e0_np).to(eng.device)
 
     def strains_at(states, ea_t):
         """Every element's strain per level at the returned point (None without strain data)."""
-        return [eng.gl_state(u, ea_t).cpu().numpy() for u in states] if have_gauges else None
+        return [eng.gl_state(u, ea_t, e0_t).cpu().numpy() for u in states] if have_gauges else None
     if method == "gauss-newton":
         ea_gn = lambda q_np: ea0 * np.exp(q_np)[groups]
         q, rho, A, states, history, counters, stop, evaluations = _gauss_newton(
@@ -495,7 +511,7 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
             factors=np.exp(q), ea=ea_gn(q), misfit=J, gradient=2.0 * A.T @ rho, evaluations=evaluations,
             converged=stop in ("misfit", "gradient", "step"), history=history,
             displacements=[s.cpu().numpy() for s in states], counters=counters, strains=strains_at(states, ea_t),
-            reactions=_reactions(eng, model, lam_last, states[-1], ea_t), jacobian=A,
+            reactions=_reactions(eng, model, lam_last, states[-1], ea_t, e0_t), jacobian=A,
             singular_values=np.linalg.svd(A, compute_uv=False), covariance=covariance,
             factor_std=None if covariance is None else np.exp(q) * np.sqrt(np.diag(covariance)), stop=stop)
     counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0}
@@ -535,7 +551,7 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
         pass
     met = bool(np.max(np.abs(best["g"]), initial=0.0) <= gtol or best["J"] <= misfit_tolerance)
     converged = met or len(history) < int(max_evaluations)          # False: the evaluation cap ended it
-    reactions = _reactions(eng, model, lam_last, best["states"][-1], best["ea"])
+    reactions = _reactions(eng, model, lam_last, best["states"][-1], best["ea"], e0_t)
     return IdentifyResult(factors=np.exp(best["q"]), ea=ea_of(best["q"]), misfit=float(best["J"]), gradient=best["g"],
                           evaluations=len(history), converged=converged, history=history,
                           displacements=[s.cpu().numpy() for s in best["states"]], counters=counters, reactions=reactions,

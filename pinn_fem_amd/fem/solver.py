@@ -61,6 +61,10 @@ class SolverConfig:
     nr_control: str = "load"
     nr_control_dof: Optional[int] = None
     nr_control_displacement: float = 0.0
+    # initial (eigen-) strain of the Green-Lagrange elements of solve_nr: None, one value for every element or n_elems
+    # values, a Green-Lagrange strain e0 with N = E*A (e - e0).  e0 < 0 is a pretension (T = -E*A e0), thermal loading is
+    # e0 = alpha dT, lack of fit e0 = (L_natural - l0) / l0.  It acts in full at every load factor
+    initial_strain: Optional[object] = None
 
 
 KINEMATICS = ("linear", "green-lagrange")
@@ -120,6 +124,51 @@ def check_control(config, model=None, method: str = "nr") -> str:
     return name
 
 
+def check_initial_strain(config, model):
+    """config.initial_strain as a float64 array [n_elems], or None when it is not given.  It belongs to the Green-Lagrange
+    Newton solve: linear kinematics, a wrong length, a non-finite value or one of magnitude >= 0.5 (no eigenstrain; 1 + 2 e
+    must stay positive) is a ValueError before an engine is built."""
+    e0 = getattr(config, "initial_strain", None)
+    if e0 is None:
+        return None
+    if config.kinematics != "green-lagrange":
+        raise ValueError("initial_strain needs kinematics 'green-lagrange': solve_gd and the linear solve_nr are untouched "
+                         "by it and would silently solve the unstrained structure.")
+    try:
+        arr = np.asarray(e0, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"initial_strain must be a number or {model.nelm} numbers (one for each element)") from None
+    if arr.ndim == 0:
+        arr = np.full(model.nelm, float(arr))
+    arr = np.ascontiguousarray(arr.reshape(-1))
+    if arr.size != model.nelm:
+        raise ValueError(f"initial_strain has {arr.size} entries, the model has {model.nelm} elements")
+    if not np.all(np.isfinite(arr)):
+        raise ValueError("initial_strain holds non-finite values")
+    if arr.size and float(np.max(np.abs(arr))) >= 0.5:
+        raise ValueError("initial_strain must be smaller than 0.5 in magnitude: it is a small Green-Lagrange eigenstrain, "
+                         f"got max |e0| = {float(np.max(np.abs(arr))):g}")
+    return arr
+
+
+def _axial_forces(model, strain, e0):
+    """N = E*A (e - e0) of every element on the host, from the strains a gl_state returned; E*A is the model's scalar one
+    as the device forms it (each factor rounded to float32 first)."""
+    ea = float(np.float32(model.material.young.value())) * float(np.float32(model.material.area.value()))
+    return ea * (strain.cpu().numpy() - e0)
+
+
+def _check_tangent_diagonal(eng, free):
+    """The pre-check of a solve with initial strains: the tangent at the starting state (the last gl_state) must have a
+    positive diagonal on every free dof.  A free dof that only a slack or compressed member holds is a mechanism."""
+    dg = eng.kt_diag().cpu().numpy()
+    bad = np.flatnonzero(free & ~(dg > 0.0))
+    if bad.size:
+        raise RuntimeError(f"Tangent stiffness is not positive definite at the starting state: its diagonal is "
+                           f"{dg[bad[0]]:.6g} at free dof {int(bad[0])} (a slack or compressed mechanism; "
+                           f"{bad.size} such dof{'s' if bad.size > 1 else ''})")
+
+
 @dataclass
 class SolverResult:
     """Unified result from any solver (solver.py:65-75)."""
@@ -131,6 +180,9 @@ class SolverResult:
     # displacement control (solve() with nr_control = "displacement"): one {control_displacement, load_factor,
     # iterations} per increment, the equilibrium path; None otherwise
     path: Optional[list] = None
+    # Green-Lagrange solve_nr with config.initial_strain: N = E*A (e - e0) of every element at the final state; None
+    # otherwise
+    axial_forces: Optional[np.ndarray] = None
 
 
 # host polls the device state every CHECK_EVERY iterations (launches after the stop are no-ops)
@@ -392,16 +444,16 @@ def _solve_gd_sharded(model, config, measured_disp, measured_dofs, lam, u_initia
                         converged=converged, history=history, nn_parameters=nn_params)
 
 
-def _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange, ea=None):
+def _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange, ea=None, e0=None):
     """The Newton iteration of solve_nr from u at the load f_ext: u += K^-1 (f_ext - f_int(u)) by CG until
     |du| / max(|u|, min_denominator) <= tolerance.  ea (Green-Lagrange only): E*A of every element in place of the
-    model's (identify.misfit_and_gradient).  Returns (u, converged, |du|/|u|, max strain of the linear branch,
-    index of the last iteration, CG iterations)."""
+    model's (identify.misfit_and_gradient); e0: their initial strain (device float64).  Returns (u, converged, |du|/|u|,
+    max strain of the linear branch, index of the last iteration, CG iterations)."""
     has_converged, residual_norm, max_e, ite = False, float("inf"), 0.0, -1
     cg0 = eng.pcg_iterations
     for ite in range(config.max_iterations):
         if green_lagrange:
-            eng.gl_state(u, ea)             # the history's max |e| is read once, from the state at the final u
+            eng.gl_state(u, ea, e0)         # the history's max |e| is read once, from the state at the final u
             rhs = f_ext - eng.gl_fint()
             du, _, ok, rr, bb = eng.pcg_solve(rhs, tangent=True, preconditioner=config.nr_preconditioner,
                                              n_aggregates=config.nr_aggregates, u=u)
@@ -451,11 +503,17 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
 
     config.nr_control = "displacement" (Green-Lagrange only) passes a limit point of the load: target_load_factor is then
     the fraction of config.nr_control_displacement the control dof is held at and the load factor is solved for
-    (_solve_nr_displacement).  There is no arc-length control."""
+    (_solve_nr_displacement).  There is no arc-length control.
+
+    config.initial_strain (Green-Lagrange only; check_initial_strain) gives every element an eigenstrain e0,
+    N = E*A (e - e0): it goes into every gl_state call, in full at every load factor, the pre-check then reads the tangent's
+    diagonal at the starting state (a free dof with a diagonal <= 0 raises RuntimeError "... not positive definite ...")
+    and the result carries axial_forces."""
     config = config or SolverConfig()
     green_lagrange = check_kinematics(config.kinematics, config.nr_preconditioner) == "green-lagrange"
+    e0_np = check_initial_strain(config, model)
     if check_control(config, model) == "displacement":
-        return _solve_nr_displacement(model, config, target_load_factor, u_initial)
+        return _solve_nr_displacement(model, config, target_load_factor, u_initial, e0_np)
     if model.material.has_trainable_params():
         raise ValueError("Newton-Raphson solver with NN materials not fully supported yet. "
                          "Use solve_gd() for problems with NN parameters.")
@@ -475,15 +533,25 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
         if u.numel() != ndof:
             raise ValueError(f"u_initial has {u.numel()} entries, the model has {ndof} dofs")
         u[torch.from_numpy(~free).to(eng.device)] = 0.0
+    e0 = None if e0_np is None else torch.from_numpy(e0_np).to(eng.device)
+    if e0 is not None:
+        # with initial strains the geometric stiffness may be all that holds a dof (a taut string): the tangent at the
+        # starting state decides, not the linear diagonal
+        eng.gl_state(u, None, e0)
+        _check_tangent_diagonal(eng, free)
     # a free dof no element stiffens makes K_ff singular: np.linalg.solve raises there (solver.py:462-467)
-    if bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
+    elif bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
         raise RuntimeError("Tangent stiffness became singular during solve")
     free_t = torch.from_numpy(free).to(eng.device)
-    u, has_converged, residual_norm, max_e, ite, _ = _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange)
+    u, has_converged, residual_norm, max_e, ite, _ = _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange,
+                                                                  e0=e0)
+    axial = None
     if green_lagrange:
-        strain = eng.gl_state(u)                      # state at the final u: its strain, and f_int for the reactions
+        strain = eng.gl_state(u, None, e0)            # state at the final u: its strain, and f_int for the reactions
         max_e = float(strain.abs().max()) if model.nelm else 0.0
         reactions = (eng.gl_fint() - f_ext).cpu().numpy()
+        if e0 is not None:
+            axial = _axial_forces(model, strain, e0_np)
     else:
         reactions = (eng.kv_f64(u) - f_ext).cpu().numpy()
     history = [{"load_factor": float(load_factor), "iterations": float(ite + 1), "residual": float(residual_norm),
@@ -492,10 +560,10 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     u_np = u.cpu().numpy()
     shape = (-1, 1) if model.dimension == 1 else (model.nnode, model.dimension)
     return SolverResult(displacements=u_np.reshape(shape), reactions=reactions.reshape(shape),
-                        converged=has_converged, history=history)
+                        converged=has_converged, history=history, axial_forces=axial)
 
 
-def _solve_nr_displacement(model, config, control_factor, u_initial) -> SolverResult:
+def _solve_nr_displacement(model, config, control_factor, u_initial, e0_np=None) -> SolverResult:
     """solve_nr under displacement control (Batoz-Dhatt), Green-Lagrange kinematics; DESIGN.md §7.
 
     The free dof c = config.nr_control_dof is held at ubar = control_factor * config.nr_control_displacement and the load
@@ -523,7 +591,13 @@ def _solve_nr_displacement(model, config, control_factor, u_initial) -> SolverRe
         if u.numel() != ndof:
             raise ValueError(f"u_initial has {u.numel()} entries, the model has {ndof} dofs")
         u[torch.from_numpy(~free).to(dev)] = 0.0
-    if bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
+    e0 = None if e0_np is None else torch.from_numpy(e0_np).to(dev)
+    if e0 is not None:
+        eng.gl_state(u, None, e0)           # solve_nr's rule; the control dof is held, so K' is what must be definite
+        held = free.copy()
+        held[c] = False
+        _check_tangent_diagonal(eng, held)
+    elif bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
         raise RuntimeError("Tangent stiffness became singular during solve")
     free_t = torch.from_numpy(free).to(dev)
     fc_t = free_t.clone()
@@ -549,12 +623,12 @@ def _solve_nr_displacement(model, config, control_factor, u_initial) -> SolverRe
             refuse("rhs.x <= 0")
         return x
 
-    eng.gl_state(u)
+    eng.gl_state(u, None, e0)
     lam = float(torch.dot(f[free_t], eng.gl_fint()[free_t])) / float(torch.dot(f[free_t], f[free_t]))
     has_converged, residual_norm, load_residual, ite = False, float("inf"), float("inf"), -1
     for ite in range(config.max_iterations):
         if ite > 0:
-            eng.gl_state(u)                 # (the first iterate's state is the one lam was started from)
+            eng.gl_state(u, None, e0)       # (the first iterate's state is the one lam was started from)
         R = eng.gl_fint() - lam * f
         du_c = ubar - float(u[c])
         k_c = eng.kt_v_f64(e_c)             # column c of K_t, every row
@@ -582,7 +656,7 @@ def _solve_nr_displacement(model, config, control_factor, u_initial) -> SolverRe
         if residual_norm <= config.tolerance and load_residual <= config.tolerance:
             has_converged = True
             break
-    strain = eng.gl_state(u)
+    strain = eng.gl_state(u, None, e0)
     max_e = float(strain.abs().max()) if model.nelm else 0.0
     reactions = (eng.gl_fint() - lam * f).cpu().numpy()
     reactions[free] = 0.0                   # the control dof is free: the load carries it, it has no reaction
@@ -592,7 +666,8 @@ def _solve_nr_displacement(model, config, control_factor, u_initial) -> SolverRe
                 "load_residual": float(load_residual)}]
     shape = (-1, 1) if model.dimension == 1 else (model.nnode, model.dimension)
     return SolverResult(displacements=u.cpu().numpy().reshape(shape), reactions=reactions.reshape(shape),
-                        converged=has_converged, history=history)
+                        converged=has_converged, history=history,
+                        axial_forces=None if e0 is None else _axial_forces(model, strain, e0_np))
 
 
 def _max_abs_strain(model, u) -> float:
@@ -731,6 +806,9 @@ def solve(
             method = "gd"
 
     displacement_control = check_control(config, model, method) == "displacement"
+    if check_initial_strain(config, model) is not None and method in ("gd", "full-nr"):
+        raise ValueError(f"initial_strain belongs to the Green-Lagrange Newton solve (solve_nr): method {method!r} is "
+                         "untouched by it.")
     path = [] if displacement_control else None
     _say(f"\n{'Inc':>4} | {'Load Factor':>12} | {'Status':>10}")
     _say("-" * 40)

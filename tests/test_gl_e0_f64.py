@@ -1,0 +1,497 @@
+"""Initial strains in the Green-Lagrange truss solve on the device: pf_gl_state_e0, pf_gl_sens_e0 and pf_kt_diag_f64 called
+through the C ABI and held against the float64 restatement of tests/gl_e0_reference.py (itself pinned by
+tests/test_gl_e0_host.py), then solve_nr / solve / the CLI / the identification on prestressed structures with closed-form
+or restated answers.
+
+Every bound is derived next to its assertion from 2^-53 and operation counts, or is a stated multiple of what the CPU
+restatement reaches itself.  The measured figures are printed in front of every assertion.
+"""
+import ctypes as C
+import json
+import os
+import shutil
+
+import numpy as np
+import pytest
+import torch
+
+import gl_e0_reference as g0
+import gl_reference as gl
+from device_driver import AREA, EA, U53, YOUNG, gl_field, gl_system, system_cache
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+MESHES = ["truss_1", "truss_255", "truss_257", "truss_1025", "chain_1", "chain_257"]
+
+
+@pytest.fixture(scope="module")
+def systems():
+    yield from system_cache(gl_system)
+
+
+def _read_state(S):
+    torch.cuda.synchronize()
+    return (S.strain.cpu().numpy(), S.fe.cpu().numpy().reshape(S.ne, S.dim), S.kt.cpu().numpy().reshape(S.ne, -1))
+
+
+def _refill(S):
+    for t in (S.kt, S.fe, S.strain):
+        t.fill_(7.0)
+
+
+def _state(S, u, e0=None, ea=None):
+    """pf_gl_state_e0 at u (e0 None: pf_gl_state or, with an ea, pf_gl_state_ea) -> (strain, fe, kt) on the host; the
+    buffers are refilled with 7.0 first, so an element the kernel misses shows."""
+    eng, lib, uu = S.eng, S.lib, S.dev(u)
+    ee, zz = (None if ea is None else S.dev(ea)), (None if e0 is None else S.dev(e0))
+    ep = None if ee is None else ee.data_ptr()
+    _refill(S)
+    with eng.on_stream():
+        P, G, s = eng._ref(), C.byref(S.rec), eng._stream()
+        if zz is not None:
+            S.capi.check(lib.pf_gl_state_e0(P, G, ep, zz.data_ptr(), uu.data_ptr(), s), "pf_gl_state_e0")
+        elif ee is not None:
+            S.capi.check(lib.pf_gl_state_ea(P, G, ep, uu.data_ptr(), s), "pf_gl_state_ea")
+        else:
+            S.capi.check(lib.pf_gl_state(P, G, uu.data_ptr(), s), "pf_gl_state")
+    return _read_state(S)
+
+
+def _sens(S, u, a, e0=None, accumulate=0, out=None):
+    eng, uu, aa = S.eng, S.dev(u), S.dev(a)
+    zz = None if e0 is None else S.dev(e0)
+    if out is None:
+        out = torch.full((S.ne,), 7.0, dtype=torch.float64, device=eng.device)
+    with eng.on_stream():
+        P, G, s = eng._ref(), C.byref(S.rec), eng._stream()
+        if zz is None:
+            S.capi.check(S.lib.pf_gl_sens(P, G, uu.data_ptr(), aa.data_ptr(), int(accumulate), out.data_ptr(), s), "pf_gl_sens")
+        else:
+            S.capi.check(S.lib.pf_gl_sens_e0(P, G, zz.data_ptr(), uu.data_ptr(), aa.data_ptr(), int(accumulate), out.data_ptr(),
+                                             s), "pf_gl_sens_e0")
+    torch.cuda.synchronize()
+    return out
+
+
+def _kt_diag(S):
+    eng = S.eng
+    out = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
+    with eng.on_stream():
+        S.capi.check(S.lib.pf_kt_diag_f64(eng._ref(), S.kt.data_ptr(), out.data_ptr(), eng._stream()), "pf_kt_diag_f64")
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def _same_bits(a, b):
+    return all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. pf_gl_state_e0
+# ---------------------------------------------------------------------------------------------------------------------
+def _state_bounds(S, u, ea, e0):
+    """tests/test_gl_f64.py's _state_bounds with the initial strain, in units of 2^-53, for device and reference together:
+      e:    8 e_abs as there, e_abs = (2 |d0|.|du| + |du|.|du|) / (2 l0^2): e0 does not enter the strain that is written.
+      e - e0: e's error and one rounding of the difference per side.  The difference cancels, so its rounding and every
+            relative error behind it is stated in |e| + |e0| (>= |e - e0|), never in |e - e0|.
+      fe_c = (E A (e - e0) / l0) d_c: the 14 relative roundings of that file's chain, on (|e| + |e0|), with the 2 of the
+            difference: 8 e_abs + 16 (|e| + |e0|), times E A |d_c| / l0.
+      B_rc = (E A / l0^3) d_r d_c + delta_rc N / l0: 25 on the first term as there, fe's chain without d_c on the second."""
+    strain, fe, B, t = g0.element_state(S.nodes, S.el, u, ea, e0, S.dim)
+    ea = np.broadcast_to(np.asarray(ea, dtype=np.float64), strain.shape)
+    b_e = 8 * U53 * t["e_abs"]
+    n_l0 = (b_e + 16 * U53 * (np.abs(strain) + np.abs(t["e0"]))) * ea / t["l0"]
+    b_fe = n_l0[:, None] * np.abs(t["d"])
+    k = ea / (t["l02"] * t["l0"])
+    dd = np.abs(t["d"][:, :, None] * t["d"][:, None, :])
+    b_B = 25 * U53 * k[:, None, None] * dd + n_l0[:, None, None] * np.eye(S.dim)
+    if S.dim == 2:
+        pick = lambda M: np.stack([M[:, 0, 0], M[:, 0, 1], M[:, 1, 1]], axis=1)
+    else:
+        pick = lambda M: M[:, 0, 0][:, None]
+    return (strain, b_e), (fe, b_fe), (pick(B), pick(b_B))
+
+
+def _check_state(got, bounds, label):
+    for what, g, (want, bound) in zip(("strain", "fe", "kt"), got, bounds):
+        g = g.reshape(want.shape)
+        assert np.all(np.isfinite(g)), what
+        err = np.abs(g - want)
+        print(f"{label} {what}: worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
+        assert np.all(err <= bound), what
+
+
+@pytest.mark.parametrize("kind", ["large", "tiny"])
+@pytest.mark.parametrize("name", MESHES)
+def test_gl_state_e0_against_the_restatement(systems, name, kind):
+    """Element counts 1, on both sides of the block (255, 257) and on several blocks (1025), 1-D chains of 1 and 257; e0
+    drawn per element from +-1e-2, with the problem's own E*A (null ea) and with E*A drawn per element from [500, 2000].
+    Then the cancelling case, e0 equal to the strain the device itself computed: N is exactly 0.0, so fe is exactly 0.0 and
+    kt is the material part alone (its 25 * 2^-53 bound, nothing for the geometric part)."""
+    S = systems(name)
+    rng = np.random.default_rng(S.ne + 15)
+    u, e0, ea = gl_field(S, kind, rng), rng.uniform(-1e-2, 1e-2, S.ne), rng.uniform(500.0, 2000.0, S.ne)
+    _check_state(_state(S, u, e0), _state_bounds(S, u, EA, e0), f"{name} {kind} e0")
+    _check_state(_state(S, u, e0, ea), _state_bounds(S, u, ea, e0), f"{name} {kind} e0, per-element ea")
+    strain = _state(S, u)[0]
+    got = _state(S, u, strain.copy(), ea)
+    assert got[0].tobytes() == strain.tobytes()                        # the strain that is written stays the total strain
+    assert not got[1].any()
+    t = gl.element_state(S.nodes, S.el, u, ea, S.dim)[3]
+    material = (ea / (t["l02"] * t["l0"]))[:, None, None] * (t["d"][:, :, None] * t["d"][:, None, :])
+    pick = (lambda M: np.stack([M[:, 0, 0], M[:, 0, 1], M[:, 1, 1]], axis=1)) if S.dim == 2 else (lambda M: M[:, 0, 0][:, None])
+    err, bound = np.abs(got[2] - pick(material)), 25 * U53 * np.abs(pick(material))
+    print(f"{name} {kind} cancelling: kt against the material part, worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
+    assert np.all(err <= bound)
+
+
+@pytest.mark.parametrize("name", MESHES)
+def test_zero_e0_and_repeated_calls_give_the_same_bits(systems, name):
+    """An all-zero e0 is pf_gl_state (null ea) and pf_gl_state_ea (an ea) to the bit, a repeated call repeats its bits;
+    the same for pf_gl_sens_e0 against pf_gl_sens, and an accumulated call is the sum of two single ones to the bit (the
+    term is rounded first)."""
+    S = systems(name)
+    rng = np.random.default_rng(S.ne + 16)
+    zero = np.zeros(S.ne)
+    for kind in ("large", "tiny"):
+        u, e0, ea = gl_field(S, kind, rng), rng.uniform(-1e-2, 1e-2, S.ne), rng.uniform(500.0, 2000.0, S.ne)
+        assert _same_bits(_state(S, u, zero), _state(S, u))
+        assert _same_bits(_state(S, u, zero, ea), _state(S, u, None, ea))
+        first = _state(S, u, e0, ea)
+        assert _same_bits(_state(S, u, e0, ea), first) and not _same_bits(first, _state(S, u, None, ea))
+        a1, a2 = rng.standard_normal(S.n), rng.standard_normal(S.n) * np.exp2(rng.uniform(-8.0, 8.0, S.n))
+        plain = _sens(S, u, a1).cpu().numpy()
+        assert _sens(S, u, a1, zero).cpu().numpy().tobytes() == plain.tobytes()
+        one, two = _sens(S, u, a1, e0).cpu().numpy(), _sens(S, u, a2, e0).cpu().numpy()
+        assert _sens(S, u, a1, e0).cpu().numpy().tobytes() == one.tobytes() and one.tobytes() != plain.tobytes()
+        acc = _sens(S, u, a2, e0, accumulate=1, out=_sens(S, u, a1, e0)).cpu().numpy()
+        assert acc.tobytes() == (one + two).tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. pf_gl_sens_e0
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", MESHES)
+def test_gl_sens_e0_against_the_restatement(systems, name):
+    """s = -((e - e0) / l0) sum_c d_c (a_j,c - a_i,c).  tests/test_identify_f64.py counts 25 * 2^-53 of
+    (e_abs / l0) sum_c |d_c| (|a_j,c| + |a_i,c|) for device and reference together; the difference e - e0 adds one rounding
+    per side, and the unit takes |e0| next to e_abs because the difference cancels (g0.sensitivity_scale): 27."""
+    S = systems(name)
+    rng = np.random.default_rng(S.ne + 17)
+    for kind in ("large", "tiny"):
+        u, e0, a = gl_field(S, kind, rng), rng.uniform(-1e-2, 1e-2, S.ne), rng.standard_normal(S.n)
+        got = _sens(S, u, a, e0).cpu().numpy()
+        want = g0.element_sensitivity(S.nodes, S.el, u, a, e0, S.dim)
+        bound = 27 * U53 * g0.sensitivity_scale(S.nodes, S.el, u, a, e0, S.dim)
+        err = np.abs(got - want)
+        print(f"{name} {kind}: sensitivity worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
+        assert np.all(np.isfinite(got)) and np.all(err <= bound)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. pf_kt_diag_f64
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", MESHES)
+def test_kt_diag_is_the_sequential_sum_of_the_blocks(systems, name):
+    """Per dof the device's own kt diagonal entries of the node's elements, added one after the other in ascending
+    incidence order (the plan's adjacency) from 0.0: the same bits.  Fixed dofs get 0.0."""
+    S = systems(name)
+    rng = np.random.default_rng(S.ne + 18)
+    kt = _state(S, gl_field(S, "large", rng), rng.uniform(-1e-2, 1e-2, S.ne))[2]
+    got = _kt_diag(S)
+    plan = S.eng.plan
+    adj_ptr, adj = np.asarray(plan.adj_ptr), np.asarray(plan.adj)
+    want = np.zeros(S.n)
+    for node in range(S.n_nodes):
+        for c in range(S.dim):
+            acc = 0.0
+            for code in adj[adj_ptr[node]:adj_ptr[node + 1]]:
+                acc = acc + float(kt[code >> 1, 2 * c if S.dim == 2 else 0])
+            want[node * S.dim + c] = acc
+    want[S.mask] = 0.0
+    assert got.tobytes() == want.tobytes()
+    assert np.all(got[S.mask] == 0.0) and np.all(got[S.free] != 7.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. argument errors
+# ---------------------------------------------------------------------------------------------------------------------
+def test_bad_arguments_are_argument_errors(systems):
+    S = systems("truss_257")
+    eng, lib, capi = S.eng, S.lib, S.capi
+    u, a, ea, e0 = S.dev(np.ones(S.n)), S.dev(np.ones(S.n)), S.dev(np.full(S.ne, EA)), S.dev(np.zeros(S.ne))
+    out = torch.full((S.ne,), 7.0, dtype=torch.float64, device=eng.device)
+    dg = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
+    _refill(S)
+    s, P, G = eng._stream(), eng._ref(), C.byref(S.rec)
+    up, ap, ep, zp, op, dp, kp = (t.data_ptr() for t in (u, a, ea, e0, out, dg, S.kt))
+
+    def problem(**mesh):
+        Q = capi.PfProblem.from_buffer_copy(eng.P)
+        for key, val in mesh.items():
+            setattr(Q.mesh, key, val)
+        return C.byref(Q)
+
+    def record(**kw):
+        R = capi.PfGl.from_buffer_copy(S.rec)
+        for key, val in kw.items():
+            setattr(R, key, val)
+        return C.byref(R)
+
+    calls = {
+        "pf_gl_state_e0": [lambda: lib.pf_gl_state_e0(None, G, ep, zp, up, s), lambda: lib.pf_gl_state_e0(P, None, ep, zp, up, s),
+                           lambda: lib.pf_gl_state_e0(P, G, ep, None, up, s), lambda: lib.pf_gl_state_e0(P, G, None, None, up, s),
+                           lambda: lib.pf_gl_state_e0(P, G, ep, zp, None, s),
+                           lambda: lib.pf_gl_state_e0(problem(dim=3), G, ep, zp, up, s),
+                           lambda: lib.pf_gl_state_e0(problem(n_elems=-1), G, ep, zp, up, s),
+                           lambda: lib.pf_gl_state_e0(P, record(d0=None), ep, zp, up, s),
+                           lambda: lib.pf_gl_state_e0(P, record(kt=None), ep, zp, up, s),
+                           lambda: lib.pf_gl_state_e0(P, record(fe=None), None, zp, up, s),
+                           lambda: lib.pf_gl_state_e0(P, record(strain=None), None, zp, up, s)],
+        "pf_gl_sens_e0": [lambda: lib.pf_gl_sens_e0(None, G, zp, up, ap, 0, op, s), lambda: lib.pf_gl_sens_e0(P, None, zp, up, ap, 0, op, s),
+                          lambda: lib.pf_gl_sens_e0(P, G, None, up, ap, 0, op, s), lambda: lib.pf_gl_sens_e0(P, G, zp, None, ap, 0, op, s),
+                          lambda: lib.pf_gl_sens_e0(P, G, zp, up, None, 0, op, s), lambda: lib.pf_gl_sens_e0(P, G, zp, up, ap, 0, None, s),
+                          lambda: lib.pf_gl_sens_e0(P, G, zp, up, ap, 2, op, s), lambda: lib.pf_gl_sens_e0(P, G, zp, up, ap, -1, op, s),
+                          lambda: lib.pf_gl_sens_e0(problem(dim=3), G, zp, up, ap, 0, op, s),
+                          lambda: lib.pf_gl_sens_e0(problem(n_elems=-1), G, zp, up, ap, 0, op, s),
+                          lambda: lib.pf_gl_sens_e0(P, record(d0=None), zp, up, ap, 0, op, s)],
+        "pf_kt_diag_f64": [lambda: lib.pf_kt_diag_f64(None, kp, dp, s), lambda: lib.pf_kt_diag_f64(P, None, dp, s),
+                           lambda: lib.pf_kt_diag_f64(P, kp, None, s)],
+    }
+    for name, group in calls.items():
+        for i, call in enumerate(group):
+            assert call() == capi.PF_ERR_ARG, (name, i)
+            assert lib.pf_last_error().decode().startswith(name + ":"), (name, i, lib.pf_last_error())
+    torch.cuda.synchronize()
+    for t in (S.kt, S.fe, S.strain, out, dg):                            # nothing was enqueued
+        assert bool((t == 7.0).all())
+    # a null ea is the problem's own E*A, not an error
+    assert lib.pf_gl_state_e0(P, G, None, zp, up, s) == capi.PF_OK
+    torch.cuda.synchronize()
+    # the engine checks the lengths, and kt_diag needs a state
+    with pytest.raises(ValueError, match="e0 has"):
+        eng.gl_state(u, None, e0[:-1])
+    with pytest.raises(ValueError, match="e0 has"):
+        eng.gl_sensitivity(u, a, e0=e0[:-1])
+    fresh = gl_system("truss_1")
+    with pytest.raises(RuntimeError, match="kt_diag: no Green-Lagrange state yet"):
+        fresh.eng.kt_diag()
+    fresh.eng.gl_state(fresh.dev(np.zeros(fresh.n)), None, fresh.dev(np.full(1, -1e-3)))
+    d = fresh.eng.kt_diag().cpu().numpy()
+    assert d.shape == (fresh.n,) and np.all(d[fresh.mask] == 0.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. the taut string: solve_nr, the CLI, axial_forces
+# ---------------------------------------------------------------------------------------------------------------------
+def _model(nodes, el, loads, fixed, dim=2):
+    from pinn_fem_amd.fem.model import FEMModel, Material
+    return FEMModel(nodes=nodes, elements=el, material=Material(YOUNG, AREA, 1.0), loads=loads, fixed_dofs=fixed, dimension=dim)
+
+
+def _config(**kw):
+    from pinn_fem_amd.fem.solver import SolverConfig
+    base = dict(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange")
+    base.update(kw)
+    return SolverConfig(**base)
+
+
+def _check_taut_string(ts, p, u, reactions, axial, label):
+    """|P(w)/P - 1| <= 32 * 2^-53.  The two free dofs do not couple, so CG is exact and a converged Newton iteration leaves
+    the round-off of one residual: about 10 roundings in the device's f_int, 3 for rounding u + du (P grows at most as
+    w^3), 6 in the closed form: 19, stated as 32.  N = E A (e - e0) from the device's strain (e_abs = e here, opposite
+    signs: no cancellation): 8 + 2 roundings and the closed form's 4, stated as 16, on E A (|e| + |e0|)."""
+    w = u[3]
+    print(f"{label}: w = {w:.15f}, P(w)/P - 1 = {ts.load(w) / p - 1:.3e}, ux = {u[2]:.1e}, N = {axial}")
+    assert w > 0.0 and u[2] == 0.0 and not u[[0, 1, 4, 5]].any()
+    assert abs(ts.load(w) / p - 1.0) <= 32 * U53
+    assert np.all(np.abs(axial - ts.force(w)) <= 16 * U53 * EA * (ts.strain(w) + abs(ts.e0)))
+    R = reactions.reshape(-1, 2)
+    assert np.all(R[1] == 0.0) and abs(R[[0, 2], 1].sum() + p) <= 32 * U53 * p and abs(R[[0, 2], 0].sum()) <= 32 * U53 * ts.force(w)
+
+
+@pytest.mark.parametrize("p", [0.01, 1.0, 20.0])
+def test_solve_nr_taut_string(p):
+    """The structure the unstrained solve refuses before its first iteration: the transverse dof has no linear stiffness."""
+    from pinn_fem_amd.fem.solver import solve_nr
+    ts = g0.TautString(ea=EA, e0=-1e-3)
+    model = _model(ts.nodes, ts.el, ts.loads(p), ts.fixed)
+    with pytest.raises(RuntimeError, match="Tangent stiffness became singular"):
+        solve_nr(model, _config(), 1.0)
+    res = solve_nr(model, _config(initial_strain=ts.e0), 1.0)
+    _, it_ref, _ = g0.newton(ts.nodes, ts.el, ts.loads(p), ts.fixed, EA, ts.e0, 2, tol=1e-10)
+    print(f"taut string P = {p}: {res.history[-1]}, restatement {it_ref} iterations")
+    assert res.converged and 3 <= res.history[-1]["iterations"] <= 15 and abs(res.history[-1]["iterations"] - it_ref) <= 1
+    u = res.displacements.reshape(-1)
+    _check_taut_string(ts, p, u, res.reactions, res.axial_forces, f"taut string P = {p}")
+    assert abs(res.history[-1]["max_strain"] - ts.strain(u[3])) <= 8 * U53 * ts.strain(u[3])
+    # per-element values: the same numbers; without an initial strain the result carries no axial forces
+    res2 = solve_nr(model, _config(initial_strain=[ts.e0, ts.e0]), 1.0)
+    assert res2.displacements.tobytes() == res.displacements.tobytes() and res2.axial_forces.tobytes() == res.axial_forces.tobytes()
+
+
+def test_cli_taut_string(tmp_path):
+    from pinn_fem_amd.cli import generic as g
+    from pinn_fem_amd.fem.solver import solve_nr
+    shutil.copy(os.path.join(HERE, "nl_inputs", "taut_string.json"), tmp_path / "taut_string.json")
+    g.main(["generic.py", str(tmp_path / "taut_string.json")])
+    out = json.loads((tmp_path / "taut_string.res.json").read_text())
+    ts = g0.TautString(ea=EA, e0=-1e-3)
+    want = solve_nr(_model(ts.nodes, ts.el, ts.loads(1.0), ts.fixed), _config(initial_strain=ts.e0), 1.0)
+    assert out["converged"] and np.array_equal(np.array(out["displacements"]), want.displacements.reshape(-1))
+    assert np.array_equal(np.array(out["axial_forces"]), want.axial_forces) and len(out["axial_forces"]) == 2
+    _check_taut_string(ts, 1.0, np.array(out["displacements"]), np.array(out["reactions"]), np.array(out["axial_forces"]), "CLI")
+    # the existing input gives its former keys: no axial forces without an initial strain
+    shutil.copy(os.path.join(HERE, "nl_inputs", "two_bar_green_lagrange.json"), tmp_path / "two_bar.json")
+    g.main(["generic.py", str(tmp_path / "two_bar.json")])
+    assert set(json.loads((tmp_path / "two_bar.res.json").read_text())) == {"success", "converged", "iterations", "history",
+                                                                             "displacements", "reactions"}
+
+
+def test_slack_string_is_refused():
+    """e0 = +1e-2 and no load: both bars are compressed at u = 0 and the transverse dof's tangent is 2 N / l0 = -20."""
+    from pinn_fem_amd.fem.solver import solve_nr
+    ts = g0.TautString(ea=EA, e0=1e-2)
+    with pytest.raises(RuntimeError, match="not positive definite") as info:
+        solve_nr(_model(ts.nodes, ts.el, ts.loads(0.0), ts.fixed), _config(initial_strain=ts.e0), 1.0)
+    assert "free dof 3" in str(info.value)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. the 256-element cable
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def cable_reference():
+    nodes, el, loads, fixed = g0.cable_chain(256)
+    u_ref, it_ref, ok = g0.newton(nodes, el, loads, fixed, EA, -1e-2, 2, tol=1e-10)
+    u_cg, it_cg, ok_cg = g0.newton(nodes, el, loads, fixed, EA, -1e-2, 2, tol=1e-10, linear_solve=gl.jacobi_cg(1e-13))
+    assert ok and ok_cg and it_ref == it_cg
+    return (nodes, el, loads, fixed), u_ref, it_ref, float(np.max(np.abs(u_cg - u_ref)) / np.max(np.abs(u_ref)))
+
+
+@pytest.mark.parametrize("pre", ["jacobi", "two-level-updated"])
+def test_solve_nr_cable_chain(cable_reference, pre):
+    """256 collinear unit elements, e0 = -1e-2, equal nodal loads, from u = 0: against the restatement's sparse direct
+    solve.  Tolerance: the distance of the restatement's own Jacobi-CG Newton run (rtol 1e-13) to that direct solve, times
+    10 for the different summation order."""
+    from pinn_fem_amd.fem.solver import solve_nr
+    (nodes, el, loads, fixed), u_ref, it_ref, err_ref = cable_reference
+    model = _model(nodes, el, loads, fixed)
+    res = solve_nr(model, _config(initial_strain=-1e-2, nr_preconditioner=pre), 1.0)
+    u = res.displacements.reshape(-1)
+    err = float(np.max(np.abs(u - u_ref)) / np.max(np.abs(u_ref)))
+    eng = model._pf_engine_cache[1]
+    print(f"cable {pre}: Newton {res.history[-1]['iterations']:.0f} (restatement {it_ref}), CG iterations {eng.pcg_iterations}, "
+          f"error {err:.3e}, restatement's CG run {err_ref:.3e}, allowed {10 * err_ref:.3e}")
+    assert res.converged and res.history[-1]["iterations"] == it_ref
+    n_ref = g0.axial_forces(nodes, el, u_ref, EA, -1e-2, 2)
+    assert res.axial_forces.shape == (256,) and np.all(res.axial_forces > 0.0)
+    assert np.max(np.abs(res.axial_forces - n_ref)) <= 1e-9 * np.max(n_ref)     # (a sanity check; u is held below)
+    assert err <= 10 * err_ref
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. displacement control through the limit point of the prestressed two-bar truss
+# ---------------------------------------------------------------------------------------------------------------------
+def test_solve_prestressed_two_bar_path():
+    """P(w) = E A ((w^2 - 2 h w) / (2 l0^2) - e0) (w - h) 2 / l0 along eleven steps of 0.2 h, through the limit point at
+    w = 0.484 h and the snap-through: |lam P_lim / P(w) - 1| <= 1e-9 (absolute at w = h, where P = 0), the allowance of
+    tests/test_dc_f64.py's unstrained path."""
+    from pinn_fem_amd.fem.solver import solve
+    tb = g0.PrestressedTwoBar(ea=EA, e0=-1e-3)
+    model = _model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
+    cfg = _config(nr_control="displacement", method="nr", nr_control_dof=5, nr_control_displacement=-2.2 * tb.h, n_increments=11,
+                  initial_strain=tb.e0)
+    res = solve(model, cfg)
+    assert res.converged and res.path is not None and len(res.path) == 11
+    lam_seen = []
+    for k, rec in enumerate(res.path, start=1):
+        w = -rec["control_displacement"]
+        want = tb.load(w) / tb.p_lim
+        lam_seen.append(rec["load_factor"])
+        print(f"prestressed two-bar path {k}: w = {w:.3f}, lam = {rec['load_factor']:+.12e}, closed form {want:+.12e}, "
+              f"iterations {rec['iterations']}")
+        assert abs(w - k * 0.2 * tb.h) <= 1e-15
+        if abs(want) > 0.1:
+            assert abs(rec["load_factor"] / want - 1.0) <= 1e-9, k
+        else:
+            assert k == 5 and abs(rec["load_factor"] - want) <= 1e-9, k                # w = h: P = 0
+    assert 0.4 < tb.w_lim < 0.6 and lam_seen[0] < lam_seen[1] > lam_seen[2] > lam_seen[3]   # the limit point: step 3
+    assert min(lam_seen) < 0.0 < lam_seen[-1]                                           # and the path snaps through
+    w = 2.2 * tb.h
+    assert np.all(np.abs(res.axial_forces - EA * (tb.strain(w) - tb.e0)) <= 1e-9 * EA * abs(tb.e0))
+    # the unstrained path on the same model is another one
+    plain = solve(model, _config(nr_control="displacement", method="nr", nr_control_dof=5, nr_control_displacement=-2.2 * tb.h,
+                                 n_increments=11))
+    assert plain.axial_forces is None and abs(plain.path[2]["load_factor"] - lam_seen[2]) > 0.1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. identification on the prestressed girder
+# ---------------------------------------------------------------------------------------------------------------------
+def _warren_model(case):
+    return _model(case.nodes, case.el, case.loads, case.fixed)
+
+
+def test_gradient_and_jacobian_against_the_reference():
+    """misfit_and_gradient and residuals_and_jacobian at all factors 1 on g0.warren_case() (e0 in +-1e-3), with both
+    preconditioners.  Allowed distance, the rule of tests/test_identify_f64.py and tests/test_identify_gn_f64.py: ten times
+    the distance the restatement itself shows between its direct-solve result and its own result with gl.jacobi_cg at
+    rtol 1e-13, both computed here."""
+    from pinn_fem_amd.fem.identify import misfit_and_gradient, residuals_and_jacobian
+    case = g0.warren_case()
+    q = np.zeros(4)
+    cg = dict(linear_solve=gl.jacobi_cg(1e-13))
+    J_ref, g_ref = case.objective(q)
+    J_cg, g_cg = case.objective(q, **cg)
+    rho_ref, A_ref, _, its_ref = g0.residuals_and_jacobian(case, q, case.e0)
+    rho_cg, A_cg, _, _ = g0.residuals_and_jacobian(case, q, case.e0, **cg)
+    tol_J, tol_g = 10 * abs(J_cg - J_ref), 10 * np.max(np.abs(g_cg - g_ref))
+    tol_rho, tol_A = 10 * np.max(np.abs(rho_cg - rho_ref)), 10 * np.max(np.abs(A_cg - A_ref))
+    print(f"reference: J = {J_ref:.15e}, Newton iterations {its_ref}, ten times direct against CG: {tol_J:.2e} (J), "
+          f"{tol_g:.2e} (dJ/dq), {tol_rho:.2e} (rho), {tol_A:.2e} (A)")
+    model = _warren_model(case)
+    ea = case.ea(q)
+    for pre in ("jacobi", "two-level-updated"):
+        cfg = _config(nr_preconditioner=pre, initial_strain=case.e0)
+        J, g_ea, states, counters = misfit_and_gradient(model, cfg, case.levels, ea)
+        eng = model._pf_engine_cache[1]
+        g = eng.group_sum(g_ea, torch.from_numpy(ea).to(eng.device), case.groups).cpu().numpy()
+        rho, A, _, c2 = residuals_and_jacobian(model, cfg, case.levels, ea, case.groups)
+        print(f"{pre}: J - J_ref = {J - J_ref:.2e}, dJ/dq distance {np.max(np.abs(g - g_ref)):.2e}, rho distance "
+              f"{np.max(np.abs(rho - rho_ref)):.2e}, A distance {np.max(np.abs(A - A_ref)):.2e}, counters {counters} {c2}")
+        assert counters["newton_iterations"] == c2["newton_iterations"] == sum(its_ref)
+        assert abs(J - J_ref) <= tol_J and np.max(np.abs(g - g_ref)) <= tol_g, pre
+        assert np.max(np.abs(rho - rho_ref)) <= tol_rho and np.max(np.abs(A - A_ref)) <= tol_A, pre
+    # the prestress is really in both: without it J and the gradient are others by far more than the allowance
+    J0, g0_ea, _, _ = misfit_and_gradient(model, _config(), case.levels, ea)
+    assert abs(J0 - J_ref) > 1e3 * tol_J
+
+
+def test_gauss_newton_needs_the_prestress():
+    """identify_nr(method="gauss-newton", misfit_tolerance=1e-15) from all factors 1 on data generated with the prestress
+    (e0 in +-1e-3, the value at which the restatement shows the gap): with config.initial_strain it takes the restatement's
+    evaluation count and recovers the factors to the restatement's own error; with initial_strain None on the same data it
+    misses them by more than 100 times that error.  "To the restatement's own error": that error (3.9e-10) is what Newton
+    states converged to 1e-10 leave in the factors at the stop J <= 1e-15; its size, not its value, is a property of the
+    method, and the device's CG-solved states leave another of that size.  So the device's error is held to ten times
+    the restatement's, the margin the cable test takes for a different summation order."""
+    from pinn_fem_amd.fem import identify_nr
+    case, run = g0.reference_run(True)
+    _, blind_ref = g0.reference_run(False)
+    err_ref = float(np.max(np.abs(run["factors"] - case.factors)))
+    assert float(np.max(np.abs(blind_ref["factors"] - case.factors))) > 100 * err_ref        # the restatement shows the gap
+    model = _warren_model(case)
+    res = identify_nr(model, _config(initial_strain=case.e0), case.levels, groups=case.groups, method="gauss-newton",
+                      misfit_tolerance=1e-15)
+    err = float(np.max(np.abs(res.factors - case.factors)))
+    print(f"with the prestress: {res.evaluations} evaluations (restatement {run['evaluations']}), stop {res.stop!r}, misfit "
+          f"{res.misfit:.2e}, error {err:.3e} (restatement {err_ref:.3e}), factors {res.factors}")
+    assert res.stop == "misfit" and res.converged and res.evaluations == run["evaluations"]
+    assert err <= 10 * err_ref
+    blind = identify_nr(model, _config(), case.levels, groups=case.groups, method="gauss-newton", misfit_tolerance=1e-15)
+    err_blind = float(np.max(np.abs(blind.factors - case.factors)))
+    print(f"without: {blind.evaluations} evaluations, stop {blind.stop!r}, misfit {blind.misfit:.2e}, error {err_blind:.3e} "
+          f"(restatement {float(np.max(np.abs(blind_ref['factors'] - case.factors))):.3e})")
+    assert err_blind > 100 * err_ref and blind.stop != "misfit"

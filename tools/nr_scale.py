@@ -3,14 +3,15 @@
 smaller ones also the oracle's dense float64 restatement of the reference (np.linalg.solve) on the host.
 
     nr_scale.py [--preconditioner jacobi|two-level|two-level-updated] [--aggregates N]
-                [--kinematics linear|green-lagrange] [panels ...]
+                [--kinematics linear|green-lagrange] [--initial-strain X] [panels ...]
 
 The timed solve includes the two-level preconditioner's setup (coarse space, Z^T K Z, its inverse).  With
 --kinematics green-lagrange the same girders run the large-displacement element (jacobi or two-level-updated; the dense
 comparison is of the linear problem and is left out).  two-level-updated refreshes its coarse space at every Newton
 iteration: the row reports the seconds spent there (refresh_seconds) and their parts: host columns, setup launch with
-the read-back, Cholesky and inverse, upload."""
-import argparse, json, os, sys, time
+the read-back, Cholesky and inverse, upload.  --initial-strain X (green-lagrange only) gives every element the initial
+strain X (X < 0: a pretension; SolverConfig.initial_strain)."""
+import argparse, json, os, re, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,11 +21,15 @@ from pinn_fem_amd.fem.solver import SolverConfig, solve_nr
 from pinn_fem_amd.plan import warren_mesh
 import torch
 ap = argparse.ArgumentParser()
+ap._negative_number_matcher = re.compile(r"^-(\d+\.?\d*|\.\d+)([eE][-+]?\d+)?$")    # -1e-3 is a value, not an option
 ap.add_argument("--preconditioner", default="jacobi", choices=["jacobi", "two-level", "two-level-updated"])
 ap.add_argument("--aggregates", type=int, default=None)
 ap.add_argument("--kinematics", default="linear", choices=["linear", "green-lagrange"])
+ap.add_argument("--initial-strain", type=float, default=None)
 ap.add_argument("panels", nargs="*", type=int)
 args = ap.parse_args()
+if args.initial_strain is not None and args.kinematics != "green-lagrange":
+    ap.error("--initial-strain goes with --kinematics green-lagrange only")
 if args.preconditioner == "two-level-updated" and args.kinematics != "green-lagrange":
     ap.error("--preconditioner two-level-updated goes with --kinematics green-lagrange only")
 rows = []
@@ -38,7 +43,8 @@ for panels in args.panels or [100, 1000, 5000]:
     green_lagrange = args.kinematics == "green-lagrange"
     lam = (panels / 100.0) * 384.0 * 0.5 / (5.0 * float(panels) ** 4) if green_lagrange else 1.0
     cfg = SolverConfig(max_iterations=25 if green_lagrange else 10, tolerance=1e-10,
-                       nr_preconditioner=args.preconditioner, nr_aggregates=args.aggregates, kinematics=args.kinematics)
+                       nr_preconditioner=args.preconditioner, nr_aggregates=args.aggregates, kinematics=args.kinematics,
+                       initial_strain=args.initial_strain)
     if panels <= 100:                                        # warm-up (library load, allocator) on a model of its own
         solve_nr(FEMModel(nodes=nodes, elements=el, material=Material(2.0, 0.5, 1.0), loads=loads, fixed_dofs=fixed, dimension=2),
                  cfg, lam)
@@ -50,6 +56,8 @@ for panels in args.panels or [100, 1000, 5000]:
            "kinematics": args.kinematics, "load_factor": lam,
            "hip_seconds": dt, "converged": bool(res.converged), "nr_iterations": res.history[-1]["iterations"],
            "cg_iterations": eng.pcg_iterations}
+    if args.initial_strain is not None:
+        row["initial_strain"] = args.initial_strain
     if args.preconditioner == "two-level-updated":
         row["refresh_seconds"] = eng.coarse_refresh_seconds
         row["refresh_parts"] = dict(eng.coarse_refresh_parts)
