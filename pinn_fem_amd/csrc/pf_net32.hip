@@ -266,22 +266,23 @@ __device__ __forceinline__ void task_fetch_b(TaskIn<IN - 1>& t, const pf_problem
   load_vec<DIM>(P.g_f, t.nn.y, t.gj);
 }
 
-// Path form: which element beside its own a lane of a task reads (lane 0: e-1, lane 63: e+1; -1: none), and whether it
-// needs f_ext / dof flags at its j node (lane 63, and the mesh's last element, whose j node no other element owns)
-__device__ __forceinline__ int path_edge_elem(int e, int n, int lane) {
-  if (lane == 0 && e > 0) return e - 1;
-  if (lane == 63 && e < n - 1) return e + 1;
-  return -1;
-}
+// Path form: the lanes of a task that read more than their own element (lane 0: element e-1, lane 63: e+1, and the mesh's
+// last element: f_ext / dof flags at its j node, which no other element owns), and the element beside its own such a lane
+// reads.  At the path's two ends that is the lane's own element again: a valid address, and path_residual drops what comes
+// of it (`first`, `last`).  ONE predicate for everything these lanes load: every lane of the wave pays for each block's
+// exec-mask save and branch.  (lane == 0 || lane == 63 || e >= n - 1, 0 <= e <= n - 1, written as one minimum: the
+// compiler turns the three-term form, with | as well as with ||, into a branch per term.)
+__device__ __forceinline__ bool path_edge_lane(int e, int n, int lane) { return min(min(lane, 63 - lane), n - 1 - e) == 0; }
+__device__ __forceinline__ int path_edge_elem(int e, int n, int lane) { return min(max(e + (lane == 0 ? -1 : 1), 0), n - 1); }
 // the far node of that element (lane 0: i(e-1), lane 63: j(e+1)): fetched two tasks ahead with the element's own node ids
-__device__ __forceinline__ int path_edge_node(const pf_problem& P, int e, int n, int lane) {
-  const int ee = path_edge_elem(e, n, lane);
-  int nd = 0;
-  if (ee >= 0) nd = P.mesh.conn[2 * ee + (lane == 0 ? 0 : 1)];
+__device__ __forceinline__ int path_edge_node(const pf_problem& P, int e, int n, int lane, int prev) {
+  int nd = prev;
+  if (path_edge_lane(e, n, lane)) nd = P.mesh.conn[2 * path_edge_elem(e, n, lane) + (lane == 0 ? 0 : 1)];
   return nd;
 }
 // the nodal part of a path task's inputs: no gather of g_f (the task forms it), but f_ext and the dof flags at the i node,
-// and the edge lanes' extras (loads under the lanes' own predicate: two lanes of 64).  The element's own stiffness record is
+// and the edge lanes' extras (loads under the lanes' own predicate, path_edge_lane: two lanes of 64; every other lane keeps
+// what t.edge held, so the caller initialises it once).  The element's own stiffness record is
 // not fetched: the task forms it from the properties and the geometry it holds anyway, by the float operations the forward
 // launch wrote it with (k_net32_forward2; the kernel runs at its register budget, and a record is three registers held over
 // both tiles).
@@ -292,33 +293,29 @@ __device__ __forceinline__ void task_fetch_b_path(TaskIn<IN - 1>& t, const pf_pr
   load_vec<DIM>(P.u, t.nn.y, t.uj);
   load_vec<DIM>(P.mesh.f_ext, t.nn.x, t.fxi);
   t.fli = load_node_flags<DIM>(P.mesh.dof_flags, t.nn.x);
-  t.edge.k = ElemK{0.f, 0.f, 0.f};
-  t.edge.u[0] = t.edge.u[1] = 0.f;
-  t.edge.fx[0] = t.edge.fx[1] = 0.f;
-  t.edge.fl = 0u;
-  const int ee = path_edge_elem(e, n, lane);
-  if (ee >= 0) {
-    t.edge.k = load_k_record<DIM>(P.elem_k, ee);
+  if (path_edge_lane(e, n, lane)) {
+    t.edge.k = load_k_record<DIM>(P.elem_k, path_edge_elem(e, n, lane));
     load_vec<DIM>(P.u, edge_node, t.edge.u);
-  }
-  if (lane == 63 || e >= n - 1) {
-    load_vec<DIM>(P.mesh.f_ext, t.nn.y, t.edge.fx);
+    load_vec<DIM>(P.mesh.f_ext, t.nn.y, t.edge.fx);          // (lane 0 does not need these two unless it is the last element)
     t.edge.fl = load_node_flags<DIM>(P.mesh.dof_flags, t.nn.y);
   }
 }
 
-// dL/d(E*A) from the fetched operands: the arithmetic of pf_elem_gea (pf_common.h), op for op
+// dL/d(E*A) from the fetched operands: the arithmetic of pf_elem_gea (pf_common.h), with ONE evaluation of the unit rows:
+// the rows of end 1 are those of end 0 negated (ke_rows_times: every product's sign flipped, both fe_modes), so -pu0 is
+// what the second evaluation returns, bit for bit, except that an exact zero has the other sign.  A zero contributes
+// gj * (+-0) = +-0 to gs, which changes gs only where it is itself a zero: g_ea can differ from pf_elem_gea's in the sign of
+// an exact zero and in nothing else.
 template <int DIM>
 __device__ __forceinline__ float task_gea(const TaskIn<DIM>& t, const float* gi, const float* gj, int fe_mode) {
-  float pu0[2], pu1[2];
+  float pu0[2];
   const ElemK k1 = elem_k_unit<DIM>(t.g);
   ke_rows_times<DIM>(k1, 0, t.ui, t.uj, pu0, fe_mode);
-  ke_rows_times<DIM>(k1, 1, t.ui, t.uj, pu1, fe_mode);
   float gs = 0.f;
 #pragma unroll
   for (int c = 0; c < DIM; ++c) gs = fmaf(gi[c], pu0[c], gs);
 #pragma unroll
-  for (int c = 0; c < DIM; ++c) gs = fmaf(gj[c], pu1[c], gs);
+  for (int c = 0; c < DIM; ++c) gs = fmaf(gj[c], -pu0[c], gs);
   return gs / t.g.l0;
 }
 
@@ -1310,12 +1307,15 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     task_fetch_a<IN, GEA>(nxt, P, onet, other, mine, e0);
     if (GEA) nn_ahead = reinterpret_cast<const int2*>(P.mesh.conn)[e1];
     if constexpr (PATH) {
-      en_next = path_edge_node(P, e0, n, lane);
-      en_ahead = path_edge_node(P, e1, n, lane);
+      en_next = path_edge_node(P, e0, n, lane, 0);
+      en_ahead = path_edge_node(P, e1, n, lane, 0);
     }
   }
   if constexpr (MODE != 2) __syncthreads();      // (image, constant blocks and scratch are in place)
-  if constexpr (PATH) task_fetch_b_path<IN>(nxt, P, min(task_base(0) + lane, n - 1), n, lane, en_next);
+  if constexpr (PATH) {
+    nxt.edge = PathEdge<DIM>{ElemK{0.f, 0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, 0u};      // (only the edge lanes ever write it)
+    task_fetch_b_path<IN>(nxt, P, min(task_base(0) + lane, n - 1), n, lane, en_next);
+  }
   else task_fetch_b<IN, GEA>(nxt, P);
 
   // block-uniform scalars: keep them in SGPRs (the kernel runs at its register budget)
@@ -1338,7 +1338,6 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     const int e = base + lane;
     const bool live = e < n;
     const TaskIn<DIM> cur = nxt;
-    const bool more = k + 1 < n_mine;
     // ---- per-element scalars: one element per lane ----------------------------------------------------------
     // softplus'(z) = sigmoid(z) = 1 - exp(-softplus(z)) from the forward's stored value (= softplus(z) * scale), so the
     // output unit need not be recomputed (torch: z > 20 ? 1 : e^z / (e^z + 1), the same number to float round-off)
@@ -1407,18 +1406,23 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     both_tiles(cur.x[1], xa0, xa1);
     both_tiles(cur.x[2], xb0, xb1);
     const float lam_in = cur.x[0];
-    if (more) {
+    {
       // The next task's inputs leave HERE, behind the last use of this task's record (everything above consumed it: the
       // tiles below work on derived values only), so the new values can land in the registers the old ones held — issued
       // at the top of the task they needed a second set and a 19-register copy per task.  Its node ids are already here
       // (fetched two tasks ahead), so its nodal gathers leave in the same breath; the ids of the task after it start now.
-      task_fetch_a<IN, GEA>(nxt, P, onet, other, mine, min(task_base(k + 1) + lane, n - 1), false);
+      // In EVERY task, the wave's last one included: past its last task task_base names the mesh's last element, a set of
+      // valid loads nobody reads.  Under `if (k + 1 < n_mine)` the loaded registers met their old values at the end of
+      // the block, and the compiler placed the copies there behind s_waitcnt vmcnt(0): every task waited out the loads it
+      // had just issued, the prefetch hid nothing.  Now the waits sit at the first uses, at the top of the next task.
+      const int e1 = min(task_base(k + 1) + lane, n - 1);
+      task_fetch_a<IN, GEA>(nxt, P, onet, other, mine, e1, false);
       if (GEA) {
         nxt.nn = nn_ahead;
         const int e2 = min(task_base(k + 2) + lane, n - 1);
         if constexpr (PATH) {
-          task_fetch_b_path<IN>(nxt, P, min(task_base(k + 1) + lane, n - 1), n, lane, en_ahead);
-          en_ahead = path_edge_node(P, e2, n, lane);
+          task_fetch_b_path<IN>(nxt, P, e1, n, lane, en_ahead);
+          en_ahead = path_edge_node(P, e2, n, lane, en_ahead);      // (the other lanes keep theirs: nobody reads it)
         } else {
           task_fetch_b<IN, GEA>(nxt, P);
         }

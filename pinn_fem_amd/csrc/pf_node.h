@@ -295,6 +295,8 @@ __device__ __forceinline__ void dof_loss_terms(unsigned fl, float r, int use_dat
 // its element's two end forces, takes the j-end force of e-1 from the lane below and adds in ascending element id like
 // gather_kv_multi above (same ke_rows_times, same 0 + fe0 + fe1 sequence: same bits).  Only the wave's two edge lanes need
 // values of an element outside the task (PathEdge).  Every lane of the wave must call this (lane shifts).
+// Only the lanes named below ever write their PathEdge; in every other lane it holds whatever it held before (zeros, or an
+// earlier task's values) and what path_residual computes from it is dropped by a select.
 template <int DIM>
 struct PathEdge {
   ElemK k;          // lane 0: record of e-1; lane 63: record of e+1
@@ -302,6 +304,16 @@ struct PathEdge {
   float fx[2];      // f_ext and dof flags at j(e): lane 63 and the mesh's last element
   unsigned fl;
 };
+// The wave's values one lane up / down on the vector pipe (DPP wave_shr:1 / wave_shl:1: no LDS round trip, no address
+// arithmetic).  The lane without a source (0 resp. 63) gets `edge`: bound_ctrl is off, so it keeps the old operand.
+__device__ __forceinline__ float wave_shr1(float x, float edge) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, x),
+                                                               0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float wave_shl1(float x, float edge) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, x),
+                                                               0x130, 0xf, 0xf, false));
+}
 // dof flags of a node, both dofs in one register
 template <int DIM>
 __device__ __forceinline__ unsigned load_node_flags(const uint8_t* __restrict__ dof_flags, int node) {
@@ -314,28 +326,37 @@ template <int DIM>
 __device__ __forceinline__ void path_residual(const ElemK& k, const PathEdge<DIM>& x, const float* ui, const float* uj,
                                               const float* fxi, unsigned fli, int e, int n, int lane, float lam,
                                               float alpha_physics, int fe_mode, float* ri, float* gi, float* rj, float* gj) {
-  float A[2], B[2], Bl[2], Ar[2];
-  ke_rows_times<DIM>(k, 0, ui, uj, A, fe_mode);        // element e at its i end -> node i(e)
-  ke_rows_times<DIM>(k, 1, ui, uj, B, fe_mode);        // element e at its j end -> node j(e)
-  ke_rows_times<DIM>(x.k, 1, x.u, ui, Bl, fe_mode);    // lane 0: element e-1 = (i(e-1), i(e)) at its j end
-  ke_rows_times<DIM>(x.k, 0, uj, x.u, Ar, fe_mode);    // lane 63: element e+1 = (j(e), j(e+1)) at its i end
-  const bool first = e == 0, last = e >= n - 1, right = lane == 63 || last;
+  // The j-end rows of an element are its i-end rows negated (ke_rows_times: the same chain with every product's sign
+  // flipped, in both fe_modes; rounding is symmetric), so ONE evaluation per element serves both ends: -A is bit for bit what
+  // end = 1 returns, except that an exact zero comes out with the other sign.  Every such value enters its sum behind
+  // `0.f + ...`, which gives +0 for either zero, so r and g_f keep their bits.
+  // No lane needs both neighbours (lane 0: e-1 at its j end, lane 63: e+1 at its i end), so one more evaluation with the
+  // lane's own operands serves both: X = the i-end rows of that element; lane 0 takes -X, lane 63 X.
+  float A[2], X[2], vi[2], vj[2];
+  ke_rows_times<DIM>(k, 0, ui, uj, A, fe_mode);        // element e at its i end -> node i(e); -A: at its j end -> node j(e)
+  const bool lo = lane == 0, first = e == 0, last = e >= n - 1;
 #pragma unroll
   for (int c = 0; c < DIM; ++c) {
-    const float below = __shfl_up(B[c], 1, 64);
-    const float Bp = lane == 0 ? Bl[c] : below;
+    vi[c] = lo ? x.u[c] : uj[c];                       // lane 0: element e-1 = (i(e-1), i(e)); lane 63: e+1 = (j(e), j(e+1))
+    vj[c] = lo ? ui[c] : x.u[c];
+  }
+  ke_rows_times<DIM>(x.k, 0, vi, vj, X, fe_mode);
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) {
+    // minus the j-end force of the element below.  At the path's start there is none: 0 there, and (0 + -0) + A has the
+    // bits of 0 + A (A itself, or +0 for either zero), the sum of the node's single incidence.
+    const float nBp = wave_shr1(A[c], first ? 0.f : X[c]);
     float acc = 0.f;
-    acc = acc + (first ? A[c] : Bp);                   // the node's first incidence: e-1, or e itself at the path's start
-    const float t = acc + A[c];
-    acc = first ? acc : t;
-    dof_residual(acc, (fli >> (8 * c)) & 0xffu, fxi[c], lam, alpha_physics, ri[c], gi[c]);
+    acc = acc + (-nBp);
+    acc = acc + A[c];
+    dof_residual(acc, fli >> (8 * c), fxi[c], lam, alpha_physics, ri[c], gi[c]);
     float accj = 0.f;
-    accj = accj + B[c];
-    const float tj = accj + Ar[c];
+    accj = accj + (-A[c]);
+    const float tj = accj + X[c];
     accj = last ? accj : tj;                           // the path's end node has one incidence
     float gje;
-    dof_residual(accj, (x.fl >> (8 * c)) & 0xffu, x.fx[c], lam, alpha_physics, rj[c], gje);
-    const float above = __shfl_down(gi[c], 1, 64);
-    gj[c] = right ? gje : above;
+    dof_residual(accj, x.fl >> (8 * c), x.fx[c], lam, alpha_physics, rj[c], gje);
+    const float above = wave_shl1(gi[c], gje);         // (lane 63 keeps its own gje)
+    gj[c] = last ? gje : above;
   }
 }
