@@ -611,6 +611,24 @@ class HipEngine:
             raise ValueError(f"{who}: {name} has {vv.numel()} entries, the mesh has {count} {what}")
         return vv
 
+    def _accumulator(self, who, out, n, new):
+        """(the float64 device vector [n] a kernel writes, whether it ADDS to it): out, checked, or new(n, ...) for None."""
+        if out is None:
+            return new(n, dtype=torch.float64, device=self.device), False
+        if out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous() or out.numel() != n:
+            raise ValueError(f"{who}: out must be a contiguous float64 vector of {n} entries on {self.device}")
+        return out, True
+
+    def _group_ids(self, who, groups, bound=None):
+        """A group map checked: (ids int64 [n_elems], their bytes as a cache key, number of groups).  bound: ids must stay
+        below it."""
+        ne = self.plan.n_elems
+        gm = np.ascontiguousarray(np.asarray(groups).reshape(-1))
+        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < 0 or (bound is not None and gm.max() >= bound))):
+            raise ValueError(f"{who}: groups must hold one non-negative group id for each of the {ne} elements")
+        gm = gm.astype(np.int64)
+        return gm, gm.tobytes(), int(gm.max()) + 1 if ne else 0
+
     @_on_engine_stream
     def gl_state(self, u: torch.Tensor, ea: Optional[torch.Tensor] = None, e0: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Green-Lagrange strain, element force and tangent block of every element at the displacements u (float64,
@@ -645,12 +663,7 @@ class HipEngine:
         aa = self._f64_vector("gl_sensitivity", "a", a, self.plan.n_dofs, "dofs")
         ne = self.plan.n_elems
         zz = None if e0 is None else self._f64_vector("gl_sensitivity", "e0", e0, ne, "elements")
-        accumulate = out is not None
-        if accumulate:
-            if (out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous() or out.numel() != ne):
-                raise ValueError(f"gl_sensitivity: out must be a contiguous float64 vector of {ne} entries on {self.device}")
-        else:
-            out = torch.empty(ne, dtype=torch.float64, device=self.device)
+        out, accumulate = self._accumulator("gl_sensitivity", out, ne, torch.empty)
         if ne:
             rec = self._gl_buffers()[4]
             if zz is None:
@@ -667,13 +680,8 @@ class HipEngine:
         ascending element id and a fixed order (pf_group_sum_f64: the same bits on every run).  groups: [n_elems]
         non-negative ints; the result has max(groups) + 1 entries.  The CSR of the last group map is cached."""
         ne = self.plan.n_elems
-        gm = np.ascontiguousarray(np.asarray(groups).reshape(-1))
-        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < 0)):
-            raise ValueError(f"group_sum: groups must hold one non-negative group id for each of the {ne} elements")
-        gm = gm.astype(np.int64)
-        key = gm.tobytes()
+        gm, key, n_groups = self._group_ids("group_sum", groups)
         if self._group_csr is None or self._group_csr[0] != key:
-            n_groups = int(gm.max()) + 1 if ne else 0
             ptr = np.zeros(n_groups + 1, dtype=np.int32)
             np.cumsum(np.bincount(gm, minlength=n_groups), out=ptr[1:])
             order = np.argsort(gm, kind="stable").astype(np.int32)          # ascending element id inside a group
@@ -695,16 +703,11 @@ class HipEngine:
         ..., g0 + m - 1 (m None: every group from g0 on): row k is minus the internal force of the elements of group
         g0 + k alone, zero on fixed dofs (pf_gl_group_rhs).  groups: [n_elems] non-negative ints.  The device copy of the
         last group map is cached.  Returns [m, n_dofs]."""
-        ne = self.plan.n_elems
-        gm = np.ascontiguousarray(np.asarray(groups).reshape(-1))
-        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < 0 or gm.max() >= 2 ** 31)):
-            raise ValueError(f"gl_group_rhs: groups must hold one non-negative group id for each of the {ne} elements")
-        gm = gm.astype(np.int64)
-        key = gm.tobytes()
+        gm, key, n_groups = self._group_ids("gl_group_rhs", groups, bound=2 ** 31)
         if self._group_map is None or self._group_map[0] != key:
-            ids = gm.astype(np.int32) if ne else np.zeros(1, dtype=np.int32)
-            self._group_map = (key, int(gm.max()) + 1 if ne else 0, torch.from_numpy(ids).to(self.device))
-        _, n_groups, ids = self._group_map
+            ids = gm.astype(np.int32) if gm.size else np.zeros(1, dtype=np.int32)
+            self._group_map = (key, n_groups, torch.from_numpy(ids).to(self.device))
+        ids = self._group_map[2]
         g0 = int(g0)
         m = n_groups - g0 if m is None else int(m)
         if g0 < 0 or m < 1:
@@ -725,12 +728,7 @@ class HipEngine:
         uu = self._f64_vector("gl_strain_rhs", "u", u, self.plan.n_dofs, "dofs")
         cc = self._f64_vector("gl_strain_rhs", "coef", coef, self.plan.n_elems, "elements")
         n = self.plan.n_dofs
-        accumulate = out is not None
-        if accumulate:
-            if (out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous() or out.numel() != n):
-                raise ValueError(f"gl_strain_rhs: out must be a contiguous float64 vector of {n} entries on {self.device}")
-        else:
-            out = torch.zeros(n, dtype=torch.float64, device=self.device)
+        out, accumulate = self._accumulator("gl_strain_rhs", out, n, torch.zeros)
         if self.plan.n_elems:
             rec = self._gl_buffers()[4]
             _capi.check(self.lib.pf_gl_strain_rhs(self._ref(), C.byref(rec), uu.data_ptr(), cc.data_ptr(), int(accumulate),

@@ -49,7 +49,7 @@ determines is what the singular values of A say, not more.  The initial strain i
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -81,13 +81,6 @@ class IdentifyResult:
     stop: Optional[str] = None                     # "misfit" | "gradient" | "step" | "cap" | "damping"
 
 
-def _level_parts(level):
-    if isinstance(level, dict):
-        return level["load_factor"], level["dofs"], level["u"]
-    lam, dofs, u = level
-    return lam, dofs, u
-
-
 def check_identify(model: FEMModel, config: SolverConfig, levels, groups=None, q0=None):
     """What identification needs, checked before an engine is built; every violation is a ValueError.
     Returns (levels as [(load factor, dofs int64 [m], values float64 [m])] in ascending order of load factor,
@@ -104,11 +97,10 @@ def check_identify(model: FEMModel, config: SolverConfig, levels, groups=None, q
     levels = list(levels) if levels is not None else []
     if not levels:
         raise ValueError("identification needs at least one load level: levels is empty.")
-    free = np.ones(model.ndof, dtype=bool)
-    free[np.asarray(model.fixed_dofs, dtype=int)] = False
+    free = _solver._free_mask(model)
     out = []
     for k, level in enumerate(levels):
-        lam, dofs, u = _level_parts(level)
+        lam, dofs, u = (level["load_factor"], level["dofs"], level["u"]) if isinstance(level, dict) else level
         lam = float(lam)
         dofs = np.asarray(dofs).reshape(-1)
         u = np.asarray(u, dtype=np.float64).reshape(-1)
@@ -196,15 +188,45 @@ def check_strains(model: FEMModel, levels):
     return [data for _, data in out]
 
 
-def _with_strains(levels, strains):
-    """check_identify's levels with check_strains' data put back, as the dict levels the two checks accept."""
-    return [lv if st is None else {"load_factor": lv[0], "dofs": lv[1], "u": lv[2], "strain_elements": st[0],
-                                   "strains": st[1], "strain_scale": st[2]} for lv, st in zip(levels, strains)]
+class _Level(NamedTuple):
+    """One load level as check_identify and check_strains pass it."""
+    load_factor: float
+    dofs: np.ndarray                     # int64 [m]
+    values: np.ndarray                   # float64 [m]
+    gauges: Optional[tuple]              # check_strains' (elements int64 [p], strains float64 [p], scale), or None
 
 
-def _strain_residual(eng, e, strain):
+def _checked(model, config, levels, groups=None, q0=None):
+    """check_identify and check_strains on the levels as they were given.
+    Returns ([_Level] in ascending order of load factor, groups, q0)."""
+    raw = list(levels) if levels is not None else []
+    levels, groups, q = check_identify(model, config, raw, groups, q0)
+    return [_Level(*lv, st) for lv, st in zip(levels, check_strains(model, raw))], groups, q
+
+
+def _check_ea(model, ea) -> np.ndarray:
+    """One evaluation's ea as float64 [n_elems] on the host; a wrong length or an entry not finite and positive: ValueError."""
+    ea_np = ea.detach().cpu().numpy() if isinstance(ea, torch.Tensor) else np.asarray(ea)
+    ea_np = np.ascontiguousarray(ea_np, dtype=np.float64).reshape(-1)
+    if ea_np.size != model.nelm:
+        raise ValueError(f"ea has {ea_np.size} entries, the model has {model.nelm} elements")
+    if not (np.all(np.isfinite(ea_np)) and np.all(ea_np > 0.0)):
+        raise ValueError("ea must be finite and positive in every element")
+    return ea_np
+
+
+_COUNTERS = ("newton_iterations", "cg_iterations", "adjoint_cg_iterations")
+_GN_COUNTERS = _COUNTERS + ("sensitivity_cg_iterations", "jacobians")
+
+
+def _add_counters(total, part):
+    for key in total:
+        total[key] += part[key]
+
+
+def _strain_residual(eng, e, gauges):
     """(ids on the device, e[ids] - ebar on the device, L, p) of one level's gauges from the element strains e."""
-    elems, values, scale = strain
+    elems, values, scale = gauges
     ids = torch.from_numpy(elems).to(eng.device)
     return ids, e[ids] - torch.from_numpy(values).to(eng.device), scale, len(elems)
 
@@ -213,37 +235,9 @@ def _base_ea(model) -> float:
     return float(model.material.young.value()) * float(model.material.area.value())
 
 
-def _prepare(model, ea, config):
-    """What misfit_and_gradient and residuals_and_jacobian share before the first level: ea and config.initial_strain
-    checked and on the device, the engine, the free mask and the loads at load factor 1.
-    Returns (engine, ea, free mask, loads, e0 or None)."""
-    ea_np = ea.detach().cpu().numpy() if isinstance(ea, torch.Tensor) else np.asarray(ea)
-    ea_np = np.asarray(ea_np, dtype=np.float64).reshape(-1)
-    if ea_np.size != model.nelm:
-        raise ValueError(f"ea has {ea_np.size} entries, the model has {model.nelm} elements")
-    if not (np.all(np.isfinite(ea_np)) and np.all(ea_np > 0.0)):
-        raise ValueError("ea must be finite and positive in every element")
-    e0_np = _solver.check_initial_strain(config, model)
-    eng = _solver._engine_for(model, None, None)
-    dev, ndof = eng.device, model.ndof
-    ea_t = ea.to(device=dev, dtype=torch.float64).reshape(-1) if isinstance(ea, torch.Tensor) else torch.from_numpy(ea_np).to(dev)
-    free = np.ones(ndof, dtype=bool)
-    free[np.asarray(model.fixed_dofs, dtype=int)] = False
-    e0_t = None if e0_np is None else torch.from_numpy(e0_np).to(dev)
-    if e0_t is not None:                    # solve_nr's rule: the tangent at the starting state u = 0 decides
-        eng.gl_state(torch.zeros(ndof, dtype=torch.float64, device=dev), ea_t, e0_t)
-        _solver._check_tangent_diagonal(eng, free)
-    elif bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
-        raise RuntimeError("Tangent stiffness became singular during solve")
-    free_t = torch.from_numpy(free).to(dev)
-    loads = torch.from_numpy(np.ascontiguousarray(np.asarray(model.loads, dtype=float).reshape(-1))).to(dev)
-    return eng, ea_t, free_t, loads, e0_t
-
-
-def _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters, e0_t=None):
-    """One level's Newton loop from u, as misfit_and_gradient runs it; no convergence is a RuntimeError."""
-    u, ok, residual, _, ite, cg = _solver._newton_loop(eng, model, config, lam * loads, u, free_t, True, ea=ea_t,
-                                                      e0=e0_t)
+def _newton_level(s, model, config, lam, u, ea_t, counters):
+    """One level's Newton loop from u, as an evaluation runs it; no convergence is a RuntimeError."""
+    u, ok, residual, _, ite, cg = _solver._newton_loop(s, model, config, lam * s.loads, u, True, ea=ea_t)
     counters["newton_iterations"] += ite + 1
     counters["cg_iterations"] += cg
     if not ok:
@@ -265,34 +259,39 @@ def misfit_and_gradient(model: FEMModel, config: SolverConfig, levels, ea):
     Returns (J, dJ/d ea [n_elems] on the device, displacements per level [n_dofs] on the device in that order,
     {"newton_iterations", "cg_iterations", "adjoint_cg_iterations"})."""
     config = config or SolverConfig()
-    raw = list(levels) if levels is not None else []
-    levels, _, _ = check_identify(model, config, raw)
-    strains = check_strains(model, raw)
-    eng, ea_t, free_t, loads, e0_t = _prepare(model, ea, config)
-    dev, ndof = eng.device, model.ndof
-    u = torch.zeros(ndof, dtype=torch.float64, device=dev)
+    levels, _, _ = _checked(model, config, levels)
+    ea_np = _check_ea(model, ea)
+    s = _solver._newton_setup(model, _solver.check_initial_strain(config, model))
+    return _misfit(s, model, config, levels, torch.from_numpy(ea_np).to(s.eng.device))
+
+
+def _misfit(s, model, config, levels, ea_t):
+    """misfit_and_gradient on checked input: s the solver's _newton_setup, levels [_Level], ea_t _check_ea's on the device."""
+    eng, dev, ndof = s.eng, s.eng.device, model.ndof
+    _solver._pre_check(s, ea_t)             # solve_nr's rule at the starting state u = 0, with this evaluation's ea
+    u = s.u
     J, grad, states = 0.0, None, []
-    counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0}
-    for (lam, dofs, ubar), strain in zip(levels, strains):
-        u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters, e0_t)
-        e = eng.gl_state(u, ea_t, e0_t)
+    counters = dict.fromkeys(_COUNTERS, 0)
+    for lam, dofs, ubar, gauges in levels:
+        u = _newton_level(s, model, config, lam, u, ea_t, counters)
+        e = eng.gl_state(u, ea_t, s.e0)
         g = torch.zeros(ndof, dtype=torch.float64, device=dev)
         if len(dofs):
             dofs_t = torch.from_numpy(dofs).to(dev)
             r = u[dofs_t] - torch.from_numpy(ubar).to(dev)
             J += float(torch.mean(r * r))
             g.index_add_(0, dofs_t, r * (2.0 / len(dofs)))
-        if strain is not None:
-            ids, r_e, scale, p = _strain_residual(eng, e, strain)
+        if gauges is not None:
+            ids, r_e, scale, p = _strain_residual(eng, e, gauges)
             J += scale * scale * float(torch.mean(r_e * r_e))
             coef = torch.zeros(model.nelm, dtype=torch.float64, device=dev)
             coef[ids] = r_e * (2.0 * scale * scale / p)
             eng.gl_strain_rhs(u, coef, out=g)
         a, it_a, ok_a, rr, bb = eng.pcg_solve(g, tangent=True, preconditioner=config.nr_preconditioner,
                                               n_aggregates=config.nr_aggregates, u=u)
-        _solver._check_cg_step(True, g, a, ok_a, rr, bb, free_t)
+        _solver._check_cg_step(True, g, a, ok_a, rr, bb, s.free_t)
         counters["adjoint_cg_iterations"] += int(it_a)
-        grad = eng.gl_sensitivity(u, a, out=grad, e0=e0_t)
+        grad = eng.gl_sensitivity(u, a, out=grad, e0=s.e0)
         states.append(u)
     return J, grad, states, counters
 
@@ -334,43 +333,47 @@ def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, gr
     Returns (rho, A or None, displacements per level on the device, misfit_and_gradient's counters plus
     "sensitivity_cg_iterations" and "jacobians")."""
     config = config or SolverConfig()
-    raw = list(levels) if levels is not None else []
-    levels, groups, _ = check_identify(model, config, raw, groups)
-    strains = check_strains(model, raw)
+    levels, groups, _ = _checked(model, config, levels, groups)
     if groups is None:
         raise ValueError("residuals_and_jacobian needs an element -> group map")
-    eng, ea_t, free_t, loads, e0_t = _prepare(model, ea, config)
-    dev, ndof = eng.device, model.ndof
+    ea_np = _check_ea(model, ea)
+    s = _solver._newton_setup(model, _solver.check_initial_strain(config, model))
     if states is not None and len(states) != len(levels):
         raise ValueError(f"states has {len(states)} entries for {len(levels)} levels")
-    counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0, "sensitivity_cg_iterations": 0,
-                "jacobians": int(bool(jacobian))}
-    u = torch.zeros(ndof, dtype=torch.float64, device=dev)
+    return _residuals(s, model, config, levels, torch.from_numpy(ea_np).to(s.eng.device), groups, states, jacobian)
+
+
+def _residuals(s, model, config, levels, ea_t, groups, states=None, jacobian=True):
+    """residuals_and_jacobian on checked input: s, levels and ea_t as _misfit takes them, groups check_identify's, states
+    None or one per level."""
+    eng, dev = s.eng, s.eng.device
+    _solver._pre_check(s, ea_t)             # solve_nr's rule at the starting state u = 0, with this evaluation's ea
+    counters = dict(dict.fromkeys(_GN_COUNTERS, 0), jacobians=int(bool(jacobian)))
+    u = s.u
     rho, rows, out_states = [], [], []
-    for k, (lam, dofs, ubar) in enumerate(levels):
+    for k, (lam, dofs, ubar, gauges) in enumerate(levels):
         if states is None:
-            u = _newton_level(eng, model, config, lam, loads, u, free_t, ea_t, counters, e0_t)
+            u = _newton_level(s, model, config, lam, u, ea_t, counters)
         else:
             u = states[k].to(device=dev, dtype=torch.float64).reshape(-1)
         dofs_t = torch.from_numpy(dofs).to(dev)
         w = 1.0 / np.sqrt(len(dofs)) if len(dofs) else 0.0
         rho.append((u[dofs_t] - torch.from_numpy(ubar).to(dev)).cpu().numpy() * w)
-        strain = strains[k]
-        if jacobian or strain is not None:
-            e = eng.gl_state(u, ea_t, e0_t)
-        if strain is not None:
-            _, r_e, scale, p = _strain_residual(eng, e, strain)
+        if jacobian or gauges is not None:
+            e = eng.gl_state(u, ea_t, s.e0)
+        if gauges is not None:
+            _, r_e, scale, p = _strain_residual(eng, e, gauges)
             w_e = scale / np.sqrt(p)
             rho.append(r_e.cpu().numpy() * w_e)
         if jacobian:
             B = eng.gl_group_rhs(groups)
             S, reports = eng.pcg_solve_many(B, preconditioner=config.nr_preconditioner, n_aggregates=config.nr_aggregates, u=u)
             for g, (it_s, ok_s, rr, bb) in enumerate(reports):
-                _solver._check_cg_step(True, B[g], S[g], ok_s, rr, bb, free_t)
+                _solver._check_cg_step(True, B[g], S[g], ok_s, rr, bb, s.free_t)
                 counters["sensitivity_cg_iterations"] += int(it_s)
             rows.append(S[:, dofs_t].t().cpu().numpy() * w)
-            if strain is not None:
-                rows.append(eng.gl_strain_jvp(u, strain[0], S).t().cpu().numpy() * w_e)
+            if gauges is not None:
+                rows.append(eng.gl_strain_jvp(u, gauges[0], S).t().cpu().numpy() * w_e)
         out_states.append(u)
     A = None
     if jacobian:
@@ -382,18 +385,17 @@ def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, gr
     return np.concatenate(rho), A, out_states, counters
 
 
-def _gauss_newton(model, config, levels, groups, q_start, ea_of, max_evaluations, gtol, misfit_tolerance, damping,
+def _gauss_newton(s, model, config, levels, groups, q_start, ea_of, max_evaluations, gtol, misfit_tolerance, damping,
                   step_tolerance):
-    """Levenberg-Marquardt on the log-factors (identify_nr, method "gauss-newton").
+    """Levenberg-Marquardt on the log-factors (identify_nr, method "gauss-newton"); s, levels, groups as _residuals' are.
     Returns (q, rho, A, states, history, counters, stop, evaluations) with q, rho, A and states those of the last accepted
     point."""
-    counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0, "sensitivity_cg_iterations": 0,
-                "jacobians": 0}
+    counters = dict.fromkeys(_GN_COUNTERS, 0)
 
     def evaluate(q_np, **kw):
-        out = residuals_and_jacobian(model, config, levels, ea_of(q_np), groups, **kw)
-        for key in counters:
-            counters[key] += out[3][key]
+        ea_t = torch.from_numpy(_check_ea(model, ea_of(q_np))).to(s.eng.device)
+        out = _residuals(s, model, config, levels, ea_t, groups, **kw)
+        _add_counters(counters, out[3])
         return out[:3]
 
     q = q_start
@@ -438,13 +440,11 @@ class _Stop(Exception):
     pass
 
 
-def _reactions(eng, model, lam, u, ea_t, e0_t=None):
+def _reactions(s, model, lam, u, ea_t):
     """Reactions of a level at its state: f_int(u; ea, e0) - lam f on the fixed dofs."""
-    eng.gl_state(u, ea_t, e0_t)
-    reactions = eng.gl_fint().cpu().numpy() - lam * np.asarray(model.loads, dtype=float).reshape(-1)
-    free = np.ones(model.ndof, dtype=bool)
-    free[np.asarray(model.fixed_dofs, dtype=int)] = False
-    reactions[free] = 0.0
+    s.eng.gl_state(u, ea_t, s.e0)
+    reactions = s.eng.gl_fint().cpu().numpy() - lam * np.asarray(model.loads, dtype=float).reshape(-1)
+    reactions[s.free] = 0.0
     return reactions
 
 
@@ -481,46 +481,40 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
     if method not in ("lbfgs", "gauss-newton"):
         raise ValueError(f"unknown identification method {method!r}: 'lbfgs' or 'gauss-newton'.")
     config = config or SolverConfig()
-    raw = list(levels) if levels is not None else []
-    levels, groups, q_start = check_identify(model, config, raw, groups, q0)
-    gauges = check_strains(model, raw)
+    levels, groups, q_start = _checked(model, config, levels, groups, q0)
     if int(max_evaluations) < 1:
         raise ValueError("max_evaluations must be at least 1")
     if method == "gauss-newton":
-        n_groups, n_rows = check_gauss_newton(levels, groups, damping, gauges)
-    have_gauges = any(st is not None for st in gauges)
-    if have_gauges:
-        levels = _with_strains(levels, gauges)
-    lam_last = float(_level_parts(levels[-1])[0])
+        n_groups, n_rows = check_gauss_newton([lv[:3] for lv in levels], groups, damping, [lv.gauges for lv in levels])
+    have_gauges = any(lv.gauges is not None for lv in levels)
+    lam_last = levels[-1].load_factor
     ea0 = _base_ea(model)
-    e0_np = _solver.check_initial_strain(config, model)
-    eng = _solver._engine_for(model, None, None)
-    e0_t = None if e0_np is None else torch.from_numpy(e0_np).to(eng.device)
-
-    def strains_at(states, ea_t):
-        """Every element's strain per level at the returned point (None without strain data)."""
-        return [eng.gl_state(u, ea_t, e0_t).cpu().numpy() for u in states] if have_gauges else None
-    if method == "gauss-newton":
-        ea_gn = lambda q_np: ea0 * np.exp(q_np)[groups]
-        q, rho, A, states, history, counters, stop, evaluations = _gauss_newton(
-            model, config, levels, groups, q_start, ea_gn, max_evaluations, gtol, misfit_tolerance, damping, step_tolerance)
-        J = float(rho @ rho)
-        covariance = J / (n_rows - n_groups) * np.linalg.inv(A.T @ A) if n_rows > n_groups else None
-        ea_t = torch.from_numpy(ea_gn(q)).to(eng.device)
-        return IdentifyResult(
-            factors=np.exp(q), ea=ea_gn(q), misfit=J, gradient=2.0 * A.T @ rho, evaluations=evaluations,
-            converged=stop in ("misfit", "gradient", "step"), history=history,
-            displacements=[s.cpu().numpy() for s in states], counters=counters, strains=strains_at(states, ea_t),
-            reactions=_reactions(eng, model, lam_last, states[-1], ea_t, e0_t), jacobian=A,
-            singular_values=np.linalg.svd(A, compute_uv=False), covariance=covariance,
-            factor_std=None if covariance is None else np.exp(q) * np.sqrt(np.diag(covariance)), stop=stop)
-    counters = {"newton_iterations": 0, "cg_iterations": 0, "adjoint_cg_iterations": 0}
-    history, best = [], {}
+    s = _solver._newton_setup(model, _solver.check_initial_strain(config, model))
+    eng = s.eng
 
     def ea_of(q_np):
         f = np.exp(q_np)
         return ea0 * (f if groups is None else f[groups])
 
+    def strains_at(states, ea_t):
+        """Every element's strain per level at the returned point (None without strain data)."""
+        return [eng.gl_state(u, ea_t, s.e0).cpu().numpy() for u in states] if have_gauges else None
+    if method == "gauss-newton":
+        q, rho, A, states, history, counters, stop, evaluations = _gauss_newton(
+            s, model, config, levels, groups, q_start, ea_of, max_evaluations, gtol, misfit_tolerance, damping,
+            step_tolerance)
+        J = float(rho @ rho)
+        covariance = J / (n_rows - n_groups) * np.linalg.inv(A.T @ A) if n_rows > n_groups else None
+        ea_t = torch.from_numpy(ea_of(q)).to(eng.device)
+        return IdentifyResult(
+            factors=np.exp(q), ea=ea_of(q), misfit=J, gradient=2.0 * A.T @ rho, evaluations=evaluations,
+            converged=stop in ("misfit", "gradient", "step"), history=history,
+            displacements=[u.cpu().numpy() for u in states], counters=counters, strains=strains_at(states, ea_t),
+            reactions=_reactions(s, model, lam_last, states[-1], ea_t), jacobian=A,
+            singular_values=np.linalg.svd(A, compute_uv=False), covariance=covariance,
+            factor_std=None if covariance is None else np.exp(q) * np.sqrt(np.diag(covariance)), stop=stop)
+    counters = dict.fromkeys(_COUNTERS, 0)
+    history, best = [], {}
     q = torch.from_numpy(q_start).requires_grad_(True)
     opt = torch.optim.LBFGS([q], lr=1, max_iter=int(max_evaluations), max_eval=int(max_evaluations),
                             history_size=int(history_size), line_search_fn="strong_wolfe", tolerance_grad=float(gtol),
@@ -531,12 +525,11 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
             raise _Stop
         opt.zero_grad()
         q_np = q.detach().numpy().copy()
-        ea_t = torch.from_numpy(ea_of(q_np)).to(eng.device)
-        J, g_ea, states, c = misfit_and_gradient(model, config, levels, ea_t)
+        ea_t = torch.from_numpy(_check_ea(model, ea_of(q_np))).to(eng.device)
+        J, g_ea, states, c = _misfit(s, model, config, levels, ea_t)
         gq = (g_ea * ea_t) if groups is None else eng.group_sum(g_ea, ea_t, groups)
         gq = gq.cpu()
-        for key in counters:
-            counters[key] += c[key]
+        _add_counters(counters, c)
         history.append({"misfit": J, "gradient_norm": float(torch.linalg.norm(gq)), "factors": np.exp(q_np)})
         if not best or J < best["J"]:
             best.update(J=J, q=q_np, g=gq.numpy().copy(), states=states, ea=ea_t)
@@ -551,8 +544,8 @@ def identify_nr(model: FEMModel, config: Optional[SolverConfig], levels, groups=
         pass
     met = bool(np.max(np.abs(best["g"]), initial=0.0) <= gtol or best["J"] <= misfit_tolerance)
     converged = met or len(history) < int(max_evaluations)          # False: the evaluation cap ended it
-    reactions = _reactions(eng, model, lam_last, best["states"][-1], best["ea"], e0_t)
+    reactions = _reactions(s, model, lam_last, best["states"][-1], best["ea"])
     return IdentifyResult(factors=np.exp(best["q"]), ea=ea_of(best["q"]), misfit=float(best["J"]), gradient=best["g"],
                           evaluations=len(history), converged=converged, history=history,
-                          displacements=[s.cpu().numpy() for s in best["states"]], counters=counters, reactions=reactions,
+                          displacements=[u.cpu().numpy() for u in best["states"]], counters=counters, reactions=reactions,
                           strains=strains_at(best["states"], best["ea"]))

@@ -21,11 +21,12 @@ import copy
 import os
 import warnings
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
 
+from .boundary import free_and_fixed_dofs
 from .model import FEMModel
 from ..engine import HipEngine
 
@@ -110,8 +111,7 @@ def check_control(config, model=None, method: str = "nr") -> str:
     c = config.nr_control_dof
     if c is None or isinstance(c, bool) or int(c) != c or not 0 <= int(c) < model.ndof:
         raise ValueError(f"nr_control 'displacement' needs nr_control_dof, a global dof in 0..{model.ndof - 1}: got {c!r}")
-    free = np.ones(model.ndof, dtype=bool)
-    free[np.asarray(model.fixed_dofs, dtype=int)] = False
+    free = _free_mask(model)
     if not free[int(c)]:
         raise ValueError(f"nr_control_dof {int(c)} is a fixed dof: the control dof must be free.")
     d = float(config.nr_control_displacement)
@@ -158,15 +158,11 @@ def _axial_forces(model, strain, e0):
     return ea * (strain.cpu().numpy() - e0)
 
 
-def _check_tangent_diagonal(eng, free):
-    """The pre-check of a solve with initial strains: the tangent at the starting state (the last gl_state) must have a
-    positive diagonal on every free dof.  A free dof that only a slack or compressed member holds is a mechanism."""
-    dg = eng.kt_diag().cpu().numpy()
-    bad = np.flatnonzero(free & ~(dg > 0.0))
-    if bad.size:
-        raise RuntimeError(f"Tangent stiffness is not positive definite at the starting state: its diagonal is "
-                           f"{dg[bad[0]]:.6g} at free dof {int(bad[0])} (a slack or compressed mechanism; "
-                           f"{bad.size} such dof{'s' if bad.size > 1 else ''})")
+def _free_mask(model) -> np.ndarray:
+    """True on the free dofs of the model, False on model.fixed_dofs (bool [n_dofs], host)."""
+    mask = np.zeros(model.ndof, dtype=bool)
+    mask[free_and_fixed_dofs(model.ndof, model.fixed_dofs)[0]] = True
+    return mask
 
 
 @dataclass
@@ -198,11 +194,8 @@ def _say(msg: str = ""):
 def _engine_for(model: FEMModel, measured_disp, measured_dofs) -> HipEngine:
     """One engine (mesh plan + device buffers) per model and measurement set, reused across load
     increments and phases like the reference reuses the nn.Modules."""
-    key = (None if measured_disp is None else np.asarray(measured_disp, dtype=float).tobytes(),
-           None if measured_dofs is None else np.asarray(measured_dofs, dtype=int).tobytes(),
-           model.nodes.tobytes(), model.elements.tobytes(), model.loads.tobytes(),
-           model.fixed_dofs.tobytes(), _material_signature(model), getattr(model, "_pf_mlp_dtype", None),
-           getattr(model, "_pf_fe_mode", None))
+    key = _engine_key_terms(model, measured_disp, measured_dofs) + (getattr(model, "_pf_mlp_dtype", None),
+                                                                    getattr(model, "_pf_fe_mode", None))
     cache = getattr(model, "_pf_engine_cache", None)
     if cache is not None and cache[0] == key and (not cache[1].n_theta or cache[1].theta.still_bound()):
         return cache[1]
@@ -221,6 +214,32 @@ def _material_signature(model: FEMModel):
         else:
             sig.append(("scalar", float(prop.value())))
     return tuple(sig)
+
+
+def _engine_key_terms(model: FEMModel, measured_disp, measured_dofs) -> tuple:
+    """What the cache key of the single-GPU engine and the one of the sharded backend share: the measurement set, the
+    mesh, the loads, the supports and the material."""
+    return (None if measured_disp is None else np.asarray(measured_disp, dtype=float).tobytes(),
+            None if measured_dofs is None else np.asarray(measured_dofs, dtype=int).tobytes(),
+            model.nodes.tobytes(), model.elements.tobytes(), model.loads.tobytes(),
+            model.fixed_dofs.tobytes(), _material_signature(model))
+
+
+def _shifted_history(first, second):
+    """The history of two phases run one after the other: first's entries, then copies of second's with their iteration
+    numbers continuing from first's last."""
+    shift = first[-1].get("iteration", 0) if first else 0
+    return list(first) + [dict(entry, iteration=entry.get("iteration", 0) + shift) for entry in second]
+
+
+def _result(model, u, reactions, free, converged, history, theta_list=(), **more) -> SolverResult:
+    """The tail of every solver: u and reactions (host, [n_dofs]) in the nodal shape, the reactions zeroed on the free
+    dofs (a mask or indices), the NN parameters when there are any."""
+    shape = (-1, 1) if model.dimension == 1 else (model.nnode, model.dimension)
+    reactions[free] = 0.0
+    nn_params = {f"param_{i}": p.detach().cpu().numpy() for i, p in enumerate(theta_list)} if theta_list else None
+    return SolverResult(displacements=u.reshape(shape), reactions=reactions.reshape(shape), converged=converged,
+                        history=history, nn_parameters=nn_params, **more)
 
 
 def solve_gd(
@@ -263,17 +282,7 @@ def solve_gd(
             main_config.preconditioning = False
             main_result = solve_gd(model, main_config, measured_disp, measured_dofs,
                                    target_load_factor, u_initial, skip_preconditioning=True)
-            precon_iterations = (precon_result.history[-1].get("iteration", 0)
-                                 if precon_result.history else 0)
-            unified_history = []
-            if precon_result.history:
-                unified_history.extend(precon_result.history)
-            if main_result.history:
-                for entry in main_result.history:
-                    new_entry = entry.copy()
-                    new_entry["iteration"] = entry.get("iteration", 0) + precon_iterations
-                    unified_history.append(new_entry)
-            main_result.history = unified_history
+            main_result.history = _shifted_history(precon_result.history, main_result.history)
             total_iterations = (main_result.history[-1].get("iteration", 0)
                                 if main_result.history else 0)
             _say(f"  Total GD (with preconditioning): {total_iterations} iterations")
@@ -325,22 +334,8 @@ def solve_gd(
     st = eng.state()
     n_iter = st.iter if st is not None else 0
     converged = bool(st.converged) if st is not None else False
-    rows = eng.history(n_iter)
-
-    history: List[Dict[str, float]] = []
-    for it in range(n_iter):
-        r = rows[it]
-        entry = {
-            "iteration": float(it + 1),
-            "loss_total": float(r[0]),
-            "loss_physics": float(r[1]),
-            "loss_data": float(r[2]) if has_measurements else 0.0,
-            "u_norm": float(r[3]),
-            "residual_norm": float(r[4]),
-        }
-        if theta_list:
-            entry["theta_norm"] = float(r[5])
-        history.append(entry)
+    history = _history_from_rows(eng.history(n_iter), n_iter, has_measurements, theta_list)
+    for it, entry in enumerate(history):
         if VERBOSE and ((it + 1) % config.print_every == 0 or it == 0):
             msg = (f"{it+1:6d} | {entry['loss_total']:12.3e} | {entry['loss_physics']:12.3e} | "
                    f"{entry['residual_norm']:12.3e} | {entry['loss_data']:12.3e} | {entry['u_norm']:10.3e}")
@@ -362,18 +357,9 @@ def solve_gd(
 
     # ---- result (solver.py:365-400) -----------------------------------------------------------------
     u_final = eng.u.detach().cpu().numpy().copy()
-    shape = (-1, 1) if model.dimension == 1 else (model.nnode, model.dimension)
-    displacements_out = u_final.reshape(shape)
     f_int_final = eng.internal_force(lam=target_load_factor)           # no-grad re-assembly :374-377
     reactions_t = f_int_final - float(np.float32(target_load_factor)) * eng.f_ext
-    reactions_np = reactions_t.cpu().numpy()
-    reactions_np[eng.plan.free_dofs] = 0.0                            # :379
-    reactions_out = reactions_np.reshape(shape)
-    nn_params = None
-    if theta_list:
-        nn_params = {f"param_{i}": p.detach().cpu().numpy() for i, p in enumerate(theta_list)}
-    return SolverResult(displacements=displacements_out, reactions=reactions_out,
-                        converged=converged, history=history, nn_parameters=nn_params)
+    return _result(model, u_final, reactions_t.cpu().numpy(), eng.plan.free_dofs, converged, history, theta_list)  # :379
 
 
 def _world_size() -> int:
@@ -400,11 +386,7 @@ def _solve_gd_sharded(model, config, measured_disp, measured_dofs, lam, u_initia
     ranks (pinn_fem_amd.dist); every rank returns the same global SolverResult."""
     import torch.distributed as dist
     from .. import dist as pfd
-    key = ("shard", dist.get_rank(), dist.get_world_size(),
-           None if measured_disp is None else np.asarray(measured_disp, dtype=float).tobytes(),
-           None if measured_dofs is None else np.asarray(measured_dofs, dtype=int).tobytes(),
-           model.nodes.tobytes(), model.elements.tobytes(), model.loads.tobytes(),
-           model.fixed_dofs.tobytes(), _material_signature(model))
+    key = ("shard", dist.get_rank(), dist.get_world_size()) + _engine_key_terms(model, measured_disp, measured_dofs)
     cache = getattr(model, "_pf_shard_cache", None)
     if cache is not None and cache[0] == key and (not cache[1].eng.n_theta or cache[1].eng.theta.still_bound()):
         be = cache[1]
@@ -429,31 +411,77 @@ def _solve_gd_sharded(model, config, measured_disp, measured_dofs, lam, u_initia
     n_iter = st.iter if st is not None else 0
     converged = bool(st.converged) if st is not None else False
     history = _history_from_rows(be.history(n_iter), n_iter, has_measurements, theta_list)
-    shape = (-1, 1) if model.dimension == 1 else (model.nnode, model.dimension)
     u_glob = pfd.gather_global_vector(be.eng.u, be, model.ndof)
     f_loc = pfd.assembled_f_int(be, lam)
     r_loc = f_loc - float(np.float32(lam)) * be.eng.f_ext
     r_glob = pfd.gather_global_vector(r_loc, be, model.ndof)
-    from .boundary import free_and_fixed_dofs
-    free, _ = free_and_fixed_dofs(model.ndof, model.fixed_dofs)
-    r_glob[free] = 0.0
-    nn_params = None
-    if theta_list:
-        nn_params = {f"param_{i}": p.detach().cpu().numpy() for i, p in enumerate(theta_list)}
-    return SolverResult(displacements=u_glob.reshape(shape), reactions=r_glob.reshape(shape),
-                        converged=converged, history=history, nn_parameters=nn_params)
+    return _result(model, u_glob, r_glob, _free_mask(model), converged, history, theta_list)
 
 
-def _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange, ea=None, e0=None):
+class _NewtonSetup(NamedTuple):
+    """What a Newton solve and an identification evaluation hold before their first iteration (_newton_setup)."""
+    eng: HipEngine
+    free: np.ndarray                        # bool [n_dofs], host
+    free_t: torch.Tensor                    # the same on the device
+    loads: torch.Tensor                     # the loads at load factor 1, float64 [n_dofs] on the device
+    e0_np: Optional[np.ndarray]             # check_initial_strain's array, or None
+    e0: Optional[torch.Tensor]              # the same on the device
+    u: torch.Tensor                         # the start vector, float64 [n_dofs] on the device, zero on the fixed dofs
+
+
+def _newton_setup(model, e0_np, u_initial=None) -> _NewtonSetup:
+    """The one host setup of solve_nr under either control and of fem/identify.py.  e0_np: check_initial_strain's
+    result; like every check_* it is the caller's to run first, this is where the engine is built.  u_initial: a tensor
+    or an array [n_dofs] (its fixed dofs are ignored); None: zeros.  It launches nothing but torch's own copies and
+    fills; _pre_check is the first to touch the kernels."""
+    eng = _engine_for(model, None, None)
+    dev, ndof = eng.device, model.ndof
+    free = _free_mask(model)
+    u = torch.zeros(ndof, dtype=torch.float64, device=dev)
+    if u_initial is not None:
+        u0 = u_initial.detach() if isinstance(u_initial, torch.Tensor) else torch.as_tensor(np.asarray(u_initial))
+        u = u0.to(device=dev, dtype=torch.float64).reshape(-1).clone()
+        if u.numel() != ndof:
+            raise ValueError(f"u_initial has {u.numel()} entries, the model has {ndof} dofs")
+        u[torch.from_numpy(~free).to(dev)] = 0.0
+    loads = torch.from_numpy(np.ascontiguousarray(np.asarray(model.loads, dtype=float).reshape(-1))).to(dev)
+    return _NewtonSetup(eng, free, torch.from_numpy(free).to(dev), loads, e0_np,
+                        None if e0_np is None else torch.from_numpy(e0_np).to(dev), u)
+
+
+def _pre_check(s: _NewtonSetup, ea=None, held=()):
+    """The pre-check of a Newton solve from s.u with the element stiffnesses ea (None: the model's), the dofs `held`
+    prescribed on top of the fixed ones.  A free dof no element stiffens makes K_ff singular: np.linalg.solve raises
+    there (solver.py:462-467).  With initial strains the geometric stiffness may be all that holds a dof (a taut
+    string), so the tangent at the starting state decides, not the linear diagonal: it must be positive on every free
+    dof that is not held (a free dof that only a slack or compressed member holds is a mechanism).  That branch leaves
+    the gl_state of (s.u, ea, s.e0) on the engine."""
+    if s.e0 is None:
+        if bool((s.eng.diag_k().cpu().numpy()[s.free] == 0.0).any()):
+            raise RuntimeError("Tangent stiffness became singular during solve")
+        return
+    s.eng.gl_state(s.u, ea, s.e0)
+    dg = s.eng.kt_diag().cpu().numpy()
+    free = s.free.copy()
+    free[list(held)] = False
+    bad = np.flatnonzero(free & ~(dg > 0.0))
+    if bad.size:
+        raise RuntimeError(f"Tangent stiffness is not positive definite at the starting state: its diagonal is "
+                           f"{dg[bad[0]]:.6g} at free dof {int(bad[0])} (a slack or compressed mechanism; "
+                           f"{bad.size} such dof{'s' if bad.size > 1 else ''})")
+
+
+def _newton_loop(s, model, config, f_ext, u, green_lagrange, ea=None):
     """The Newton iteration of solve_nr from u at the load f_ext: u += K^-1 (f_ext - f_int(u)) by CG until
-    |du| / max(|u|, min_denominator) <= tolerance.  ea (Green-Lagrange only): E*A of every element in place of the
-    model's (identify.misfit_and_gradient); e0: their initial strain (device float64).  Returns (u, converged, |du|/|u|,
-    max strain of the linear branch, index of the last iteration, CG iterations)."""
+    |du| / max(|u|, min_denominator) <= tolerance.  s: the _newton_setup (its engine, free mask and initial strain);
+    ea (Green-Lagrange only): E*A of every element in place of the model's (fem/identify.py).  Returns (u, converged,
+    |du|/|u|, max strain of the linear branch, index of the last iteration, CG iterations)."""
+    eng = s.eng
     has_converged, residual_norm, max_e, ite = False, float("inf"), 0.0, -1
     cg0 = eng.pcg_iterations
     for ite in range(config.max_iterations):
         if green_lagrange:
-            eng.gl_state(u, ea, e0)         # the history's max |e| is read once, from the state at the final u
+            eng.gl_state(u, ea, s.e0)       # the history's max |e| is read once, from the state at the final u
             rhs = f_ext - eng.gl_fint()
             du, _, ok, rr, bb = eng.pcg_solve(rhs, tangent=True, preconditioner=config.nr_preconditioner,
                                              n_aggregates=config.nr_aggregates, u=u)
@@ -462,7 +490,7 @@ def _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange, ea=None, 
             rhs = f_ext - eng.kv_f64(u)
             du, _, ok, rr, bb = eng.pcg_solve(rhs, preconditioner=config.nr_preconditioner,
                                              n_aggregates=config.nr_aggregates)
-        _check_cg_step(green_lagrange, rhs, du, ok, rr, bb, free_t)
+        _check_cg_step(green_lagrange, rhs, du, ok, rr, bb, s.free_t)
         u = u + du
         residual_norm = float(torch.linalg.norm(du)) / max(float(torch.linalg.norm(u)), config.min_denominator)
         if residual_norm <= config.tolerance:
@@ -471,17 +499,25 @@ def _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange, ea=None, 
     return u, has_converged, residual_norm, max_e, ite, eng.pcg_iterations - cg0
 
 
-def _check_cg_step(green_lagrange, rhs, x, ok, rr, bb, free_t):
-    """What solve_nr asks of a CG solve K x = rhs."""
+# what load control says when _check_cg_step refuses a solve: (the residual does not come down, rhs.x <= 0)
+_LOAD_REFUSALS = ("Tangent stiffness became singular during solve",
+                  "Tangent stiffness is not positive definite (limit point or buckling): the CG solve of "
+                  "the Green-Lagrange Newton step needs an SPD tangent; reduce the load step")
+
+
+def _check_cg_step(spd, rhs, x, ok, rr, bb, free_t, refusals=_LOAD_REFUSALS):
+    """What solve_nr asks of a CG solve K x = rhs, under either control; refusals: the two RuntimeError messages.
+    free_t: the mask the rhs.x test runs over; None: rhs is zero outside the solve's dofs already, no gather."""
     # np.linalg.solve either succeeds or raises on a singular matrix; CG shows singularity (or a hopeless
     # condition number for the Jacobi preconditioner) as a residual that does not come down at all.  An
     # inner solve that merely stops short of 1e-13 is fine: the Newton loop then acts as iterative refinement.
     if not np.isfinite(rr) or (not ok and rr > 1e-4 * bb):
-        raise RuntimeError("Tangent stiffness became singular during solve")
+        raise RuntimeError(refusals[0])
     # CG is only valid for a positive definite operator: x = K_t^-1 rhs must be an ascent direction of rhs
-    if green_lagrange and bb > 0.0 and not float(torch.dot(rhs[free_t], x[free_t])) > 0.0:
-        raise RuntimeError("Tangent stiffness is not positive definite (limit point or buckling): the CG solve of "
-                           "the Green-Lagrange Newton step needs an SPD tangent; reduce the load step")
+    if spd and bb > 0.0:
+        dot = torch.dot(rhs, x) if free_t is None else torch.dot(rhs[free_t], x[free_t])
+        if not float(dot) > 0.0:
+            raise RuntimeError(refusals[1])
 
 
 def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> SolverResult:
@@ -520,47 +556,23 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     if green_lagrange:
         if _world_size() > 1:
             raise ValueError("kinematics 'green-lagrange' does not support a sharded (multi-GPU) run.")
-    eng = _engine_for(model, None, None)
-    ndof = model.ndof
-    free = np.ones(ndof, dtype=bool)
-    free[np.asarray(model.fixed_dofs, dtype=int)] = False
-    load_factor = target_load_factor
-    f_ext = torch.from_numpy(np.ascontiguousarray(load_factor * np.asarray(model.loads, dtype=float))).to(eng.device)
-    u = torch.zeros(ndof, dtype=torch.float64, device=eng.device)
-    if green_lagrange and u_initial is not None:
-        u0 = u_initial.detach() if isinstance(u_initial, torch.Tensor) else torch.as_tensor(np.asarray(u_initial))
-        u = u0.to(device=eng.device, dtype=torch.float64).reshape(-1).clone()
-        if u.numel() != ndof:
-            raise ValueError(f"u_initial has {u.numel()} entries, the model has {ndof} dofs")
-        u[torch.from_numpy(~free).to(eng.device)] = 0.0
-    e0 = None if e0_np is None else torch.from_numpy(e0_np).to(eng.device)
-    if e0 is not None:
-        # with initial strains the geometric stiffness may be all that holds a dof (a taut string): the tangent at the
-        # starting state decides, not the linear diagonal
-        eng.gl_state(u, None, e0)
-        _check_tangent_diagonal(eng, free)
-    # a free dof no element stiffens makes K_ff singular: np.linalg.solve raises there (solver.py:462-467)
-    elif bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
-        raise RuntimeError("Tangent stiffness became singular during solve")
-    free_t = torch.from_numpy(free).to(eng.device)
-    u, has_converged, residual_norm, max_e, ite, _ = _newton_loop(eng, model, config, f_ext, u, free_t, green_lagrange,
-                                                                  e0=e0)
+    s = _newton_setup(model, e0_np, u_initial if green_lagrange else None)
+    _pre_check(s)
+    eng, load_factor = s.eng, target_load_factor
+    f_ext = float(load_factor) * s.loads
+    u, has_converged, residual_norm, max_e, ite, _ = _newton_loop(s, model, config, f_ext, s.u, green_lagrange)
     axial = None
     if green_lagrange:
-        strain = eng.gl_state(u, None, e0)            # state at the final u: its strain, and f_int for the reactions
+        strain = eng.gl_state(u, None, s.e0)          # state at the final u: its strain, and f_int for the reactions
         max_e = float(strain.abs().max()) if model.nelm else 0.0
         reactions = (eng.gl_fint() - f_ext).cpu().numpy()
-        if e0 is not None:
-            axial = _axial_forces(model, strain, e0_np)
+        if s.e0 is not None:
+            axial = _axial_forces(model, strain, s.e0_np)
     else:
         reactions = (eng.kv_f64(u) - f_ext).cpu().numpy()
     history = [{"load_factor": float(load_factor), "iterations": float(ite + 1), "residual": float(residual_norm),
                 "max_strain": float(max_e), "converged": float(1.0 if has_converged else 0.0)}]
-    reactions[free] = 0.0
-    u_np = u.cpu().numpy()
-    shape = (-1, 1) if model.dimension == 1 else (model.nnode, model.dimension)
-    return SolverResult(displacements=u_np.reshape(shape), reactions=reactions.reshape(shape),
-                        converged=has_converged, history=history, axial_forces=axial)
+    return _result(model, u.cpu().numpy(), reactions, s.free, has_converged, history, axial_forces=axial)
 
 
 def _solve_nr_displacement(model, config, control_factor, u_initial, e0_np=None) -> SolverResult:
@@ -578,57 +590,34 @@ def _solve_nr_displacement(model, config, control_factor, u_initial, e0_np=None)
     lam starts at f[F].f_int(u)[F] / f[F].f[F]: the previous increment's lam when u is a converged state."""
     c = int(config.nr_control_dof)
     ubar = float(control_factor) * float(config.nr_control_displacement)
-    eng = _engine_for(model, None, None)
-    ndof = model.ndof
-    free = np.ones(ndof, dtype=bool)
-    free[np.asarray(model.fixed_dofs, dtype=int)] = False
-    dev, f64 = eng.device, torch.float64
-    f = torch.from_numpy(np.ascontiguousarray(np.asarray(model.loads, dtype=float).reshape(-1))).to(dev)
-    u = torch.zeros(ndof, dtype=f64, device=dev)
-    if u_initial is not None:
-        u0 = u_initial.detach() if isinstance(u_initial, torch.Tensor) else torch.as_tensor(np.asarray(u_initial))
-        u = u0.to(device=dev, dtype=f64).reshape(-1).clone()
-        if u.numel() != ndof:
-            raise ValueError(f"u_initial has {u.numel()} entries, the model has {ndof} dofs")
-        u[torch.from_numpy(~free).to(dev)] = 0.0
-    e0 = None if e0_np is None else torch.from_numpy(e0_np).to(dev)
-    if e0 is not None:
-        eng.gl_state(u, None, e0)           # solve_nr's rule; the control dof is held, so K' is what must be definite
-        held = free.copy()
-        held[c] = False
-        _check_tangent_diagonal(eng, held)
-    elif bool((eng.diag_k().cpu().numpy()[free] == 0.0).any()):
-        raise RuntimeError("Tangent stiffness became singular during solve")
-    free_t = torch.from_numpy(free).to(dev)
+    s = _newton_setup(model, e0_np, u_initial)
+    _pre_check(s, held=[c])                 # solve_nr's rule; the control dof is held, so K' is what must be definite
+    eng, f, u, free_t = s.eng, s.loads, s.u, s.free_t
     fc_t = free_t.clone()
     fc_t[c] = False                                     # F'
     f_fc = torch.where(fc_t, f, torch.zeros_like(f))
     f_c = float(f[c])
     have_a = bool((f_fc != 0.0).any())
-    e_c = torch.zeros(ndof, dtype=f64, device=dev)
+    e_c = torch.zeros_like(f)
     e_c[c] = 1.0
     pcg_args = dict(tangent=True, preconditioner=config.nr_preconditioner, n_aggregates=config.nr_aggregates,
                     extra_fixed=[c])
-
-    def refuse(why):
-        raise RuntimeError(f"Tangent stiffness with control dof {c} removed is not positive definite ({why}): "
-                           "displacement control needs an SPD K' (a turning point of the control displacement or a "
-                           "bifurcation is not passed); choose another control dof or a smaller step")
+    refusals = tuple(f"Tangent stiffness with control dof {c} removed is not positive definite ({why}): "
+                     "displacement control needs an SPD K' (a turning point of the control displacement or a "
+                     "bifurcation is not passed); choose another control dof or a smaller step"
+                     for why in ("the CG residual does not come down", "rhs.x <= 0"))
 
     def checked(x, rhs, report):
-        _, ok, rr, bb = report
-        if not np.isfinite(rr) or (not ok and rr > 1e-4 * bb):
-            refuse("the CG residual does not come down")
-        if bb > 0.0 and not float(torch.dot(rhs, x)) > 0.0:
-            refuse("rhs.x <= 0")
+        _check_cg_step(True, rhs, x, *report[1:], None, refusals)      # rhs is zero outside F'
         return x
 
-    eng.gl_state(u, None, e0)
+    if s.e0 is None:                        # (with initial strains the pre-check has just formed this state)
+        eng.gl_state(u, None, None)
     lam = float(torch.dot(f[free_t], eng.gl_fint()[free_t])) / float(torch.dot(f[free_t], f[free_t]))
     has_converged, residual_norm, load_residual, ite = False, float("inf"), float("inf"), -1
     for ite in range(config.max_iterations):
         if ite > 0:
-            eng.gl_state(u, None, e0)       # (the first iterate's state is the one lam was started from)
+            eng.gl_state(u, None, s.e0)     # (the first iterate's state is the one lam was started from)
         R = eng.gl_fint() - lam * f
         du_c = ubar - float(u[c])
         k_c = eng.kt_v_f64(e_c)             # column c of K_t, every row
@@ -656,18 +645,16 @@ def _solve_nr_displacement(model, config, control_factor, u_initial, e0_np=None)
         if residual_norm <= config.tolerance and load_residual <= config.tolerance:
             has_converged = True
             break
-    strain = eng.gl_state(u, None, e0)
+    strain = eng.gl_state(u, None, s.e0)
     max_e = float(strain.abs().max()) if model.nelm else 0.0
     reactions = (eng.gl_fint() - lam * f).cpu().numpy()
-    reactions[free] = 0.0                   # the control dof is free: the load carries it, it has no reaction
     history = [{"load_factor": float(lam), "iterations": float(ite + 1), "residual": float(residual_norm),
                 "max_strain": float(max_e), "converged": float(1.0 if has_converged else 0.0),
                 "control_factor": float(control_factor), "control_displacement": float(ubar),
                 "load_residual": float(load_residual)}]
-    shape = (-1, 1) if model.dimension == 1 else (model.nnode, model.dimension)
-    return SolverResult(displacements=u.cpu().numpy().reshape(shape), reactions=reactions.reshape(shape),
-                        converged=has_converged, history=history,
-                        axial_forces=None if e0 is None else _axial_forces(model, strain, e0_np))
+    # the control dof is free: the load carries it, it has no reaction
+    return _result(model, u.cpu().numpy(), reactions, s.free, has_converged, history,
+                   axial_forces=None if s.e0 is None else _axial_forces(model, strain, s.e0_np))
 
 
 def _max_abs_strain(model, u) -> float:
@@ -746,16 +733,9 @@ def solve_hybrid(
         nr_iterations = nr_result.history[-1].get("iterations", 1) if nr_result.history else 1
         _say(f"  NR Phase: {nr_iterations} iterations")
         if gd_result:
-            gd_iterations = gd_result.history[-1].get("iteration", 0) if gd_result.history else 0
-            total_iterations = gd_iterations + nr_iterations
-            unified_history = []
-            if gd_result.history:
-                unified_history.extend(gd_result.history)
-            if nr_result.history:
-                nr_entry = nr_result.history[-1].copy()
-                nr_entry["iteration"] = total_iterations
-                unified_history.append(nr_entry)
-            nr_result.history = unified_history
+            # the Newton phase is one entry, its last, whose "iteration" becomes the total of both phases
+            nr_result.history = _shifted_history(gd_result.history, [dict(entry, iteration=nr_iterations)
+                                                                     for entry in nr_result.history[-1:]])
         _say(f"  Hybrid Total: {nr_result.history[-1].get('iteration', nr_iterations)} iterations")
         return nr_result
     _say("  NN parameters detected. Using GD for final convergence with tight tolerance.")
@@ -767,16 +747,7 @@ def solve_hybrid(
     final_result = solve_gd(model, final_config, measured_disp, measured_dofs, target_load_factor,
                             u_warm, skip_preconditioning=True)
     if gd_result:
-        gd_iterations = gd_result.history[-1].get("iteration", 0) if gd_result.history else 0
-        unified_history = []
-        if gd_result.history:
-            unified_history.extend(gd_result.history)
-        if final_result.history:
-            for entry in final_result.history:
-                new_entry = entry.copy()
-                new_entry["iteration"] = entry.get("iteration", 0) + gd_iterations
-                unified_history.append(new_entry)
-        final_result.history = unified_history
+        final_result.history = _shifted_history(gd_result.history, final_result.history)
     total_iterations = final_result.history[-1].get("iteration", 0) if final_result.history else 0
     _say(f"  Hybrid Total: {total_iterations} iterations")
     return final_result
