@@ -520,6 +520,18 @@ int pf_gl_strain_rhs(const pf_problem* p, const pf_gl* g, const double* u, const
                      void* stream);
 int pf_gl_strain_jvp(const pf_problem* p, const pf_gl* g, const double* u, const int* elems, int n_meas, const double* v,
                      int m, double* out, void* stream);
+/* Right-hand sides of the sensitivity solves K_t s = -d f_int / d t_h for m groups of elements (t_h: a strain ADDED to the
+ * initial strain e0 of every element of group h; the identification of a prestress, fem/prestress.py).  f_int is affine in
+ * e0 with d fe / d e0 = -(E*A / l0) d, so row k of out (dev double [m][n_dofs]) is, per dof, the sum over the elements e of
+ * the dof's node with elem_group[e] == g0 + k of +-(ea[e] / l0) d_e: + at the element's second node, - at its first,
+ * ascending incidence order, 0.0 on PF_DOF_FIXED dofs.  d = d0 + u_j - u_i is formed from g->d0 and u as pf_gl_strain_rhs
+ * forms it and l0 = |d0|: it needs no previous pf_gl_state and does not contain e0.  ea: dev double [n_elems], never null
+ * (the host fills the problem's own E*A in); elem_group: dev int [n_elems]; an id outside g0..g0+m-1 (-1, "e0 is given",
+ * included) adds nothing.  One node per thread, the group in blockIdx.y, no atomics: the same bits on every run, and row k
+ * of an m-row call is the bits of the (g0 + k, 1) call.  A null pointer, m < 1 (or above 65535, the grid's limit), g0 < 0
+ * or a bad mesh is PF_ERR_ARG before anything is enqueued.  Additive: the version stays 9. */
+int pf_gl_prestress_rhs(const pf_problem* p, const pf_gl* g, const double* ea, const double* u, const int* elem_group, int g0,
+                        int m, double* out, void* stream);
 /* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */
 int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream);
 /* out (dev double [n_dofs]) = the diagonal of K_t from the element blocks of kt: per dof the sum of the diagonal entries

@@ -108,6 +108,14 @@ def parse_problem(problem_file):
     #                                                 1; the level adds L^2 mean (e - ebar)^2 to the misfit); "dofs" and "u"
     #                                                 may then be empty, and the .res.json gains "strains" (every element's
     #                                                 strain at the last level)
+    #           "identify_prestress": {"prestress_groups": [...], "levels": [...], "groups": [...]|null, "t0": [...],
+    #                                  "prestress_scale": s, "max_evaluations": N, "damping": mu}
+    #                                                 identify one strain per prestress group (-1: the element's e0 is
+    #                                                 given) ADDED to "initial_strain", alone or (with "groups") together with
+    #                                                 the factors on E*A, from identify_nr's levels (method "nr";
+    #                                                 fem/prestress.py); not together with "identify_nr"; the .res.json gains
+    #                                                 "identified_prestress", "prestress_std", "identified_initial_strain",
+    #                                                 "axial_forces" and, with "groups", "identified_factors", "factor_std"
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -204,8 +212,13 @@ def parse_problem(problem_file):
         model._pf_mlp_dtype = str(accel["mlp_dtype"])
     parsed = {"model": model, "solver_config": solver_config, "measured_data": measured_data,
               "accel": accel}
+    if accel.get("identify_nr") is not None and accel.get("identify_prestress") is not None:
+        raise ValueError("accel holds both identify_nr and identify_prestress: a file runs one identification "
+                         "(identify_prestress takes the stiffness group map as its \"groups\").")
     if accel.get("identify_nr") is not None:
         parsed["identify_nr"] = _identify_block(accel["identify_nr"], solver_config)
+    if accel.get("identify_prestress") is not None:
+        parsed["identify_prestress"] = _identify_prestress_block(accel["identify_prestress"], solver_config)
     return parsed
 
 
@@ -232,6 +245,32 @@ def _identify_block(block, solver_config):
         out["method"] = str(block["method"])
     if block.get("damping") is not None:
         out["damping"] = float(block["damping"])
+    return out
+
+
+def _identify_prestress_block(block, solver_config):
+    """accel.identify_prestress, checked for its shape (what it holds is checked by fem.prestress.check_prestress)."""
+    shape = ('accel.identify_prestress must be {"prestress_groups": [...], "levels": [{"load_factor": .., "dofs": [..], '
+             '"u": [..]}, ..], "groups": [...] | null, "t0": [...], "prestress_scale": s, "max_evaluations": N, "damping": mu}; '
+             'a level may also hold "strain_elements": [..] and "strains": [..] (both or neither) and "strain_scale": L')
+    if (not isinstance(block, dict) or "levels" not in block or "prestress_groups" not in block
+            or not set(block) <= {"prestress_groups", "levels", "groups", "t0", "prestress_scale", "max_evaluations", "damping"}):
+        raise ValueError(shape)
+    levels = block["levels"]
+    base, gauges = {"load_factor", "dofs", "u"}, {"strain_elements", "strains"}
+    key_sets = (base, base | gauges, base | gauges | {"strain_scale"})
+    if not isinstance(levels, list) or not all(isinstance(lv, dict) and set(lv) in key_sets for lv in levels):
+        raise ValueError(shape)
+    if not isinstance(block["prestress_groups"], list):
+        raise ValueError(shape)
+    if solver_config.method != "nr":
+        raise ValueError(f'accel.identify_prestress belongs to the Newton-Raphson solve (method "nr"): method '
+                         f'{solver_config.method!r} does not support it.')
+    out = {"prestress_groups": block["prestress_groups"], "levels": levels, "groups": block.get("groups"),
+           "t0": block.get("t0")}
+    for key, kind in (("prestress_scale", float), ("max_evaluations", int), ("damping", float)):
+        if block.get(key) is not None:
+            out[key] = kind(block[key])
     return out
 
 
@@ -379,6 +418,8 @@ def solve_problem(parsed_data):
     log_print(f"Solver method: {solver_config.method}")
     if parsed_data.get("identify_nr") is not None:
         return _identify_problem(model, solver_config, parsed_data["identify_nr"])
+    if parsed_data.get("identify_prestress") is not None:
+        return _identify_prestress_problem(model, solver_config, parsed_data["identify_prestress"])
     result = solve(model=model, config=solver_config,
                    measured_disp=measured_data.get("values", None),
                    measured_dofs=measured_data.get("dofs", None))
@@ -448,6 +489,42 @@ def _identify_problem(model, solver_config, block):
                       covariance=as_list(res.covariance), stop=res.stop)
     if res.strains is not None:             # some level carries strain-gauge data: every element's strain at the last level
         output["strains"] = res.strains[-1].tolist()
+    return output
+
+
+def _identify_prestress_problem(model, solver_config, block):
+    """accel.identify_prestress: the prestress strains (and, with "groups", the factors on E*A) and the state of the last
+    load level at them."""
+    from ..fem.prestress import identify_prestress
+    kw = {key: block[key] for key in ("prestress_scale", "max_evaluations", "damping") if key in block}
+    res = identify_prestress(model, solver_config, block["levels"], block["prestress_groups"], groups=block["groups"],
+                             t0=block["t0"], **kw)
+    log_print(f"Prestress identification: {res.evaluations} evaluations, misfit {res.misfit:.3e}, stop {res.stop!r}, "
+              f"prestress {res.prestress.tolist()}")
+    as_list = lambda a: None if a is None else a.tolist()
+    output = {
+        "success": res.converged,
+        "converged": res.converged,
+        "iterations": res.evaluations,
+        "history": [{"misfit": h["misfit"], "gradient_norm": h["gradient_norm"], "factors": as_list(h["factors"]),
+                     "prestress": h["prestress"].tolist(), "accepted": h["accepted"], "damping": h["damping"],
+                     **({"error": h["error"]} if "error" in h else {})} for h in res.history],
+        "identified_prestress": res.prestress.tolist(),
+        "prestress_std": as_list(res.prestress_std),
+        "identified_initial_strain": res.initial_strain.tolist(),
+        "identified_ea": res.ea.tolist(),
+        "misfit": res.misfit,
+        "evaluations": res.evaluations,
+        "stop": res.stop,
+        "singular_values": as_list(res.singular_values),
+        "covariance": as_list(res.covariance),
+        "displacements": res.displacements[-1].tolist(),
+        "reactions": res.reactions.tolist(),
+        "strains": res.strains[-1].tolist(),
+        "axial_forces": res.axial_forces.tolist(),
+    }
+    if res.factors is not None:
+        output.update(identified_factors=res.factors.tolist(), factor_std=as_list(res.factor_std))
     return output
 
 

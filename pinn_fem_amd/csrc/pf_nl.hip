@@ -35,6 +35,12 @@
 // k_gl_strain_jvp: B v, that derivative applied to vectors, at the measured elements only: (d_e / l0^2).(v_j - v_i), one
 //             (gauge, row) pair per thread with the row in blockIdx.y; an element id outside the mesh writes 0.0 and
 //             reads nothing, k_group_sum's rule.
+// k_gl_prestress_rhs: the right-hand side of the sensitivity solve K_t s = -d f_int / d t_h for an additive initial strain
+//             t_h on the elements of group h: f_int is affine in e0 with d fe / d e0 = -(E*A / l0) d, so the row is the
+//             node gather of +-(ea_e / l0) d_e over the group's elements.  k_gl_group_rhs's shape: one node per thread, the
+//             group in blockIdx.y, two incidences per round whose codes, group ids, conn, d0 records and ea are loaded
+//             together, and an incidence of another group adds +0.0 by a select.  d is formed from d0 and u as
+//             k_gl_strain_rhs forms it, so it reads no record of pf_gl_state.  Fixed dofs get 0.0.  No atomics.
 #include <limits.h>
 #include <stdio.h>
 #include "pf_common.h"
@@ -244,6 +250,69 @@ __device__ __forceinline__ void load_strain_term(const pf_mesh& M, const double*
   for (int c = 0; c < DIM; ++c) out[c] = sg * (w * (d0[c] + du[c]));
 }
 
+// +-(ea[e] / l0) d of one incidence, load_strain_term's loads, signs and d; `in` false: +0.0 (the loads are issued all the same)
+template <int DIM>
+__device__ __forceinline__ void load_prestress_term(const pf_mesh& M, const double* __restrict__ d0_in, const double* __restrict__ u,
+                                                    const double* __restrict__ ea, int code, bool in, double* out) {
+  const int e = code >> 1;
+  const double sg = (code & 1) ? 1.0 : -1.0;
+  const int2 nn = reinterpret_cast<const int2*>(M.conn)[e];
+  double d0[DIM], du[DIM];
+  if (DIM == 2) {
+    const double2 g = reinterpret_cast<const double2*>(d0_in)[e];
+    const double2 ui = reinterpret_cast<const double2*>(u)[nn.x], uj = reinterpret_cast<const double2*>(u)[nn.y];
+    d0[0] = g.x; d0[DIM - 1] = g.y;
+    du[0] = uj.x - ui.x; du[DIM - 1] = uj.y - ui.y;
+  } else {
+    d0[0] = d0_in[e];
+    du[0] = u[nn.y] - u[nn.x];
+  }
+  double l02 = 0.0;
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) l02 += d0[c] * d0[c];
+  const double w = ea[e] / sqrt(l02);
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) {
+    const double t = sg * (w * (d0[c] + du[c]));
+    out[c] = in ? t : 0.0;
+  }
+}
+
+// out[k][dof] = sum of +-(ea[e] / l0) d_e over the node's elements e with elem_group[e] == g0 + k, k = blockIdx.y; 0.0 on
+// fixed dofs
+template <int DIM>
+__global__ __launch_bounds__(256) void k_gl_prestress_rhs(pf_problem P, const double* __restrict__ d0_in,
+                                                          const double* __restrict__ ea, const double* __restrict__ u,
+                                                          const int* __restrict__ elem_group, int g0, double* __restrict__ out) {
+  const pf_mesh& M = P.mesh;
+  const int group = g0 + (int)blockIdx.y;
+  double* __restrict__ row = out + (size_t)blockIdx.y * (size_t)M.n_dofs;
+  for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < M.n_nodes; node += gridDim.x * blockDim.x) {
+    const int b = M.adj_ptr[node], e_ = M.adj_ptr[node + 1];
+    double acc[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) acc[c] = 0.0;
+    for (int idx = b; idx < e_; idx += 2) {
+      const bool two = idx + 1 < e_;
+      const int code0 = M.adj[idx], code1 = M.adj[two ? idx + 1 : idx];
+      const bool in0 = elem_group[code0 >> 1] == group, in1 = two && elem_group[code1 >> 1] == group;
+      double t0[DIM], t1[DIM];
+      load_prestress_term<DIM>(M, d0_in, u, ea, code0, in0, t0);
+      load_prestress_term<DIM>(M, d0_in, u, ea, code1, in1, t1);
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) {
+        acc[c] += t0[c];
+        acc[c] += t1[c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const int dof = node * DIM + c;
+      row[dof] = (M.dof_flags[dof] & PF_DOF_FIXED) ? 0.0 : acc[c];
+    }
+  }
+}
+
 // out[dof] = sum over the node's incidences of +-(coef[e] / l0^2) d_e; accumulate: out += that sum, rounded first
 template <int DIM>
 __global__ __launch_bounds__(256) void k_gl_strain_rhs(pf_problem P, const double* __restrict__ d0_in,
@@ -418,6 +487,23 @@ int pf_gl_group_rhs(const pf_problem* p, const pf_gl* g, const int* elem_group, 
   const hipStream_t s = (hipStream_t)stream;
   if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_group_rhs<2>, grid, dim3(256), 0, s, *p, g->fe, elem_group, g0, out);
   else hipLaunchKernelGGL(k_gl_group_rhs<1>, grid, dim3(256), 0, s, *p, g->fe, elem_group, g0, out);
+  if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
+  return PF_OK;
+}
+
+int pf_gl_prestress_rhs(const pf_problem* p, const pf_gl* g, const double* ea, const double* u, const int* elem_group, int g0,
+                        int m, double* out, void* stream) {
+  const char* who = "pf_gl_prestress_rhs";
+  if (!mesh_ok(p) || !p->mesh.conn || !p->mesh.adj_ptr || !p->mesh.adj || !p->mesh.dof_flags || p->mesh.n_nodes < 0 ||
+      p->mesh.n_dofs != p->mesh.n_nodes * p->mesh.dim || !g || !g->d0 || !ea || !u || !elem_group || !out)
+    return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (m < 1 || m > 65535) return gl_fail(PF_ERR_ARG, who, "bad group count (m)");
+  if (g0 < 0 || g0 > INT_MAX - m) return gl_fail(PF_ERR_ARG, who, "bad first group (g0)");
+  if (p->mesh.n_nodes == 0) return PF_OK;
+  const dim3 grid(pf_node_blocks(p->mesh.n_nodes), m);
+  const hipStream_t s = (hipStream_t)stream;
+  if (p->mesh.dim == 2) hipLaunchKernelGGL(k_gl_prestress_rhs<2>, grid, dim3(256), 0, s, *p, g->d0, ea, u, elem_group, g0, out);
+  else hipLaunchKernelGGL(k_gl_prestress_rhs<1>, grid, dim3(256), 0, s, *p, g->d0, ea, u, elem_group, g0, out);
   if (hipGetLastError() != hipSuccess) return gl_fail(PF_ERR_HIP, who, "HIP launch failed");
   return PF_OK;
 }

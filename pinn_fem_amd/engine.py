@@ -228,6 +228,7 @@ class HipEngine:
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
         self._group_csr = None          # group_sum: (key of the group map, n_groups, device CSR pointer, device element ids)
         self._group_map = None          # gl_group_rhs: (key of the group map, n_groups, device int32 group ids)
+        self._prestress_map = None      # gl_prestress_rhs: the same of its own map (ids may be -1 there)
         self._configured = False
         env_k = os.environ.get("PINNFEM_GRAPH_ITERS")
         self.GRAPH_ITERS = int(env_k) if env_k else (self.GRAPH_ITERS_LARGE if hp.n_elems >= 200_000 else self.GRAPH_ITERS)
@@ -716,6 +717,45 @@ class HipEngine:
         out = torch.empty((m, self.plan.n_dofs), dtype=torch.float64, device=self.device)
         _capi.check(self.lib.pf_gl_group_rhs(self._ref(), C.byref(rec), ids.data_ptr(), g0, m, out.data_ptr(),
                                              self._stream()), "pf_gl_group_rhs")
+        return out
+
+    @_on_engine_stream
+    def gl_prestress_rhs(self, u: torch.Tensor, ea: Optional[torch.Tensor], groups, g0: int = 0,
+                         m: Optional[int] = None) -> torch.Tensor:
+        """Right-hand sides of the sensitivity solves K_t s_h = -d f_int / d t_h at the displacements u for the prestress
+        groups g0, ..., g0 + m - 1 (m None: every group from g0 on), t_h a strain added to the initial strain of the
+        elements of group h: row k is, per dof, the sum of +-(ea_e / l0) d_e over the node's elements of group g0 + k, zero
+        on fixed dofs (pf_gl_prestress_rhs).  ea: E*A of every element [n_elems] in float64; None: the model's scalar
+        E*A as the device forms it (each factor rounded to float32 first), filled in on the host side.  groups: [n_elems]
+        ints >= -1; -1: the element belongs to no group.  The device copy of the last group map is cached.  It reads d0
+        and u only: no gl_state is needed first.  Returns [m, n_dofs]."""
+        ne = self.plan.n_elems
+        uu = self._f64_vector("gl_prestress_rhs", "u", u, self.plan.n_dofs, "dofs")
+        gm = np.ascontiguousarray(np.asarray(groups).reshape(-1))
+        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < -1 or gm.max() >= 2 ** 31)):
+            raise ValueError(f"gl_prestress_rhs: groups must hold one group id >= -1 for each of the {ne} elements")
+        gm = gm.astype(np.int64)
+        key = gm.tobytes()
+        if self._prestress_map is None or self._prestress_map[0] != key:
+            ids = gm.astype(np.int32) if ne else np.zeros(1, dtype=np.int32)
+            self._prestress_map = (key, int(gm.max()) + 1 if ne else 0, torch.from_numpy(ids).to(self.device))
+        _, n_groups, ids = self._prestress_map
+        g0 = int(g0)
+        m = n_groups - g0 if m is None else int(m)
+        if g0 < 0 or m < 1:
+            raise ValueError(f"gl_prestress_rhs: no groups in the range asked for (g0 = {g0}, m = {m}, {n_groups} groups)")
+        if ea is None:
+            mat = self.model.material
+            ee = torch.full((max(ne, 1),), float(np.float32(mat.young.value())) * float(np.float32(mat.area.value())),
+                            dtype=torch.float64, device=self.device)
+        else:
+            ee = self._f64_vector("gl_prestress_rhs", "ea", ea, ne, "elements")
+            if not ne:
+                ee = torch.zeros(1, dtype=torch.float64, device=self.device)
+        rec = self._gl_buffers()[4]
+        out = torch.empty((m, self.plan.n_dofs), dtype=torch.float64, device=self.device)
+        _capi.check(self.lib.pf_gl_prestress_rhs(self._ref(), C.byref(rec), ee.data_ptr(), uu.data_ptr(), ids.data_ptr(), g0, m,
+                                                 out.data_ptr(), self._stream()), "pf_gl_prestress_rhs")
         return out
 
     @_on_engine_stream

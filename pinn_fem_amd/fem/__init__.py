@@ -5,15 +5,19 @@ from .boundary import free_and_fixed_dofs
 
 __all__ = ["FEMModel", "Material", "Property", "ScalarProperty", "NNProperty", "to_property",
            "free_and_fixed_dofs", "IdentifyResult", "check_identify", "identify_nr", "misfit_and_gradient", "residuals_and_jacobian",
-           "check_strains"]
+           "check_strains", "PrestressResult", "check_prestress", "identify_prestress", "residuals_and_jacobian_prestress"]
 
 _IDENTIFY = ("IdentifyResult", "check_identify", "identify_nr", "misfit_and_gradient", "residuals_and_jacobian",
              "check_strains")
+_PRESTRESS = ("PrestressResult", "check_prestress", "identify_prestress", "residuals_and_jacobian_prestress")
 
 
 def __getattr__(name):
-    # fem.identify imports the solver (and with it the engine): only when it is asked for
+    # fem.identify and fem.prestress import the solver (and with it the engine): only when they are asked for
     if name in _IDENTIFY:
         from . import identify
         return getattr(identify, name)
+    if name in _PRESTRESS:
+        from . import prestress
+        return getattr(prestress, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -44,7 +44,7 @@ the error goes into the factors.
 
 Limits: states with a positive definite tangent only (the CG solves), load control only, a scalar base material, no
 regularisation term, no bounds on the factors and no weight per sensor but strain_scale; what a set of gauges
-determines is what the singular values of A say, not more.  The initial strain is given, not identified.
+determines is what the singular values of A say, not more.  The initial strain is given here; fem/prestress.py identifies it.
 """
 from __future__ import annotations
 
