@@ -181,6 +181,29 @@ __device__ __forceinline__ void load_x(float (&x)[3], const pf_problem& P, int e
   }
 }
 
+// the same from the coordinate array alone (k_net32_forward2's task loop, which reads its base pointers from the kernel
+// argument task by task); x[0], the load factor, is the caller's
+template <int IN>
+__device__ __forceinline__ void load_x_from(float (&x)[3], const float* __restrict__ ecent, int e) {
+  if (IN == 3) {
+    const float2 c = reinterpret_cast<const float2*>(ecent)[e];
+    x[1] = c.x;
+    x[2] = c.y;
+  } else {
+    x[1] = ecent[e];
+    x[2] = 0.f;
+  }
+}
+
+// the problem record in the kernel-argument segment (pf_problem is every net kernel's FIRST argument: offset 0), behind an
+// opaque move: what is read through it is loaded where the read stands and not hoisted to the top of the launch
+__device__ __forceinline__ const __attribute__((address_space(4))) pf_problem* kernarg_problem() {
+  const __attribute__((address_space(4))) pf_problem* pk =
+      (const __attribute__((address_space(4))) pf_problem*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(pk));
+  return pk;
+}
+
 __device__ __forceinline__ void copy_image(unsigned char* dst, const unsigned char* __restrict__ src, int bytes) {
   const uint4* __restrict__ s = reinterpret_cast<const uint4*>(src);
   uint4* d = reinterpret_cast<uint4*>(dst);
@@ -916,21 +939,15 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward(pf_problem P, int 
   const int per_round = gridDim.x * waves;
   const int rounds = (ntasks + per_round - 1) / per_round;        // block-uniform trip count: equal barrier counts
   int task = blockIdx.x * waves + wv;
-  float xn[3];
-  // ws: this launch also writes the stiffness records from both properties: the other property and the element geometry
-  // travel with the coordinates, one round ahead (loaded where they are used they cost a global round trip per round)
+  float xn[3] = {0.f, 0.f, 0.f};
+  // ws: this launch also writes the stiffness records from both properties: a round loads the other property and the
+  // element geometry of its own task at its head (nothing reads them before the stores: a whole task to land); only the
+  // coordinates travel a round ahead.  (All three a round ahead under `if (r + 1 < rounds)` met their old values at the
+  // loop's join: a second register set, and the copies there stood behind s_waitcnt vmcnt(0), which on this ISA counts
+  // the round's own stores: see k_net32_forward2.)
   const pf_net onet = P.net[1 - which];
   const float* __restrict__ oprop = which == 0 ? P.prop_a : P.prop_e;
-  float on = onet.scale;
-  ElemGeo gn = ElemGeo{0.f, 0.f, 0.f, 1.f};
-  if (n > 0) {
-    const int e0 = min(task * 64 + lane, n - 1);
-    load_x<IN>(xn, P, e0);
-    if (ws) {
-      if (onet.enabled) on = oprop[e0];
-      gn = load_geo(P.mesh.egeo, e0);
-    }
-  }
+  if (n > 0) load_x<IN>(xn, P, min(task * 64 + lane, n - 1));
   // the stop flag, one read per block (the bookkeeping that raises it may run beside this launch: a block whose waves
   // disagreed would part ways before the lockstep barriers below)
   __shared__ int s_done;
@@ -945,25 +962,36 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward(pf_problem P, int 
   const float bo = reinterpret_cast<const float*>(smem + pf_n32_off_bo())[0];
   unsigned long long st0 = 0, sr0 = 0;
   if (dbg & 16) { st0 = __builtin_amdgcn_s_memtime(); sr0 = __builtin_amdgcn_s_memrealtime(); }
+  // an empty use of the coordinates on their way: the compiler's wait for them stands where this is called (below, in front
+  // of the stores, and here in front of the loop: on every way to the loop's head)
+  auto x_landed = [&]() {
+    if constexpr (IN == 3) asm volatile("" : : "v"(xn[1]), "v"(xn[2]));
+    else asm volatile("" : : "v"(xn[1]));
+  };
+  x_landed();
   for (int r = 0; r < rounds; ++r, task += per_round) {
     if (grp == 0) __builtin_amdgcn_s_barrier();
     const int e = task * 64 + lane;
-    float x0[3], x1[3];
-    sfor<0, 3>([&](auto c) { constexpr int C = c; both_tiles(xn[C], x0[C], x1[C]); });
-    const float o = on;
-    const ElemGeo g = gn;
-    if (r + 1 < rounds) {
-      const int en = min(e + per_round * 64, n - 1);
-      load_x<IN>(xn, P, en);
-      if (ws) {
-        if (onet.enabled) on = oprop[en];
-        gn = load_geo(P.mesh.egeo, en);
-      }
+    float o = onet.scale;
+    ElemGeo g = ElemGeo{0.f, 0.f, 0.f, 1.f};
+    if (ws) {
+      const int ec = min(e, n - 1);
+      if (onet.enabled) o = oprop[ec];
+      g = load_geo(P.mesh.egeo, ec);
     }
+    float x0[3], x1[3];
+    x0[0] = x1[0] = xn[0];       // (the load factor: one value for the launch, nothing to exchange)
+    sfor<1, 3>([&](auto c) { constexpr int C = c; both_tiles(xn[C], x0[C], x1[C]); });
+    // the next round's coordinates, in EVERY round (past the last one the clamped index names a valid element nobody reads)
+    load_x<IN>(xn, P, min(e + per_round * 64, n - 1));
     typename E::template TileAct<L, false> A0, A1;
     float p0, p1;
     E::template forward_tiles<L, IN, false>(smem, lane, x0, x1, A0, A1, p0, p1, dbg, grp);
     const float z = own_total(p0, p1) * (1.0f / PF_N32_KA) + bo;
+    // every load of this round is waited for HERE, a net after its issue and in front of the stores: behind the stores (which
+    // sit behind a branch) a wait for an older load is a wait for the stores as well (k_net32_forward2)
+    x_landed();
+    if (ws) asm volatile("" : : "v"(o), "v"(g.l0));
     if (e < n) {
       const float v = (net.positive ? pf_softplus(z) : z) * net.scale;
       out[e] = v;
@@ -1021,7 +1049,10 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     copy_images2(smem, reinterpret_cast<const unsigned char*>(P.net_op + P.op_off[0]), smem + IMGP,
                  reinterpret_cast<const unsigned char*>(P.net_op + P.op_off[1]), IMG);
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  const int lane = threadIdx.x & 63, waves = blockDim.x >> 6;
+  // (readfirstlane: provably wave-uniform, so the task loop's counters live in scalar registers and its tests branch on SCC;
+  //  as a plain shift they sat in vector registers and the loop body was cut into exec-masked regions)
+  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int n = P.mesh.n_elems;
   const int ntasks = (n + 63) >> 6;
   const int per_block = (ntasks + (int)gridDim.x - 1) / (int)gridDim.x;
@@ -1033,13 +1064,8 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     s_next_n = 0;
   }
   int task = t0 + wv;
-  float xn[3];
-  ElemGeo gn = ElemGeo{0.f, 0.f, 0.f, 1.f};
-  if (n > 0) {
-    const int e0 = min(task * 64 + lane, n - 1);
-    load_x<IN>(xn, P, e0);
-    gn = load_geo(P.mesh.egeo, e0);
-  }
+  float xn[3] = {0.f, 0.f, 0.f};
+  if (n > 0) load_x<IN>(xn, P, min(task * 64 + lane, n - 1));
   // node tasks of this block (gu_nb > 0)
   constexpr int GUN = 64 * PF_GU_M;
   const int n_ntasks = gu_nb > 0 ? (P.mesh.n_nodes + GUN - 1) / GUN : 0;
@@ -1059,9 +1085,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     // what the task needs of the problem is read from the kernel argument HERE (P is the first argument: offset 0 of the
     // kernarg segment), behind an opaque move: left to the compiler, every pointer is loaded once at the top of the launch
     // and the element loop spills scalar registers (75 against 7 without the node tasks)
-    const __attribute__((address_space(4))) pf_problem* pk =
-        (const __attribute__((address_space(4))) pf_problem*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(pk));
+    const __attribute__((address_space(4))) pf_problem* pk = kernarg_problem();
     const NodeView NV = node_view_from(pk);
     const GraduConsts GK = gradu_consts_from(pk);
     float su = node_gradu_task<IN - 1, PF_GU_M>(NV, gu_k, GK, (nt0 + k) * GUN, lane);
@@ -1084,29 +1108,47 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
   if (s_done || n <= 0) return;
   const float bo_e = reinterpret_cast<const float*>(img_e + pf_n32_off_bo())[0];
   const float bo_a = reinterpret_cast<const float*>(img_a + pf_n32_off_bo())[0];
+  // an empty use of the coordinates on their way: the compiler's wait for them stands where this is called (see the stores
+  // below), on EVERY way to the loop's head, or the wait at the head comes back
+  auto x_landed = [&]() {
+    if constexpr (IN == 3) asm volatile("" : : "v"(xn[1]), "v"(xn[2]));
+    else asm volatile("" : : "v"(xn[1]));
+  };
+  x_landed();
   while (task < t1 || gu) {
     if (gu && (since >= gu_every || task >= t1)) {
-      // a node task: the next element task's inputs (already on their way) are not touched
+      // a node task: the next element task's inputs are not touched
       since = 0;
       gu = node_task();
+      x_landed();
       continue;
     }
     if (task >= t1) break;
     ++since;
+    // The element path's base pointers are read from the kernel argument where they are needed, behind an opaque move like
+    // the node task's: the scalar registers do not hold them across the loop (left to the compiler it reloads them inside
+    // the task, each load with its own s_waitcnt lgkmcnt(0) in front of the first use).  The two input pointers leave ahead
+    // of the queue draw, whose wait for the LDS atomic covers them.
+    const __attribute__((address_space(4))) pf_problem* pin = kernarg_problem();
+    const float* __restrict__ const ecent = pin->mesh.ecent;
+    const float* __restrict__ const egeo = pin->mesh.egeo;
     // the task after this one: drawn now so that its inputs travel while this one computes
     int k = 0;
     if (lane == 0) k = atomicAdd(&s_next, 1);
     const int nxt = t0 + __builtin_amdgcn_readfirstlane(k);
-    const bool more = nxt < t1;
     const int e = task * 64 + lane;
+    // The task's own geometry: nothing reads it before store_k at the task's end, a whole task for the load to land.  Carried
+    // a task ahead under `if (more)`, it met its old value at the loop's join and got a second register set; the copies
+    // stood at the join behind s_waitcnt vmcnt(0), and on this ISA vmcnt counts stores: every task waited until its own
+    // three stores were acknowledged.
+    const ElemGeo g = load_geo(egeo, min(e, n - 1));
     float x0[3], x1[3];
-    sfor<0, 3>([&](auto c) { constexpr int C = c; both_tiles(xn[C], x0[C], x1[C]); });
-    const ElemGeo g = gn;
-    if (more) {
-      const int en = min(nxt * 64 + lane, n - 1);
-      load_x<IN>(xn, P, en);
-      gn = load_geo(P.mesh.egeo, en);
-    }
+    x0[0] = x1[0] = xn[0];       // (the load factor: one value for the launch, nothing to exchange)
+    sfor<1, 3>([&](auto c) { constexpr int C = c; both_tiles(xn[C], x0[C], x1[C]); });
+    // The next task's coordinates leave HERE, behind the last use of this task's (the half-wave exchange), into the
+    // registers the next task reads.  In EVERY task: past the block's last task the clamped index names valid elements
+    // nobody reads (as in backward_phase), so no loaded register meets an old value at a join.
+    load_x_from<IN>(xn, ecent, min(nxt * 64 + lane, n - 1));
     float ze, za;
     {
       typename EE::template TileAct<L, false> A0, A1;
@@ -1120,12 +1162,24 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
       EA::template forward_tiles<L, IN, false>(img_a, lane, x0, x1, A0, A1, p0, p1, dbg);
       za = own_total(p0, p1) * (1.0f / PF_N32_KA) + bo_a;
     }
+    // the output pointers leave ahead of the softplus; their wait sits at the stores' address arithmetic
+    const __attribute__((address_space(4))) pf_problem* pout = kernarg_problem();
+    float* __restrict__ const prop_e = pout->prop_e;
+    float* __restrict__ const prop_a = pout->prop_a;
+    float* __restrict__ const rec = pout->elem_k;
+    // Both loads of this task (geometry, the next task's coordinates) are waited for HERE, two nets after their issue and in
+    // front of the stores.  The stores sit behind a branch (`e < n`: no lane may be left), so the compiler's count of what is
+    // in flight at the loop's head is the smaller of two ways: any wait behind the stores for a load issued before them is
+    // a wait for the stores as well.  With the empty uses below no such wait exists: the wave issues its three stores and
+    // goes on, the next vmcnt wait is this place of the next task.
+    x_landed();
+    asm volatile("" : : "v"(g.l0));
     if (e < n) {
       const float ve = (net_e.positive ? pf_softplus(ze) : ze) * net_e.scale;
       const float va = (net_a.positive ? pf_softplus(za) : za) * net_a.scale;
-      P.prop_e[e] = ve;
-      P.prop_a[e] = va;
-      if (P.elem_k) store_k<IN - 1>(P.elem_k, e, g, (ve * va) / g.l0);    // (young * area) / l0, nn_assembly.py:74, :37
+      prop_e[e] = ve;
+      prop_a[e] = va;
+      if (rec) store_k<IN - 1>(rec, e, g, (ve * va) / g.l0);    // (young * area) / l0, nn_assembly.py:74, :37
     }
     task = nxt;
   }
