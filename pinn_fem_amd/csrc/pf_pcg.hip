@@ -101,18 +101,6 @@ __global__ __launch_bounds__(256) void k_kt_diag64(pf_problem P, const double* _
   }
 }
 
-__device__ __forceinline__ double block_sum64(double v, double* smem) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if (lane == 0) smem[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < nw; ++i) t += smem[i];
-  return t;
-}
-
 // ---- several right-hand sides per launch ----------------------------------------------------------------------------
 // Every CG kernel below serves right-hand side k = blockIdx.y of a launch with grid (blocks, m): its b and x are rows k of
 // [m][n_dofs] arrays (stride xs = n_dofs) and every part of its workspace lies wss doubles behind the same part of
@@ -148,7 +136,7 @@ __global__ __launch_bounds__(256) void k_pcg_init(pf_problem P, const double* __
       rz += bi * zi; bb += bi * bi;
     }
   }
-  const double t0 = block_sum64(rz, red), t1 = block_sum64(bb, red);
+  const double t0 = pf_block_sum_d(rz, red), t1 = pf_block_sum_d(bb, red);
   if (threadIdx.x == 0) { part[blockIdx.x] = t0; part[PF_NODE_SLOTS + blockIdx.x] = t1; }
 }
 
@@ -174,7 +162,7 @@ __global__ __launch_bounds__(256) void k_pcg_ap(pf_problem P, const double* __re
       pap += p[dof] * a;
     }
   }
-  const double t = block_sum64(pap, red);
+  const double t = pf_block_sum_d(pap, red);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
@@ -187,7 +175,7 @@ __global__ __launch_bounds__(1024) void k_pcg_scalars(double* st, const double* 
   __shared__ double red[16];
   double a = 0.0, b = 0.0;
   for (int i = threadIdx.x; i < nb; i += blockDim.x) { a += part[i]; b += part[PF_NODE_SLOTS + i]; }
-  const double ta = block_sum64(a, red), tb = block_sum64(b, red);
+  const double ta = pf_block_sum_d(a, red), tb = pf_block_sum_d(b, red);
   if (threadIdx.x != 0) return;
   if (phase == 0) {
     st[ST_RZ] = ta; st[ST_BB] = tb; st[ST_RR] = tb; st[ST_ITERS] = 0.0; st[ST_RTOL2] = rtol2;
@@ -221,7 +209,7 @@ __global__ __launch_bounds__(256) void k_pcg_update(const double* __restrict__ s
     z[i] = zi;
     rz += ri * zi; rr += ri * ri;
   }
-  const double t0 = block_sum64(rz, red), t1 = block_sum64(rr, red);
+  const double t0 = pf_block_sum_d(rz, red), t1 = pf_block_sum_d(rr, red);
   if (threadIdx.x == 0) { part[blockIdx.x] = t0; part[PF_NODE_SLOTS + blockIdx.x] = t1; }
 }
 
@@ -238,7 +226,7 @@ __global__ __launch_bounds__(256) void k_pcg_dir(const double* __restrict__ st, 
 // ---- two-level preconditioner: M^-1 r = dinv r + Z (Z^T K Z)^-1 Z^T r -------------------------------------------------
 // Z is held as per-dof coefficients: column agg_off[a] + k of Z has zcoef[dof][k] on the dofs of aggregate a's nodes and
 // zeros elsewhere (pinnfem_hip.h: pf_coarse).  Every sum over an aggregate runs over its node list (ascending node
-// id) strided over the block's threads and then through block_sum64: a fixed order, no atomics.
+// id) strided over the block's threads and then through pf_block_sum_d: a fixed order, no atomics.
 
 // columns of aggregate J at one node: the node's coefficient rows if it belongs to J, zeros otherwise
 template <int DIM>
@@ -348,7 +336,7 @@ __global__ __launch_bounds__(256) void k_coarse_setup(pf_problem P, const double
     for (int ki = 0; ki < PF_COARSE_MODES; ++ki)
 #pragma unroll
       for (int kj = 0; kj < PF_COARSE_MODES; ++kj) {
-        const double t = block_sum64(acc[ki][kj], red);
+        const double t = pf_block_sum_d(acc[ki][kj], red);
         if (threadIdx.x == 0 && ki < nI && kj < nJ) ac[(size_t)(offI + ki) * nc + offJ + kj] = t;
       }
   }
@@ -388,10 +376,10 @@ __global__ __launch_bounds__(256) void k_pcg2_restrict(pf_coarse C, const double
   }
 #pragma unroll
   for (int k = 0; k < PF_COARSE_MODES; ++k) {
-    const double t = block_sum64(acc[k], red);
+    const double t = pf_block_sum_d(acc[k], red);
     if (threadIdx.x == 0 && k < nk) w[off + k] = t;
   }
-  const double t = block_sum64(rr, red);
+  const double t = pf_block_sum_d(rr, red);
   if (threadIdx.x == 0) part[PF_NODE_SLOTS + a] = t;
 }
 
@@ -441,7 +429,7 @@ __global__ __launch_bounds__(256) void k_pcg2_apply(pf_coarse C, const double* _
       rz += ri * zi;
     }
   }
-  const double t = block_sum64(rz, red);
+  const double t = pf_block_sum_d(rz, red);
   if (threadIdx.x == 0) part[a] = t;
 }
 
@@ -452,7 +440,7 @@ __global__ __launch_bounds__(256) void k_pcg2_rz0(double* st, const double* __re
   __shared__ double red[8];
   double a = 0.0;
   for (int i = threadIdx.x; i < nb; i += blockDim.x) a += part[i];
-  const double t = block_sum64(a, red);
+  const double t = pf_block_sum_d(a, red);
   if (threadIdx.x == 0) st[ST_RZ] = t;
 }
 

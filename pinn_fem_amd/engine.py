@@ -227,8 +227,7 @@ class HipEngine:
         self._fixed_views = {}          # extra fixed dofs (tuple) -> (device dof_flags copy, PfProblem view, host fixed mask)
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
         self._group_csr = None          # group_sum: (key of the group map, n_groups, device CSR pointer, device element ids)
-        self._group_map = None          # gl_group_rhs: (key of the group map, n_groups, device int32 group ids)
-        self._prestress_map = None      # gl_prestress_rhs: the same of its own map (ids may be -1 there)
+        self._group_maps = {}           # _device_group_map: method name -> (key of its last map, n_groups, device int32 ids)
         self._configured = False
         env_k = os.environ.get("PINNFEM_GRAPH_ITERS")
         self.GRAPH_ITERS = int(env_k) if env_k else (self.GRAPH_ITERS_LARGE if hp.n_elems >= 200_000 else self.GRAPH_ITERS)
@@ -620,15 +619,33 @@ class HipEngine:
             raise ValueError(f"{who}: out must be a contiguous float64 vector of {n} entries on {self.device}")
         return out, True
 
-    def _group_ids(self, who, groups, bound=None):
-        """A group map checked: (ids int64 [n_elems], their bytes as a cache key, number of groups).  bound: ids must stay
-        below it."""
+    def _group_ids(self, who, groups, lowest=0, bound=None):
+        """A group map checked: (ids int64 [n_elems], their bytes as a cache key, number of groups).  lowest: the lowest id
+        admitted, 0 or -1 (the element belongs to no group); bound: ids must stay below it."""
         ne = self.plan.n_elems
         gm = np.ascontiguousarray(np.asarray(groups).reshape(-1))
-        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < 0 or (bound is not None and gm.max() >= bound))):
-            raise ValueError(f"{who}: groups must hold one non-negative group id for each of the {ne} elements")
-        gm = gm.astype(np.int64)
-        return gm, gm.tobytes(), int(gm.max()) + 1 if ne else 0
+        top = int(gm.max()) if gm.size and gm.dtype.kind in "iu" else -1
+        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < lowest or (bound is not None and top >= bound))):
+            what = "non-negative group id" if lowest == 0 else f"group id >= {lowest}"
+            raise ValueError(f"{who}: groups must hold one {what} for each of the {ne} elements")
+        gm = gm.astype(np.int64, copy=False)         # read only from here on
+        return gm, gm.tobytes(), top + 1
+
+    def _device_group_map(self, who, groups, lowest=0):
+        """(number of groups, device int32 ids) of a group map; each method keeps its last map's copy, since the joint
+        identification calls gl_group_rhs and gl_prestress_rhs in turn with two maps."""
+        gm, key, n_groups = self._group_ids(who, groups, lowest, bound=2 ** 31)
+        if who not in self._group_maps or self._group_maps[who][0] != key:
+            ids = gm.astype(np.int32) if gm.size else np.zeros(1, dtype=np.int32)
+            self._group_maps[who] = (key, n_groups, torch.from_numpy(ids).to(self.device))
+        return self._group_maps[who][1:]
+
+    @staticmethod
+    def _group_range(who, n_groups, g0, m):
+        g0, m = int(g0), n_groups - int(g0) if m is None else int(m)
+        if g0 < 0 or m < 1:
+            raise ValueError(f"{who}: no groups in the range asked for (g0 = {g0}, m = {m}, {n_groups} groups)")
+        return g0, m
 
     @_on_engine_stream
     def gl_state(self, u: torch.Tensor, ea: Optional[torch.Tensor] = None, e0: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -704,15 +721,8 @@ class HipEngine:
         ..., g0 + m - 1 (m None: every group from g0 on): row k is minus the internal force of the elements of group
         g0 + k alone, zero on fixed dofs (pf_gl_group_rhs).  groups: [n_elems] non-negative ints.  The device copy of the
         last group map is cached.  Returns [m, n_dofs]."""
-        gm, key, n_groups = self._group_ids("gl_group_rhs", groups, bound=2 ** 31)
-        if self._group_map is None or self._group_map[0] != key:
-            ids = gm.astype(np.int32) if gm.size else np.zeros(1, dtype=np.int32)
-            self._group_map = (key, n_groups, torch.from_numpy(ids).to(self.device))
-        ids = self._group_map[2]
-        g0 = int(g0)
-        m = n_groups - g0 if m is None else int(m)
-        if g0 < 0 or m < 1:
-            raise ValueError(f"gl_group_rhs: no groups in the range asked for (g0 = {g0}, m = {m}, {n_groups} groups)")
+        n_groups, ids = self._device_group_map("gl_group_rhs", groups)
+        g0, m = self._group_range("gl_group_rhs", n_groups, g0, m)
         rec = self._gl_ready("gl_group_rhs")[4]
         out = torch.empty((m, self.plan.n_dofs), dtype=torch.float64, device=self.device)
         _capi.check(self.lib.pf_gl_group_rhs(self._ref(), C.byref(rec), ids.data_ptr(), g0, m, out.data_ptr(),
@@ -731,19 +741,8 @@ class HipEngine:
         and u only: no gl_state is needed first.  Returns [m, n_dofs]."""
         ne = self.plan.n_elems
         uu = self._f64_vector("gl_prestress_rhs", "u", u, self.plan.n_dofs, "dofs")
-        gm = np.ascontiguousarray(np.asarray(groups).reshape(-1))
-        if gm.size != ne or (ne and (gm.dtype.kind not in "iu" or gm.min() < -1 or gm.max() >= 2 ** 31)):
-            raise ValueError(f"gl_prestress_rhs: groups must hold one group id >= -1 for each of the {ne} elements")
-        gm = gm.astype(np.int64)
-        key = gm.tobytes()
-        if self._prestress_map is None or self._prestress_map[0] != key:
-            ids = gm.astype(np.int32) if ne else np.zeros(1, dtype=np.int32)
-            self._prestress_map = (key, int(gm.max()) + 1 if ne else 0, torch.from_numpy(ids).to(self.device))
-        _, n_groups, ids = self._prestress_map
-        g0 = int(g0)
-        m = n_groups - g0 if m is None else int(m)
-        if g0 < 0 or m < 1:
-            raise ValueError(f"gl_prestress_rhs: no groups in the range asked for (g0 = {g0}, m = {m}, {n_groups} groups)")
+        n_groups, ids = self._device_group_map("gl_prestress_rhs", groups, lowest=-1)
+        g0, m = self._group_range("gl_prestress_rhs", n_groups, g0, m)
         if ea is None:
             mat = self.model.material
             ee = torch.full((max(ne, 1),), float(np.float32(mat.young.value())) * float(np.float32(mat.area.value())),

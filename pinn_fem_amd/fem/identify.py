@@ -343,11 +343,12 @@ def residuals_and_jacobian(model: FEMModel, config: SolverConfig, levels, ea, gr
     return _residuals(s, model, config, levels, torch.from_numpy(ea_np).to(s.eng.device), groups, states, jacobian)
 
 
-def _residuals(s, model, config, levels, ea_t, groups, states=None, jacobian=True):
-    """residuals_and_jacobian on checked input: s, levels and ea_t as _misfit takes them, groups check_identify's, states
-    None or one per level."""
+def _residuals(s, model, config, levels, ea_t, groups, states=None, jacobian=True, prestress=None):
+    """residuals_and_jacobian on checked input: s, levels and ea_t as _misfit takes them (s.e0 this evaluation's initial
+    strain), groups check_identify's, states None or one per level.  prestress: a prestress group map (fem/prestress.py)
+    whose gl_prestress_rhs rows are stacked under the factors' rows, so A = [A_q | A_t]; groups may then be None."""
     eng, dev = s.eng, s.eng.device
-    _solver._pre_check(s, ea_t)             # solve_nr's rule at the starting state u = 0, with this evaluation's ea
+    _solver._pre_check(s, ea_t)             # solve_nr's rule at the starting state u = 0, with this evaluation's ea and e0
     counters = dict(dict.fromkeys(_GN_COUNTERS, 0), jacobians=int(bool(jacobian)))
     u = s.u
     rho, rows, out_states = [], [], []
@@ -366,7 +367,9 @@ def _residuals(s, model, config, levels, ea_t, groups, states=None, jacobian=Tru
             w_e = scale / np.sqrt(p)
             rho.append(r_e.cpu().numpy() * w_e)
         if jacobian:
-            B = eng.gl_group_rhs(groups)
+            B = None if prestress is None else eng.gl_prestress_rhs(u, ea_t, prestress)
+            if groups is not None:
+                B = eng.gl_group_rhs(groups) if B is None else torch.cat([eng.gl_group_rhs(groups), B], dim=0)
             S, reports = eng.pcg_solve_many(B, preconditioner=config.nr_preconditioner, n_aggregates=config.nr_aggregates, u=u)
             for g, (it_s, ok_s, rr, bb) in enumerate(reports):
                 _solver._check_cg_step(True, B[g], S[g], ok_s, rr, bb, s.free_t)
@@ -380,29 +383,25 @@ def _residuals(s, model, config, levels, ea_t, groups, states=None, jacobian=Tru
         A = np.concatenate(rows, axis=0)
         dead = np.flatnonzero(~np.any(A != 0.0, axis=0))
         if dead.size:
-            raise RuntimeError(f"group {int(dead[0])} moves no measured dof and no gauge (a zero column of the Jacobian): its "
-                               "factor is not determined by these measurements")
+            c, n_q = int(dead[0]), 0 if groups is None else int(groups.max()) + 1
+            name = f"group {c}" if prestress is None else f"stiffness group {c}" if c < n_q else f"prestress group {c - n_q}"
+            raise RuntimeError(f"{name} moves no measured dof and no gauge (a zero column of the Jacobian): its "
+                               f"{'factor' if prestress is None else 'parameter'} is not determined by these measurements")
     return np.concatenate(rho), A, out_states, counters
 
 
-def _gauss_newton(s, model, config, levels, groups, q_start, ea_of, max_evaluations, gtol, misfit_tolerance, damping,
-                  step_tolerance):
-    """Levenberg-Marquardt on the log-factors (identify_nr, method "gauss-newton"); s, levels, groups as _residuals' are.
-    Returns (q, rho, A, states, history, counters, stop, evaluations) with q, rho, A and states those of the last accepted
-    point."""
-    counters = dict.fromkeys(_GN_COUNTERS, 0)
-
-    def evaluate(q_np, **kw):
-        ea_t = torch.from_numpy(_check_ea(model, ea_of(q_np))).to(s.eng.device)
-        out = _residuals(s, model, config, levels, ea_t, groups, **kw)
-        _add_counters(counters, out[3])
-        return out[:3]
-
-    q = q_start
-    rho, A, states = evaluate(q)
+def _levenberg_marquardt(evaluate, x_start, describe, max_evaluations, gtol, misfit_tolerance, damping, step_tolerance,
+                         reject_errors=True):
+    """The Levenberg-Marquardt loop of identify_nr(method="gauss-newton") and identify_prestress, whose docstrings state its
+    stops and its mu rule.  evaluate(x, states=None, jacobian=True) returns (rho, A or None, states); describe(x) the
+    history's view of x.  reject_errors: a trial point whose evaluation raises RuntimeError is a rejected step (mu <- 10 mu,
+    the history entry carries the message under "error" and misfit None); otherwise the error propagates.
+    Returns (x, rho, A, states, history, stop, evaluations) of the last accepted point."""
+    x = x_start
+    rho, A, states = evaluate(x)            # the first evaluation's error propagates
     J, mu, evaluations = float(rho @ rho), float(damping), 1
-    history = [{"misfit": J, "gradient_norm": float(np.linalg.norm(2.0 * A.T @ rho)), "factors": np.exp(q),
-                "accepted": True, "damping": mu}]
+    history = [{"misfit": J, "gradient_norm": float(np.linalg.norm(2.0 * A.T @ rho)), **describe(x), "accepted": True,
+                "damping": mu}]
     while True:
         if J <= misfit_tolerance:
             stop = "misfit"
@@ -418,14 +417,21 @@ def _gauss_newton(s, model, config, levels, groups, q_start, ea_of, max_evaluati
         if np.max(np.abs(delta)) <= step_tolerance:
             stop = "step"
             break
-        rho_t, _, states_t = evaluate(q + delta, jacobian=False)
-        evaluations += 1
-        J_t = float(rho_t @ rho_t)
-        entry = {"misfit": J_t, "gradient_norm": None, "factors": np.exp(q + delta), "accepted": J_t < J, "damping": mu}
+        entry = {"misfit": None, "gradient_norm": None, **describe(x + delta), "accepted": False, "damping": mu}
         history.append(entry)
+        evaluations += 1
+        try:
+            rho_t, _, states_t = evaluate(x + delta, jacobian=False)
+            J_t = entry["misfit"] = float(rho_t @ rho_t)
+        except RuntimeError as exc:
+            if not reject_errors:
+                raise
+            J_t = float("inf")
+            entry["error"] = str(exc)
         if J_t < J:
-            q, rho, J, states = q + delta, rho_t, J_t, states_t
-            _, A, _ = evaluate(q, states=states)                # the Jacobian at the trial's own states: no Newton solves
+            x, rho, J, states = x + delta, rho_t, J_t, states_t
+            _, A, _ = evaluate(x, states=states)                # the Jacobian at the trial's own states: no Newton solves
+            entry["accepted"] = True
             entry["gradient_norm"] = float(np.linalg.norm(2.0 * A.T @ rho))
             mu = max(mu / 10.0, 1e-12)
         else:
@@ -433,6 +439,24 @@ def _gauss_newton(s, model, config, levels, groups, q_start, ea_of, max_evaluati
             if mu > 1e12:
                 stop = "damping"
                 break
+    return x, rho, A, states, history, stop, evaluations
+
+
+def _gauss_newton(s, model, config, levels, groups, q_start, ea_of, max_evaluations, gtol, misfit_tolerance, damping,
+                  step_tolerance):
+    """_levenberg_marquardt on the log-factors (identify_nr, method "gauss-newton"); s, levels, groups as _residuals' are.  A
+    trial's error propagates.  Returns (q, rho, A, states, history, counters, stop, evaluations)."""
+    counters = dict.fromkeys(_GN_COUNTERS, 0)
+
+    def evaluate(q_np, **kw):
+        ea_t = torch.from_numpy(_check_ea(model, ea_of(q_np))).to(s.eng.device)
+        out = _residuals(s, model, config, levels, ea_t, groups, **kw)
+        _add_counters(counters, out[3])
+        return out[:3]
+
+    q, rho, A, states, history, stop, evaluations = _levenberg_marquardt(
+        evaluate, q_start, lambda q: {"factors": np.exp(q)}, max_evaluations, gtol, misfit_tolerance, damping, step_tolerance,
+        reject_errors=False)
     return q, rho, A, states, history, counters, stop, evaluations
 
 

@@ -13,7 +13,7 @@ f_int(u_k; ea, e0) = lam_k f with respect to t_h,
 
 on the tangent the Newton loop has just converged on.  All H right-hand sides of a level are one launch; they are stacked
 under the G right-hand sides of the factors (pf_gl_group_rhs) and solved by one pcg_solve_many behind one preconditioner
-setup.  The rows of the Jacobian are formed exactly as identify._residuals forms them: s at the measured dofs over
+setup.  identify._residuals forms these rows as it forms the factors': s at the measured dofs over
 sqrt|m_k|, and (L / sqrt p) B s at the gauges (pf_gl_strain_jvp).  The measured strain is the TOTAL strain e: it depends on
 t only through u.  The joint Jacobian is A = [A_q | A_t].
 
@@ -34,8 +34,9 @@ import numpy as np
 import torch
 
 from . import solver as _solver
-from .identify import (_GN_COUNTERS, _add_counters, _base_ea, _check_ea, _checked, _newton_level, _strain_residual,
+from .identify import (_GN_COUNTERS, _add_counters, _base_ea, _check_ea, _checked, _levenberg_marquardt, _newton_level,
                        check_gauss_newton)
+from .identify import _residuals as _factor_residuals
 from .model import FEMModel
 from .solver import SolverConfig
 
@@ -142,101 +143,11 @@ def residuals_and_jacobian_prestress(model: FEMModel, config: SolverConfig, leve
 
 def _residuals(s, model, config, levels, pg, t, groups, q, states=None, jacobian=True):
     """residuals_and_jacobian_prestress on checked input: s the solver's _newton_setup with the BASE initial strain, the
-    rest check_prestress's."""
+    rest check_prestress's.  This point's e0 and ea, then identify._residuals with the prestress map."""
     e0_np = _initial_strain(s, model, pg, t)
-    eng, dev = s.eng, s.eng.device
-    s = s._replace(e0_np=e0_np, e0=torch.from_numpy(e0_np).to(dev))
-    ea_t = torch.from_numpy(_check_ea(model, _ea_of(model, groups, q))).to(dev)
-    n_q = len(q)
-    _solver._pre_check(s, ea_t)             # solve_nr's rule at the starting state u = 0, with this evaluation's ea and e0
-    counters = dict(dict.fromkeys(_GN_COUNTERS, 0), jacobians=int(bool(jacobian)))
-    u = s.u
-    rho, rows, out_states = [], [], []
-    for k, (lam, dofs, ubar, gauges) in enumerate(levels):
-        if states is None:
-            u = _newton_level(s, model, config, lam, u, ea_t, counters)
-        else:
-            u = states[k].to(device=dev, dtype=torch.float64).reshape(-1)
-        dofs_t = torch.from_numpy(dofs).to(dev)
-        w = 1.0 / np.sqrt(len(dofs)) if len(dofs) else 0.0
-        rho.append((u[dofs_t] - torch.from_numpy(ubar).to(dev)).cpu().numpy() * w)
-        if jacobian or gauges is not None:
-            e = eng.gl_state(u, ea_t, s.e0)
-        if gauges is not None:
-            _, r_e, scale, p = _strain_residual(eng, e, gauges)
-            w_e = scale / np.sqrt(p)
-            rho.append(r_e.cpu().numpy() * w_e)
-        if jacobian:
-            B = eng.gl_prestress_rhs(u, ea_t, pg)
-            if n_q:
-                B = torch.cat([eng.gl_group_rhs(groups), B], dim=0)
-            S, reports = eng.pcg_solve_many(B, preconditioner=config.nr_preconditioner, n_aggregates=config.nr_aggregates, u=u)
-            for g, (it_s, ok_s, rr, bb) in enumerate(reports):
-                _solver._check_cg_step(True, B[g], S[g], ok_s, rr, bb, s.free_t)
-                counters["sensitivity_cg_iterations"] += int(it_s)
-            rows.append(S[:, dofs_t].t().cpu().numpy() * w)
-            if gauges is not None:
-                rows.append(eng.gl_strain_jvp(u, gauges[0], S).t().cpu().numpy() * w_e)
-        out_states.append(u)
-    A = None
-    if jacobian:
-        A = np.concatenate(rows, axis=0)
-        dead = np.flatnonzero(~np.any(A != 0.0, axis=0))
-        if dead.size:
-            c = int(dead[0])
-            name = f"stiffness group {c}" if c < n_q else f"prestress group {c - n_q}"
-            raise RuntimeError(f"{name} moves no measured dof and no gauge (a zero column of the Jacobian): its parameter is "
-                               "not determined by these measurements")
-    return np.concatenate(rho), A, out_states, counters
-
-
-def _levenberg_marquardt(evaluate, x_start, describe, max_evaluations, gtol, misfit_tolerance, damping, step_tolerance):
-    """identify._gauss_newton's loop on x, with its stops and its mu rule.  evaluate(x, states=None, jacobian=True) returns
-    (rho, A or None, states); describe(x) the history's view of x.  One difference: a trial point whose evaluation raises
-    RuntimeError is a rejected step (mu <- 10 mu, the history entry carries the message under "error" and misfit None).
-    Returns (x, rho, A, states, history, stop, evaluations) of the last accepted point."""
-    x = x_start
-    rho, A, states = evaluate(x)            # the first evaluation's error propagates
-    J, mu, evaluations = float(rho @ rho), float(damping), 1
-    history = [{"misfit": J, "gradient_norm": float(np.linalg.norm(2.0 * A.T @ rho)), **describe(x), "accepted": True,
-                "damping": mu}]
-    while True:
-        if J <= misfit_tolerance:
-            stop = "misfit"
-            break
-        if np.max(np.abs(2.0 * A.T @ rho)) <= gtol:
-            stop = "gradient"
-            break
-        if evaluations >= int(max_evaluations):
-            stop = "cap"
-            break
-        H = A.T @ A
-        delta = np.linalg.solve(H + mu * np.diag(np.diag(H)), -(A.T @ rho))
-        if np.max(np.abs(delta)) <= step_tolerance:
-            stop = "step"
-            break
-        entry = {"misfit": None, "gradient_norm": None, **describe(x + delta), "accepted": False, "damping": mu}
-        history.append(entry)
-        evaluations += 1
-        try:
-            rho_t, _, states_t = evaluate(x + delta, jacobian=False)
-            J_t = float(rho_t @ rho_t)
-            entry["misfit"] = J_t
-        except RuntimeError as exc:
-            J_t = float("inf")
-            entry["error"] = str(exc)
-        if J_t < J:
-            x, rho, J, states = x + delta, rho_t, J_t, states_t
-            _, A, _ = evaluate(x, states=states)                # the Jacobian at the trial's own states: no Newton solves
-            entry["accepted"] = True
-            entry["gradient_norm"] = float(np.linalg.norm(2.0 * A.T @ rho))
-            mu = max(mu / 10.0, 1e-12)
-        else:
-            mu *= 10.0
-            if mu > 1e12:
-                stop = "damping"
-                break
-    return x, rho, A, states, history, stop, evaluations
+    s = s._replace(e0_np=e0_np, e0=torch.from_numpy(e0_np).to(s.eng.device))
+    ea_t = torch.from_numpy(_check_ea(model, _ea_of(model, groups, q))).to(s.eng.device)
+    return _factor_residuals(s, model, config, levels, ea_t, groups, states, jacobian, prestress=pg)
 
 
 def identify_prestress(model: FEMModel, config: Optional[SolverConfig], levels, prestress_groups, groups=None, t0=None,

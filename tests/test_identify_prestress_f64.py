@@ -214,6 +214,40 @@ def test_bad_arguments_are_argument_errors(systems):
         eng.gl_prestress_rhs(S.dev(uu), S.dev(ee)[:-1], groups)
 
 
+def test_the_two_group_map_slots_do_not_evict_each_other(systems):
+    """The joint identification calls gl_group_rhs(groups) and gl_prestress_rhs(u, ea, pg) in turn with two maps.  On one
+    engine, twice in turn: every result is, to the bit, what a fresh engine returns for that call alone, and after the first
+    pair each method's cached device map stays the same tensor at the same address (the first pair's tensors are held here,
+    so an upload in the second pair could not land on their addresses)."""
+    from pinn_fem_amd.engine import HipEngine
+    S = systems("truss_257")
+    rng = np.random.default_rng(11)
+    u, ea = S.dev(gl_field(S, "large", rng)), S.dev(EA * np.exp2(rng.uniform(-1.0, 1.0, S.ne)))
+    groups, pg = rng.integers(0, 4, S.ne), rng.integers(-1, 3, S.ne)
+    calls = (lambda eng: eng.gl_group_rhs(groups), lambda eng: eng.gl_prestress_rhs(u, ea, pg))
+
+    def bits(eng, call):
+        out = call(eng)
+        torch.cuda.synchronize()
+        return out.cpu().numpy().tobytes()
+
+    want = []
+    for call in calls:
+        fresh = HipEngine(S.model)
+        fresh.gl_state(u, ea)
+        want.append(bits(fresh, call))
+    eng = S.eng
+    eng.gl_state(u, ea)
+    assert [bits(eng, call) for call in calls] == want and want[0] != want[1]
+    held = {who: slot[2] for who, slot in eng._group_maps.items()}
+    ptrs = {who: t.data_ptr() for who, t in held.items()}
+    assert sorted(held) == ["gl_group_rhs", "gl_prestress_rhs"] and ptrs["gl_group_rhs"] != ptrs["gl_prestress_rhs"]
+    assert [bits(eng, call) for call in calls] == want
+    for who, t in held.items():
+        assert eng._group_maps[who][2] is t and t.data_ptr() == ptrs[who], who
+    print(f"truss_257: both calls twice in turn, the bits of a fresh engine each time; device maps at {ptrs} throughout")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. residuals_and_jacobian_prestress, identify_prestress and the CLI
 # ---------------------------------------------------------------------------------------------------------------------

@@ -203,6 +203,42 @@ def test_the_loop_rejects_a_trial_whose_evaluation_raises():
         prestress._levenberg_marquardt(broken, np.zeros(2), describe, 50, 1e-12, 0.0, 1e-3, 1e-12)
 
 
+def test_the_loop_without_rejection_propagates_a_trial_error_and_is_the_same_loop():
+    """identify._levenberg_marquardt with reject_errors=False, as identify_nr(method="gauss-newton") runs it: the evaluation
+    of the test above, which raises on its second call, propagates.  On the linear problem without that fault the two settings
+    take the same path: the same x, stop, evaluations and history values; identify_nr's describe gives its entries no
+    "prestress" key, and neither run has an "error" key."""
+    from pinn_fem_amd.fem import identify, prestress
+    assert prestress._levenberg_marquardt is identify._levenberg_marquardt
+    target = np.array([1.0, 2.0])
+    calls = []
+
+    def evaluate(x, states=None, jacobian=True):
+        calls.append(jacobian)
+        if len(calls) == 2:
+            raise RuntimeError("Tangent stiffness is not positive definite at the starting state: slack")
+        return x - target, (np.eye(2) if jacobian else None), ["state"]
+
+    factors = lambda x: {"factors": np.exp(x)}
+    with pytest.raises(RuntimeError, match="slack"):
+        identify._levenberg_marquardt(evaluate, np.zeros(2), factors, 50, 1e-12, 1e-20, 1e-3, 1e-12, reject_errors=False)
+    assert calls == [True, False]                                   # it ended at the trial
+
+    linear = lambda x, states=None, jacobian=True: (x - target, (np.eye(2) if jacobian else None), ["state"])
+    both = lambda x: {"factors": np.exp(x), "prestress": x.copy()}
+    plain = identify._levenberg_marquardt(linear, np.zeros(2), factors, 50, 1e-12, 1e-20, 1e-3, 1e-12, reject_errors=False)
+    rejecting = identify._levenberg_marquardt(linear, np.zeros(2), both, 50, 1e-12, 1e-20, 1e-3, 1e-12, reject_errors=True)
+    print(f"stop {plain[5]!r}, {plain[6]} evaluations, history {plain[4]}")
+    assert plain[5] == rejecting[5] == "misfit" and plain[6] == rejecting[6] == len(plain[4]) == len(rejecting[4])
+    for a, b in zip(plain[:3], rejecting[:3]):                      # x, rho, A
+        assert np.array_equal(a, b)
+    assert np.allclose(plain[0], target, atol=1e-9)
+    for h, g in zip(plain[4], rejecting[4]):
+        assert list(h) == ["misfit", "gradient_norm", "factors", "accepted", "damping"]
+        assert list(g) == ["misfit", "gradient_norm", "factors", "prestress", "accepted", "damping"]
+        assert all(np.array_equal(h[key], g[key]) for key in h) and h["accepted"] is True
+
+
 # ---- 3. refusals ----------------------------------------------------------------------------------------------------
 def _model():
     from pinn_fem_amd.fem.model import FEMModel, Material
