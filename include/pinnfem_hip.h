@@ -219,7 +219,7 @@ int pf_padded_width(int width);
 int pf_net_pad_count(int in_dim, int width, int n_hidden);
 /* padded-image index (inside the net's image) of the net's `local`-th torch parameter */
 int pf_net_pad_index(int in_dim, int width, int n_hidden, int local);
-/* sizeof of the ABI structs: 0 pf_mesh, 1 pf_net, 2 pf_state, 3 pf_problem, 4 pf_scalar_id, 5 pf_coarse, 6 pf_gl (binding self-check) */
+/* sizeof of the ABI structs: 0 pf_mesh, 1 pf_net, 2 pf_state, 3 pf_problem, 4 pf_scalar_id, 5 pf_coarse, 6 pf_gl, 7 pf_dyn (binding self-check) */
 int pf_sizeof(int what);
 /* floats of operand-image workspace (pf_problem.net_op) one net needs with the MFMA32 engine, or <0 */
 int pf_net_op_count(int in_dim, int width, int n_hidden);
@@ -532,6 +532,46 @@ int pf_gl_strain_jvp(const pf_problem* p, const pf_gl* g, const double* u, const
  * or a bad mesh is PF_ERR_ARG before anything is enqueued.  Additive: the version stays 9. */
 int pf_gl_prestress_rhs(const pf_problem* p, const pf_gl* g, const double* ea, const double* u, const int* elem_group, int g0,
                         int m, double* out, void* stream);
+/* ---- explicit dynamics of the Green-Lagrange element (pf_nl.hip) ------------------------------------------
+ * Central differences with a lumped mass and mass-proportional damping alpha.  With u_n, v_{n-1/2}, t_n = n dt and
+ * lam(t) = lam0 + (lam1 - lam0) min(1, t / t_ramp) (t_ramp = 0: lam1), step n is ONE launch, one node per thread:
+ *   f_int(u_n)  the element above, N = E*A (e - e0), formed per incidence from g->d0 and u_n and summed per node in
+ *               ascending incidence order (it reads no record of pf_gl_state and writes none)
+ *   v_{n+1/2} = c1 v_{n-1/2} + gk (lam(t_n) f_ext - f_int(u_n)) minv     c1 = (1 - alpha dt/2) / (1 + alpha dt/2)
+ *   u_{n+1}   = u_n + dt v_{n+1/2}                                       gk = dt / (1 + alpha dt/2)
+ * and PF_DOF_FIXED dofs get v = 0.0, u = 0.0.  v is advanced in place; u_n is read from u0 for even n and from u1 for odd n
+ * and u_{n+1} is written to the other.  n lives on the device in *clock: launch k of a sequence uses *clock + k, and a
+ * last one-thread launch adds the sequence's length, so a captured sequence can be replayed.  No atomics: the same bits on
+ * every run, eager or replayed.  All arrays dev double, caller-owned. */
+typedef struct pf_dyn {
+  const double* minv;    /* [n_dofs] 1 / lumped mass of the dof's node */
+  const double* f_ext;   /* [n_dofs] the load at load factor 1 */
+  const double* ea;      /* [n_elems] E*A of every element, or null: the problem's own (as pf_gl_state_ea) */
+  const double* e0;      /* [n_elems] initial strain, or null (as pf_gl_state_e0) */
+  double* u0;            /* [n_dofs] u_n for even n */
+  double* u1;            /* [n_dofs] u_n for odd n */
+  double* v;             /* [n_dofs] v_{n-1/2} */
+  long long* clock;      /* [1] n */
+  double dt, alpha, lam0, lam1, t_ramp;
+} pf_dyn;
+/* doubles of pf_gl_dyn_energy's out4: the four results, then its block partials */
+#define PF_DYN_ENERGY_COUNT (4 + 4 * PF_MAX_NODE_BLOCKS)
+/* pf_gl_dyn_start: the half kick from (u_0, v_0) at *clock == 0 (read back and checked; anything else is PF_ERR_ARG): the
+ *   step's launch with c1 = 1 - alpha dt/2 and gk = dt/2, which leaves v_{1/2} and u_1, and the clock at 1.
+ * pf_gl_dyn_steps: n_steps step launches and the clock's.
+ * pf_gl_dyn_graph_create: the same sequence captured as one hipGraph, a single chain (handle for pf_graph_launch /
+ *   pf_graph_destroy); the record is baked in by value, the clock is read when the launches run.
+ * pf_gl_dyn_energy: at the state the clock points to (u_{n+1}, v_{n+1/2}), out4[0] = sum m v^2 / 2, out4[1] =
+ *   sum E*A l0 (e - e0)^2 / 2, out4[2] = f_ext.u, out4[3] = max |v|; out4: dev double [PF_DYN_ENERGY_COUNT].  Two launches
+ *   (block partials, then one block), a fixed order.
+ * A null required pointer (ea and e0 may be null), dt <= 0 or non-finite, alpha < 0, t_ramp < 0, n_steps < 1 or a bad mesh
+ * is PF_ERR_ARG, with a pf_last_error text that begins with the function's name, before anything is enqueued.  Additive:
+ * the version stays 9. */
+int pf_gl_dyn_start(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, void* stream);
+int pf_gl_dyn_steps(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, int n_steps, void* stream);
+int pf_gl_dyn_graph_create(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, int n_steps, void* stream,
+                           void** graph_out);
+int pf_gl_dyn_energy(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, double* out4, void* stream);
 /* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */
 int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream);
 /* out (dev double [n_dofs]) = the diagonal of K_t from the element blocks of kt: per dof the sum of the diagonal entries

@@ -28,6 +28,7 @@ PF_KERNEL_SLOTS = 9
 PF_COARSE_MAX_AGG, PF_COARSE_MODES = 256, 3
 PF_COARSE_MAX = PF_COARSE_MAX_AGG * PF_COARSE_MODES
 PF_PCG_MAX_RHS = 2
+PF_DYN_ENERGY_COUNT = 4 + 4 * PF_MAX_NODE_BLOCKS
 PF_GRAPH_CONT_HEAD, PF_GRAPH_NO_TAIL = 1, 2
 PF_GRAPH_FORM_FOLDED_RESIDUAL = 1
 PF_FUSED_FORWARD, PF_FUSED_BACKWARD, PF_FUSED_THETA_UPDATE, PF_FUSED_U_PINGPONG, PF_FUSED_U_UPDATE = 1, 2, 4, 8, 16
@@ -115,10 +116,18 @@ class PfGl(C.Structure):
     _fields_ = [("d0", C.c_void_p), ("kt", C.c_void_p), ("fe", C.c_void_p), ("strain", C.c_void_p)]
 
 
+class PfDyn(C.Structure):
+    _fields_ = [("minv", C.c_void_p), ("f_ext", C.c_void_p), ("ea", C.c_void_p), ("e0", C.c_void_p),
+                ("u0", C.c_void_p), ("u1", C.c_void_p), ("v", C.c_void_p), ("clock", C.c_void_p),
+                ("dt", C.c_double), ("alpha", C.c_double), ("lam0", C.c_double), ("lam1", C.c_double),
+                ("t_ramp", C.c_double)]
+
+
 # every symbol include/pinnfem_hip.h declares: name -> (restype, argtypes)
 _PP = C.POINTER(PfProblem)
 _PC = C.POINTER(PfCoarse)
 _PG = C.POINTER(PfGl)
+_PD = C.POINTER(PfDyn)
 SYMBOLS = {
     "pf_abi_version": (C.c_int, []),
     "pf_last_error": (C.c_char_p, []),
@@ -180,6 +189,10 @@ SYMBOLS = {
     "pf_gl_strain_rhs": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_gl_strain_jvp": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_gl_prestress_rhs": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pf_gl_dyn_start": (C.c_int, [_PP, _PG, _PD, C.c_void_p]),
+    "pf_gl_dyn_steps": (C.c_int, [_PP, _PG, _PD, C.c_int, C.c_void_p]),
+    "pf_gl_dyn_graph_create": (C.c_int, [_PP, _PG, _PD, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pf_gl_dyn_energy": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_void_p]),
     "pf_kt_v_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_kt_diag_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_pcgt_begin": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
@@ -267,7 +280,7 @@ def load():
         fn.argtypes = args
     if lib.pf_abi_version() != PF_ABI_VERSION:
         raise PinnFemHipError("libpinnfem_hip.so ABI version mismatch; rebuild the library")
-    for idx, st in enumerate((PfMesh, PfNet, PfState, PfProblem, PfScalarId, PfCoarse, PfGl)):
+    for idx, st in enumerate((PfMesh, PfNet, PfState, PfProblem, PfScalarId, PfCoarse, PfGl, PfDyn)):
         if lib.pf_sizeof(idx) != C.sizeof(st):
             raise PinnFemHipError(
                 f"struct layout mismatch for {st.__name__}: C {lib.pf_sizeof(idx)} vs ctypes {C.sizeof(st)}")

@@ -116,6 +116,14 @@ def parse_problem(problem_file):
     #                                                 fem/prestress.py); not together with "identify_nr"; the .res.json gains
     #                                                 "identified_prestress", "prestress_std", "identified_initial_strain",
     #                                                 "axial_forces" and, with "groups", "identified_factors", "factor_std"
+    #           "dynamics": {"t_end": T | "n_steps": N, "dt": dt, "dt_safety": s, "damping": alpha, "ramp_time": t,
+    #                        "load_factor_initial": l0, "load_factor_final": l1, "record_every": k, "record_dofs": [...],
+    #                        "nodal_mass": m | [...], "rest_tolerance": r, "u_initial": [...], "v_initial": [...]}
+    #                                                 explicit time integration of the green-lagrange structure in place of
+    #                                                 the static solve (fem/dynamics.py): central differences,
+    #                                                 lumped mass from the material's density; the .res.json holds the last
+    #                                                 step's displacements and reactions and gains "dynamics" (times,
+    #                                                 recorded displacements, energies, dt, steps, at_rest)
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -219,7 +227,31 @@ def parse_problem(problem_file):
         parsed["identify_nr"] = _identify_block(accel["identify_nr"], solver_config)
     if accel.get("identify_prestress") is not None:
         parsed["identify_prestress"] = _identify_prestress_block(accel["identify_prestress"], solver_config)
+    if accel.get("dynamics") is not None:
+        if "identify_nr" in parsed or "identify_prestress" in parsed:
+            raise ValueError("accel holds both dynamics and an identification: a file runs one of them.")
+        parsed["dynamics"] = _dynamics_block(accel["dynamics"])
     return parsed
+
+
+_DYNAMICS_KEYS = {"dt": float, "dt_safety": float, "t_end": float, "n_steps": int, "damping": float, "ramp_time": float,
+                  "load_factor_initial": float, "load_factor_final": float, "record_every": int, "record_dofs": list,
+                  "nodal_mass": None, "rest_tolerance": float}
+
+
+def _dynamics_block(block):
+    """accel.dynamics, checked for its shape (what it holds is checked by fem.dynamics.check_dynamics): the DynamicsConfig
+    and the initial state."""
+    from ..fem.dynamics import DynamicsConfig
+    if not isinstance(block, dict) or not set(block) <= set(_DYNAMICS_KEYS) | {"u_initial", "v_initial"}:
+        raise ValueError("accel.dynamics must be an object with keys out of "
+                         f"{sorted(set(_DYNAMICS_KEYS) | {'u_initial', 'v_initial'})}")
+    try:
+        kw = {key: (block[key] if kind is None else kind(block[key])) for key, kind in _DYNAMICS_KEYS.items()
+              if block.get(key) is not None}
+    except (TypeError, ValueError):
+        raise ValueError("accel.dynamics holds a value of the wrong type") from None
+    return {"config": DynamicsConfig(**kw), "u_initial": block.get("u_initial"), "v_initial": block.get("v_initial")}
 
 
 def _identify_block(block, solver_config):
@@ -420,6 +452,8 @@ def solve_problem(parsed_data):
         return _identify_problem(model, solver_config, parsed_data["identify_nr"])
     if parsed_data.get("identify_prestress") is not None:
         return _identify_prestress_problem(model, solver_config, parsed_data["identify_prestress"])
+    if parsed_data.get("dynamics") is not None:
+        return _dynamics_problem(model, solver_config, parsed_data["dynamics"])
     result = solve(model=model, config=solver_config,
                    measured_disp=measured_data.get("values", None),
                    measured_dofs=measured_data.get("dofs", None))
@@ -462,6 +496,25 @@ def solve_problem(parsed_data):
         output["nn_parameters"] = {k: v.tolist() for k, v in result.nn_parameters.items()}
         output["identified_properties"] = extract_nn_properties(model)
     return output
+
+
+def _dynamics_problem(model, solver_config, block):
+    """accel.dynamics: the time integration and the state of its last step."""
+    from ..fem.dynamics import solve_dynamic
+    res = solve_dynamic(model, solver_config, block["config"], u_initial=block["u_initial"], v_initial=block["v_initial"])
+    log_print(f"Dynamics: {res.steps} steps of dt = {res.dt:.6g}, at rest: {res.at_rest}, residual {res.residual_norm:.3e}")
+    return {
+        "success": True,
+        "converged": bool(res.at_rest),
+        "iterations": res.steps,
+        "history": [],
+        "displacements": res.displacements.flatten().tolist(),
+        "reactions": res.reactions.flatten().tolist(),
+        "axial_forces": res.axial_forces.tolist(),
+        "dynamics": {"times": res.times.tolist(), "recorded_displacements": res.recorded.tolist(), "energies": res.energies,
+                     "velocities": res.velocities.flatten().tolist(), "residual_norm": res.residual_norm, "dt": res.dt,
+                     "steps": res.steps, "at_rest": bool(res.at_rest)},
+    }
 
 
 def _identify_problem(model, solver_config, block):

@@ -277,6 +277,7 @@ int pf_sizeof(int what) {
     case 4: return (int)sizeof(pf_scalar_id);
     case 5: return (int)sizeof(pf_coarse);
     case 6: return (int)sizeof(pf_gl);
+    case 7: return (int)sizeof(pf_dyn);
   }
   return PF_ERR_ARG;
 }

@@ -31,9 +31,17 @@
 //                       get 0.0, or stay untouched when it accumulates.
 // k_group_sum: out[g] = sum of values[e] * weights[e] over the elements of group g (CSR, ascending element id): one
 //   workgroup per group, thread t adds elements t, t + 256, ... in that order, then pf_block_sum_d.  No atomics.
+// Explicit dynamics (central differences, lumped mass, mass-proportional damping):
+//   k_gl_dyn_step       node_gather with +-(ea (e - e0) / l0) d formed from d0 and u (dyn_term), the store advancing the
+//                       node's own v (in place) and u (into the other of two buffers): one launch per time step.
+//   k_gl_dyn_clock      adds a sequence's length to the step number on the device, so that a captured sequence replays.
+//   k_gl_dyn_energy     per-block partials of the kinetic and strain energy, f_ext.u and max |v|; k_gl_dyn_energy_sum adds
+//                       them in one block.  pf_block_sum_d, a fixed order, no atomics.
 #include <limits.h>
+#include <math.h>
 #include <stdio.h>
 #include "pf_common.h"
+#include "pf_graph.h"
 
 namespace {
 
@@ -295,6 +303,133 @@ __global__ __launch_bounds__(256) void k_gl_strain_rhs(pf_problem P, const doubl
     });
 }
 
+// ---- explicit dynamics: the central-difference step -----------------------------------------------------
+// the strain that carries stress, e - e0, of element e from d0 and u, with e as k_gl_state forms it (the difference of squares
+// written out); also the element's E*A (ea and e0 nullable, the same decision in every thread), d0, du and l0^2
+template <int DIM>
+__device__ __forceinline__ double dyn_strain(const pf_problem& P, const double* d0_in, const double* u, const double* ea_in,
+                                             const double* e0_in, int e, double* d0, double* du, double& l02, double& ea) {
+  int ni, nj;
+  load_gl_geo<DIM>(P.mesh, d0_in, u, e, ni, nj, d0, du);
+  ea = ea_in ? ea_in[e] : elem_ea64(P, e);
+  double d0du = 0.0, dudu = 0.0;
+  l02 = 0.0;
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) { l02 += d0[c] * d0[c]; d0du += d0[c] * du[c]; dudu += du[c] * du[c]; }
+  const double strain = (2.0 * d0du + dudu) / (2.0 * l02);
+  return e0_in ? strain - e0_in[e] : strain;
+}
+
+// +-(ea (e - e0) / l0) d: k_gl_state's fe formed per incidence, so a step reads no element record
+template <int DIM>
+struct dyn_term {
+  const pf_problem& P;
+  const double* __restrict__ d0_in;
+  const double* __restrict__ u;
+  const double* __restrict__ ea_in;
+  const double* __restrict__ e0_in;
+  __device__ __forceinline__ void operator()(int code, double* out) const {
+    const int e = code >> 1;
+    const double sg = (code & 1) ? 1.0 : -1.0;
+    double d0[DIM], du[DIM], l02, ea;
+    const double se = dyn_strain<DIM>(P, d0_in, u, ea_in, e0_in, e, d0, du, l02, ea);
+    const double n_l0 = (ea * se) / sqrt(l02);
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) out[c] = sg * (n_l0 * (d0[c] + du[c]));
+  }
+};
+
+// the displacements of step n: the steps ping-pong between u0 and u1, step n reads buffer n & 1 and writes the other
+__device__ __forceinline__ const double* dyn_u_at(const pf_dyn& D, long long n) { return (n & 1) ? D.u1 : D.u0; }
+
+// Step n = *clock + k of the sequence, one node per thread:
+//   v <- c1 v + g (lam(t_n) f_ext - f_int(u_n)) / m,   u_{n+1} = u_n + dt v;   fixed dofs: v = 0, u = 0.
+// A thread reads and writes only its own dofs of v (in place); its neighbours read u_n, so u_{n+1} goes to the other buffer.
+template <int DIM>
+__global__ __launch_bounds__(256) void k_gl_dyn_step(pf_problem P, const double* __restrict__ d0_in, pf_dyn D, long long k,
+                                                     double c1, double g, double dt) {
+  const pf_mesh& M = P.mesh;
+  const long long n = *D.clock + k;
+  const double* __restrict__ u_n = dyn_u_at(D, n);
+  double* __restrict__ u_next = const_cast<double*>(dyn_u_at(D, n + 1));
+  const double t = (double)n * D.dt;
+  const double lam = D.t_ramp > 0.0 ? D.lam0 + (D.lam1 - D.lam0) * fmin(1.0, t / D.t_ramp) : D.lam1;
+  PF_EACH_NODE(node, M)
+    node_gather<DIM, false>(M, node, nullptr, 0, dyn_term<DIM>{P, d0_in, u_n, D.ea, D.e0}, [&](int dof, double f_int) {
+      const bool fixed = dof_fixed(M, dof);
+      const double v = c1 * D.v[dof] + g * ((lam * D.f_ext[dof] - f_int) * D.minv[dof]);
+      D.v[dof] = fixed ? 0.0 : v;
+      u_next[dof] = fixed ? 0.0 : u_n[dof] + dt * v;
+    });
+}
+
+// the clock after a sequence of n steps: one thread, a plain store
+__global__ void k_gl_dyn_clock(long long* clock, long long n) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *clock = *clock + n;
+}
+
+__device__ __forceinline__ double block_max_d(double v, double* smem) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if (lane == 0) smem[w] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int i = 0; i < nw; ++i) t = fmax(t, smem[i]);
+  return t;
+}
+
+// Per block, partial sums at the state the clock points to (u_{n+1}, v_{n+1/2}): kinetic energy sum m v^2 / 2 (m = 1 / minv;
+// a dof at rest adds nothing, whatever its minv), strain energy sum E*A l0 (e - e0)^2 / 2, f_ext.u and max |v|.  Thread i
+// takes node i and element i.  part: [gridDim.x][4].
+template <int DIM>
+__global__ __launch_bounds__(256) void k_gl_dyn_energy(pf_problem P, const double* __restrict__ d0_in, pf_dyn D,
+                                                       double* __restrict__ part) {
+  __shared__ double red[8];
+  const pf_mesh& M = P.mesh;
+  const double* __restrict__ u = dyn_u_at(D, *D.clock);
+  double kin = 0.0, se_sum = 0.0, work = 0.0, vmax = 0.0;
+  const int count = M.n_nodes > M.n_elems ? M.n_nodes : M.n_elems;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+    if (i < M.n_nodes) {
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) {
+        const int dof = i * DIM + c;
+        const double v = D.v[dof];
+        if (v != 0.0) kin += 0.5 * (v * v) / D.minv[dof];
+        work += D.f_ext[dof] * u[dof];
+        vmax = fmax(vmax, fabs(v));
+      }
+    }
+    if (i < M.n_elems) {
+      double d0[DIM], du[DIM], l02, ea;
+      const double se = dyn_strain<DIM>(P, d0_in, u, D.ea, D.e0, i, d0, du, l02, ea);
+      se_sum += 0.5 * (ea * sqrt(l02)) * (se * se);
+    }
+  }
+  const double s0 = pf_block_sum_d(kin, red), s1 = pf_block_sum_d(se_sum, red), s2 = pf_block_sum_d(work, red);
+  const double s3 = block_max_d(vmax, red);
+  if (threadIdx.x == 0) {
+    double* __restrict__ o = part + 4 * (size_t)blockIdx.x;
+    o[0] = s0; o[1] = s1; o[2] = s2; o[3] = s3;
+  }
+}
+
+// out[0..2] = the sums of the nb block partials, thread t adding blocks t, t + 256, ... in that order; out[3] = their maximum
+__global__ __launch_bounds__(256) void k_gl_dyn_energy_sum(const double* __restrict__ part, int nb, double* __restrict__ out) {
+  __shared__ double red[8];
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = (int)threadIdx.x; b < nb; b += (int)blockDim.x) {
+    const double* __restrict__ r = part + 4 * (size_t)b;
+    a[0] += r[0]; a[1] += r[1]; a[2] += r[2]; a[3] = fmax(a[3], r[3]);
+  }
+  const double s0 = pf_block_sum_d(a[0], red), s1 = pf_block_sum_d(a[1], red), s2 = pf_block_sum_d(a[2], red);
+  const double s3 = block_max_d(a[3], red);
+  if (threadIdx.x == 0) { out[0] = s0; out[1] = s1; out[2] = s2; out[3] = s3; }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 int gl_fail(int code, const char* who, const char* what) {
   char buf[160];
@@ -351,9 +486,84 @@ int gl_sens(const char* who, const pf_problem* p, const pf_gl* g, const double* 
                 out);
 }
 
+// everything a dynamics entry point is given, before anything is enqueued
+int dyn_check(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d) {
+  if (!node_mesh_ok(p)) return gl_fail(PF_ERR_ARG, who, "bad mesh");
+  if (!g || !g->d0 || !d || !d->minv || !d->f_ext || !d->u0 || !d->u1 || !d->v || !d->clock)
+    return gl_fail(PF_ERR_ARG, who, "null pointer");
+  if (!(d->dt > 0.0) || !isfinite(d->dt)) return gl_fail(PF_ERR_ARG, who, "dt must be positive and finite");
+  if (!(d->alpha >= 0.0) || !isfinite(d->alpha)) return gl_fail(PF_ERR_ARG, who, "alpha must not be negative");
+  if (!(d->t_ramp >= 0.0) || !isfinite(d->t_ramp)) return gl_fail(PF_ERR_ARG, who, "t_ramp must not be negative");
+  if (!isfinite(d->lam0) || !isfinite(d->lam1)) return gl_fail(PF_ERR_ARG, who, "non-finite load factor");
+  return PF_OK;
+}
+
+// n_steps launches of the step with the coefficients (c1, gk), then the clock's: a single chain on s
+int dyn_enqueue(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, double c1, double gk,
+                hipStream_t s) {
+  if (p->mesh.n_nodes > 0) {
+    const dim3 grid(pf_node_blocks(p->mesh.n_nodes));
+    for (int k = 0; k < n_steps; ++k)
+      if (const int rc = launch(who, p, k_gl_dyn_step<2>, k_gl_dyn_step<1>, grid, s, g->d0, *d, (long long)k, c1, gk, d->dt))
+        return rc;
+  }
+  hipLaunchKernelGGL(k_gl_dyn_clock, dim3(1), dim3(64), 0, s, d->clock, (long long)n_steps);
+  return launched(who);
+}
+
+// the coefficients of a full step: c1 = (1 - alpha dt / 2) / (1 + alpha dt / 2), g = dt / (1 + alpha dt / 2)
+void dyn_coefficients(const pf_dyn* d, double& c1, double& gk) {
+  const double h = 0.5 * d->alpha * d->dt;
+  c1 = (1.0 - h) / (1.0 + h);
+  gk = d->dt / (1.0 + h);
+}
+
 }  // namespace
 
 extern "C" {
+
+int pf_gl_dyn_start(const pf_problem* p, const pf_gl* g, const pf_dyn* d, void* stream) {
+  const char* who = "pf_gl_dyn_start";
+  if (const int rc = dyn_check(who, p, g, d)) return rc;
+  long long clock = -1;
+  if (hipMemcpyAsync(&clock, d->clock, sizeof(clock), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+      hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+    return gl_fail(PF_ERR_HIP, who, "reading the clock failed");
+  if (clock != 0) return gl_fail(PF_ERR_ARG, who, "the clock must be 0 (the half kick starts a run)");
+  return dyn_enqueue(who, p, g, d, 1, 1.0 - 0.5 * d->alpha * d->dt, 0.5 * d->dt, (hipStream_t)stream);
+}
+
+int pf_gl_dyn_steps(const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, void* stream) {
+  const char* who = "pf_gl_dyn_steps";
+  if (const int rc = dyn_check(who, p, g, d)) return rc;
+  if (n_steps < 1) return gl_fail(PF_ERR_ARG, who, "n_steps must be at least 1");
+  double c1, gk;
+  dyn_coefficients(d, c1, gk);
+  return dyn_enqueue(who, p, g, d, n_steps, c1, gk, (hipStream_t)stream);
+}
+
+int pf_gl_dyn_graph_create(const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, void* stream, void** graph_out) {
+  const char* who = "pf_gl_dyn_graph_create";
+  if (const int rc = dyn_check(who, p, g, d)) return rc;
+  if (n_steps < 1) return gl_fail(PF_ERR_ARG, who, "n_steps must be at least 1");
+  if (!graph_out) return gl_fail(PF_ERR_ARG, who, "null pointer");
+  double c1, gk;
+  dyn_coefficients(d, c1, gk);
+  return capture_graph((hipStream_t)stream, 0, hipStreamCaptureModeThreadLocal, graph_out,
+                       [&](pf_capture& cap) { return dyn_enqueue(who, p, g, d, n_steps, c1, gk, cap.s); });
+}
+
+int pf_gl_dyn_energy(const pf_problem* p, const pf_gl* g, const pf_dyn* d, double* out4, void* stream) {
+  const char* who = "pf_gl_dyn_energy";
+  if (const int rc = dyn_check(who, p, g, d)) return rc;
+  if (!out4) return gl_fail(PF_ERR_ARG, who, "null pointer");
+  const int count = p->mesh.n_nodes > p->mesh.n_elems ? p->mesh.n_nodes : p->mesh.n_elems;
+  const int nb = pf_node_blocks(count);
+  if (const int rc = launch(who, p, k_gl_dyn_energy<2>, k_gl_dyn_energy<1>, dim3(nb), stream, g->d0, *d, out4 + 4)) return rc;
+  hipLaunchKernelGGL(k_gl_dyn_energy_sum, dim3(1), dim3(256), 0, (hipStream_t)stream, out4 + 4, nb, out4);
+  return launched(who);
+}
+
 
 int pf_gl_state(const pf_problem* p, const pf_gl* g, const double* u, void* stream) {
   return gl_state("pf_gl_state", p, g, nullptr, nullptr, u, stream);

@@ -226,6 +226,7 @@ class HipEngine:
         self.pcg_batch_solves = 0       # pcg_solve_batch calls so far
         self._fixed_views = {}          # extra fixed dofs (tuple) -> (device dof_flags copy, PfProblem view, host fixed mask)
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
+        self._dyn = None                # explicit dynamics: buffers, pf_dyn record, step count and graphs of the run (dyn_begin)
         self._group_csr = None          # group_sum: (key of the group map, n_groups, device CSR pointer, device element ids)
         self._group_maps = {}           # _device_group_map: method name -> (key of its last map, n_groups, device int32 ids)
         self._configured = False
@@ -459,6 +460,7 @@ class HipEngine:
     def __del__(self):
         try:
             self._drop_graph()
+            self._drop_dyn_graphs()
         except Exception:
             pass
 
@@ -807,6 +809,98 @@ class HipEngine:
         out = torch.empty(self.plan.n_dofs, dtype=torch.float64, device=self.device)
         _capi.check(self.lib.pf_gl_fint(self._ref(), C.byref(rec), out.data_ptr(), self._stream()), "pf_gl_fint")
         return out
+
+    # ---- explicit dynamics of the Green-Lagrange element (pf_gl_dyn_*) ---------------------------------
+    def _drop_dyn_graphs(self):
+        d = getattr(self, "_dyn", None)         # (__del__ may run on a half-built engine)
+        if d:
+            for g in d["graphs"].values():
+                self.lib.pf_graph_destroy(g)
+            d["graphs"] = {}
+
+    @_on_engine_stream
+    def dyn_begin(self, u0, v0, minv, dt, alpha, lam0, lam1, t_ramp, ea=None, e0=None, start=True):
+        """Begin a central-difference run at step 0 (pf_dyn).  u0, v0, minv: float64 [n_dofs] (minv = 1 / lumped mass of
+        the dof's node; the loads are the model's, at load factor 1); ea, e0: as gl_state.  start: v0 is the velocity at
+        t = 0 and the half kick (pf_gl_dyn_start) turns it into v_{1/2} and u_1, the run then stands at step 1; False: v0 is
+        taken as v_{-1/2} and the run stands at step 0.  The buffers live on the engine; the graphs of dyn_steps are kept
+        for as long as the scalars and the presence of ea / e0, which they bake in, stay the same."""
+        nd, ne = self.plan.n_dofs, self.plan.n_elems
+        vec = {name: self._f64_vector("dyn_begin", name, t, nd, "dofs") for name, t in (("u0", u0), ("v0", v0), ("minv", minv))}
+        opt = {name: None if t is None else self._f64_vector("dyn_begin", name, t, ne, "elements")
+               for name, t in (("ea", ea), ("e0", e0))}
+        scalars = tuple(float(x) for x in (dt, alpha, lam0, lam1, t_ramp))
+        key = scalars + (ea is None, e0 is None)
+        d = self._dyn
+        if d is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            d = self._dyn = dict(graphs={}, key=None, rec=_capi.PfDyn(), n=0,
+                                 f_ext=torch.from_numpy(np.ascontiguousarray(
+                                     np.asarray(self.model.loads, dtype=np.float64).reshape(-1))).to(self.device),
+                                 out=torch.zeros(_capi.PF_DYN_ENERGY_COUNT, **f64),
+                                 clock=torch.zeros(1, dtype=torch.int64, device=self.device),
+                                 **{name: torch.zeros(max(nd, 1), **f64) for name in ("u0", "u1", "v", "minv")},
+                                 **{name: torch.zeros(max(ne, 1), **f64) for name in ("ea", "e0")})
+        if d["key"] != key:
+            self._drop_dyn_graphs()
+            d["key"] = key
+        for name, src in (("u0", "u0"), ("v", "v0"), ("minv", "minv")):
+            d[name][:nd].copy_(vec[src])
+        d["u1"].zero_()
+        d["clock"].zero_()
+        for name, t in opt.items():
+            if t is not None:
+                d[name][:ne].copy_(t)
+        rec = d["rec"]
+        rec.minv, rec.f_ext, rec.u0, rec.u1, rec.v = (d[k].data_ptr() for k in ("minv", "f_ext", "u0", "u1", "v"))
+        rec.ea = None if ea is None else d["ea"].data_ptr()
+        rec.e0 = None if e0 is None else d["e0"].data_ptr()
+        rec.clock = d["clock"].data_ptr()
+        rec.dt, rec.alpha, rec.lam0, rec.lam1, rec.t_ramp = scalars
+        d["n"] = 0
+        if start:
+            _capi.check(self.lib.pf_gl_dyn_start(self._ref(), C.byref(self._gl_buffers()[4]), C.byref(rec), self._stream()),
+                        "pf_gl_dyn_start")
+            d["n"] = 1
+
+    def _dyn_ready(self, who):
+        d = self._dyn
+        if d is None:
+            raise RuntimeError(f"{who}: no dynamic run yet; call dyn_begin first")
+        return d
+
+    @_on_engine_stream
+    def dyn_steps(self, n: int, use_graph: bool = True):
+        """n time steps, one launch each (pf_gl_dyn_steps), or one replay of their hipGraph (pf_gl_dyn_graph_create, cached
+        for each n until dyn_begin changes what it bakes in).  Enqueues only."""
+        d, n = self._dyn_ready("dyn_steps"), int(n)
+        if n < 1:
+            raise ValueError(f"dyn_steps: n must be at least 1, got {n}")
+        head = (self._ref(), C.byref(self._gl_buffers()[4]), C.byref(d["rec"]))
+        if use_graph and os.environ.get("PINNFEM_GRAPH", "1") != "0":
+            if n not in d["graphs"]:
+                g = C.c_void_p()
+                _capi.check(self.lib.pf_gl_dyn_graph_create(*head, n, self._stream(), C.byref(g)), "pf_gl_dyn_graph_create")
+                d["graphs"][n] = g
+            _capi.check(self.lib.pf_graph_launch(d["graphs"][n], self._stream()), "pf_graph_launch")
+        else:
+            _capi.check(self.lib.pf_gl_dyn_steps(*head, n, self._stream()), "pf_gl_dyn_steps")
+        d["n"] += n
+
+    @_on_engine_stream
+    def dyn_state(self):
+        """(u_n, v_{n-1/2}, n) of the run: copies, float64 [n_dofs] on the device."""
+        d, nd = self._dyn_ready("dyn_state"), self.plan.n_dofs
+        return d["u1" if d["n"] & 1 else "u0"][:nd].clone(), d["v"][:nd].clone(), d["n"]
+
+    @_on_engine_stream
+    def dyn_energy(self):
+        """(kinetic energy sum m v^2 / 2, strain energy sum E*A l0 (e - e0)^2 / 2, f_ext.u at load factor 1, max |v|) at
+        the run's state (pf_gl_dyn_energy), on the host: it synchronises."""
+        d = self._dyn_ready("dyn_energy")
+        _capi.check(self.lib.pf_gl_dyn_energy(self._ref(), C.byref(self._gl_buffers()[4]), C.byref(d["rec"]),
+                                              d["out"].data_ptr(), self._stream()), "pf_gl_dyn_energy")
+        return tuple(float(x) for x in d["out"][:4].cpu())
 
     @_on_engine_stream
     def kt_v_f64(self, v: torch.Tensor, zero_fixed: bool = False, extra_fixed=None) -> torch.Tensor:
