@@ -1,9 +1,17 @@
-"""What the device tests of the float64 CG solve share: the one raw-ABI driver of the six exported families (CgRun), one
-truss on the device (DeviceTruss) with the two subclasses that more than one test file uses, and the seeded meshes, fields
-and constants those files have in common.  A plain support module like helpers.py: no fixtures, no tests.
+"""What the float64 device tests share: the one raw-ABI driver of the six exported CG families (CgRun); one truss on the
+device (DeviceTruss) with LinearTruss for the linear operator and GlTruss, which owns the Green-Lagrange element buffers
+and wraps every raw pf_gl_* entry point that more than one file calls (state, fint, kt_v, kt_diag, sens, group_rhs,
+prestress_rhs, strain_rhs, strain_jvp), each on an output filled with 7.0; device_ids, group_maps and check_state beside
+it; the Green-Lagrange solver configuration and models of the solve and identification tests (gl_config, truss_model,
+case_model) and the CLI run on a copy of a tests/nl_inputs file (run_cli); and the seeded meshes, fields and constants
+those files have in common.  The round-off bounds stay in the test files, beside the tests that derive and use them.  A
+plain support module like helpers.py: no fixtures, no tests.
 """
 import ctypes as C
+import json
 import math
+import os
+import shutil
 
 import numpy as np
 import torch
@@ -196,48 +204,155 @@ class LinearTruss(DeviceTruss):
 
 
 class GlTruss(DeviceTruss):
-    """A truss with test-owned Green-Lagrange element buffers (d0, kt, fe, strain) and the raw entry points on them
-    (test_gl_f64.py, test_identify_f64.py)."""
+    """A truss with test-owned Green-Lagrange element buffers (d0, kt, fe, strain) and the raw entry points on them, each
+    with its output filled with 7.0 first: what the kernel does not write stays visible."""
 
     def __init__(self, nodes, el, fixed, dim):
         super().__init__(nodes, el, fixed, dim, YOUNG, AREA)
         d0 = self.nodes[self.el[:, 1]] - self.nodes[self.el[:, 0]]
         self.d0 = self.dev(d0.reshape(-1))
-        mk = lambda k: torch.full((k,), 7.0, dtype=torch.float64, device=self.eng.device)  # the kernel must overwrite it
-        self.kt, self.fe, self.strain = mk(self.ne * (3 if dim == 2 else 1)), mk(self.ne * dim), mk(self.ne)
+        self.kt, self.fe, self.strain = (self._sevens(k) for k in (self.ne * (3 if dim == 2 else 1), self.ne * dim, self.ne))
         self.rec = self.capi.PfGl()
         self.rec.d0, self.rec.kt, self.rec.fe, self.rec.strain = (t.data_ptr() for t in (self.d0, self.kt, self.fe, self.strain))
 
-    def state(self, u):
-        """pf_gl_state at u -> (strain, fe [ne, dim], kt [ne, 3 or 1]) on the host."""
-        eng, uu = self.eng, self.dev(u)
+    def _sevens(self, *shape):
+        return torch.full(shape, 7.0, dtype=torch.float64, device=self.eng.device)
+
+    def _call(self, name, *args, record=True):
+        """lib.<name>(engine, [the element record,] *args, stream) on the engine's stream, checked and waited for."""
+        eng = self.eng
+        head = (eng._ref(), C.byref(self.rec)) if record else (eng._ref(),)
         with eng.on_stream():
-            self.capi.check(self.lib.pf_gl_state(eng._ref(), C.byref(self.rec), uu.data_ptr(), eng._stream()), "pf_gl_state")
+            self.capi.check(getattr(self.lib, name)(*head, *args, eng._stream()), name)
         torch.cuda.synchronize()
+
+    def refill(self):
+        for t in (self.kt, self.fe, self.strain):
+            t.fill_(7.0)
+
+    def state(self, u, e0=None, ea=None):
+        """pf_gl_state at u, pf_gl_state_ea with a per-element ea, pf_gl_state_e0 with an initial strain (ea then given
+        too or NULL) -> (strain, fe [ne, dim], kt [ne, 3 or 1]) on the host."""
+        uu, ee, zz = self.dev(u), (None if ea is None else self.dev(ea)), (None if e0 is None else self.dev(e0))
+        ep = None if ee is None else ee.data_ptr()
+        self.refill()
+        if zz is not None:
+            self._call("pf_gl_state_e0", ep, zz.data_ptr(), uu.data_ptr())
+        elif ee is not None:
+            self._call("pf_gl_state_ea", ep, uu.data_ptr())
+        else:
+            self._call("pf_gl_state", uu.data_ptr())
         return (self.strain.cpu().numpy(), self.fe.cpu().numpy().reshape(self.ne, self.dim),
                 self.kt.cpu().numpy().reshape(self.ne, -1))
 
     def fint(self):
-        eng = self.eng
-        out = torch.full((self.n,), 7.0, dtype=torch.float64, device=eng.device)
-        with eng.on_stream():
-            self.capi.check(self.lib.pf_gl_fint(eng._ref(), C.byref(self.rec), out.data_ptr(), eng._stream()), "pf_gl_fint")
-        torch.cuda.synchronize()
+        out = self._sevens(self.n)
+        self._call("pf_gl_fint", out.data_ptr())
         return out.cpu().numpy()
 
     def kt_v(self, v, zero_fixed=False):
-        eng, vv = self.eng, self.dev(v)
-        out = torch.full((self.n,), 7.0, dtype=torch.float64, device=eng.device)
-        with eng.on_stream():
-            self.capi.check(self.lib.pf_kt_v_f64(eng._ref(), self.kt.data_ptr(), vv.data_ptr(), out.data_ptr(),
-                                                 int(zero_fixed), eng._stream()), "pf_kt_v_f64")
-        torch.cuda.synchronize()
+        vv, out = self.dev(v), self._sevens(self.n)
+        self._call("pf_kt_v_f64", self.kt.data_ptr(), vv.data_ptr(), out.data_ptr(), int(zero_fixed), record=False)
+        return out.cpu().numpy()
+
+    def kt_diag(self):
+        out = self._sevens(self.n)
+        self._call("pf_kt_diag_f64", self.kt.data_ptr(), out.data_ptr(), record=False)
         return out.cpu().numpy()
 
     def kv_linear(self, v):
         out = self.eng.kv_f64(self.dev(v))
         torch.cuda.synchronize()
         return out.cpu().numpy()
+
+    def sens(self, u, a, e0=None, accumulate=0, out=None):
+        """pf_gl_sens (e0 given: pf_gl_sens_e0) -> the device tensor [ne], `out` if given."""
+        uu, aa, zz = self.dev(u), self.dev(a), (None if e0 is None else self.dev(e0))
+        out = self._sevens(self.ne) if out is None else out
+        if zz is None:
+            self._call("pf_gl_sens", uu.data_ptr(), aa.data_ptr(), int(accumulate), out.data_ptr())
+        else:
+            self._call("pf_gl_sens_e0", zz.data_ptr(), uu.data_ptr(), aa.data_ptr(), int(accumulate), out.data_ptr())
+        return out
+
+    def group_rhs(self, ids, g0, m):
+        """pf_gl_group_rhs on the element buffers as the last state() left them, ids a device group map -> [m, n] on the host."""
+        out = self._sevens(m, self.n)
+        self._call("pf_gl_group_rhs", ids.data_ptr(), g0, m, out.data_ptr())
+        return out.cpu().numpy()
+
+    def prestress_rhs(self, u, ea, ids, g0, m):
+        uu, ee, out = self.dev(u), self.dev(ea), self._sevens(m, self.n)
+        self._call("pf_gl_prestress_rhs", ee.data_ptr(), uu.data_ptr(), ids.data_ptr(), g0, m, out.data_ptr())
+        return out.cpu().numpy()
+
+    def strain_rhs(self, u, coef, accumulate=0, out=None):
+        uu, cc = self.dev(u), self.dev(coef)
+        out = self._sevens(self.n) if out is None else out
+        self._call("pf_gl_strain_rhs", uu.data_ptr(), cc.data_ptr(), int(accumulate), out.data_ptr())
+        return out.cpu().numpy()
+
+    def strain_jvp(self, u, elems, V):
+        """pf_gl_strain_jvp for the rows of V [m, n_dofs] -> [m, len(elems)] on the host."""
+        uu, vv, ids = self.dev(u), self.dev(np.asarray(V).reshape(-1)), device_ids(self, elems)
+        out = self._sevens(len(V), len(elems))
+        self._call("pf_gl_strain_jvp", uu.data_ptr(), ids.data_ptr(), len(elems), vv.data_ptr(), len(V), out.data_ptr())
+        return out.cpu().numpy()
+
+
+def device_ids(S, groups):
+    return torch.from_numpy(np.ascontiguousarray(groups, dtype=np.int32)).to(S.eng.device)
+
+
+def group_maps(S, rng, n_groups):
+    """name -> [n_elems] group ids: random in 0..n_groups - 1; group 3 empty; some elements at -1 and some at G + 3."""
+    random = rng.integers(0, n_groups, S.ne)
+    hole = np.where(random == 3, 1, random)
+    stray = random.copy()
+    pick = rng.permutation(S.ne)
+    stray[pick[: max(1, S.ne // 7)]] = -1
+    stray[pick[max(1, S.ne // 7): max(1, S.ne // 7) + S.ne // 9]] = n_groups + 3
+    return {"random": random, "one empty group": hole, "ids -1 and G + 3": stray}
+
+
+def check_state(got, bounds, label):
+    """(strain, fe, kt) as GlTruss.state returns them against [(want, bound)] in that order, entry by entry."""
+    for what, g, (want, bound) in zip(("strain", "fe", "kt"), got, bounds):
+        g = g.reshape(want.shape)
+        assert np.all(np.isfinite(g)), what
+        err = np.abs(g - want)
+        print(f"{label} {what}: worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}, "
+              f"relative {np.max(err) / np.max(np.abs(want)):.2e}")
+        assert np.all(err <= bound), what
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the Green-Lagrange Newton solve and the CLI
+# ---------------------------------------------------------------------------------------------------------------------
+def gl_config(**kw):
+    from pinn_fem_amd.fem.solver import SolverConfig
+    return SolverConfig(**{**dict(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange"), **kw})
+
+
+def truss_model(nodes, el, loads, fixed, dim=2):
+    from pinn_fem_amd.fem.model import FEMModel, Material
+    return FEMModel(nodes=nodes, elements=el, material=Material(YOUNG, AREA, 1.0), loads=loads, fixed_dofs=fixed, dimension=dim)
+
+
+def case_model(case):
+    """The model of an identification case of the restatements (identify_reference.Case and its kin)."""
+    return truss_model(case.nodes, case.el, case.loads, case.fixed)
+
+
+def run_cli(tmp_path, input_name, as_name=None, parse=False):
+    """Copy tests/nl_inputs/<input_name>.json to tmp_path (as <as_name>.json) and run the generic CLI on it -> the parsed
+    .res.json; parse: (that, the CLI's own parse of the input)."""
+    from pinn_fem_amd.cli import generic as g
+    copy = tmp_path / ((as_name or input_name) + ".json")
+    shutil.copy(os.path.join(os.path.dirname(os.path.abspath(__file__)), "nl_inputs", input_name + ".json"), copy)
+    g.main(["generic.py", str(copy)])
+    out = json.loads(copy.with_suffix(".res.json").read_text())
+    return (out, g.parse_problem(str(copy))) if parse else out
 
 
 def system_cache(make):

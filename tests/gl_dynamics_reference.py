@@ -149,8 +149,7 @@ class Truss:
     def omega_true(self, u):
         """The highest frequency of K_t v = omega^2 M v on the free dofs (dense)."""
         import scipy.linalg
-        import gl_e0_reference as g0
-        K = gl.restrict(g0.k_t(self.X, self.el, u, self.ea, self.e0, self.dim), self.free).toarray()
+        K = gl.restrict(gl.k_t(self.X, self.el, u, self.ea, self.dim, e0=self.e0), self.free).toarray()
         return float(np.sqrt(scipy.linalg.eigvalsh(K, np.diag(self.mass[self.free]))[-1]))
 
 

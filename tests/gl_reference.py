@@ -1,10 +1,14 @@
 """The total-Lagrangian (Green-Lagrange) truss element in numpy / scipy float64: element state, internal force, tangent
-as CSR, a Newton loop with a sparse direct solve, and the closed forms the tests pin the element to.  Written from the
-virtual-work derivation, vectorised over elements with scatter-adds; it shares no code with the kernels (which gather
-per node).  tests/test_gl_host.py checks it against finite differences, rigid motions and the two-bar closed form.
+as CSR, a Newton loop with a sparse direct solve, each with the initial (eigen-) strain as the keyword e0; the element-level
+sensitivities, right-hand sides and strain maps the identification (tests/identify_reference.py) is built from; and the
+closed forms the tests pin the element to.  Written from the virtual-work derivation, vectorised over elements with
+scatter-adds; it shares no code with the kernels (which gather per node) or with pinn_fem_amd/fem.  tests/test_gl_host.py
+checks it against finite differences, rigid motions and the two-bar closed form, tests/test_gl_e0_host.py with an e0.
 
-  W(u) = sum_e  E A l0 e^2 / 2,   e = (|d|^2 - |d0|^2) / (2 l0^2),  d = d0 + du
-  dW/du_j = E A e d / l0 = fe,    d fe / d du = (E A / l0^3) d d^T + (E A e / l0) I = B
+  W(u) = sum_e  E A l0 (e - e0)^2 / 2,   e = (|d|^2 - |d0|^2) / (2 l0^2),  d = d0 + du
+  N = E A (e - e0),   dW/du_j = (N / l0) d = fe,    d fe / d du = (E A / l0^3) d d^T + (N / l0) I = B
+e0 < 0 is a pretension (T = -E A e0), thermal loading is e0 = alpha dT, lack of fit e0 = (L_natural - l0) / l0.  e0 acts
+in full at every load factor.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -15,9 +19,11 @@ def _as2d(nodes, dim):
     return np.asarray(nodes, dtype=np.float64).reshape(-1, dim)
 
 
-def element_state(nodes, el, u, ea, dim):
-    """(strain [ne], fe [ne, dim], B [ne, dim, dim], terms) with `ea` a scalar or [ne].  `terms` holds what the
-    round-off bounds of the GPU tests are stated in: d0, du, d, l0^2."""
+def element_state(nodes, el, u, ea, dim, e0=None):
+    """(strain [ne] (the total strain e), fe [ne, dim], B [ne, dim, dim], terms) with `ea` and the initial strain `e0` a
+    scalar or [ne]; e0 None: no initial strain, the bytes of e0 = 0.0.  `terms` holds what the round-off bounds of the GPU
+    tests are stated in: d0, du, d, l0^2, l0, ea, the axial force n = E A (e - e0), e0 [ne] and
+    e_abs = (2 |d0|.|du| + |du|.|du|) / (2 l0^2)."""
     X, el = _as2d(nodes, dim), np.asarray(el, dtype=np.int64)
     U = np.asarray(u, dtype=np.float64).reshape(-1, dim)
     d0 = X[el[:, 1]] - X[el[:, 0]]
@@ -28,24 +34,47 @@ def element_state(nodes, el, u, ea, dim):
     # the difference of squares written out: |d|^2 - |d0|^2 = 2 d0.du + du.du
     strain = (2.0 * np.sum(d0 * du, axis=1) + np.sum(du * du, axis=1)) / (2.0 * l02)
     ea = np.broadcast_to(np.asarray(ea, dtype=np.float64), strain.shape)
-    n = ea * strain
-    fe = (n / l0)[:, None] * d
-    B = (ea / (l02 * l0))[:, None, None] * (d[:, :, None] * d[:, None, :]) + (n / l0)[:, None, None] * np.eye(dim)
-    return strain, fe, B, dict(d0=d0, du=du, d=d, l02=l02, l0=l0, ea=ea, n=n)
+    e0 = np.broadcast_to(np.asarray(0.0 if e0 is None else e0, dtype=np.float64), strain.shape)
+    n = ea * (strain - e0)
+    n_l0 = n / l0
+    fe = n_l0[:, None] * d
+    B = (ea / (l02 * l0))[:, None, None] * (d[:, :, None] * d[:, None, :]) + n_l0[:, None, None] * np.eye(dim)
+    e_abs = (2.0 * np.sum(np.abs(d0) * np.abs(du), axis=1) + np.sum(du * du, axis=1)) / (2.0 * l02)
+    return strain, fe, B, dict(d0=d0, du=du, d=d, l02=l02, l0=l0, ea=ea, n=n, e0=e0, e_abs=e_abs)
 
 
-def f_int(nodes, el, u, ea, dim, absolute=False):
+def axial_forces(nodes, el, u, ea, dim, e0=None):
+    return element_state(nodes, el, u, ea, dim, e0)[3]["n"]
+
+
+def energy(nodes, el, u, ea, dim, e0=None):
+    strain, _, _, t = element_state(nodes, el, u, ea, dim, e0)
+    return float(np.sum(t["ea"] * t["l0"] * (strain - t["e0"]) ** 2) / 2.0)
+
+
+def _scatter(n_nodes, dim, el, term, sign):
+    """[n_dofs]: per element, term [ne, dim] added at the second node and sign * term at the first."""
+    out = np.zeros((n_nodes, dim))
+    np.add.at(out, el[:, 1], term)
+    np.add.at(out, el[:, 0], sign * term)
+    return out.reshape(-1)
+
+
+def f_int(nodes, el, u, ea, dim, absolute=False, e0=None):
     """Internal force [n_dofs]; absolute: the sum of the magnitudes of the same terms (the unit of round-off bounds)."""
     X, el = _as2d(nodes, dim), np.asarray(el, dtype=np.int64)
-    fe = element_state(nodes, el, u, ea, dim)[1]
-    out = np.zeros((len(X), dim))
-    if absolute:
-        np.add.at(out, el[:, 1], np.abs(fe))
-        np.add.at(out, el[:, 0], np.abs(fe))
-    else:
-        np.add.at(out, el[:, 1], fe)
-        np.add.at(out, el[:, 0], -fe)
-    return out.reshape(-1)
+    fe = element_state(nodes, el, u, ea, dim, e0)[1]
+    return _scatter(len(X), dim, el, np.abs(fe), 1.0) if absolute else _scatter(len(X), dim, el, fe, -1.0)
+
+
+def f_int_scale(nodes, el, u, ea, dim, e0=None):
+    """Per dof, the sum over the node's elements of |E A| (e_abs + |e0|) |d_c| / l0: the magnitude of the terms f_int is
+    summed from, in front of the cancellation of e - e0 and of the sum over the node's elements, which does not vanish
+    where the terms cancel (rigid motions)."""
+    X, el = _as2d(nodes, dim), np.asarray(el, dtype=np.int64)
+    t = element_state(nodes, el, u, ea, dim, e0)[3]
+    mag = (np.abs(t["ea"]) * (t["e_abs"] + np.abs(t["e0"])) / t["l0"])[:, None] * np.abs(t["d"])
+    return _scatter(len(X), dim, el, mag, 1.0)
 
 
 def blocks_csr(B, el, n_nodes, dim, absolute=False):
@@ -64,9 +93,9 @@ def blocks_csr(B, el, n_nodes, dim, absolute=False):
     return sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n)).tocsr()
 
 
-def k_t(nodes, el, u, ea, dim, absolute=False):
+def k_t(nodes, el, u, ea, dim, absolute=False, e0=None):
     X = _as2d(nodes, dim)
-    return blocks_csr(element_state(nodes, el, u, ea, dim)[2], el, len(X), dim, absolute)
+    return blocks_csr(element_state(nodes, el, u, ea, dim, e0)[2], el, len(X), dim, absolute)
 
 
 def free_mask(n, fixed):
@@ -98,18 +127,19 @@ def jacobi_cg(rtol=1e-13):
 
 
 def newton(nodes, el, loads, fixed, ea, dim, lam=1.0, u0=None, tol=1e-10, max_iter=50, min_den=1e-10, on_iterate=None,
-           linear_solve=spla.spsolve):
+           linear_solve=spla.spsolve, e0=None):
     """solve_nr's loop with a sparse direct solve: u += K_t(u)^-1 (lam f_ext - f_int(u)) until
-    |du| / max(|u|, min_den) <= tol.  Returns (u, iterations, converged)."""
+    |du| / max(|u|, min_den) <= tol.  The load factor scales the loads only: the initial strain e0 acts in full.
+    on_iterate(u, K, free, rhs) sees every iterate.  Returns (u, iterations, converged)."""
     n = len(_as2d(nodes, dim)) * dim
     free = free_mask(n, fixed)
     f = lam * np.asarray(loads, dtype=np.float64).reshape(-1)
     u = np.zeros(n) if u0 is None else np.where(free, np.asarray(u0, dtype=np.float64).reshape(-1), 0.0)
     for it in range(max_iter):
-        K = k_t(nodes, el, u, ea, dim)
+        K = k_t(nodes, el, u, ea, dim, e0=e0)
+        rhs = f - f_int(nodes, el, u, ea, dim, e0=e0)
         if on_iterate is not None:
-            on_iterate(u, K, free)
-        rhs = f - f_int(nodes, el, u, ea, dim)
+            on_iterate(u, K, free, rhs)
         du = np.zeros(n)
         du[free] = linear_solve(restrict(K, free), rhs[free])
         u = u + du
@@ -126,6 +156,101 @@ def incremental(nodes, el, loads, fixed, ea, dim, n_inc, **kw):
         assert ok, f"reference Newton did not converge in increment {k}"
         its.append(it)
     return u, its
+
+
+# ---- what the identification is built from: sensitivities, right-hand sides, B = d e / d u ------------------------------
+def element_sensitivity(nodes, el, u, a, dim, e0=None):
+    """-((e - e0) / l0) d.(a_j - a_i) per element (d f_int / d ea_e = fe_e / ea_e, which does not contain ea)."""
+    strain, _, _, t = element_state(nodes, el, u, 1.0, dim, e0)
+    A = np.asarray(a, dtype=np.float64).reshape(-1, dim)
+    el = np.asarray(el, dtype=np.int64)
+    return -((strain - t["e0"]) / t["l0"]) * np.sum(t["d"] * (A[el[:, 1]] - A[el[:, 0]]), axis=1)
+
+
+def sensitivity_scale(nodes, el, u, a, dim, e0=None):
+    """The magnitude of the terms element_sensitivity is summed from, in front of any cancellation (of e - e0 as well):
+    ((e_abs + |e0|) / l0) sum_c |d_c| (|a_j,c| + |a_i,c|)."""
+    t = element_state(nodes, el, u, 1.0, dim, e0)[3]
+    A = np.abs(np.asarray(a, dtype=np.float64).reshape(-1, dim))
+    el = np.asarray(el, dtype=np.int64)
+    return ((t["e_abs"] + np.abs(t["e0"])) / t["l0"]) * np.sum(np.abs(t["d"]) * (A[el[:, 1]] + A[el[:, 0]]), axis=1)
+
+
+def group_rhs(nodes, el, u, ea, dim, groups, n_groups, fixed, e0=None):
+    """[G, n_dofs]: minus the internal force of the elements of every group alone, zero on the fixed dofs."""
+    ea = np.broadcast_to(np.asarray(ea, dtype=np.float64), (len(el),))
+    groups = np.asarray(groups, dtype=int)
+    out = np.stack([-f_int(nodes, el, u, np.where(groups == g, ea, 0.0), dim, e0=e0) for g in range(n_groups)])
+    out[:, np.asarray(fixed, dtype=int)] = 0.0
+    return out
+
+
+def _abs_d(nodes, el, u, dim):
+    """|d0_c| + |u_j,c| + |u_i,c| per element and component: the magnitude d = d0 + (u_j - u_i) is summed from."""
+    t = element_state(nodes, el, u, 1.0, dim)[3]
+    U = np.abs(np.asarray(u, dtype=np.float64).reshape(-1, dim))
+    el = np.asarray(el, dtype=np.int64)
+    return np.abs(t["d0"]) + U[el[:, 1]] + U[el[:, 0]], t
+
+
+def _group_rows(nodes, el, dim, term, pgroups, n_t, sign):
+    """[n_t, n_dofs]: row h is _scatter over the elements of group h alone."""
+    el, n_nodes = np.asarray(el, dtype=np.int64), len(_as2d(nodes, dim))
+    picks = [np.flatnonzero(np.asarray(pgroups) == h) for h in range(n_t)]
+    return np.stack([_scatter(n_nodes, dim, el[pick], term[pick], sign) for pick in picks])
+
+
+def prestress_rhs(nodes, el, u, ea, pgroups, n_t, dim):
+    """[n_t, n_dofs], every row (fixed dofs included): with e0_e = base_e + t_h(e) and d fe / d e0 = -(ea / l0) d, row h =
+    -d f_int / d t_h = the sum over the elements of group h of +-(ea_e / l0_e) d_e, + at the second node, - at the first."""
+    t = element_state(nodes, el, u, ea, dim)[3]
+    return _group_rows(nodes, el, dim, (t["ea"] / t["l0"])[:, None] * t["d"], pgroups, n_t, -1.0)
+
+
+def prestress_rhs_scale(nodes, el, u, ea, pgroups, n_t, dim):
+    """Per row and dof, the sum over the node's elements of group h of (|ea_e| / l0_e) (|d0_c| + |u_j,c| + |u_i,c|): the
+    magnitude of the terms prestress_rhs is summed from, in front of any cancellation (in d as well)."""
+    mag_d, t = _abs_d(nodes, el, u, dim)
+    ea = np.abs(np.broadcast_to(np.asarray(ea, dtype=np.float64), t["l0"].shape))
+    return _group_rows(nodes, el, dim, (ea / t["l0"])[:, None] * mag_d, pgroups, n_t, 1.0)
+
+
+def strains(nodes, el, u, dim):
+    return element_state(nodes, el, u, 1.0, dim)[0]
+
+
+def bt_c(nodes, el, u, c, dim):
+    """B^T c [n_dofs] with B = d e / d u (d e_e / d u_j = +d / l0^2, d e_e / d u_i = -d / l0^2): +(c_e / l0^2) d_e at the
+    element's second node, - at its first, every row (fixed dofs included)."""
+    t = element_state(nodes, el, u, 1.0, dim)[3]
+    term = (np.asarray(c, dtype=np.float64) / t["l02"])[:, None] * t["d"]
+    return _scatter(len(_as2d(nodes, dim)), dim, np.asarray(el, dtype=np.int64), term, -1.0)
+
+
+def bt_c_scale(nodes, el, u, c, dim):
+    """Per dof, the sum over the node's elements of (|c_e| / l0^2) (|d0_c| + |u_j,c| + |u_i,c|): the magnitude of the terms
+    bt_c is summed from, in front of any cancellation (in d as well)."""
+    mag_d, t = _abs_d(nodes, el, u, dim)
+    term = (np.abs(np.asarray(c, dtype=np.float64)) / t["l02"])[:, None] * mag_d
+    return _scatter(len(_as2d(nodes, dim)), dim, np.asarray(el, dtype=np.int64), term, 1.0)
+
+
+def b_v(nodes, el, u, elements, v, dim):
+    """(B v)[i] = (d_e / l0^2).(v_j - v_i) for e = elements[i]."""
+    t = element_state(nodes, el, u, 1.0, dim)[3]
+    V = np.asarray(v, dtype=np.float64).reshape(-1, dim)
+    pick = np.asarray(elements, dtype=int)
+    el = np.asarray(el, dtype=np.int64)[pick]
+    return np.sum(t["d"][pick] * (V[el[:, 1]] - V[el[:, 0]]), axis=1) / t["l02"][pick]
+
+
+def b_v_scale(nodes, el, u, elements, v, dim):
+    """sum_c (|d0_c| + |u_j,c| + |u_i,c|) (|v_j,c| + |v_i,c|) / l0^2 per gauge: b_v's terms in front of any cancellation."""
+    mag_d, t = _abs_d(nodes, el, u, dim)
+    V = np.abs(np.asarray(v, dtype=np.float64).reshape(-1, dim))
+    pick = np.asarray(elements, dtype=int)
+    el = np.asarray(el, dtype=np.int64)[pick]
+    return np.sum(mag_d[pick] * (V[el[:, 1]] + V[el[:, 0]]), axis=1) / t["l02"][pick]
 
 
 # ---- closed forms ---------------------------------------------------------------------------------------------------
@@ -219,19 +344,6 @@ def irregular_truss(n_elems, rng, hub_degree=6):
     flip = rng.random(len(el)) < 0.5
     el[flip] = el[flip][:, ::-1]
     return out_nodes, el
-
-
-def f_int_scale(nodes, el, u, ea, dim):
-    """Per dof, the sum over the node's elements of |E A| e_abs |d_c| / l0 with e_abs = (2 |d0|.|du| + |du|.|du|) / (2 l0^2):
-    the magnitude of the terms f_int is summed from, which does not vanish where the terms cancel (rigid motions)."""
-    X, el = _as2d(nodes, dim), np.asarray(el, dtype=np.int64)
-    t = element_state(nodes, el, u, ea, dim)[3]
-    e_abs = (2.0 * np.sum(np.abs(t["d0"]) * np.abs(t["du"]), axis=1) + np.sum(t["du"] ** 2, axis=1)) / (2.0 * t["l02"])
-    mag = (np.abs(t["ea"]) * e_abs / t["l0"])[:, None] * np.abs(t["d"])
-    out = np.zeros((len(X), dim))
-    np.add.at(out, el[:, 1], mag)
-    np.add.at(out, el[:, 0], mag)
-    return out.reshape(-1)
 
 
 def f_int_exact(nodes, el, u, ea, dim):

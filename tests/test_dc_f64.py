@@ -1,9 +1,6 @@
 """Displacement control in the Green-Lagrange Newton solve on the device: solve_nr and solve() through the limit point of
 the two-bar truss (closed form) and of a shallow Warren arch (tests/dc_reference.py with direct solves), the refusal of
 a K' that is not positive definite, and the CLI."""
-import json
-import os
-import shutil
 
 import numpy as np
 import pytest
@@ -11,30 +8,18 @@ import torch
 
 import dc_reference as dc
 import gl_reference as gl
+from device_driver import EA, gl_config, run_cli, truss_model
 
 pytestmark = pytest.mark.gpu
-
-YOUNG, AREA = 2000.0, 0.5                       # E*A = 1000, exact in float32
-EA = YOUNG * AREA
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _model(nodes, el, loads, fixed):
-    from pinn_fem_amd.fem.model import FEMModel, Material
-    return FEMModel(nodes=nodes, elements=el, material=Material(YOUNG, AREA, 1.0), loads=loads, fixed_dofs=fixed,
-                    dimension=2)
 
 
 def _two_bar():
     tb = gl.TwoBar(ea=EA)
-    return tb, _model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
+    return tb, truss_model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
 
 
 def _config(**kw):
-    from pinn_fem_amd.fem.solver import SolverConfig
-    base = dict(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange", nr_control="displacement", method="nr")
-    base.update(kw)
-    return SolverConfig(**base)
+    return gl_config(**{**dict(nr_control="displacement", method="nr"), **kw})
 
 
 # ---- 8. solve_nr, one step past the limit point ------------------------------------------------------------------------
@@ -110,7 +95,7 @@ def test_solve_arch_through_its_limit_point(arch_reference, pre):
     _check_two_bar."""
     from pinn_fem_amd.fem import solver
     nodes, el, loads, fixed, c, u_ref, lam_ref, its_ref, kappa = arch_reference
-    model = _model(nodes, el, loads, fixed)
+    model = truss_model(nodes, el, loads, fixed)
     eng = solver._engine_for(model, None, None)
     batches = eng.pcg_batch_solves
     res = solver.solve(model, _config(nr_control_dof=c, nr_control_displacement=-1.1, n_increments=11,
@@ -145,11 +130,8 @@ def test_indefinite_reduced_tangent_is_refused():
 
 # ---- 12. CLI ------------------------------------------------------------------------------------------------------------
 def test_cli_displacement_control(tmp_path):
-    from pinn_fem_amd.cli import generic as g
     tb = gl.TwoBar(ea=EA)
-    shutil.copy(os.path.join(HERE, "nl_inputs", "two_bar_displacement_control.json"), tmp_path / "dc.json")
-    g.main(["generic.py", str(tmp_path / "dc.json")])
-    out = json.loads((tmp_path / "dc.res.json").read_text())
+    out = run_cli(tmp_path, "two_bar_displacement_control", "dc")
     path = out["equilibrium_path"]
     print(f"CLI displacement control: {path[-1]}")
     assert out["converged"] and len(path) == 11
@@ -157,6 +139,4 @@ def test_cli_displacement_control(tmp_path):
     assert last["control_displacement"] == -2.2 and out["displacements"][5] == -2.2
     assert abs(last["load_factor"] / (tb.load(2.2) / tb.p_lim) - 1.0) <= 1e-9
     # load control writes no path
-    shutil.copy(os.path.join(HERE, "nl_inputs", "two_bar_green_lagrange.json"), tmp_path / "lc.json")
-    g.main(["generic.py", str(tmp_path / "lc.json")])
-    assert "equilibrium_path" not in json.loads((tmp_path / "lc.res.json").read_text())
+    assert "equilibrium_path" not in run_cli(tmp_path, "two_bar_green_lagrange")

@@ -7,9 +7,6 @@ Every bound is derived next to its assertion from 2^-53 and operation counts, or
 restatement reaches itself.  The measured figures are printed in front of every assertion.
 """
 import ctypes as C
-import json
-import os
-import shutil
 
 import numpy as np
 import pytest
@@ -17,70 +14,17 @@ import torch
 
 import gl_e0_reference as g0
 import gl_reference as gl
-from device_driver import AREA, EA, U53, YOUNG, gl_field, gl_system, system_cache
+import identify_reference as ir
+from device_driver import EA, U53, case_model, check_state, gl_config, gl_field, gl_system, run_cli, system_cache, truss_model
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 MESHES = ["truss_1", "truss_255", "truss_257", "truss_1025", "chain_1", "chain_257"]
 
 
 @pytest.fixture(scope="module")
 def systems():
     yield from system_cache(gl_system)
-
-
-def _read_state(S):
-    torch.cuda.synchronize()
-    return (S.strain.cpu().numpy(), S.fe.cpu().numpy().reshape(S.ne, S.dim), S.kt.cpu().numpy().reshape(S.ne, -1))
-
-
-def _refill(S):
-    for t in (S.kt, S.fe, S.strain):
-        t.fill_(7.0)
-
-
-def _state(S, u, e0=None, ea=None):
-    """pf_gl_state_e0 at u (e0 None: pf_gl_state or, with an ea, pf_gl_state_ea) -> (strain, fe, kt) on the host; the
-    buffers are refilled with 7.0 first, so an element the kernel misses shows."""
-    eng, lib, uu = S.eng, S.lib, S.dev(u)
-    ee, zz = (None if ea is None else S.dev(ea)), (None if e0 is None else S.dev(e0))
-    ep = None if ee is None else ee.data_ptr()
-    _refill(S)
-    with eng.on_stream():
-        P, G, s = eng._ref(), C.byref(S.rec), eng._stream()
-        if zz is not None:
-            S.capi.check(lib.pf_gl_state_e0(P, G, ep, zz.data_ptr(), uu.data_ptr(), s), "pf_gl_state_e0")
-        elif ee is not None:
-            S.capi.check(lib.pf_gl_state_ea(P, G, ep, uu.data_ptr(), s), "pf_gl_state_ea")
-        else:
-            S.capi.check(lib.pf_gl_state(P, G, uu.data_ptr(), s), "pf_gl_state")
-    return _read_state(S)
-
-
-def _sens(S, u, a, e0=None, accumulate=0, out=None):
-    eng, uu, aa = S.eng, S.dev(u), S.dev(a)
-    zz = None if e0 is None else S.dev(e0)
-    if out is None:
-        out = torch.full((S.ne,), 7.0, dtype=torch.float64, device=eng.device)
-    with eng.on_stream():
-        P, G, s = eng._ref(), C.byref(S.rec), eng._stream()
-        if zz is None:
-            S.capi.check(S.lib.pf_gl_sens(P, G, uu.data_ptr(), aa.data_ptr(), int(accumulate), out.data_ptr(), s), "pf_gl_sens")
-        else:
-            S.capi.check(S.lib.pf_gl_sens_e0(P, G, zz.data_ptr(), uu.data_ptr(), aa.data_ptr(), int(accumulate), out.data_ptr(),
-                                             s), "pf_gl_sens_e0")
-    torch.cuda.synchronize()
-    return out
-
-
-def _kt_diag(S):
-    eng = S.eng
-    out = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
-    with eng.on_stream():
-        S.capi.check(S.lib.pf_kt_diag_f64(eng._ref(), S.kt.data_ptr(), out.data_ptr(), eng._stream()), "pf_kt_diag_f64")
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
 
 
 def _same_bits(a, b):
@@ -98,7 +42,7 @@ def _state_bounds(S, u, ea, e0):
       fe_c = (E A (e - e0) / l0) d_c: the 14 relative roundings of that file's chain, on (|e| + |e0|), with the 2 of the
             difference: 8 e_abs + 16 (|e| + |e0|), times E A |d_c| / l0.
       B_rc = (E A / l0^3) d_r d_c + delta_rc N / l0: 25 on the first term as there, fe's chain without d_c on the second."""
-    strain, fe, B, t = g0.element_state(S.nodes, S.el, u, ea, e0, S.dim)
+    strain, fe, B, t = gl.element_state(S.nodes, S.el, u, ea, S.dim, e0=e0)
     ea = np.broadcast_to(np.asarray(ea, dtype=np.float64), strain.shape)
     b_e = 8 * U53 * t["e_abs"]
     n_l0 = (b_e + 16 * U53 * (np.abs(strain) + np.abs(t["e0"]))) * ea / t["l0"]
@@ -113,15 +57,6 @@ def _state_bounds(S, u, ea, e0):
     return (strain, b_e), (fe, b_fe), (pick(B), pick(b_B))
 
 
-def _check_state(got, bounds, label):
-    for what, g, (want, bound) in zip(("strain", "fe", "kt"), got, bounds):
-        g = g.reshape(want.shape)
-        assert np.all(np.isfinite(g)), what
-        err = np.abs(g - want)
-        print(f"{label} {what}: worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
-        assert np.all(err <= bound), what
-
-
 @pytest.mark.parametrize("kind", ["large", "tiny"])
 @pytest.mark.parametrize("name", MESHES)
 def test_gl_state_e0_against_the_restatement(systems, name, kind):
@@ -132,10 +67,10 @@ def test_gl_state_e0_against_the_restatement(systems, name, kind):
     S = systems(name)
     rng = np.random.default_rng(S.ne + 15)
     u, e0, ea = gl_field(S, kind, rng), rng.uniform(-1e-2, 1e-2, S.ne), rng.uniform(500.0, 2000.0, S.ne)
-    _check_state(_state(S, u, e0), _state_bounds(S, u, EA, e0), f"{name} {kind} e0")
-    _check_state(_state(S, u, e0, ea), _state_bounds(S, u, ea, e0), f"{name} {kind} e0, per-element ea")
-    strain = _state(S, u)[0]
-    got = _state(S, u, strain.copy(), ea)
+    check_state(S.state(u, e0), _state_bounds(S, u, EA, e0), f"{name} {kind} e0")
+    check_state(S.state(u, e0, ea), _state_bounds(S, u, ea, e0), f"{name} {kind} e0, per-element ea")
+    strain = S.state(u)[0]
+    got = S.state(u, strain.copy(), ea)
     assert got[0].tobytes() == strain.tobytes()                        # the strain that is written stays the total strain
     assert not got[1].any()
     t = gl.element_state(S.nodes, S.el, u, ea, S.dim)[3]
@@ -156,16 +91,16 @@ def test_zero_e0_and_repeated_calls_give_the_same_bits(systems, name):
     zero = np.zeros(S.ne)
     for kind in ("large", "tiny"):
         u, e0, ea = gl_field(S, kind, rng), rng.uniform(-1e-2, 1e-2, S.ne), rng.uniform(500.0, 2000.0, S.ne)
-        assert _same_bits(_state(S, u, zero), _state(S, u))
-        assert _same_bits(_state(S, u, zero, ea), _state(S, u, None, ea))
-        first = _state(S, u, e0, ea)
-        assert _same_bits(_state(S, u, e0, ea), first) and not _same_bits(first, _state(S, u, None, ea))
+        assert _same_bits(S.state(u, zero), S.state(u))
+        assert _same_bits(S.state(u, zero, ea), S.state(u, None, ea))
+        first = S.state(u, e0, ea)
+        assert _same_bits(S.state(u, e0, ea), first) and not _same_bits(first, S.state(u, None, ea))
         a1, a2 = rng.standard_normal(S.n), rng.standard_normal(S.n) * np.exp2(rng.uniform(-8.0, 8.0, S.n))
-        plain = _sens(S, u, a1).cpu().numpy()
-        assert _sens(S, u, a1, zero).cpu().numpy().tobytes() == plain.tobytes()
-        one, two = _sens(S, u, a1, e0).cpu().numpy(), _sens(S, u, a2, e0).cpu().numpy()
-        assert _sens(S, u, a1, e0).cpu().numpy().tobytes() == one.tobytes() and one.tobytes() != plain.tobytes()
-        acc = _sens(S, u, a2, e0, accumulate=1, out=_sens(S, u, a1, e0)).cpu().numpy()
+        plain = S.sens(u, a1).cpu().numpy()
+        assert S.sens(u, a1, zero).cpu().numpy().tobytes() == plain.tobytes()
+        one, two = S.sens(u, a1, e0).cpu().numpy(), S.sens(u, a2, e0).cpu().numpy()
+        assert S.sens(u, a1, e0).cpu().numpy().tobytes() == one.tobytes() and one.tobytes() != plain.tobytes()
+        acc = S.sens(u, a2, e0, accumulate=1, out=S.sens(u, a1, e0)).cpu().numpy()
         assert acc.tobytes() == (one + two).tobytes()
 
 
@@ -176,14 +111,14 @@ def test_zero_e0_and_repeated_calls_give_the_same_bits(systems, name):
 def test_gl_sens_e0_against_the_restatement(systems, name):
     """s = -((e - e0) / l0) sum_c d_c (a_j,c - a_i,c).  tests/test_identify_f64.py counts 25 * 2^-53 of
     (e_abs / l0) sum_c |d_c| (|a_j,c| + |a_i,c|) for device and reference together; the difference e - e0 adds one rounding
-    per side, and the unit takes |e0| next to e_abs because the difference cancels (g0.sensitivity_scale): 27."""
+    per side, and the unit takes |e0| next to e_abs because the difference cancels (gl.sensitivity_scale): 27."""
     S = systems(name)
     rng = np.random.default_rng(S.ne + 17)
     for kind in ("large", "tiny"):
         u, e0, a = gl_field(S, kind, rng), rng.uniform(-1e-2, 1e-2, S.ne), rng.standard_normal(S.n)
-        got = _sens(S, u, a, e0).cpu().numpy()
-        want = g0.element_sensitivity(S.nodes, S.el, u, a, e0, S.dim)
-        bound = 27 * U53 * g0.sensitivity_scale(S.nodes, S.el, u, a, e0, S.dim)
+        got = S.sens(u, a, e0).cpu().numpy()
+        want = gl.element_sensitivity(S.nodes, S.el, u, a, S.dim, e0=e0)
+        bound = 27 * U53 * gl.sensitivity_scale(S.nodes, S.el, u, a, S.dim, e0=e0)
         err = np.abs(got - want)
         print(f"{name} {kind}: sensitivity worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
         assert np.all(np.isfinite(got)) and np.all(err <= bound)
@@ -198,8 +133,8 @@ def test_kt_diag_is_the_sequential_sum_of_the_blocks(systems, name):
     incidence order (the plan's adjacency) from 0.0: the same bits.  Fixed dofs get 0.0."""
     S = systems(name)
     rng = np.random.default_rng(S.ne + 18)
-    kt = _state(S, gl_field(S, "large", rng), rng.uniform(-1e-2, 1e-2, S.ne))[2]
-    got = _kt_diag(S)
+    kt = S.state(gl_field(S, "large", rng), rng.uniform(-1e-2, 1e-2, S.ne))[2]
+    got = S.kt_diag()
     plan = S.eng.plan
     adj_ptr, adj = np.asarray(plan.adj_ptr), np.asarray(plan.adj)
     want = np.zeros(S.n)
@@ -223,7 +158,7 @@ def test_bad_arguments_are_argument_errors(systems):
     u, a, ea, e0 = S.dev(np.ones(S.n)), S.dev(np.ones(S.n)), S.dev(np.full(S.ne, EA)), S.dev(np.zeros(S.ne))
     out = torch.full((S.ne,), 7.0, dtype=torch.float64, device=eng.device)
     dg = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
-    _refill(S)
+    S.refill()
     s, P, G = eng._stream(), eng._ref(), C.byref(S.rec)
     up, ap, ep, zp, op, dp, kp = (t.data_ptr() for t in (u, a, ea, e0, out, dg, S.kt))
 
@@ -285,18 +220,6 @@ def test_bad_arguments_are_argument_errors(systems):
 # ---------------------------------------------------------------------------------------------------------------------
 # 5. the taut string: solve_nr, the CLI, axial_forces
 # ---------------------------------------------------------------------------------------------------------------------
-def _model(nodes, el, loads, fixed, dim=2):
-    from pinn_fem_amd.fem.model import FEMModel, Material
-    return FEMModel(nodes=nodes, elements=el, material=Material(YOUNG, AREA, 1.0), loads=loads, fixed_dofs=fixed, dimension=dim)
-
-
-def _config(**kw):
-    from pinn_fem_amd.fem.solver import SolverConfig
-    base = dict(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange")
-    base.update(kw)
-    return SolverConfig(**base)
-
-
 def _check_taut_string(ts, p, u, reactions, axial, label):
     """|P(w)/P - 1| <= 32 * 2^-53.  The two free dofs do not couple, so CG is exact and a converged Newton iteration leaves
     the round-off of one residual: about 10 roundings in the device's f_int, 3 for rounding u + du (P grows at most as
@@ -316,36 +239,31 @@ def test_solve_nr_taut_string(p):
     """The structure the unstrained solve refuses before its first iteration: the transverse dof has no linear stiffness."""
     from pinn_fem_amd.fem.solver import solve_nr
     ts = g0.TautString(ea=EA, e0=-1e-3)
-    model = _model(ts.nodes, ts.el, ts.loads(p), ts.fixed)
+    model = truss_model(ts.nodes, ts.el, ts.loads(p), ts.fixed)
     with pytest.raises(RuntimeError, match="Tangent stiffness became singular"):
-        solve_nr(model, _config(), 1.0)
-    res = solve_nr(model, _config(initial_strain=ts.e0), 1.0)
-    _, it_ref, _ = g0.newton(ts.nodes, ts.el, ts.loads(p), ts.fixed, EA, ts.e0, 2, tol=1e-10)
+        solve_nr(model, gl_config(), 1.0)
+    res = solve_nr(model, gl_config(initial_strain=ts.e0), 1.0)
+    _, it_ref, _ = gl.newton(ts.nodes, ts.el, ts.loads(p), ts.fixed, EA, 2, tol=1e-10, e0=ts.e0)
     print(f"taut string P = {p}: {res.history[-1]}, restatement {it_ref} iterations")
     assert res.converged and 3 <= res.history[-1]["iterations"] <= 15 and abs(res.history[-1]["iterations"] - it_ref) <= 1
     u = res.displacements.reshape(-1)
     _check_taut_string(ts, p, u, res.reactions, res.axial_forces, f"taut string P = {p}")
     assert abs(res.history[-1]["max_strain"] - ts.strain(u[3])) <= 8 * U53 * ts.strain(u[3])
     # per-element values: the same numbers; without an initial strain the result carries no axial forces
-    res2 = solve_nr(model, _config(initial_strain=[ts.e0, ts.e0]), 1.0)
+    res2 = solve_nr(model, gl_config(initial_strain=[ts.e0, ts.e0]), 1.0)
     assert res2.displacements.tobytes() == res.displacements.tobytes() and res2.axial_forces.tobytes() == res.axial_forces.tobytes()
 
 
 def test_cli_taut_string(tmp_path):
-    from pinn_fem_amd.cli import generic as g
     from pinn_fem_amd.fem.solver import solve_nr
-    shutil.copy(os.path.join(HERE, "nl_inputs", "taut_string.json"), tmp_path / "taut_string.json")
-    g.main(["generic.py", str(tmp_path / "taut_string.json")])
-    out = json.loads((tmp_path / "taut_string.res.json").read_text())
+    out = run_cli(tmp_path, "taut_string")
     ts = g0.TautString(ea=EA, e0=-1e-3)
-    want = solve_nr(_model(ts.nodes, ts.el, ts.loads(1.0), ts.fixed), _config(initial_strain=ts.e0), 1.0)
+    want = solve_nr(truss_model(ts.nodes, ts.el, ts.loads(1.0), ts.fixed), gl_config(initial_strain=ts.e0), 1.0)
     assert out["converged"] and np.array_equal(np.array(out["displacements"]), want.displacements.reshape(-1))
     assert np.array_equal(np.array(out["axial_forces"]), want.axial_forces) and len(out["axial_forces"]) == 2
     _check_taut_string(ts, 1.0, np.array(out["displacements"]), np.array(out["reactions"]), np.array(out["axial_forces"]), "CLI")
     # the existing input gives its former keys: no axial forces without an initial strain
-    shutil.copy(os.path.join(HERE, "nl_inputs", "two_bar_green_lagrange.json"), tmp_path / "two_bar.json")
-    g.main(["generic.py", str(tmp_path / "two_bar.json")])
-    assert set(json.loads((tmp_path / "two_bar.res.json").read_text())) == {"success", "converged", "iterations", "history",
+    assert set(run_cli(tmp_path, "two_bar_green_lagrange")) == {"success", "converged", "iterations", "history",
                                                                              "displacements", "reactions"}
 
 
@@ -354,7 +272,7 @@ def test_slack_string_is_refused():
     from pinn_fem_amd.fem.solver import solve_nr
     ts = g0.TautString(ea=EA, e0=1e-2)
     with pytest.raises(RuntimeError, match="not positive definite") as info:
-        solve_nr(_model(ts.nodes, ts.el, ts.loads(0.0), ts.fixed), _config(initial_strain=ts.e0), 1.0)
+        solve_nr(truss_model(ts.nodes, ts.el, ts.loads(0.0), ts.fixed), gl_config(initial_strain=ts.e0), 1.0)
     assert "free dof 3" in str(info.value)
 
 
@@ -364,8 +282,8 @@ def test_slack_string_is_refused():
 @pytest.fixture(scope="module")
 def cable_reference():
     nodes, el, loads, fixed = g0.cable_chain(256)
-    u_ref, it_ref, ok = g0.newton(nodes, el, loads, fixed, EA, -1e-2, 2, tol=1e-10)
-    u_cg, it_cg, ok_cg = g0.newton(nodes, el, loads, fixed, EA, -1e-2, 2, tol=1e-10, linear_solve=gl.jacobi_cg(1e-13))
+    u_ref, it_ref, ok = gl.newton(nodes, el, loads, fixed, EA, 2, tol=1e-10, e0=-1e-2)
+    u_cg, it_cg, ok_cg = gl.newton(nodes, el, loads, fixed, EA, 2, tol=1e-10, linear_solve=gl.jacobi_cg(1e-13), e0=-1e-2)
     assert ok and ok_cg and it_ref == it_cg
     return (nodes, el, loads, fixed), u_ref, it_ref, float(np.max(np.abs(u_cg - u_ref)) / np.max(np.abs(u_ref)))
 
@@ -377,15 +295,15 @@ def test_solve_nr_cable_chain(cable_reference, pre):
     10 for the different summation order."""
     from pinn_fem_amd.fem.solver import solve_nr
     (nodes, el, loads, fixed), u_ref, it_ref, err_ref = cable_reference
-    model = _model(nodes, el, loads, fixed)
-    res = solve_nr(model, _config(initial_strain=-1e-2, nr_preconditioner=pre), 1.0)
+    model = truss_model(nodes, el, loads, fixed)
+    res = solve_nr(model, gl_config(initial_strain=-1e-2, nr_preconditioner=pre), 1.0)
     u = res.displacements.reshape(-1)
     err = float(np.max(np.abs(u - u_ref)) / np.max(np.abs(u_ref)))
     eng = model._pf_engine_cache[1]
     print(f"cable {pre}: Newton {res.history[-1]['iterations']:.0f} (restatement {it_ref}), CG iterations {eng.pcg_iterations}, "
           f"error {err:.3e}, restatement's CG run {err_ref:.3e}, allowed {10 * err_ref:.3e}")
     assert res.converged and res.history[-1]["iterations"] == it_ref
-    n_ref = g0.axial_forces(nodes, el, u_ref, EA, -1e-2, 2)
+    n_ref = gl.axial_forces(nodes, el, u_ref, EA, 2, e0=-1e-2)
     assert res.axial_forces.shape == (256,) and np.all(res.axial_forces > 0.0)
     assert np.max(np.abs(res.axial_forces - n_ref)) <= 1e-9 * np.max(n_ref)     # (a sanity check; u is held below)
     assert err <= 10 * err_ref
@@ -400,9 +318,9 @@ def test_solve_prestressed_two_bar_path():
     tests/test_dc_f64.py's unstrained path."""
     from pinn_fem_amd.fem.solver import solve
     tb = g0.PrestressedTwoBar(ea=EA, e0=-1e-3)
-    model = _model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
-    cfg = _config(nr_control="displacement", method="nr", nr_control_dof=5, nr_control_displacement=-2.2 * tb.h, n_increments=11,
-                  initial_strain=tb.e0)
+    model = truss_model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
+    cfg = gl_config(nr_control="displacement", method="nr", nr_control_dof=5, nr_control_displacement=-2.2 * tb.h,
+                    n_increments=11, initial_strain=tb.e0)
     res = solve(model, cfg)
     assert res.converged and res.path is not None and len(res.path) == 11
     lam_seen = []
@@ -422,18 +340,14 @@ def test_solve_prestressed_two_bar_path():
     w = 2.2 * tb.h
     assert np.all(np.abs(res.axial_forces - EA * (tb.strain(w) - tb.e0)) <= 1e-9 * EA * abs(tb.e0))
     # the unstrained path on the same model is another one
-    plain = solve(model, _config(nr_control="displacement", method="nr", nr_control_dof=5, nr_control_displacement=-2.2 * tb.h,
-                                 n_increments=11))
+    plain = solve(model, gl_config(nr_control="displacement", method="nr", nr_control_dof=5,
+                                   nr_control_displacement=-2.2 * tb.h, n_increments=11))
     assert plain.axial_forces is None and abs(plain.path[2]["load_factor"] - lam_seen[2]) > 0.1
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # 8. identification on the prestressed girder
 # ---------------------------------------------------------------------------------------------------------------------
-def _warren_model(case):
-    return _model(case.nodes, case.el, case.loads, case.fixed)
-
-
 def test_gradient_and_jacobian_against_the_reference():
     """misfit_and_gradient and residuals_and_jacobian at all factors 1 on g0.warren_case() (e0 in +-1e-3), with both
     preconditioners.  Allowed distance, the rule of tests/test_identify_f64.py and tests/test_identify_gn_f64.py: ten times
@@ -445,16 +359,16 @@ def test_gradient_and_jacobian_against_the_reference():
     cg = dict(linear_solve=gl.jacobi_cg(1e-13))
     J_ref, g_ref = case.objective(q)
     J_cg, g_cg = case.objective(q, **cg)
-    rho_ref, A_ref, _, its_ref = g0.residuals_and_jacobian(case, q, case.e0)
-    rho_cg, A_cg, _, _ = g0.residuals_and_jacobian(case, q, case.e0, **cg)
+    rho_ref, A_ref, _, its_ref = ir.case_residuals(case, q, case.e0)
+    rho_cg, A_cg, _, _ = ir.case_residuals(case, q, case.e0, **cg)
     tol_J, tol_g = 10 * abs(J_cg - J_ref), 10 * np.max(np.abs(g_cg - g_ref))
     tol_rho, tol_A = 10 * np.max(np.abs(rho_cg - rho_ref)), 10 * np.max(np.abs(A_cg - A_ref))
     print(f"reference: J = {J_ref:.15e}, Newton iterations {its_ref}, ten times direct against CG: {tol_J:.2e} (J), "
           f"{tol_g:.2e} (dJ/dq), {tol_rho:.2e} (rho), {tol_A:.2e} (A)")
-    model = _warren_model(case)
+    model = case_model(case)
     ea = case.ea(q)
     for pre in ("jacobi", "two-level-updated"):
-        cfg = _config(nr_preconditioner=pre, initial_strain=case.e0)
+        cfg = gl_config(nr_preconditioner=pre, initial_strain=case.e0)
         J, g_ea, states, counters = misfit_and_gradient(model, cfg, case.levels, ea)
         eng = model._pf_engine_cache[1]
         g = eng.group_sum(g_ea, torch.from_numpy(ea).to(eng.device), case.groups).cpu().numpy()
@@ -465,7 +379,7 @@ def test_gradient_and_jacobian_against_the_reference():
         assert abs(J - J_ref) <= tol_J and np.max(np.abs(g - g_ref)) <= tol_g, pre
         assert np.max(np.abs(rho - rho_ref)) <= tol_rho and np.max(np.abs(A - A_ref)) <= tol_A, pre
     # the prestress is really in both: without it J and the gradient are others by far more than the allowance
-    J0, g0_ea, _, _ = misfit_and_gradient(model, _config(), case.levels, ea)
+    J0, g0_ea, _, _ = misfit_and_gradient(model, gl_config(), case.levels, ea)
     assert abs(J0 - J_ref) > 1e3 * tol_J
 
 
@@ -482,15 +396,15 @@ def test_gauss_newton_needs_the_prestress():
     _, blind_ref = g0.reference_run(False)
     err_ref = float(np.max(np.abs(run["factors"] - case.factors)))
     assert float(np.max(np.abs(blind_ref["factors"] - case.factors))) > 100 * err_ref        # the restatement shows the gap
-    model = _warren_model(case)
-    res = identify_nr(model, _config(initial_strain=case.e0), case.levels, groups=case.groups, method="gauss-newton",
+    model = case_model(case)
+    res = identify_nr(model, gl_config(initial_strain=case.e0), case.levels, groups=case.groups, method="gauss-newton",
                       misfit_tolerance=1e-15)
     err = float(np.max(np.abs(res.factors - case.factors)))
     print(f"with the prestress: {res.evaluations} evaluations (restatement {run['evaluations']}), stop {res.stop!r}, misfit "
           f"{res.misfit:.2e}, error {err:.3e} (restatement {err_ref:.3e}), factors {res.factors}")
     assert res.stop == "misfit" and res.converged and res.evaluations == run["evaluations"]
     assert err <= 10 * err_ref
-    blind = identify_nr(model, _config(), case.levels, groups=case.groups, method="gauss-newton", misfit_tolerance=1e-15)
+    blind = identify_nr(model, gl_config(), case.levels, groups=case.groups, method="gauss-newton", misfit_tolerance=1e-15)
     err_blind = float(np.max(np.abs(blind.factors - case.factors)))
     print(f"without: {blind.evaluations} evaluations, stop {blind.stop!r}, misfit {blind.misfit:.2e}, error {err_blind:.3e} "
           f"(restatement {float(np.max(np.abs(blind_ref['factors'] - case.factors))):.3e})")

@@ -10,7 +10,6 @@ import ctypes as C
 import json
 import math
 import os
-import shutil
 
 import numpy as np
 import pytest
@@ -18,7 +17,8 @@ import scipy.sparse.linalg as spla
 import torch
 
 import gl_reference as gl
-from device_driver import AREA, EA, RTOL, U24, U53, YOUNG, CgRun, gl_field, gl_system, system_cache, wide_vector
+from device_driver import (EA, RTOL, U24, U53, CgRun, gl_config, gl_field, gl_system, run_cli, system_cache, truss_model,
+                           wide_vector)
 from device_driver import GlTruss as System
 
 pytestmark = pytest.mark.gpu
@@ -329,15 +329,8 @@ def test_pcgt_edge_semantics(spd_case):
 # 5, 6. solve_nr and solve on the two-bar truss
 # ---------------------------------------------------------------------------------------------------------------------
 def _two_bar(p):
-    from pinn_fem_amd.fem.model import FEMModel, Material
     tb = gl.TwoBar(ea=EA)
-    return tb, FEMModel(nodes=tb.nodes, elements=tb.el, material=Material(YOUNG, AREA, 1.0), loads=tb.loads(p),
-                        fixed_dofs=tb.fixed, dimension=2)
-
-
-def _config(**kw):
-    from pinn_fem_amd.fem.solver import SolverConfig
-    return SolverConfig(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange", **kw)
+    return tb, truss_model(tb.nodes, tb.el, tb.loads(p), tb.fixed)
 
 
 def _check_two_bar(tb, p, res, label):
@@ -357,7 +350,7 @@ def _check_two_bar(tb, p, res, label):
 def test_solve_nr_two_bar_half_the_limit_load():
     from pinn_fem_amd.fem.solver import solve_nr
     tb, model = _two_bar(0.5 * gl.TwoBar().p_lim)
-    res = solve_nr(model, _config(), 1.0)
+    res = solve_nr(model, gl_config(), 1.0)
     _check_two_bar(tb, 0.5 * tb.p_lim, res, "two-bar 0.5 P_lim")
     assert 3 <= res.history[-1]["iterations"] <= 8                     # a real Newton iteration (the CPU loop takes 5)
     # the linear default on the same model: one step to w = P l0^3 / (2 E A h^2)
@@ -370,7 +363,7 @@ def test_solve_nr_two_bar_half_the_limit_load():
 def test_solve_two_bar_ninety_percent_in_ten_increments():
     from pinn_fem_amd.fem.solver import solve
     tb, model = _two_bar(0.9 * gl.TwoBar().p_lim)
-    res = solve(model, _config(n_increments=10, method="nr"))
+    res = solve(model, gl_config(n_increments=10, method="nr"))
     u = _check_two_bar(tb, 0.9 * tb.p_lim, res, "two-bar 0.9 P_lim, 10 increments")
     u_ref, its = gl.incremental(tb.nodes, tb.el, tb.loads(0.9 * tb.p_lim), tb.fixed, EA, 2, 10, tol=1e-10)
     # warm-started: the last increment takes what the CPU loop takes (from zero it would take many more)
@@ -387,7 +380,7 @@ def test_non_positive_definite_tangent_is_refused():
     u0 = np.zeros(6)
     u0[5] = -tb.h
     with pytest.raises(RuntimeError, match="not positive definite"):
-        solve_nr(model, _config(), 1.0, u_initial=torch.from_numpy(u0))
+        solve_nr(model, gl_config(), 1.0, u_initial=torch.from_numpy(u0))
     # the linear branch ignores u_initial, as the reference does
     from pinn_fem_amd.fem.solver import SolverConfig
     lin = solve_nr(model, SolverConfig(max_iterations=50, tolerance=1e-10), 1.0, u_initial=torch.from_numpy(u0))
@@ -402,16 +395,15 @@ def test_solve_warren_cantilever_in_ten_increments():
     CPU: the restatement's K_t,ff has its smallest eigenvalue, 1.897e-2, at the unloaded state and larger ones at every
     later iterate (checked below), and its Newton loop takes 5 iterations in each of the ten increments, the fourth
     ending at |du|/|u| = 3.0e-10 .. 8.4e-10 and the fifth below 1e-15: well clear of the tolerance 1e-10 on both sides."""
-    from pinn_fem_amd.fem.model import FEMModel, Material
     from pinn_fem_amd.fem.solver import solve
     nodes, el, unit, fixed, tip = gl.cantilever_warren(20)
     loads = 0.375 * unit
     eigs = []
     u_ref, its = gl.incremental(nodes, el, loads, fixed, EA, 2, 10, tol=1e-10,
-                                on_iterate=lambda u, K, free: eigs.append(gl.min_eig_ff(K, free)))
+                                on_iterate=lambda u, K, free, rhs: eigs.append(gl.min_eig_ff(K, free)))
     u_cg, its_cg = gl.incremental(nodes, el, loads, fixed, EA, 2, 10, tol=1e-10, linear_solve=gl.jacobi_cg(RTOL))
     assert min(eigs) > 1.8e-2 and its == its_cg == [5] * 10 and 1.8 < -u_ref[tip] < 2.0
-    model = FEMModel(nodes=nodes, elements=el, material=Material(YOUNG, AREA, 1.0), loads=loads, fixed_dofs=fixed, dimension=2)
+    model = truss_model(nodes, el, loads, fixed)
     counts = []
     import pinn_fem_amd.fem.solver as solver
     inner = solver.solve_nr
@@ -422,7 +414,7 @@ def test_solve_warren_cantilever_in_ten_increments():
         return r
     solver.solve_nr = counting
     try:
-        res = solve(model, _config(n_increments=10, method="nr"))
+        res = solve(model, gl_config(n_increments=10, method="nr"))
     finally:
         solver.solve_nr = inner
     u = res.displacements.reshape(-1)
@@ -438,13 +430,10 @@ def test_solve_warren_cantilever_in_ten_increments():
 # 8. 1-D
 # ---------------------------------------------------------------------------------------------------------------------
 def _solve_1d(x, el, f_end):
-    from pinn_fem_amd.fem.model import FEMModel, Material
     from pinn_fem_amd.fem.solver import solve_nr
     loads = np.zeros(len(x))
     loads[-1] = f_end
-    model = FEMModel(nodes=x, elements=el, material=Material(YOUNG, AREA, 1.0), loads=loads, fixed_dofs=np.array([0]),
-                     dimension=1)
-    return loads, solve_nr(model, _config(), 1.0)
+    return loads, solve_nr(truss_model(x, el, loads, np.array([0]), dim=1), gl_config(), 1.0)
 
 
 def test_solve_nr_one_bar_1d_closed_form():
@@ -486,11 +475,9 @@ def test_cli_kinematics_key(tmp_path):
     from pinn_fem_amd.cli import generic as g
     from pinn_fem_amd.fem.solver import solve_nr
     src = os.path.join(HERE, "nl_inputs", "two_bar_green_lagrange.json")
-    shutil.copy(src, tmp_path / "two_bar.json")
-    g.main(["generic.py", str(tmp_path / "two_bar.json")])
-    out = json.loads((tmp_path / "two_bar.res.json").read_text())
+    out = run_cli(tmp_path, "two_bar_green_lagrange", "two_bar")
     tb, model = _two_bar(0.5 * gl.TwoBar().p_lim)
-    want = solve_nr(model, _config(), 1.0).displacements.reshape(-1)           # test 5's run
+    want = solve_nr(model, gl_config(), 1.0).displacements.reshape(-1)           # test 5's run
     got = np.array(out["displacements"])
     print(f"CLI green-lagrange: {got}")
     assert np.array_equal(got, want)

@@ -7,10 +7,7 @@ restatement itself shows between its direct and its CG solves.  The measured fig
 assertion.
 """
 import ctypes as C
-import json
 import math
-import os
-import shutil
 
 import numpy as np
 import pytest
@@ -18,49 +15,16 @@ import torch
 
 import gl_reference as gl
 import identify_reference as ir
-from device_driver import EA, U53, gl_field, gl_system, system_cache
+from device_driver import EA, U53, case_model, check_state, gl_config, gl_field, gl_system, run_cli, system_cache, truss_model
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 MESHES = ["truss_1", "truss_255", "truss_256", "truss_257", "truss_1025", "chain_1", "chain_257"]
 
 
 @pytest.fixture(scope="module")
 def systems():
     yield from system_cache(gl_system)
-
-
-def _read_state(S):
-    torch.cuda.synchronize()
-    return (S.strain.cpu().numpy(), S.fe.cpu().numpy().reshape(S.ne, S.dim), S.kt.cpu().numpy().reshape(S.ne, -1))
-
-
-def _refill(S):
-    for t in (S.kt, S.fe, S.strain):
-        t.fill_(7.0)
-
-
-def _state_ea(S, u, ea):
-    """pf_gl_state_ea at u with the per-element ea -> (strain, fe, kt) on the host; the buffers are refilled with 7.0
-    first, so an element the kernel misses shows."""
-    eng, uu, ee = S.eng, S.dev(u), S.dev(ea)
-    _refill(S)
-    with eng.on_stream():
-        S.capi.check(S.lib.pf_gl_state_ea(eng._ref(), C.byref(S.rec), ee.data_ptr(), uu.data_ptr(), eng._stream()),
-                     "pf_gl_state_ea")
-    return _read_state(S)
-
-
-def _sens(S, u, a, accumulate=0, out=None):
-    eng, uu, aa = S.eng, S.dev(u), S.dev(a)
-    if out is None:
-        out = torch.full((S.ne,), 7.0, dtype=torch.float64, device=eng.device)
-    with eng.on_stream():
-        S.capi.check(S.lib.pf_gl_sens(eng._ref(), C.byref(S.rec), uu.data_ptr(), aa.data_ptr(), int(accumulate),
-                                      out.data_ptr(), eng._stream()), "pf_gl_sens")
-    torch.cuda.synchronize()
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -88,16 +52,6 @@ def _state_bounds(S, u, ea):
     return (strain, b_e), (fe, b_fe), (pick(B), pick(b_B))
 
 
-def _check_state(got, bounds, label):
-    for what, g, (want, bound) in zip(("strain", "fe", "kt"), got, bounds):
-        g = g.reshape(want.shape)
-        assert np.all(np.isfinite(g)), what
-        err = np.abs(g - want)
-        print(f"{label} {what}: worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}, "
-              f"relative {np.max(err) / np.max(np.abs(want)):.2e}")
-        assert np.all(err <= bound), what
-
-
 @pytest.mark.parametrize("kind", ["large", "tiny"])
 @pytest.mark.parametrize("name", MESHES)
 def test_gl_state_ea_against_the_restatement(systems, name, kind):
@@ -106,13 +60,12 @@ def test_gl_state_ea_against_the_restatement(systems, name, kind):
     S = systems(name)
     rng = np.random.default_rng(S.ne + 5)
     u, ea = gl_field(S, kind, rng), rng.uniform(500.0, 2000.0, S.ne)
-    _check_state(_state_ea(S, u, ea), _state_bounds(S, u, ea), f"{name} {kind} per-element ea")
+    check_state(S.state(u, ea=ea), _state_bounds(S, u, ea), f"{name} {kind} per-element ea")
     # pf_gl_state itself: the restatement bound of tests/test_gl_f64.py with the model's scalar E*A ...
-    _refill(S)
     scalar = S.state(u)
-    _check_state(scalar, _state_bounds(S, u, EA), f"{name} {kind} pf_gl_state")
+    check_state(scalar, _state_bounds(S, u, EA), f"{name} {kind} pf_gl_state")
     # ... and pf_gl_state_ea with ea filled with that scalar gives its bits
-    filled = _state_ea(S, u, np.full(S.ne, EA))
+    filled = S.state(u, ea=np.full(S.ne, EA))
     for what, a, b in zip(("strain", "fe", "kt"), filled, scalar):
         assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), what
 
@@ -122,10 +75,10 @@ def test_gl_state_ea_against_the_restatement(systems, name, kind):
 # ---------------------------------------------------------------------------------------------------------------------
 def _sens_bound(S, u, a):
     """s = -(e / l0) sum_c d_c (a_j,c - a_i,c).  Per side, in units of 2^-53 of (e_abs / l0) sum_c |d_c| (|a_j,c| + |a_i,c|)
-    (ir.sensitivity_scale): e 4 (half of the 8 e_abs of the state bounds), l0 = sqrt(l0^2) 2.5 (l0^2: 3, halved by the
+    (gl.sensitivity_scale): e 4 (half of the 8 e_abs of the state bounds), l0 = sqrt(l0^2) 2.5 (l0^2: 3, halved by the
     root, + 1), the division 1, d_c 1, a_j - a_i 1, their product 1, the sum over c 1, the last product 1: 12.5; 25 for
     device and reference together."""
-    return 25 * U53 * ir.sensitivity_scale(S.nodes, S.el, u, a, S.dim)
+    return 25 * U53 * gl.sensitivity_scale(S.nodes, S.el, u, a, S.dim)
 
 
 @pytest.mark.parametrize("name", MESHES)
@@ -135,20 +88,20 @@ def test_gl_sens_against_the_restatement(systems, name):
     for kind in ("large", "tiny"):
         u = gl_field(S, kind, rng)
         a1, a2 = rng.standard_normal(S.n), rng.standard_normal(S.n) * np.exp2(rng.uniform(-8.0, 8.0, S.n))
-        one = _sens(S, u, a1).cpu().numpy()
-        want, bound = ir.element_sensitivity(S.nodes, S.el, u, a1, S.dim), _sens_bound(S, u, a1)
+        one = S.sens(u, a1).cpu().numpy()
+        want, bound = gl.element_sensitivity(S.nodes, S.el, u, a1, S.dim), _sens_bound(S, u, a1)
         err = np.abs(one - want)
         print(f"{name} {kind}: sensitivity worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}, "
               f"relative {np.max(err) / np.max(np.abs(want)):.2e}")
         assert np.all(np.isfinite(one)) and np.all(err <= bound)
         # a rigid translation of the adjoint: a_j - a_i is exactly zero in every element
         shift = np.tile([3.0, -2.5][: S.dim], S.n_nodes)
-        rigid = _sens(S, u, shift).cpu().numpy()
+        rigid = S.sens(u, shift).cpu().numpy()
         assert np.all(rigid == 0.0)
         # accumulate: out + s with s rounded first, so the sum of two single calls to one rounding per element
-        two = _sens(S, u, a2).cpu().numpy()
-        acc = _sens(S, u, a1)
-        acc = _sens(S, u, a2, accumulate=1, out=acc).cpu().numpy()
+        two = S.sens(u, a2).cpu().numpy()
+        acc = S.sens(u, a1)
+        acc = S.sens(u, a2, accumulate=1, out=acc).cpu().numpy()
         err = np.abs(acc - (one + two))
         print(f"{name} {kind}: accumulated against the sum of two calls, worst {np.max(err / np.maximum(np.abs(one + two), 1e-300)) / U53:.2f} * 2^-53")
         assert np.all(err <= U53 * np.abs(one + two))
@@ -233,7 +186,7 @@ def test_bad_arguments_are_argument_errors(systems):
     S.state(np.zeros(S.n))
     u, a, ea = S.dev(np.ones(S.n)), S.dev(np.ones(S.n)), S.dev(np.full(S.ne, EA))
     out = torch.full((S.ne,), 7.0, dtype=torch.float64, device=eng.device)
-    _refill(S)
+    S.refill()
     s, P, G = eng._stream(), eng._ref(), C.byref(S.rec)
     up, ap, ep, op = u.data_ptr(), a.data_ptr(), ea.data_ptr(), out.data_ptr()
 
@@ -292,17 +245,6 @@ def test_bad_arguments_are_argument_errors(systems):
 # ---------------------------------------------------------------------------------------------------------------------
 # 5, 6. misfit_and_gradient, identify_nr and the CLI on the 8-panel Warren cantilever
 # ---------------------------------------------------------------------------------------------------------------------
-def _config(**kw):
-    from pinn_fem_amd.fem.solver import SolverConfig
-    return SolverConfig(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange", **kw)
-
-
-def _warren_model(case):
-    from pinn_fem_amd.fem.model import FEMModel, Material
-    return FEMModel(nodes=case.nodes, elements=case.el, material=Material(2000.0, 0.5, 1.0), loads=case.loads,
-                    fixed_dofs=case.fixed, dimension=2)
-
-
 def test_misfit_and_gradient_against_the_reference():
     """J and dJ/dq at all factors 1, with both preconditioners.  Allowed distance: ten times the distance the restatement
     itself shows between its direct-solve result and its own result with gl.jacobi_cg at rtol 1e-13, both computed here."""
@@ -315,11 +257,11 @@ def test_misfit_and_gradient_against_the_reference():
     J_cg, g_cg = case.objective(q, linear_solve=gl.jacobi_cg(1e-13))
     tol_J, tol_g = 10 * abs(J_cg - J_ref), 10 * np.max(np.abs(g_cg - g_ref))
     print(f"reference: J = {J_ref:.15e}, Newton iterations {its_ref}, direct against CG {abs(J_cg - J_ref):.2e} (J), {np.max(np.abs(g_cg - g_ref)):.2e} (dJ/dq)")
-    model = _warren_model(case)
+    model = case_model(case)
     ea = case.ea(q)
     got = {}
     for pre in ("jacobi", "two-level-updated"):
-        J, g_ea, states, counters = misfit_and_gradient(model, _config(nr_preconditioner=pre), case.levels, ea)
+        J, g_ea, states, counters = misfit_and_gradient(model, gl_config(nr_preconditioner=pre), case.levels, ea)
         eng = model._pf_engine_cache[1]
         assert isinstance(eng, HipEngine) and g_ea.is_cuda and g_ea.dtype == torch.float64 and len(states) == 3
         g = eng.group_sum(g_ea, torch.from_numpy(ea).to(eng.device), case.groups).cpu().numpy()
@@ -341,7 +283,7 @@ def test_identify_nr_recovers_the_four_factors():
     from pinn_fem_amd.fem import identify_nr
     case, ref_factors, ref_evaluations = ir.reference_recovery(8)
     cap = int(1.5 * ref_evaluations)
-    res = identify_nr(_warren_model(case), _config(), case.levels, groups=case.groups, max_evaluations=cap, gtol=1e-14)
+    res = identify_nr(case_model(case), gl_config(), case.levels, groups=case.groups, max_evaluations=cap, gtol=1e-14)
     err = np.max(np.abs(res.factors - case.factors))
     print(f"identify_nr: factors {res.factors}, error {err:.2e}, {res.evaluations} evaluations (reference {ref_evaluations}, "
           f"cap {cap}), misfit {res.misfit:.2e}, converged {res.converged}, counters {res.counters}")
@@ -358,18 +300,15 @@ def test_identify_nr_recovers_the_four_factors():
 def test_identify_nr_evaluation_cap_and_per_element_parameters():
     from pinn_fem_amd.fem import identify_nr
     case = ir.warren_case(8)
-    res = identify_nr(_warren_model(case), _config(), case.levels, groups=None, max_evaluations=3)
+    res = identify_nr(case_model(case), gl_config(), case.levels, groups=None, max_evaluations=3)
     print(f"per element, 3 evaluations: misfit {[h['misfit'] for h in res.history]}")
     assert res.evaluations == 3 and not res.converged and res.factors.shape == (31,) and res.gradient.shape == (31,)
     assert res.misfit == min(h["misfit"] for h in res.history) < res.history[0]["misfit"]
 
 
 def test_cli_identify(tmp_path):
-    from pinn_fem_amd.cli import generic as g
     case, _, ref_evaluations = ir.reference_recovery(8)
-    shutil.copy(os.path.join(HERE, "nl_inputs", "warren_identify.json"), tmp_path / "warren.json")
-    g.main(["generic.py", str(tmp_path / "warren.json")])
-    out = json.loads((tmp_path / "warren.res.json").read_text())
+    out = run_cli(tmp_path, "warren_identify", "warren")
     factors = np.array(out["identified_factors"])
     print(f"CLI: factors {factors}, {out['evaluations']} evaluations, misfit {out['misfit']:.2e}")
     assert np.max(np.abs(factors - case.factors)) <= 1e-5 and out["evaluations"] <= int(1.5 * ref_evaluations)
@@ -381,12 +320,6 @@ def test_cli_identify(tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------
 # 7, 8. the two-bar truss
 # ---------------------------------------------------------------------------------------------------------------------
-def _two_bar_model(tb, p):
-    from pinn_fem_amd.fem.model import FEMModel, Material
-    return FEMModel(nodes=tb.nodes, elements=tb.el, material=Material(2000.0, 0.5, 1.0), loads=tb.loads(p),
-                    fixed_dofs=tb.fixed, dimension=2)
-
-
 def test_two_bar_closed_form_on_the_device():
     """dJ/d(ea) = 2 (w - w_bar) (-P / (ea tangent(w))) at half the limit load.  Bound: ir.two_bar_bound (the Newton
     tolerance) plus 1e-9 for the CG solves, as tests/test_gl_f64.py allows them on this truss (rtol 1e-13 times the
@@ -396,7 +329,8 @@ def test_two_bar_closed_form_on_the_device():
     p, tol = 0.5 * tb.p_lim, 1e-10
     w_ref = -gl.newton(tb.nodes, tb.el, tb.loads(p), tb.fixed, EA, 2, tol=tol)[0][5]
     w_bar = 0.9 * w_ref
-    J, g, states, _ = misfit_and_gradient(_two_bar_model(tb, p), _config(), [(1.0, [5], [-w_bar])], np.full(2, EA))
+    model = truss_model(tb.nodes, tb.el, tb.loads(p), tb.fixed)
+    J, g, states, _ = misfit_and_gradient(model, gl_config(), [(1.0, [5], [-w_bar])], np.full(2, EA))
     w = -float(states[0][5])
     g = g.cpu().numpy()
     want = ir.two_bar_closed_form(tb, p, w, w_bar)
@@ -417,11 +351,11 @@ def test_a_level_beyond_the_limit_point_is_refused():
     u0 = gl.newton(tb.nodes, tb.el, tb.loads(0.5 * tb.p_lim), tb.fixed, EA, 2)[0]
     eigs = []
     gl.newton(tb.nodes, tb.el, tb.loads(2.0 * tb.p_lim), tb.fixed, EA, 2, u0=u0, max_iter=2,
-              on_iterate=lambda u, K, free: eigs.append(gl.min_eig_ff(K, free)))
+              on_iterate=lambda u, K, free, rhs: eigs.append(gl.min_eig_ff(K, free)))
     assert eigs[0] > 1.0 and eigs[1] < -0.3
-    model = _two_bar_model(tb, tb.p_lim)
+    model = truss_model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
     levels = [(0.5, [5], [u0[5]]), (2.0, [5], [-0.5])]
     with pytest.raises(RuntimeError, match="not positive definite"):
-        misfit_and_gradient(model, _config(), levels, np.full(2, EA))
+        misfit_and_gradient(model, gl_config(), levels, np.full(2, EA))
     with pytest.raises(RuntimeError, match="not positive definite"):
-        identify_nr(model, _config(), levels, groups=[0, 0])
+        identify_nr(model, gl_config(), levels, groups=[0, 0])

@@ -8,23 +8,19 @@ bound is a stated multiple of what the CPU restatement itself shows between its 
 the stop rule; the measured figures are printed in front of every assertion.
 """
 import ctypes as C
-import json
 import math
-import os
-import shutil
 
 import numpy as np
 import pytest
 import torch
 
 import gl_reference as gl
-import identify_gn_reference as gn
 import identify_reference as ir
-from device_driver import AREA, EA, RTOL, YOUNG, DeviceTruss, gl_field, gl_system, irregular_truss_with_supports, system_cache
+from device_driver import (AREA, EA, RTOL, YOUNG, DeviceTruss, case_model, device_ids, gl_config, gl_field, gl_system,
+                           group_maps, irregular_truss_with_supports, run_cli, system_cache, truss_model)
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 MESHES = ["truss_1", "truss_255", "truss_257", "truss_1025", "chain_1", "chain_257"]
 N_GROUPS = 5
 RANGES = [(0, 5), (2, 2), (4, 1)]
@@ -38,21 +34,6 @@ def systems():
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. pf_gl_group_rhs
 # ---------------------------------------------------------------------------------------------------------------------
-def _group_rhs(S, ids, g0, m):
-    """pf_gl_group_rhs on S's own element buffers with the device group map ids; out pre-filled with 7.0."""
-    eng = S.eng
-    out = torch.full((m, S.n), 7.0, dtype=torch.float64, device=eng.device)
-    with eng.on_stream():
-        S.capi.check(S.lib.pf_gl_group_rhs(eng._ref(), C.byref(S.rec), ids.data_ptr(), g0, m, out.data_ptr(), eng._stream()),
-                     "pf_gl_group_rhs")
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def _ids(S, groups):
-    return torch.from_numpy(np.ascontiguousarray(groups, dtype=np.int32)).to(S.eng.device)
-
-
 def _host_rhs(S, fe, groups, g):
     """Minus the sum of +-fe over the elements of group g, per node in ascending element id, one addition at a time;
     0.0 on the fixed dofs."""
@@ -66,29 +47,18 @@ def _host_rhs(S, fe, groups, g):
     return out
 
 
-def _group_maps(S, rng):
-    """name -> [n_elems] group ids: random in 0..4; group 3 empty; some elements at -1 and some at G + 3."""
-    random = rng.integers(0, N_GROUPS, S.ne)
-    hole = np.where(random == 3, 1, random)
-    stray = random.copy()
-    pick = rng.permutation(S.ne)
-    stray[pick[: max(1, S.ne // 7)]] = -1
-    stray[pick[max(1, S.ne // 7): max(1, S.ne // 7) + S.ne // 9]] = N_GROUPS + 3
-    return {"random": random, "one empty group": hole, "ids -1 and G + 3": stray}
-
-
 @pytest.mark.parametrize("name", MESHES)
 def test_group_rhs_is_the_sequential_host_sum_bit_for_bit(systems, name):
     S = systems(name)
     rng = np.random.default_rng(77)
     fe = S.state(gl_field(S, "large", rng))[1]
     assert np.all(np.isfinite(fe)) and np.any(fe != 0.0)
-    for label, groups in _group_maps(S, rng).items():
-        ids = _ids(S, groups)
+    for label, groups in group_maps(S, rng, N_GROUPS).items():
+        ids = device_ids(S, groups)
         want = {g: _host_rhs(S, fe, groups, g) for g in range(N_GROUPS)}
         for g0, m in RANGES:
-            got = _group_rhs(S, ids, g0, m)
-            again = _group_rhs(S, ids, g0, m)
+            got = S.group_rhs(ids, g0, m)
+            again = S.group_rhs(ids, g0, m)
             differing = [g0 + k for k in range(m) if got[k].tobytes() != want[g0 + k].tobytes()]
             nonzero = [int(np.count_nonzero(got[k])) for k in range(m)]
             print(f"{name}, {label}, (g0, m) = ({g0}, {m}): rows that differ from the host sum {differing}, nonzero entries "
@@ -97,7 +67,7 @@ def test_group_rhs_is_the_sequential_host_sum_bit_for_bit(systems, name):
             assert got.tobytes() == again.tobytes()
             assert not got[:, S.mask].any()
         if label == "one empty group":
-            assert not _group_rhs(S, ids, 3, 1).any()
+            assert not S.group_rhs(ids, 3, 1).any()
 
 
 @pytest.mark.parametrize("name", MESHES)
@@ -105,7 +75,7 @@ def test_one_group_is_minus_the_internal_force(systems, name):
     S = systems(name)
     S.state(gl_field(S, "large", np.random.default_rng(78)))
     fint = S.fint()
-    got = _group_rhs(S, _ids(S, np.zeros(S.ne, dtype=int)), 0, 1)[0]
+    got = S.group_rhs(device_ids(S, np.zeros(S.ne, dtype=int)), 0, 1)[0]
     same = got[S.free].tobytes() == (-fint)[S.free].tobytes()
     print(f"{name}: every element in one group: -f_int on the {int(S.free.sum())} free dofs to the bit: {same}; "
           f"max |f_int| {np.max(np.abs(fint)):.3e}")
@@ -116,7 +86,7 @@ def test_group_rhs_argument_errors(systems):
     S = systems("truss_257")
     eng, lib, capi = S.eng, S.lib, S.capi
     S.state(np.zeros(S.n))
-    ids = _ids(S, np.zeros(S.ne, dtype=int))
+    ids = device_ids(S, np.zeros(S.ne, dtype=int))
     out = torch.full((2, S.n), 7.0, dtype=torch.float64, device=eng.device)
     S.fe.fill_(7.0)
     s, P, G, ip, op = eng._stream(), eng._ref(), C.byref(S.rec), ids.data_ptr(), out.data_ptr()
@@ -206,17 +176,6 @@ def test_pcg_solve_many_equals_its_single_solves(truss, pre):
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. residuals_and_jacobian, identify_nr and the CLI on the 8-panel Warren cantilever
 # ---------------------------------------------------------------------------------------------------------------------
-def _config(**kw):
-    from pinn_fem_amd.fem.solver import SolverConfig
-    return SolverConfig(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange", **kw)
-
-
-def _warren_model(case):
-    from pinn_fem_amd.fem.model import FEMModel, Material
-    return FEMModel(nodes=case.nodes, elements=case.el, material=Material(2000.0, 0.5, 1.0), loads=case.loads,
-                    fixed_dofs=case.fixed, dimension=2)
-
-
 def test_residuals_and_jacobian_against_the_reference():
     """rho, A and 2 A^T rho at all factors 1, with both preconditioners.  Allowed distance: ten times the distance the
     restatement itself shows between its direct-solve result and its own result with gl.jacobi_cg at rtol 1e-13, both
@@ -225,18 +184,18 @@ def test_residuals_and_jacobian_against_the_reference():
     from pinn_fem_amd.fem.identify import misfit_and_gradient, residuals_and_jacobian
     case = ir.warren_case(8)
     q = np.zeros(4)
-    rho_ref, A_ref, _, its_ref = gn.residuals_and_jacobian(case, q)
-    rho_cg, A_cg, _, _ = gn.residuals_and_jacobian(case, q, linear_solve=gl.jacobi_cg(1e-13))
+    rho_ref, A_ref, _, its_ref = ir.case_residuals(case, q)
+    rho_cg, A_cg, _, _ = ir.case_residuals(case, q, linear_solve=gl.jacobi_cg(1e-13))
     g_ref, g_cg = 2.0 * A_ref.T @ rho_ref, 2.0 * A_cg.T @ rho_cg
     tol_rho, tol_A, tol_g = (10 * np.max(np.abs(rho_cg - rho_ref)), 10 * np.max(np.abs(A_cg - A_ref)),
                              10 * np.max(np.abs(g_cg - g_ref)))
     print(f"reference: J = {rho_ref @ rho_ref:.15e}, Newton iterations {its_ref}, ten times direct against CG: "
           f"{tol_rho:.2e} (rho), {tol_A:.2e} (A), {tol_g:.2e} (2 A^T rho)")
-    model = _warren_model(case)
+    model = case_model(case)
     ea = case.ea(q)
     got = {}
     for pre in ("jacobi", "two-level-updated"):
-        cfg = _config(nr_preconditioner=pre)
+        cfg = gl_config(nr_preconditioner=pre)
         rho, A, states, counters = residuals_and_jacobian(model, cfg, case.levels, ea, case.groups)
         eng = model._pf_engine_cache[1]
         J_adj, g_ea, _, _ = misfit_and_gradient(model, cfg, case.levels, ea)
@@ -268,9 +227,9 @@ def test_gauss_newton_recovers_the_factors(n_groups):
     max |q - q_true| <= 2 (sqrt J + 1e-10 max_k |u_k|) / sigma_min(A): the first-order bound A dq = rho from the stop rule
     and the Newton tolerance (|du| <= 1e-10 |u_k| in the Euclidean norm), the factor 2 covering the linearisation."""
     from pinn_fem_amd.fem import identify_nr
-    case, run = gn.reference_run(n_groups)
-    model = _warren_model(case)
-    res = identify_nr(model, _config(), case.levels, groups=case.groups, method="gauss-newton", misfit_tolerance=1e-15)
+    case, run = ir.reference_run(n_groups)
+    model = case_model(case)
+    res = identify_nr(model, gl_config(), case.levels, groups=case.groups, method="gauss-newton", misfit_tolerance=1e-15)
     A, M, G = res.jacobian, 90, n_groups
     q_err = np.max(np.abs(np.log(res.factors) - np.log(case.factors)))
     u_max = max(float(np.linalg.norm(u)) for u in res.displacements)
@@ -296,7 +255,7 @@ def test_gauss_newton_recovers_the_factors(n_groups):
     assert res.counters["jacobians"] == sum(h["accepted"] for h in res.history)
     if n_groups == 4:
         # L-BFGS on the same model is as before: none of the Gauss-Newton fields
-        old = identify_nr(model, _config(), case.levels, groups=case.groups, max_evaluations=2)
+        old = identify_nr(model, gl_config(), case.levels, groups=case.groups, max_evaluations=2)
         assert old.jacobian is None and old.singular_values is None and old.covariance is None
         assert old.factor_std is None and old.stop is None and old.evaluations == 2
         assert set(old.history[0]) == {"misfit", "gradient_norm", "factors"} and set(old.counters) == {
@@ -306,23 +265,20 @@ def test_gauss_newton_recovers_the_factors(n_groups):
 def test_evaluation_cap_and_a_group_that_moves_nothing():
     from pinn_fem_amd.fem import identify_nr
     case = ir.warren_case(8)
-    model = _warren_model(case)
-    res = identify_nr(model, _config(), case.levels, groups=case.groups, method="gauss-newton", max_evaluations=2)
+    model = case_model(case)
+    res = identify_nr(model, gl_config(), case.levels, groups=case.groups, method="gauss-newton", max_evaluations=2)
     print(f"cap 2: stop {res.stop!r}, misfit {[h['misfit'] for h in res.history]}")
     assert res.stop == "cap" and not res.converged and res.evaluations == 2 and res.misfit < res.history[0]["misfit"]
     # element 1 joins the two clamped nodes: a group of its own moves no dof at all
     assert set(case.el[1]) == {0, 1} and set(case.fixed) == {0, 1, 2, 3}
     groups = np.where(np.arange(31) == 1, 4, case.groups)
     with pytest.raises(RuntimeError, match="group 4 moves no measured dof"):
-        identify_nr(model, _config(), case.levels, groups=groups, method="gauss-newton")
+        identify_nr(model, gl_config(), case.levels, groups=groups, method="gauss-newton")
 
 
 def test_cli_identify_gauss_newton(tmp_path):
-    from pinn_fem_amd.cli import generic as g
-    case, run = gn.reference_run(4)
-    shutil.copy(os.path.join(HERE, "nl_inputs", "warren_identify_gn.json"), tmp_path / "warren.json")
-    g.main(["generic.py", str(tmp_path / "warren.json")])
-    out = json.loads((tmp_path / "warren.res.json").read_text())
+    case, run = ir.reference_run(4)
+    out = run_cli(tmp_path, "warren_identify_gn", "warren")
     factors = np.array(out["identified_factors"])
     print(f"CLI: factors {factors}, {out['evaluations']} evaluations, misfit {out['misfit']:.2e}, stop {out['stop']!r}, "
           f"factor_std {out['factor_std']}, singular values {out['singular_values']}")
@@ -345,13 +301,11 @@ def test_a_level_beyond_the_limit_point_is_refused():
     point, and gauss-newton propagates the existing error as L-BFGS does."""
     from pinn_fem_amd.fem import identify_nr
     from pinn_fem_amd.fem.identify import residuals_and_jacobian
-    from pinn_fem_amd.fem.model import FEMModel, Material
     tb = gl.TwoBar(ea=EA)
     u0 = gl.newton(tb.nodes, tb.el, tb.loads(0.5 * tb.p_lim), tb.fixed, EA, 2)[0]
-    model = FEMModel(nodes=tb.nodes, elements=tb.el, material=Material(2000.0, 0.5, 1.0), loads=tb.loads(tb.p_lim),
-                     fixed_dofs=tb.fixed, dimension=2)
+    model = truss_model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
     levels = [(0.5, [5], [u0[5]]), (2.0, [5], [-0.5])]
     with pytest.raises(RuntimeError, match="not positive definite"):
-        residuals_and_jacobian(model, _config(), levels, np.full(2, EA), [0, 0])
+        residuals_and_jacobian(model, gl_config(), levels, np.full(2, EA), [0, 0])
     with pytest.raises(RuntimeError, match="not positive definite"):
-        identify_nr(model, _config(), levels, groups=[0, 0], method="gauss-newton")
+        identify_nr(model, gl_config(), levels, groups=[0, 0], method="gauss-newton")

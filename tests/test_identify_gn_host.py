@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 import gl_reference as gl
-import identify_gn_reference as gn
 import identify_reference as ir
+from device_driver import case_model
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 U53 = 2.0 ** -53
@@ -28,13 +28,13 @@ def test_jacobian_against_central_differences():
     case = ir.warren_case(8)
     h = 1e-5
     for q in POINTS:
-        rho, A, _, _ = gn.residuals_and_jacobian(case, q, tol=1e-12)
+        rho, A, _, _ = ir.case_residuals(case, q, tol=1e-12)
         fd = np.zeros_like(A)
         for g in range(4):
             e = np.zeros(4)
             e[g] = h
-            fd[:, g] = (gn.residuals_and_jacobian(case, q + e, jacobian=False, tol=1e-12)[0]
-                        - gn.residuals_and_jacobian(case, q - e, jacobian=False, tol=1e-12)[0]) / (2 * h)
+            fd[:, g] = (ir.case_residuals(case, q + e, jacobian=False, tol=1e-12)[0]
+                        - ir.case_residuals(case, q - e, jacobian=False, tol=1e-12)[0]) / (2 * h)
         err = np.max(np.abs(A - fd)) / np.max(np.abs(A))
         print(f"q = {q}: A {A.shape}, max |A| = {np.max(np.abs(A)):.3e}, against differences {err:.2e}")
         assert A.shape == (3 * 30, 4) and rho.shape == (90,) and err <= 1e-8
@@ -48,7 +48,7 @@ def test_twice_a_transpose_rho_is_the_adjoint_gradient():
     case = ir.warren_case(8)
     free = gl.free_mask(len(case.loads), case.fixed)
     for q in POINTS:
-        rho, A, us, _ = gn.residuals_and_jacobian(case, q)
+        rho, A, us, _ = ir.case_residuals(case, q)
         J, g = case.objective(q)
         cond = max(np.linalg.cond(gl.restrict(gl.k_t(case.nodes, case.el, u, case.ea(q), 2), free).toarray()) for u in us)
         err = np.max(np.abs(2.0 * A.T @ rho - g)) / np.max(np.abs(g))
@@ -66,9 +66,9 @@ def test_group_right_hand_sides_sum_to_minus_the_load():
     free = gl.free_mask(len(case.loads), case.fixed)
     q = POINTS[1]
     ea = case.ea(q)
-    us = gn.residuals_and_jacobian(case, q, jacobian=False)[2]
+    us = ir.case_residuals(case, q, jacobian=False)[2]
     for (lam, _, _), u in zip(case.levels, us):
-        B = gn.group_rhs(case.nodes, case.el, u, ea, 2, case.groups, 4, case.fixed)
+        B = gl.group_rhs(case.nodes, case.el, u, ea, 2, case.groups, 4, case.fixed)
         residual = lam * case.loads - gl.f_int(case.nodes, case.el, u, ea, 2)
         gap = np.max(np.abs(B.sum(axis=0) + lam * case.loads - residual)[free])
         allowed = 4 * U53 * np.max(gl.f_int_scale(case.nodes, case.el, u, ea, 2))
@@ -84,7 +84,7 @@ def test_levenberg_marquardt_takes_five_evaluations(n_groups):
     """From all factors 1 with misfit_tolerance 1e-15: five evaluations, every step accepted, and the count does not
     hinge on round-off: the last misfit above 1e-15 is more than 150 times it and the first below more than 150 times
     under it."""
-    case, run = gn.reference_run(n_groups)
+    case, run = ir.reference_run(n_groups)
     misfits = [h["misfit"] for h in run["history"]]
     err = np.max(np.abs(run["factors"] - case.factors))
     s = np.linalg.svd(run["jacobian"], compute_uv=False)
@@ -97,8 +97,8 @@ def test_levenberg_marquardt_takes_five_evaluations(n_groups):
 
 
 def test_the_newton_tolerance_does_not_change_the_count():
-    case = gn.case_with_groups(4)
-    counts = [gn.levenberg_marquardt(case, misfit_tolerance=1e-15, tol=tol)["evaluations"] for tol in (1e-8, 1e-10)]
+    case = ir.case_with_groups(4)
+    counts = [ir.identify_factors(case, misfit_tolerance=1e-15, tol=tol)["evaluations"] for tol in (1e-8, 1e-10)]
     print(f"evaluations with the Newton tolerance at 1e-8 and 1e-10: {counts}")
     assert counts == [5, 5]
 
@@ -108,13 +108,13 @@ def test_noisy_measurements_and_the_covariance():
     standard deviations of the log-factors are those of sigma^2 (A~^T A~)^-1 with the known sigma and the unweighted
     Jacobian A~ = sqrt|m| A to within three standard errors of a variance estimate, 3 / sqrt(2 (M - G)); and every
     log-factor lies within 4 estimated standard deviations of the truth."""
-    case = gn.noisy_case()
-    run = gn.levenberg_marquardt(case)
+    case = ir.noisy_case()
+    run = ir.identify_factors(case)
     A = run["jacobian"]
     M, G = A.shape
-    std = np.sqrt(np.diag(gn.covariance(A, run["misfit"])))
+    std = np.sqrt(np.diag(ir.covariance(A, run["misfit"])))
     m = len(case.levels[0][1])
-    known = gn.NOISE_SIGMA * np.sqrt(np.diag(np.linalg.inv((m * A).T @ A)))
+    known = ir.NOISE_SIGMA * np.sqrt(np.diag(np.linalg.inv((m * A).T @ A)))
     off = (run["q"] - np.log(case.factors)) / std
     print(f"noisy: {run['evaluations']} evaluations, stop {run['stop']!r}, J = {run['misfit']:.3e}, std of log-factors {std}, "
           f"std / known - 1 = {std / known - 1.0} (allowed {3 / np.sqrt(2 * (M - G)):.3f}), (q - q_true) / std = {off}")
@@ -125,10 +125,8 @@ def test_noisy_measurements_and_the_covariance():
 
 # ---- 3. refusals ----------------------------------------------------------------------------------------------------
 def _model(n_panels=8):
-    from pinn_fem_amd.fem.model import FEMModel, Material
     case = ir.warren_case(n_panels)
-    return case, FEMModel(nodes=case.nodes, elements=case.el, material=Material(2000.0, 0.5, 1.0), loads=case.loads,
-                          fixed_dofs=case.fixed, dimension=2)
+    return case, case_model(case)
 
 
 def test_every_refusal_is_a_value_error_before_an_engine_is_built(monkeypatch):

@@ -11,10 +11,10 @@ import re
 import numpy as np
 import pytest
 
-import gl_e0_reference as g0
 import gl_reference as gl
 import identify_prestress_reference as pr
 import identify_reference as ir
+from device_driver import case_model
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 U53 = 2.0 ** -53
@@ -24,10 +24,10 @@ POINTS = ((np.zeros(4), np.zeros(4)), (np.array([0.1, -0.2, 0.05, 0.3]), np.arra
 # ---- 1. the right-hand side and the Jacobian -----------------------------------------------------------------------------
 def test_prestress_rhs_is_the_difference_quotient_of_the_internal_force():
     """f_int is affine in e0, so (f_int(e0) - f_int(e0 + tau 1_h)) / tau is row h exactly; e0 in multiples of 2^-20 and
-    tau = 2^-10 make e0 + tau exact.  Allowed, per dof: each f_int carries at most (16 + deg) 2^-53 of g0.f_int_scale (the 16
+    tau = 2^-10 make e0 + tau exact.  Allowed, per dof: each f_int carries at most (16 + deg) 2^-53 of gl.f_int_scale (the 16
     roundings of fe's chain on the magnitude in front of the cancellation of e - e0, test_gl_e0_f64.py's count, and deg - 1
     of the node sum), their difference 2^-53 (|f1| + |f2|), all over tau; the row itself (5 + deg) 2^-53 of
-    pr.prestress_rhs_scale (6 roundings per term, deg - 1 of the sum)."""
+    gl.prestress_rhs_scale (6 roundings per term, deg - 1 of the sum)."""
     case = pr.warren_case(True, True)
     rng = np.random.default_rng(3)
     n = len(case.loads)
@@ -36,22 +36,22 @@ def test_prestress_rhs_is_the_difference_quotient_of_the_internal_force():
     e0 = rng.integers(-1000, 1001, len(case.el)) * 2.0 ** -20
     tau = 2.0 ** -10
     deg = np.repeat(np.bincount(case.el.reshape(-1), minlength=n // 2), 2)
-    rows = pr.prestress_rhs(case.nodes, case.el, u, ea, case.pgroups, 4, 2)
-    scale = pr.prestress_rhs_scale(case.nodes, case.el, u, ea, case.pgroups, 4, 2)
-    f1 = g0.f_int(case.nodes, case.el, u, ea, e0, 2)
-    s1 = g0.f_int_scale(case.nodes, case.el, u, ea, e0, 2)
+    rows = gl.prestress_rhs(case.nodes, case.el, u, ea, case.pgroups, 4, 2)
+    scale = gl.prestress_rhs_scale(case.nodes, case.el, u, ea, case.pgroups, 4, 2)
+    f1 = gl.f_int(case.nodes, case.el, u, ea, 2, e0=e0)
+    s1 = gl.f_int_scale(case.nodes, case.el, u, ea, 2, e0=e0)
     for h in range(4):
         e0_h = e0 + tau * (case.pgroups == h)
-        f2 = g0.f_int(case.nodes, case.el, u, ea, e0_h, 2)
-        s2 = g0.f_int_scale(case.nodes, case.el, u, ea, e0_h, 2)
+        f2 = gl.f_int(case.nodes, case.el, u, ea, 2, e0=e0_h)
+        s2 = gl.f_int_scale(case.nodes, case.el, u, ea, 2, e0=e0_h)
         allowed = ((16 + deg) * U53 * (s1 + s2) + U53 * (np.abs(f1) + np.abs(f2))) / tau + (5 + deg) * U53 * scale[h]
         err = np.abs((f1 - f2) / tau - rows[h])
         print(f"group {h}: worst error / allowed {np.max(err / allowed):.3f}, max |row| {np.max(np.abs(rows[h])):.3e}")
         assert np.all(err <= allowed) and np.any(rows[h] != 0.0)
     # elements of no group (-1) and ids above the range add nothing
     stray = np.where(np.arange(len(case.el)) % 3 == 0, -1, case.pgroups)
-    part = pr.prestress_rhs(case.nodes, case.el, u, ea, stray, 4, 2)
-    rest = pr.prestress_rhs(case.nodes, case.el, u, ea, np.where(stray == -1, case.pgroups, -1), 4, 2)
+    part = gl.prestress_rhs(case.nodes, case.el, u, ea, stray, 4, 2)
+    rest = gl.prestress_rhs(case.nodes, case.el, u, ea, np.where(stray == -1, case.pgroups, -1), 4, 2)
     assert np.allclose(part + rest, rows, rtol=0.0, atol=8 * U53 * np.max(scale))
 
 
@@ -60,8 +60,8 @@ def _central(case, q, t, h):
     for c in range(8):
         e = np.zeros(8)
         e[c] = h
-        up = pr.residuals_and_jacobian(case, q + e[:4], t + e[4:], jacobian=False, tol=1e-12)[0]
-        down = pr.residuals_and_jacobian(case, q - e[:4], t - e[4:], jacobian=False, tol=1e-12)[0]
+        up = ir.case_residuals(case, q + e[:4], jacobian=False, tol=1e-12, t=t + e[4:])[0]
+        down = ir.case_residuals(case, q - e[:4], jacobian=False, tol=1e-12, t=t - e[4:])[0]
         fd[:, c] = (up - down) / (2 * h)
     return fd
 
@@ -78,14 +78,14 @@ def test_jacobian_and_gradient_against_central_differences():
     case = pr.warren_case(True, True)
     h = 1e-5
     for q, t in POINTS:
-        rho, A, _, _ = pr.residuals_and_jacobian(case, q, t, tol=1e-12)
+        rho, A, _, _ = ir.case_residuals(case, q, tol=1e-12, t=t)
         fd = _central(case, q, t, h)
         g, g_fd = 2.0 * A.T @ rho, np.zeros(8)
         for c in range(8):
             e = np.zeros(8)
             e[c] = h
-            up = pr.residuals_and_jacobian(case, q + e[:4], t + e[4:], jacobian=False, tol=1e-12)[0]
-            down = pr.residuals_and_jacobian(case, q - e[:4], t - e[4:], jacobian=False, tol=1e-12)[0]
+            up = ir.case_residuals(case, q + e[:4], jacobian=False, tol=1e-12, t=t + e[4:])[0]
+            down = ir.case_residuals(case, q - e[:4], jacobian=False, tol=1e-12, t=t - e[4:])[0]
             g_fd[c] = (up @ up - down @ down) / (2 * h)
         norms, r = np.linalg.norm(A, axis=0), np.linalg.norm(rho)
         g_allowed = h * h * (10.0 * norms ** 2 + 34.0 * r * norms) + 100 * U53 * (rho @ rho) / h
@@ -102,7 +102,7 @@ def test_joint_jacobian_is_well_conditioned():
     """The singular values of the joint Jacobian at x = 0 with unit columns: 2.1 .. 0.080, so the eight
     parameters are determined together; the raw columns differ by the scale gap, which the LM step does not see."""
     case = pr.warren_case(True, True)
-    A = pr.residuals_and_jacobian(case, np.zeros(4), np.zeros(4))[1]
+    A = ir.case_residuals(case, np.zeros(4), t=np.zeros(4))[1]
     norms = np.linalg.norm(A, axis=0)
     s = np.linalg.svd(A / norms, compute_uv=False)
     print(f"column norms {norms}, singular values of the unit-column Jacobian {s}")
@@ -134,9 +134,9 @@ def test_left_out_prestress_goes_into_the_factors():
     an error above 1e-2 in the factors, against 1e-9 with the offsets identified alongside (the reason for identifying
     the prestress)."""
     case = pr.warren_case(True, True)
-    blind = g0.Case(case.nodes, case.el, case.loads, case.fixed, 0, case.ea0, case.groups, case.factors, case.levels,
-                    case.e0_base)
-    run = g0.levenberg_marquardt(blind, case.e0_base, misfit_tolerance=1e-15, max_evaluations=30)
+    blind = ir.Case(case.nodes, case.el, case.loads, case.fixed, 0, case.ea0, case.groups, case.factors, case.levels,
+                    e0=case.e0_base)
+    run = ir.identify_factors(blind, misfit_tolerance=1e-15, max_evaluations=30, e0=case.e0_base)
     err = np.max(np.abs(run["factors"] - case.factors))
     print(f"factors without the offsets: {run['factors']}, error {err:.3f}, misfit {run['misfit']:.2e}, stop {run['stop']!r}")
     assert err > 1e-2 and run["misfit"] > 1e-9
@@ -146,11 +146,11 @@ def test_cable_from_a_nearly_slack_start_and_the_slack_refusal():
     """The cable from t = -1e-3 (a tenth of its pretension) with next to no damping still arrives at -1e-2; from t = 0 the
     first evaluation is refused (no stiffness across), and that error propagates."""
     case = pr.cable_case()
-    run = pr.levenberg_marquardt(case, t0=np.array([-1e-3]), damping=1e-9, misfit_tolerance=1e-15)
+    run = ir.identify_prestress(case, t0=np.array([-1e-3]), damping=1e-9, misfit_tolerance=1e-15)
     print(f"cable from -1e-3: {run['evaluations']} evaluations, stop {run['stop']!r}, history {run['history']}")
     assert run["stop"] == "misfit" and abs(run["t"][0] + 1e-2) <= 1e-9
-    with pytest.raises(pr.Refused, match="slack"):
-        pr.levenberg_marquardt(case, t0=np.zeros(1))
+    with pytest.raises(ir.Refused, match="slack"):
+        ir.identify_prestress(case, t0=np.zeros(1))
 
 
 def test_noisy_measurements_and_the_covariance():
@@ -159,7 +159,7 @@ def test_noisy_measurements_and_the_covariance():
     the unweighted Jacobian A~ = sqrt|m| A to within three standard errors of a variance estimate, 3 / sqrt(2 (M - P));
     and every parameter lies within 4 estimated standard deviations of the truth."""
     case = pr.noisy_case()
-    run = pr.levenberg_marquardt(case)
+    run = ir.identify_prestress(case)
     A = run["jacobian"]
     M, P = A.shape
     std = np.sqrt(np.diag(pr.covariance(A, run["misfit"])))
@@ -241,10 +241,8 @@ def test_the_loop_without_rejection_propagates_a_trial_error_and_is_the_same_loo
 
 # ---- 3. refusals ----------------------------------------------------------------------------------------------------
 def _model():
-    from pinn_fem_amd.fem.model import FEMModel, Material
     case = ir.warren_case(8)
-    return case, FEMModel(nodes=case.nodes, elements=case.el, material=Material(2000.0, 0.5, 1.0), loads=case.loads,
-                          fixed_dofs=case.fixed, dimension=2)
+    return case, case_model(case)
 
 
 def test_every_refusal_is_a_value_error_before_an_engine_is_built(monkeypatch):

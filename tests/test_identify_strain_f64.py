@@ -7,10 +7,7 @@ stated multiple of what the CPU restatement itself shows between its direct and 
 printed in front of every assertion.
 """
 import ctypes as C
-import json
 import math
-import os
-import shutil
 
 import numpy as np
 import pytest
@@ -19,11 +16,10 @@ import torch
 import gl_reference as gl
 import identify_reference as ir
 import identify_strain_reference as sr
-from device_driver import EA, U53, gl_field, gl_system, system_cache
+from device_driver import EA, U53, case_model, gl_config, gl_field, gl_system, run_cli, system_cache, truss_model
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 MESHES = ["truss_1", "truss_255", "truss_256", "truss_257", "truss_1025", "chain_1", "chain_257"]
 GAUGE_COUNTS = [1, 255, 257, None]                 # None: every element
 
@@ -31,31 +27,6 @@ GAUGE_COUNTS = [1, 255, 257, None]                 # None: every element
 @pytest.fixture(scope="module")
 def systems():
     yield from system_cache(gl_system)
-
-
-def _rhs(S, u, coef, accumulate=0, out=None):
-    """pf_gl_strain_rhs on S's own d0; out pre-filled with 7.0 unless given."""
-    eng, uu, cc = S.eng, S.dev(u), S.dev(coef)
-    if out is None:
-        out = torch.full((S.n,), 7.0, dtype=torch.float64, device=eng.device)
-    with eng.on_stream():
-        S.capi.check(S.lib.pf_gl_strain_rhs(eng._ref(), C.byref(S.rec), uu.data_ptr(), cc.data_ptr(), int(accumulate),
-                                            out.data_ptr(), eng._stream()), "pf_gl_strain_rhs")
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def _jvp(S, u, elems, V):
-    """pf_gl_strain_jvp for the rows of V [m, n_dofs]; out [m, n_meas] pre-filled with 7.0."""
-    eng, uu, vv = S.eng, S.dev(u), S.dev(np.asarray(V).reshape(-1))
-    ids = torch.from_numpy(np.ascontiguousarray(elems, dtype=np.int32)).to(eng.device)
-    m = len(V)
-    out = torch.full((m, len(elems)), 7.0, dtype=torch.float64, device=eng.device)
-    with eng.on_stream():
-        S.capi.check(S.lib.pf_gl_strain_jvp(eng._ref(), C.byref(S.rec), uu.data_ptr(), ids.data_ptr(), len(elems),
-                                            vv.data_ptr(), m, out.data_ptr(), eng._stream()), "pf_gl_strain_jvp")
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
 
 
 def _gauge_sets(S, rng):
@@ -67,15 +38,15 @@ def _gauge_sets(S, rng):
 def _rhs_bound(S, u, coef):
     """Per term +-(c / l0^2) d_c: u_j - u_i 1 rounding and d0 + du 1 more, both of at most |d0_c| + |u_j,c| + |u_i,c|; l0^2
     2 (the products, their sum); the division 1; the product with d_c 1: 6.  A dof's deg terms are added with deg - 1
-    roundings of at most the sum of their magnitudes: (5 + deg) * 2^-53 of sr.bt_c_scale per side, (10 + 2 deg) for device
+    roundings of at most the sum of their magnitudes: (5 + deg) * 2^-53 of gl.bt_c_scale per side, (10 + 2 deg) for device
     and restatement together (an FMA only takes roundings away)."""
-    return (10 + 2 * S.degree) * U53 * sr.bt_c_scale(S.nodes, S.el, u, coef, S.dim)
+    return (10 + 2 * S.degree) * U53 * gl.bt_c_scale(S.nodes, S.el, u, coef, S.dim)
 
 
 def _jvp_bound(S, u, elems, v):
     """Per gauge sum_c d_c (v_j,c - v_i,c) / l0^2: d_c 2 as above, v_j - v_i 1, their product 1, the sum over c 1, l0^2 2,
-    the division 1: 8 * 2^-53 of sr.b_v_scale per side, 16 for device and restatement together."""
-    return 16 * U53 * sr.b_v_scale(S.nodes, S.el, u, elems, v, S.dim)
+    the division 1: 8 * 2^-53 of gl.b_v_scale per side, 16 for device and restatement together."""
+    return 16 * U53 * gl.b_v_scale(S.nodes, S.el, u, elems, v, S.dim)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -91,8 +62,8 @@ def test_strain_rhs_against_the_restatement(systems, name, kind):
     for elems in _gauge_sets(S, rng):
         coef = np.zeros(S.ne)
         coef[elems] = rng.standard_normal(len(elems)) * np.exp2(rng.uniform(-8.0, 8.0, len(elems)))
-        got, again = _rhs(S, u, coef), _rhs(S, u, coef)
-        want = np.where(S.mask, 0.0, sr.bt_c(S.nodes, S.el, u, coef, S.dim))
+        got, again = S.strain_rhs(u, coef), S.strain_rhs(u, coef)
+        want = np.where(S.mask, 0.0, gl.bt_c(S.nodes, S.el, u, coef, S.dim))
         bound = _rhs_bound(S, u, coef)
         err = np.abs(got - want)
         untouched = (bound == 0.0)                      # every incident coef is 0.0
@@ -107,7 +78,7 @@ def test_strain_rhs_against_the_restatement(systems, name, kind):
         assert np.any(got != 0.0) or not S.free[gauge_dofs].any()
         # accumulate: out + (the sum, rounded first) with one rounding on the free dofs; fixed dofs untouched
         start = rng.standard_normal(S.n)
-        acc = _rhs(S, u, coef, accumulate=1, out=S.dev(start))
+        acc = S.strain_rhs(u, coef, accumulate=1, out=S.dev(start))
         assert np.array_equal(acc[S.free].view(np.uint64), (start + got)[S.free].view(np.uint64))
         assert np.array_equal(acc[S.mask].view(np.uint64), start[S.mask].view(np.uint64))
     print(f"{name} {kind}: worst error / bound over the gauge sets {worst:.3f}")
@@ -126,10 +97,10 @@ def test_strain_jvp_against_the_restatement(systems, name, kind):
     for elems in _gauge_sets(S, rng):
         for m in (1, 2, 3):
             V = rng.standard_normal((m, S.n)) * np.exp2(rng.uniform(-8.0, 8.0, (m, S.n)))
-            got, again = _jvp(S, u, elems, V), _jvp(S, u, elems, V)
+            got, again = S.strain_jvp(u, elems, V), S.strain_jvp(u, elems, V)
             assert got.shape == (m, len(elems)) and np.all(np.isfinite(got)) and got.tobytes() == again.tobytes()
             for k in range(m):
-                err = np.abs(got[k] - sr.b_v(S.nodes, S.el, u, elems, V[k], S.dim))
+                err = np.abs(got[k] - gl.b_v(S.nodes, S.el, u, elems, V[k], S.dim))
                 bound = _jvp_bound(S, u, elems, V[k])
                 worst = max(worst, float(np.max(err / bound)))
                 assert np.all(err <= bound), (len(elems), m, k)
@@ -139,7 +110,7 @@ def test_strain_jvp_against_the_restatement(systems, name, kind):
     stray = np.concatenate([elems, [-1, S.ne, 2 ** 31 - 1, -2 ** 31]])
     stray = stray[rng.permutation(len(stray))]
     V = rng.standard_normal((2, S.n))
-    got, clean = _jvp(S, u, stray, V), _jvp(S, u, elems, V)
+    got, clean = S.strain_jvp(u, stray, V), S.strain_jvp(u, elems, V)
     inside = (stray >= 0) & (stray < S.ne)
     assert np.all(got[:, ~inside] == 0.0) and int((~inside).sum()) == 4
     order = {int(e): i for i, e in enumerate(elems)}
@@ -147,7 +118,7 @@ def test_strain_jvp_against_the_restatement(systems, name, kind):
     assert np.array_equal(got[:, inside].view(np.uint64), clean[:, pick].view(np.uint64))
     # a rigid translation of v: v_j - v_i is exactly zero in every element
     shift = np.tile([3.0, -2.5][: S.dim], S.n_nodes)
-    assert np.all(_jvp(S, u, elems, shift[None, :]) == 0.0)
+    assert np.all(S.strain_jvp(u, elems, shift[None, :]) == 0.0)
 
 
 @pytest.mark.parametrize("name", ["truss_257", "truss_1025", "chain_257"])
@@ -164,7 +135,7 @@ def test_jvp_and_rhs_are_adjoint(systems, name):
     coef = np.zeros(S.ne)
     coef[elems] = c
     V = np.where(S.mask, 0.0, rng.standard_normal((3, S.n)))
-    rhs, jvp = _rhs(S, u, coef), _jvp(S, u, elems, V)
+    rhs, jvp = S.strain_rhs(u, coef), S.strain_jvp(u, elems, V)
     rhs_bound = _rhs_bound(S, u, coef)
     for k in range(3):
         lhs_k, rhs_k = math.fsum(c * jvp[k]), math.fsum(rhs * V[k])
@@ -234,15 +205,15 @@ def test_bad_arguments_are_argument_errors(systems):
     assert eng._gl is None
     got = eng.gl_strain_rhs(S.dev(uu), S.dev(cc))
     torch.cuda.synchronize()
-    assert got.cpu().numpy().tobytes() == _rhs(S, uu, cc).tobytes()
+    assert got.cpu().numpy().tobytes() == S.strain_rhs(uu, cc).tobytes()
     start = S.dev(rng.standard_normal(S.n))
-    want = _rhs(S, uu, cc, accumulate=1, out=start.clone())
+    want = S.strain_rhs(uu, cc, accumulate=1, out=start.clone())
     assert eng.gl_strain_rhs(S.dev(uu), S.dev(cc), out=start) is start
     torch.cuda.synchronize()
     assert start.cpu().numpy().tobytes() == want.tobytes()
     got = eng.gl_strain_jvp(S.dev(uu), elems, S.dev(VV.reshape(-1)).reshape(3, S.n))
     torch.cuda.synchronize()
-    assert got.shape == (3, 40) and got.cpu().numpy().tobytes() == _jvp(S, uu, elems, VV).tobytes()
+    assert got.shape == (3, 40) and got.cpu().numpy().tobytes() == S.strain_jvp(uu, elems, VV).tobytes()
     assert eng.gl_strain_jvp(S.dev(uu), np.zeros(0, dtype=int), S.dev(VV.reshape(-1)).reshape(3, S.n)).shape == (3, 0)
     with pytest.raises(ValueError, match="gl_strain_rhs: coef has"):
         eng.gl_strain_rhs(S.dev(uu), S.dev(cc)[:-1])
@@ -257,17 +228,6 @@ def test_bad_arguments_are_argument_errors(systems):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. misfit_and_gradient, residuals_and_jacobian, identify_nr and the CLI on the 8-panel Warren cantilever
 # ---------------------------------------------------------------------------------------------------------------------
-def _config(**kw):
-    from pinn_fem_amd.fem.solver import SolverConfig
-    return SolverConfig(max_iterations=50, tolerance=1e-10, kinematics="green-lagrange", **kw)
-
-
-def _model(case):
-    from pinn_fem_amd.fem.model import FEMModel, Material
-    return FEMModel(nodes=case.nodes, elements=case.el, material=Material(2000.0, 0.5, 1.0), loads=case.loads,
-                    fixed_dofs=case.fixed, dimension=2)
-
-
 @pytest.mark.parametrize("tip", [False, True])
 def test_misfit_gradient_residuals_and_jacobian_against_the_reference(tip):
     """J, dJ/dq, rho and A at all factors 1 on strain_case(4) (strains only, and with the tip dof), with both preconditioners.
@@ -279,17 +239,17 @@ def test_misfit_gradient_residuals_and_jacobian_against_the_reference(tip):
     cg = dict(linear_solve=gl.jacobi_cg(1e-13))
     J_ref, g_ref = case.objective(q)
     J_cg, g_cg = case.objective(q, **cg)
-    rho_ref, A_ref, _, its_ref = sr.residuals_and_jacobian(case, q)
-    rho_cg, A_cg, _, _ = sr.residuals_and_jacobian(case, q, **cg)
+    rho_ref, A_ref, _, its_ref = ir.case_residuals(case, q)
+    rho_cg, A_cg, _, _ = ir.case_residuals(case, q, **cg)
     tol_J, tol_g = 10 * abs(J_cg - J_ref), 10 * np.max(np.abs(g_cg - g_ref))
     tol_rho, tol_A = 10 * np.max(np.abs(rho_cg - rho_ref)), 10 * np.max(np.abs(A_cg - A_ref))
     print(f"reference, tip {tip}: J = {J_ref:.15e}, Newton iterations {its_ref}, ten times direct against CG: {tol_J:.2e} (J), "
           f"{tol_g:.2e} (dJ/dq), {tol_rho:.2e} (rho), {tol_A:.2e} (A)")
-    model, levels, ea = _model(case), case.dict_levels(), case.ea(q)
+    model, levels, ea = case_model(case), case.dict_levels(), case.ea(q)
     M = case.n_rows
     got = {}
     for pre in ("jacobi", "two-level-updated"):
-        cfg = _config(nr_preconditioner=pre)
+        cfg = gl_config(nr_preconditioner=pre)
         J, g_ea, states, counters = misfit_and_gradient(model, cfg, levels, ea)
         eng = model._pf_engine_cache[1]
         g = eng.group_sum(g_ea, torch.from_numpy(ea).to(eng.device), case.groups).cpu().numpy()
@@ -320,9 +280,9 @@ def test_gauss_newton_recovers_the_factors_from_strains_only(n_groups):
     level at the gauges equal the measured ones to that same distance."""
     from pinn_fem_amd.fem import identify_nr
     case, run = sr.reference_run(n_groups)
-    run_cg = sr.levenberg_marquardt(case, misfit_tolerance=1e-15, linear_solve=gl.jacobi_cg(1e-13))
+    run_cg = ir.identify_factors(case, misfit_tolerance=1e-15, linear_solve=gl.jacobi_cg(1e-13))
     bound = max(10 * np.max(np.abs(run_cg["factors"] - run["factors"])), 1e-9)
-    res = identify_nr(_model(case), _config(), case.dict_levels(), groups=case.groups, method="gauss-newton",
+    res = identify_nr(case_model(case), gl_config(), case.dict_levels(), groups=case.groups, method="gauss-newton",
                       misfit_tolerance=1e-15)
     err = np.max(np.abs(res.factors - case.factors))
     elements, measured, _ = case.gauges[-1]
@@ -346,7 +306,7 @@ def test_lbfgs_recovers_the_factors_from_strains_only():
     from pinn_fem_amd.fem import identify_nr
     case, ref_factors, ref_evaluations = sr.reference_recovery()
     cap = int(1.5 * ref_evaluations)
-    res = identify_nr(_model(case), _config(), case.dict_levels(), groups=case.groups, max_evaluations=cap, gtol=1e-14)
+    res = identify_nr(case_model(case), gl_config(), case.dict_levels(), groups=case.groups, max_evaluations=cap, gtol=1e-14)
     err = np.max(np.abs(res.factors - case.factors))
     elements, measured, _ = case.gauges[-1]
     print(f"L-BFGS: factors {res.factors}, error {err:.2e} (restatement {np.max(np.abs(ref_factors - case.factors)):.2e}), "
@@ -356,16 +316,13 @@ def test_lbfgs_recovers_the_factors_from_strains_only():
     assert np.max(np.abs(res.strains[-1][elements] - measured)) <= 1e-5 * np.max(np.abs(measured))
     # displacement levels alone: no strains in the result
     base = ir.warren_case(8)
-    old = identify_nr(_model(base), _config(), base.levels, groups=base.groups, max_evaluations=2)
+    old = identify_nr(case_model(base), gl_config(), base.levels, groups=base.groups, max_evaluations=2)
     assert old.strains is None and old.evaluations == 2
 
 
 def test_cli_identify_from_strains(tmp_path):
-    from pinn_fem_amd.cli import generic as g
     case = sr.strain_case(4, tip=True)
-    shutil.copy(os.path.join(HERE, "nl_inputs", "warren_identify_strain.json"), tmp_path / "warren.json")
-    g.main(["generic.py", str(tmp_path / "warren.json")])
-    out = json.loads((tmp_path / "warren.res.json").read_text())
+    out = run_cli(tmp_path, "warren_identify_strain", "warren")
     factors = np.array(out["identified_factors"])
     elements, measured, _ = case.gauges[-1]
     print(f"CLI: factors {factors}, {out['evaluations']} evaluations, misfit {out['misfit']:.2e}, stop {out['stop']!r}, "
@@ -386,21 +343,19 @@ def test_a_strain_level_beyond_the_limit_point_is_refused():
     level's Newton loop steps past the limit point and both methods raise the RuntimeError a displacement level raises."""
     from pinn_fem_amd.fem import identify_nr
     from pinn_fem_amd.fem.identify import misfit_and_gradient
-    from pinn_fem_amd.fem.model import FEMModel, Material
     tb = gl.TwoBar(ea=EA)
     u0 = gl.newton(tb.nodes, tb.el, tb.loads(0.5 * tb.p_lim), tb.fixed, EA, 2)[0]
-    model = FEMModel(nodes=tb.nodes, elements=tb.el, material=Material(2000.0, 0.5, 1.0), loads=tb.loads(tb.p_lim),
-                     fixed_dofs=tb.fixed, dimension=2)
-    e0 = sr.strains(tb.nodes, tb.el, u0, 2)
+    model = truss_model(tb.nodes, tb.el, tb.loads(tb.p_lim), tb.fixed)
+    e0 = gl.strains(tb.nodes, tb.el, u0, 2)
     gauge = lambda lam, e: {"load_factor": lam, "dofs": [], "u": [], "strain_elements": [0, 1], "strains": e, "strain_scale": tb.l0}
     levels = [gauge(0.5, 0.9 * e0), gauge(2.0, [-0.004, -0.004])]
     with pytest.raises(RuntimeError, match="not positive definite"):
-        misfit_and_gradient(model, _config(), levels, np.full(2, EA))
+        misfit_and_gradient(model, gl_config(), levels, np.full(2, EA))
     for method in ("lbfgs", "gauss-newton"):
         with pytest.raises(RuntimeError, match="not positive definite"):
-            identify_nr(model, _config(), levels, groups=[0, 1], method=method)
+            identify_nr(model, gl_config(), levels, groups=[0, 1], method=method)
     # the first level alone is fine: J = L^2 (0.1 e)^2 at the true E*A, up to the Newton tolerance
-    J = misfit_and_gradient(model, _config(), levels[:1], np.full(2, EA))[0]
+    J = misfit_and_gradient(model, gl_config(), levels[:1], np.full(2, EA))[0]
     want = tb.l0 ** 2 * float(np.mean((0.1 * e0) ** 2))
     print(f"two-bar, the level at half the limit load alone: J = {J:.6e} (restatement {want:.6e})")
     assert abs(J - want) <= 1e-8 * want

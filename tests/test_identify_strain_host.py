@@ -15,6 +15,7 @@ import pytest
 import gl_reference as gl
 import identify_reference as ir
 import identify_strain_reference as sr
+from device_driver import case_model
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 U53 = 2.0 ** -53
@@ -37,16 +38,16 @@ def test_b_v_is_the_central_difference_of_the_strain():
     """e is quadratic in u, so (e(u + h v) - e(u - h v)) / 2h = B(u) v exactly; with a dyadic step h = 2^-8 on dyadic
     fields the only errors are the roundings of the two strains, 4 * 2^-53 e_abs each (half of the 8 e_abs that
     test_identify_f64.py allows device and reference together), over 2h, and those of B v itself: d is exact here, v_j - v_i
-    is exact, so per gauge the products 1, their sum 1, l0^2 2 and the division 1: 5 * 2^-53 of sr.b_v_scale."""
+    is exact, so per gauge the products 1, their sum 1, l0^2 2 and the division 1: 5 * 2^-53 of gl.b_v_scale."""
     case = sr.strain_case(4)
     rng = np.random.default_rng(5)
     u, v = _dyadic_fields(case, rng)
     h = 2.0 ** -8
     elements = np.arange(len(case.el))
-    fd = (sr.strains(case.nodes, case.el, u + h * v, 2) - sr.strains(case.nodes, case.el, u - h * v, 2)) / (2 * h)
-    got = sr.b_v(case.nodes, case.el, u, elements, v, 2)
+    fd = (gl.strains(case.nodes, case.el, u + h * v, 2) - gl.strains(case.nodes, case.el, u - h * v, 2)) / (2 * h)
+    got = gl.b_v(case.nodes, case.el, u, elements, v, 2)
     bound = (4 * U53 * (_e_abs(case, u + h * v) + _e_abs(case, u - h * v)) / (2 * h)
-             + 5 * U53 * sr.b_v_scale(case.nodes, case.el, u, elements, v, 2))
+             + 5 * U53 * gl.b_v_scale(case.nodes, case.el, u, elements, v, 2))
     err = np.abs(got - fd)
     print(f"B v against the central difference: worst error / bound {np.max(err / bound):.3f}, relative "
           f"{np.max(err) / np.max(np.abs(got)):.2e}")
@@ -62,15 +63,15 @@ def test_b_and_its_transpose_are_adjoint():
     n, ne = len(case.loads), len(case.el)
     u, v, c = 0.3 * rng.standard_normal(n), rng.standard_normal(n), rng.standard_normal(ne)
     elements = np.arange(ne)
-    lhs = float(c @ sr.b_v(case.nodes, case.el, u, elements, v, 2))
-    rhs = float(sr.bt_c(case.nodes, case.el, u, c, 2) @ v)
-    bound = (16 + 2 * (2 * ne + n)) * U53 * float(np.abs(c) @ sr.b_v_scale(case.nodes, case.el, u, elements, v, 2))
+    lhs = float(c @ gl.b_v(case.nodes, case.el, u, elements, v, 2))
+    rhs = float(gl.bt_c(case.nodes, case.el, u, c, 2) @ v)
+    bound = (16 + 2 * (2 * ne + n)) * U53 * float(np.abs(c) @ gl.b_v_scale(case.nodes, case.el, u, elements, v, 2))
     print(f"<c, B v> = {lhs:.15e}, <B^T c, v> = {rhs:.15e}, apart by {abs(lhs - rhs):.2e} (bound {bound:.2e})")
     assert abs(lhs - rhs) <= bound and abs(lhs) > 1e-3
     # a coefficient vector that is zero but on two elements moves the dofs of their four nodes only
     c0 = np.zeros(ne)
     c0[[3, 20]] = 1.0
-    out = sr.bt_c(case.nodes, case.el, u, c0, 2).reshape(-1, 2)
+    out = gl.bt_c(case.nodes, case.el, u, c0, 2).reshape(-1, 2)
     touched = np.unique(case.el[[3, 20]])
     assert np.all(out[np.setdiff1d(np.arange(len(out)), touched)] == 0.0) and np.all(out[touched] != 0.0)
 
@@ -84,14 +85,14 @@ def test_jacobian_and_gradient_against_central_differences(tip):
     case = sr.strain_case(4, tip=tip)
     h = 1e-5
     for q in POINTS:
-        rho, A, _, _ = sr.residuals_and_jacobian(case, q, tol=1e-12)
+        rho, A, _, _ = ir.case_residuals(case, q, tol=1e-12)
         _, g = case.objective(q, tol=1e-12)
         fd_A, fd_g = np.zeros_like(A), np.zeros(4)
         for k in range(4):
             e = np.zeros(4)
             e[k] = h
-            rp = sr.residuals_and_jacobian(case, q + e, jacobian=False, tol=1e-12)[0]
-            rm = sr.residuals_and_jacobian(case, q - e, jacobian=False, tol=1e-12)[0]
+            rp = ir.case_residuals(case, q + e, jacobian=False, tol=1e-12)[0]
+            rm = ir.case_residuals(case, q - e, jacobian=False, tol=1e-12)[0]
             fd_A[:, k] = (rp - rm) / (2 * h)
             fd_g[k] = (case.objective(q + e, tol=1e-12)[0] - case.objective(q - e, tol=1e-12)[0]) / (2 * h)
         err_A = np.max(np.abs(A - fd_A)) / np.max(np.abs(A))
@@ -109,7 +110,7 @@ def test_twice_a_transpose_rho_is_the_adjoint_gradient(tip):
     case = sr.strain_case(4, tip=tip)
     free = gl.free_mask(len(case.loads), case.fixed)
     for q in POINTS:
-        rho, A, us, _ = sr.residuals_and_jacobian(case, q)
+        rho, A, us, _ = ir.case_residuals(case, q)
         J, g = case.objective(q)
         cond = max(np.linalg.cond(gl.restrict(gl.k_t(case.nodes, case.el, u, case.ea(q), 2), free).toarray()) for u in us)
         err = np.max(np.abs(2.0 * A.T @ rho - g)) / np.max(np.abs(g))
@@ -148,7 +149,7 @@ def test_two_bar_closed_form():
     w_ref = -gl.newton(tb.nodes, tb.el, tb.loads(p), tb.fixed, tb.ea, 2, tol=tol)[0][5]
     e_bar = 0.9 * tb.strain(w_ref)
     levels, gauges = [(1.0, [], [])], [([0, 1], [e_bar, e_bar], scale)]
-    J, g, us, _ = sr.misfit_and_gradient(tb.nodes, tb.el, tb.loads(p), tb.fixed, np.full(2, tb.ea), 2, levels, gauges, tol=tol)
+    J, g, us, _ = ir.misfit_and_gradient(tb.nodes, tb.el, tb.loads(p), tb.fixed, np.full(2, tb.ea), 2, levels, gauges, tol=tol)
     w = -us[0][5]
     want = sr.two_bar_closed_form(tb, p, w, e_bar, scale)
     rel, bound = abs(g.sum() - want) / abs(want), sr.two_bar_bound(tb, w, e_bar, tol)
@@ -159,17 +160,11 @@ def test_two_bar_closed_form():
 
 
 # ---- 5. refusals -----------------------------------------------------------------------------------------------------
-def _model(case):
-    from pinn_fem_amd.fem.model import FEMModel, Material
-    return FEMModel(nodes=case.nodes, elements=case.el, material=Material(2000.0, 0.5, 1.0), loads=case.loads,
-                    fixed_dofs=case.fixed, dimension=2)
-
-
 def test_every_refusal_of_check_strains(monkeypatch):
     from pinn_fem_amd.fem import identify, solver
     monkeypatch.setattr(solver, "_engine_for", lambda *a, **k: pytest.fail("an engine was built"))
     case = sr.strain_case(4, tip=True)
-    model = _model(case)
+    model = case_model(case)
     cfg = solver.SolverConfig(kinematics="green-lagrange", max_iterations=50, tolerance=1e-10)
     good = case.dict_levels()
 
@@ -214,7 +209,7 @@ def test_every_refusal_of_check_strains(monkeypatch):
 def test_check_strains_and_check_identify_on_good_levels():
     from pinn_fem_amd.fem import identify, solver
     case = sr.strain_case(4, tip=True)
-    model = _model(case)
+    model = case_model(case)
     cfg = solver.SolverConfig(kinematics="green-lagrange")
     good = case.dict_levels()
     mixed = [good[2], (good[0]["load_factor"], [33], [-0.4]), good[1]]           # unsorted, one tuple level without strains

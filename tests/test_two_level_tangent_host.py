@@ -13,15 +13,14 @@ import pytest
 import gl_reference as gl
 import two_level_reference as tl
 import two_level_tangent_reference as tt
+from device_driver import truss_model
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _two_bar_model():
-    from pinn_fem_amd.fem.model import FEMModel, Material
     tb = gl.TwoBar()
-    return FEMModel(nodes=tb.nodes, elements=tb.el, material=Material(2000.0, 0.5, 1.0), loads=tb.loads(0.1),
-                    fixed_dofs=tb.fixed, dimension=2)
+    return truss_model(tb.nodes, tb.el, tb.loads(0.1), tb.fixed)
 
 
 # ---- 1. configuration surface ---------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ def warren_case(panels=100, n_agg=32, n_inc=4, sag=0.1):
     loads = p_tip * unit
     states = []
     u_ref, its = gl.incremental(nodes, el, loads, fixed, EA, 2, n_inc, tol=1e-10,
-                                on_iterate=lambda u, K, fr: states.append((u.copy(), K)))
+                                on_iterate=lambda u, K, fr, rhs: states.append((u.copy(), K)))
     rhs, k = [], 0
     for inc, it in enumerate(its, 1):               # the right-hand side of every state's Newton step
         for _ in range(it):
@@ -87,7 +87,7 @@ def cg_newton(panels=100, n_agg=32, n_inc=4):
     total = [0]
     state = {}
 
-    def on_iterate(u, K, free):
+    def on_iterate(u, K, free, rhs):
         state["u"], state["K"] = u, K
 
     def solve(Kff_small, rhs_small):
