@@ -712,6 +712,32 @@ def test_sharded_c_driver_real_rccl_world1():
     assert got["driver_used_c"] == "c-rccl" and got["driver_used_c+graph"] == "c-rccl+graph", got
 
 
+def test_sharded_c_driver_real_rccl_world1_middle_shard():
+    """The same three drivers on a shard WITH an interface: rank 1 of a 3-shard chain (n_shared > 0, ghost elements on
+    both sides, own_lo > 0), still on the one-rank RCCL group where the all-reduce is the identity.  One rank's share is
+    no solution, so the drivers are compared with each other: the C driver and its hipGraph form (node_gradu on the side
+    branch beside the second backward and the collective) give the torch.distributed driver's bits in u, theta, the Adam
+    moments of u and every history column after 40 iterations on 20000 local elements."""
+    import subprocess
+    import sys
+    from helpers import ROOT
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29642", RANK="0", WORLD_SIZE="1",
+               PINNFEM_QUIET="1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "nccl_world1.py"), "20000", "30", "1", "3"],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    got = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    sh = got["shard"]
+    assert sh["n_shared"] == 12 and sh["n_iface"] == 12 and sh["own_lo"] == 1 and sh["own_hi"] == 20001
+    assert sh["n_elems"] == 20002                                   # one ghost element on either side
+    assert got["iters"] == [40, 40, 40] and got["history_rows"] == [40, 40, 40]
+    assert got["u_max"] > 0 and all(v > 0 for v in got["history_max"])        # six live columns, the lagging u-norm included
+    for drv in ("c", "c+graph"):
+        assert all(got["bitwise"][drv].values()), got["bitwise"]
+    assert got["driver_used_python"] == "python"
+    assert got["driver_used_c"] == "c-rccl" and got["driver_used_c+graph"] == "c-rccl+graph", got
+
+
 # ---- classical Newton-Raphson on the device (SURVEY.md §8f rank 3) ------------------------------------
 @pytest.mark.parametrize("name", ["nr_warren_scalar.npz", "nr_chain300_scalar.npz"])
 def test_newton_raphson_meshes_vs_reference(name):
