@@ -249,6 +249,16 @@ int pf_fusion_info(const pf_problem* p);
  * device (one small launch and a 4-byte copy; synchronous), as pf_graph_create does. */
 #define PF_GRAPH_FORM_FOLDED_RESIDUAL 1
 int pf_graph_form_info(const pf_problem* p);
+/* Does this problem's iteration graph run its path form (PF_GRAPH_FORM_FOLDED_RESIDUAL) with the LIGHT forward?  1 / 0, or
+ * PF_ERR_ARG.  1: both nets enabled, two hidden layers, split-f16 operands (the bf16-operand build keeps the full forward), and
+ * not a young net 21 to 24 wide with three inputs (its backward kernel has no register left for the form).
+ * The graph's forward launch then evaluates the E net only for the first and the last element of every 64-element task and
+ * stores prop_a and those elements' stiffness records; the fused backward launch, which recomputes the E net's hidden layers
+ * anyway, forms E itself and stores prop_e and every other record.  Same bits in prop_e, prop_a, elem_k and everything
+ * computed from them; each location is written once per iteration, and both launches of an iteration always complete
+ * together.  Eager launches and every other graph form run the full forward.  pf_graph_form_info is not affected.
+ * Additive: PF_ABI_VERSION stays 9. */
+int pf_graph_light_forward(const pf_problem* p);
 
 /* ---- building blocks (each replaces the cited reference lines) ------------------------ */
 /* torch-layout theta -> padded image (no reference analogue; internal layout change) */

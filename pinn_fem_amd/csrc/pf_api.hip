@@ -573,6 +573,15 @@ static bool can_fold_residual_static(const pf_problem* p) {
          can_fuse_theta_update(p) && pf_n32_bwd2_has_path(p) && p->n_iface == 0 && p->mesh.dim == p->net[0].in_dim - 1;
 }
 static bool can_fold_residual(const pf_problem* p) { return can_fold_residual_static(p) && mesh_is_path(p); }
+// Does the path form run with the LIGHT forward (pf_net32.hip: k_net32_forward2 / backward_phase, LIGHT)?  Then the forward
+// launch evaluates the E net only for the elements at task edges and the backward launch, which recomputes the E net's hidden
+// layers anyway, stores prop_e and the other records.  forward(i) and backward(i) always complete together (the stop flag is
+// only raised behind backward(i), in stage 1), and every reader of prop_e, prop_a and the records — forward(i+1)'s node
+// tasks, the replay's tail, pf_graph_tail, a continuation head, the results — runs behind backward(i): it sees the bytes the
+// full forward writes.
+static bool can_light_forward(const pf_problem* p, bool fold) {
+  return fold && p->net[0].enabled && p->net[1].enabled && pf_n32_has_light_forward(p);
+}
 
 // The buffers iteration i of the graph works on.  Properties and stiffness records ping-pong between iterations
 // (prop_double), so the forwards of iteration i do not wait for gradu(i-1), the last reader of the other half.  The
@@ -616,6 +625,7 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
   const bool fuse_s2 = can_fuse_theta_update(p);
   const int tn_ready = p->wg_mode == PF_WG_MFMA32 ? 1 : 0;   // k_theta_stage2 leaves the theta-norm monitor in the state
   const size_t k_half = (size_t)p->mesh.n_elems * (p->mesh.dim == 2 ? 3 : 1);   // floats of one half of the records
+  const bool light = can_light_forward(p, fold);
   for (int i = 0; i < iters; ++i) {
     hipEvent_t* e = c.ev + PF_CAP_EV * i;
     hipEvent_t* ep = c.ev + PF_CAP_EV * (i - 1);
@@ -638,9 +648,10 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
       return fail(PF_ERR_HIP, "graph edge failed");
     // (both nets in one launch where the engine has it; else one after the other: side by side on two branches they
     // measured slower, the same issue pipe, and the second one writes the stiffness records from both)
+    fo.light = light ? 1 : 0;
     PF_TRY(net_forward_all(&q, s, fo), "net_forward");
     if (fold) {
-      PF_TRY(net_backward2(&q, s, 1), "net_backward2");
+      PF_TRY(net_backward2(&q, s, light ? 2 : 1), "net_backward2");
       PF_TRY(pf_launch_theta_stage1_path(&q, s, carries ? (tn_ready ? 2 : 1) : 0), "theta_stage1");
       if (i == iters - 1 && !no_tail) {
         PF_TRY(pf_launch_theta_stage2(&q, 1, s), "theta_stage2");
@@ -679,6 +690,11 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
 int pf_graph_form_info(const pf_problem* p) {
   if (check_problem(p) != PF_OK) return PF_ERR_ARG;
   return can_fold_residual(p) ? PF_GRAPH_FORM_FOLDED_RESIDUAL : 0;
+}
+
+int pf_graph_light_forward(const pf_problem* p) {
+  if (check_problem(p) != PF_OK) return PF_ERR_ARG;
+  return can_light_forward(p, can_fold_residual(p)) ? 1 : 0;
 }
 
 int pf_graph_create(const pf_problem* p, int iters_per_graph, void* stream, void** graph_out) {

@@ -416,6 +416,7 @@ struct pf_fwd2_opts {
   bool calc_index = false;
   int gu_nb = 0;
   const float* gu_k = nullptr;
+  int light = 0;      // the light form (k_net32_forward2, LIGHT): the path backward that follows forms E and the records
 };
 // launchers of pf_net32.hip, one translation unit per register bucket (-DPF_NR=<nr>): nets of width <= 2*nr
 #define PF_DECL_NET32_LAUNCHERS(NRB)                                                       \

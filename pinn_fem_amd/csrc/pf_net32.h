@@ -160,6 +160,13 @@ inline bool pf_n32_bwd2_has_path(const pf_problem* p) {
   const int be = pf_net32_bucket(p->net[0].width), ba = pf_net32_bucket(p->net[1].width);
   return be > 0 && ba > 0 && be <= 12 && ba <= 12;
 }
+// Have the fused launches the light forward form for this problem's nets (pf_net32.hip: n32_has_light)?  Wherever the path
+// backward exists, with split-f16 operands and two hidden layers, except a young net of bucket 12 (widths 21..24) with three
+// inputs, whose light backward would spill; the bf16-operand build keeps the full forward.
+inline bool pf_n32_has_light_forward(const pf_problem* p) {
+  return pf_n32_bwd2_has_path(p) && p->mlp_dtype != PF_MLP_BF16 && p->net[0].n_hidden == 2 && p->net[1].n_hidden == 2 &&
+         !(pf_net32_bucket(p->net[0].width) == 12 && p->net[0].in_dim == 3);
+}
 inline bool pf_n32_fwd2_can_update_u(const pf_problem* p, int gu_nb) {
   if (!p->adj_other || !p->m_u || !p->v_u || p->mesh.n_elems <= 0) return false;
   if (p->n_shared != 0 || p->own_lo != 0 || p->own_hi != 0) return false;

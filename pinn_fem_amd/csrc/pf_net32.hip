@@ -261,13 +261,14 @@ __device__ __forceinline__ float one_minus_exp_neg(float s) {
 
 // with_nn: also load the element's node ids (the main loop has them already: they are fetched TWO tasks ahead, so that
 // the nodal gathers of task_fetch_b, which need them as addresses, never wait for a load issued in the same iteration)
-template <int IN, bool GEA>
+// OWN = false (light forward form: backward_phase, LIGHT): the net's own forward value is not loaded, the task forms it
+template <int IN, bool GEA, bool OWN = true>
 __device__ __forceinline__ void task_fetch_a(TaskIn<IN - 1>& t, const pf_problem& P, const pf_net& onet,
                                              const float* __restrict__ other, const float* __restrict__ mine, int e,
                                              bool with_nn = true) {
   load_x<IN>(t.x, P, e);
   t.oth = onet.enabled ? other[e] : onet.scale;
-  t.own = mine[e];
+  t.own = OWN ? mine[e] : 0.f;
   t.gea = 0.f;
   if (GEA) {
     if (with_nn) t.nn = reinterpret_cast<const int2*>(P.mesh.conn)[e];
@@ -513,7 +514,9 @@ struct Eng {
   }
   // forward through the hidden layers for BOTH tiles of a task; x0 / x1 = (load factor, coordinates) of the tile's
   // element on this lane's column.  p0 / p1: this lane's partial sums of the output unit, KA * sum_r wo[2r+h] a_L[2r+h].
-  template <int L, int IN, bool BWD>
+  // OUT: also the output unit's partial sums (the backward pass takes the output from the forward launch's stored value,
+  // except in the light forward form, where it forms the value itself: backward_phase, LIGHT)
+  template <int L, int IN, bool BWD, bool OUT = !BWD>
   static __device__ __forceinline__ void forward_tiles(const unsigned char* __restrict__ img, int lane, const float (&x0)[3],
                                                 const float (&x1)[3], TileAct<L, BWD>& A0, TileAct<L, BWD>& A1,
                                                 float& p0, float& p1, int dbg = 0, int grp = -1, float* go = nullptr,
@@ -605,7 +608,7 @@ struct Eng {
     if (grp == 2) __builtin_amdgcn_s_barrier();
     p0 = 0.f;
     p1 = 0.f;
-    if constexpr (!BWD) {      // (the backward pass takes the output from the forward launch's stored value)
+    if constexpr (OUT) {
       sfor<0, NR>([&](auto r) {
         constexpr int R = r;
         p0 = fmaf(wv[R], A0.aL[R], p0);
@@ -1031,8 +1034,16 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward(pf_problem P, int 
 // and the block adds them in index order: the monitor does not depend on which wave drew what.  The block's sum goes to
 // partials[PF_PART_U2 + block]; entries up to gu_nb (what the bookkeeping sums: pf_node_blocks) are zeroed.  gu_k: the
 // stiffness records of the previous iteration (the half this launch does NOT write).
+// LIGHT (the iteration graph's path form with the light forward: pf_api.hip, can_light_forward): the backward launch that
+// follows recomputes the E net's hidden layers anyway and rebuilds every element's stiffness record itself, so it also forms
+// E and stores prop_e and the records (backward_phase, LIGHT).  What it needs from this launch is A for every element and the
+// records of the elements its tasks read from BESIDE themselves: the first and the last element of every 64-element task
+// (lane 0 reads e-1, lane 63 e+1; the mesh's last element counts as a task's last).  So a regular element task here is the A
+// net alone and stores prop_a; the block's edge elements — two per task of its run — are packed 64 to a wave into EDGE
+// tasks, which follow the block's regular tasks in the same queue (task ids t1 .. t1e-1), run today's full body and store the
+// record alone.  No location is written twice in an iteration: prop_a here, prop_e and every other record in the backward.
 #define PF_GU_MAX_TASKS 1024
-template <int NRE, int NRA, int L, int IN>
+template <int NRE, int NRA, int L, int IN, bool LIGHT = false>
 __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int dbg_arg, int s2_half, int gu_nb,
                                                                const float* __restrict__ gu_k) {
   using EE = Eng<NRE>;
@@ -1063,9 +1074,29 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     s_next = waves;           // tasks t0 .. t0+waves-1 go to the waves in order, the rest through the queue
     s_next_n = 0;
   }
+  // LIGHT: the block's edge tasks behind its regular ones.  Slot j = 64 (task - t1) + lane of the edge tasks holds the first
+  // (j even) or the last (j odd; the mesh's last element in the mesh's last task) element of task t0 + j / 2.  A slot past
+  // the block's run, or an odd one whose element is its task's first as well (n = 1 mod 64), names a valid element and
+  // stores nothing.
+  const int n_run = max(t1 - t0, 0);
+  const int t1e = LIGHT ? t1 + ((2 * n_run + 63) >> 6) : t1;
+  auto task_elem = [&](int tk, bool& live) {         // the lane's element of task tk (clamped: a valid address), and: does it store?
+    int e = tk * 64 + lane;
+    live = e < n;
+    if constexpr (LIGHT) {
+      if (tk >= t1) {
+        const int j = (tk - t1) * 64 + lane;
+        const int first = max(min(t0 + (j >> 1), t1 - 1), 0) * 64;
+        e = (j & 1) ? min(first + 63, n - 1) : first;
+        live = j < 2 * n_run && !((j & 1) && e == first);
+      }
+    }
+    return min(e, n - 1);
+  };
   int task = t0 + wv;
   float xn[3] = {0.f, 0.f, 0.f};
-  if (n > 0) load_x<IN>(xn, P, min(task * 64 + lane, n - 1));
+  bool live_unused = false;
+  if (n > 0) load_x<IN>(xn, P, task_elem(task, live_unused));
   // node tasks of this block (gu_nb > 0)
   constexpr int GUN = 64 * PF_GU_M;
   const int n_ntasks = gu_nb > 0 ? (P.mesh.n_nodes + GUN - 1) / GUN : 0;
@@ -1115,15 +1146,15 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     else asm volatile("" : : "v"(xn[1]));
   };
   x_landed();
-  while (task < t1 || gu) {
-    if (gu && (since >= gu_every || task >= t1)) {
+  while (task < t1e || gu) {
+    if (gu && (since >= gu_every || task >= t1e)) {
       // a node task: the next element task's inputs are not touched
       since = 0;
       gu = node_task();
       x_landed();
       continue;
     }
-    if (task >= t1) break;
+    if (task >= t1e) break;
     ++since;
     // The element path's base pointers are read from the kernel argument where they are needed, behind an opaque move like
     // the node task's: the scalar registers do not hold them across the loop (left to the compiler it reloads them inside
@@ -1136,19 +1167,42 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     int k = 0;
     if (lane == 0) k = atomicAdd(&s_next, 1);
     const int nxt = t0 + __builtin_amdgcn_readfirstlane(k);
-    const int e = task * 64 + lane;
+    bool live;
+    const int e = task_elem(task, live);           // (clamped; equal to task * 64 + lane wherever `live`, outside the edge tasks)
+    const bool edge = LIGHT && task >= t1;         // (wave-uniform: task lives in a scalar register)
     // The task's own geometry: nothing reads it before store_k at the task's end, a whole task for the load to land.  Carried
     // a task ahead under `if (more)`, it met its old value at the loop's join and got a second register set; the copies
     // stood at the join behind s_waitcnt vmcnt(0), and on this ISA vmcnt counts stores: every task waited until its own
     // three stores were acknowledged.
-    const ElemGeo g = load_geo(egeo, min(e, n - 1));
+    // (LIGHT: only the edge tasks need it; they load it behind the branch below)
+    ElemGeo g = ElemGeo{0.f, 0.f, 0.f, 1.f};
+    if constexpr (!LIGHT) g = load_geo(egeo, e);
     float x0[3], x1[3];
     x0[0] = x1[0] = xn[0];       // (the load factor: one value for the launch, nothing to exchange)
     sfor<1, 3>([&](auto c) { constexpr int C = c; both_tiles(xn[C], x0[C], x1[C]); });
     // The next task's coordinates leave HERE, behind the last use of this task's (the half-wave exchange), into the
     // registers the next task reads.  In EVERY task: past the block's last task the clamped index names valid elements
     // nobody reads (as in backward_phase), so no loaded register meets an old value at a join.
-    load_x_from<IN>(xn, ecent, min(nxt * 64 + lane, n - 1));
+    load_x_from<IN>(xn, ecent, task_elem(nxt, live_unused));
+    if constexpr (LIGHT) {
+      if (!edge) {
+        // a regular task of the light form: the A net alone (the backward launch forms E and the record)
+        float za;
+        {
+          typename EA::template TileAct<L, false> A0, A1;
+          float p0, p1;
+          EA::template forward_tiles<L, IN, false>(img_a, lane, x0, x1, A0, A1, p0, p1, dbg);
+          za = own_total(p0, p1) * (1.0f / PF_N32_KA) + bo_a;
+        }
+        const __attribute__((address_space(4))) pf_problem* pout = kernarg_problem();
+        float* __restrict__ const prop_a = pout->prop_a;
+        x_landed();                                  // (the one vmcnt wait of the task, in front of the store: see below)
+        if (live) prop_a[e] = (net_a.positive ? pf_softplus(za) : za) * net_a.scale;
+        task = nxt;
+        continue;
+      }
+      g = load_geo(egeo, e);
+    }
     float ze, za;
     {
       typename EE::template TileAct<L, false> A0, A1;
@@ -1174,11 +1228,13 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     // goes on, the next vmcnt wait is this place of the next task.
     x_landed();
     asm volatile("" : : "v"(g.l0));
-    if (e < n) {
+    if (live) {
       const float ve = (net_e.positive ? pf_softplus(ze) : ze) * net_e.scale;
       const float va = (net_a.positive ? pf_softplus(za) : za) * net_a.scale;
-      prop_e[e] = ve;
-      prop_a[e] = va;
+      if constexpr (!LIGHT) {                        // (an edge task of the light form stores the record alone)
+        prop_e[e] = ve;
+        prop_a[e] = va;
+      }
       if (rec) store_k<IN - 1>(rec, e, g, (ve * va) / g.l0);    // (young * area) / l0, nn_assembly.py:74, :37
     }
     task = nxt;
@@ -1229,21 +1285,25 @@ __device__ __forceinline__ void bw_park(float* __restrict__ mine, const f32x16 (
 }
 // every thread of the block; the caller has placed a block barrier behind the last bw_park.  No barrier inside except the
 // one between the row's zero fill and its entries.
-template <int NR, int L, int IN>
+// FRESH (the light forward form, whose young-net task loop has no register to spare): the thread id behind an opaque move,
+// like backward_phase's — what is derived from it is formed here and not ahead of the task loops, where it was spilled.
+template <int NR, int L, int IN, bool FRESH = false>
 __device__ __forceinline__ void bw_row_from_parked(const pf_problem& P, int which, int hp, const float* __restrict__ park,
                                                    float kl, float kx) {
+  int tid = (int)threadIdx.x;
+  if constexpr (FRESH) asm volatile("" : "+v"(tid));
   const pf_net net = P.net[which];
   const int waves = blockDim.x >> 6, W = net.width;
   constexpr int PS = bw_park_floats<L>();
   float* __restrict__ prow = P.partials + PF_PART_WG + (size_t)blockIdx.x * P.pad_total + net.pad_off;
   const int padc = pf_pad_count(hp, L);
-  for (int i = threadIdx.x; i < padc; i += blockDim.x) prow[i] = 0.f;
+  for (int i = tid; i < padc; i += blockDim.x) prow[i] = 0.f;
   __syncthreads();
   sfor<0, L>([&](auto l) {
     constexpr int LL = l + 1;                      // layer whose weight gradient tile T[LL-1] holds
     float sc = 1.f;
     for (int k = 0; k < L - LL; ++k) sc *= 4.f;
-    for (int idx = threadIdx.x; idx < 1024; idx += blockDim.x) {
+    for (int idx = tid; idx < 1024; idx += blockDim.x) {
       const int m = idx >> 5, c = idx & 31;
       const int j = 2 * (m & 15) + (m >> 4);
       if ((m & 15) >= NR || j >= W) continue;
@@ -1264,15 +1324,15 @@ __device__ __forceinline__ void bw_row_from_parked(const pf_problem& P, int whic
     }
   });
   float* const pwo = prow + pf_pad_wo(hp, L);      // the output unit's weights, then its bias
-  if (threadIdx.x < 32) {
-    const int hh = threadIdx.x >> 4, r = threadIdx.x & 15, u = 2 * r + hh;
+  if (tid < 32) {
+    const int hh = tid >> 4, r = tid & 15, u = 2 * r + hh;
     if (r < NR && u < W) {
       float t = 0.f;
       for (int q = 0; q < waves; ++q) t += park[q * PS + L * 1024 + hh * 16 + r];
       pwo[u] = t * (1.0f / PF_N32_KA);
     }
   }
-  if (threadIdx.x == 32) {
+  if (tid == 32) {
     float t = 0.f;
     for (int q = 0; q < waves; ++q) t += park[q * PS + L * 1024 + 32];
     pwo[hp] = t;
@@ -1297,7 +1357,15 @@ __device__ __forceinline__ void bw_row_from_parked(const pf_problem& P, int whic
 // no register left for them (they were spilled to scratch in front of the loop and reloaded behind it).  The empty asm is a
 // hint that this compiler's register allocator took: profiles/r04_bwd2_registers.txt records what it gave (252 VGPRs, no
 // spill, for <10,8,2,3,true>); re-read .vgpr_spill_count in the code-object metadata after a toolchain change.
-template <int NR, int L, int IN, bool GEA, int MODE = 0, class FirstRow = int, bool PATH = false, bool FRESH = false>
+// LIGHT (a PATH phase of the light forward form: k_net32_forward2, LIGHT): the forward launch has stored neither E nor the
+// records of this phase's elements (only the records of the elements at task edges).  The task runs the hidden layers FIRST
+// (the recompute it does anyway), forms the output unit and E from them by the forward kernel's float operations — the same
+// bits — and takes that E where the other forms take the loaded value; it stores prop_e[e] (phase 2 of the same wave reads
+// it back as the other property, like g_ea; the results read it after the solve) and the element's record (the next forward
+// launch's node tasks read it), except where the forward launch's edge tasks wrote it: the lanes of path_edge_lane.  The
+// output row's sums g_z a'_L follow once g_z is known, tile 0 then tile 1 per unit as in activate2.
+template <int NR, int L, int IN, bool GEA, int MODE = 0, class FirstRow = int, bool PATH = false, bool FRESH = false,
+          bool LIGHT = false, bool ROW_FRESH = LIGHT>      // ROW_FRESH: bw_row_from_parked, FRESH
 __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, int hp, int dbg, const unsigned char* smem,
                                                unsigned char* cst, unsigned char* wscr,
                                                unsigned long long* stamps = nullptr, float* park = nullptr,
@@ -1353,12 +1421,13 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     return n - 1;
   };
   static_assert(!PATH || GEA, "the path form belongs to the phase that computes the element adjoint");
+  static_assert(!LIGHT || (PATH && E::template bw_pair<L>()), "the light forward form belongs to a path phase with the paired recompute");
   TaskIn<DIM> nxt;
   int2 nn_ahead = int2{0, 0};                    // node ids of the task after next (GEA only)
   int en_ahead = 0, en_next = 0;                 // PATH: the edge lanes' far node of the task after next / of the next task
   if (n > 0) {
     const int e0 = min(task_base(0) + lane, n - 1), e1 = min(task_base(1) + lane, n - 1);
-    task_fetch_a<IN, GEA>(nxt, P, onet, other, mine, e0);
+    task_fetch_a<IN, GEA, !LIGHT>(nxt, P, onet, other, mine, e0);
     if (GEA) nn_ahead = reinterpret_cast<const int2*>(P.mesh.conn)[e1];
     if constexpr (PATH) {
       en_next = path_edge_node(P, e0, n, lane, 0);
@@ -1379,6 +1448,8 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
   // scale of the load factor inside the f16 gradient products: the power of two with 2^13 <= kl |lam| < 2^14 (like the
   // coordinates' kx; a fixed factor would overflow f16 for large |lam| and lose the lo part for small ones)
   const float kl = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pf_n32_lam_scale(P.lam))));
+  // LIGHT: the output unit's bias
+  const float bo = LIGHT ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, reinterpret_cast<const float*>(smem + pf_n32_off_bo())[0]))) : 0.f;
   f32x16 T[L];          // sum over this wave's tasks of S * (tile products); S = Srun, a power of two that only falls
   sfor<0, L>([&](auto l) { constexpr int LL = l; T[LL] = zero16(); });
   float Srun = 0.f;     // 0: not chosen yet
@@ -1392,6 +1463,18 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     const int e = base + lane;
     const bool live = e < n;
     const TaskIn<DIM> cur = nxt;
+    float own = cur.own;                               // this net's forward value of the lane's element
+    float xa0, xa1, xb0, xb1;
+    typename E::template TileAct<L, true> LA0, LA1;    // LIGHT: both tiles' activations, formed ahead of the head
+    if constexpr (LIGHT) {
+      both_tiles(cur.x[1], xa0, xa1);
+      both_tiles(cur.x[2], xb0, xb1);
+      const float x0[3] = {cur.x[0], xa0, xb0}, x1[3] = {cur.x[0], xa1, xb1};
+      float p0, p1;
+      E::template forward_tiles<L, IN, true, true>(smem, lane, x0, x1, LA0, LA1, p0, p1);
+      const float z = own_total(p0, p1) * (1.0f / PF_N32_KA) + bo;
+      own = (net.positive ? pf_softplus(z) : z) * net.scale;       // = what the full forward launch stores as prop_e[e]
+    }
     // ---- per-element scalars: one element per lane ----------------------------------------------------------
     // softplus'(z) = sigmoid(z) = 1 - exp(-softplus(z)) from the forward's stored value (= softplus(z) * scale), so the
     // output unit need not be recomputed (torch: z > 20 ? 1 : e^z / (e^z + 1), the same number to float round-off)
@@ -1405,7 +1488,7 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
       // every lane (lane shifts inside); a lane past the mesh's end holds the last element again and stores nothing
       float ri[2], rj[2];
       const int ec = min(e, n - 1);
-      const ElemK k_own = elem_k_from<DIM>(cur.g, (cur.own * cur.oth) / cur.g.l0);      // = the forward launch's record of e
+      const ElemK k_own = elem_k_from<DIM>(cur.g, (own * cur.oth) / cur.g.l0);      // = the forward launch's record of e
       path_residual<DIM>(k_own, cur.edge, cur.ui, cur.uj, cur.fxi, cur.fli, ec, n, lane, P.lam, P.alpha_physics, P.fe_mode,
                          ri, gi, rj, gj);
       if (live) {
@@ -1414,6 +1497,17 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
         if (e == n - 1) {
           store_vec<DIM>(P.g_f, cur.nn.y, gj);
           store_vec<DIM>(P.u_alt, cur.nn.y, rj);
+        }
+        if constexpr (LIGHT) {
+          P.prop_e[e] = own;
+          if (!path_edge_lane(e, n, lane)) {           // (the edge lanes' records: the forward launch's edge tasks wrote them)
+            if constexpr (DIM == 2) {
+              float* __restrict__ r = P.elem_k + 3 * (size_t)e;
+              r[0] = k_own.c2; r[1] = k_own.cs; r[2] = k_own.s2;
+            } else {
+              P.elem_k[e] = k_own.c2;
+            }
+          }
         }
       }
     }
@@ -1427,7 +1521,7 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
       }
       float g = gea * cur.oth;   // mul backward of young*area        (nn_assembly.py:74)
       g = g * net.scale;         // output*scale backward              (properties.py:156)
-      gz = net.positive ? g * one_minus_exp_neg(cur.own * inv_scale) : g;
+      gz = net.positive ? g * one_minus_exp_neg(own * inv_scale) : g;
     }
     // power-of-two scale: max |d| S <= 2^14 with the weight bound of the image header; S only ever falls, T follows
     // The wave-wide maximum (seven DPP steps) is only formed when it can change something: S = 2^(14 - ex) with
@@ -1456,10 +1550,18 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     const float S = Srun == 0.f ? 1.0f : Srun;
     float g0, g1;
     both_tiles(gz, g0, g1);
-    float xa0, xa1, xb0, xb1;
-    both_tiles(cur.x[1], xa0, xa1);
-    both_tiles(cur.x[2], xb0, xb1);
+    if constexpr (!LIGHT) {
+      both_tiles(cur.x[1], xa0, xa1);
+      both_tiles(cur.x[2], xb0, xb1);
+    }
     const float lam_in = cur.x[0];
+    if constexpr (LIGHT) {      // the output row's sums, per unit tile 0 then tile 1 (activate2's order)
+      sfor<0, NR>([&](auto r) {
+        constexpr int R = r;
+        go[R] = fmaf(g0, LA0.aL[R], go[R]);
+        go[R] = fmaf(g1, LA1.aL[R], go[R]);
+      });
+    }
     {
       // The next task's inputs leave HERE, behind the last use of this task's record (everything above consumed it: the
       // tiles below work on derived values only), so the new values can land in the registers the old ones held — issued
@@ -1470,7 +1572,7 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
       // the block, and the compiler placed the copies there behind s_waitcnt vmcnt(0): every task waited out the loads it
       // had just issued, the prefetch hid nothing.  Now the waits sit at the first uses, at the top of the next task.
       const int e1 = min(task_base(k + 1) + lane, n - 1);
-      task_fetch_a<IN, GEA>(nxt, P, onet, other, mine, e1, false);
+      task_fetch_a<IN, GEA, !LIGHT>(nxt, P, onet, other, mine, e1, false);
       if (GEA) {
         nxt.nn = nn_ahead;
         const int e2 = min(task_base(k + 2) + lane, n - 1);
@@ -1494,7 +1596,11 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
       if (!go_done) sfor<0, NR>([&](auto r) { constexpr int R = r; go[R] = fmaf(gt, A.aL[R], go[R]); });
       if (!(dbg & 2)) E::template backward_tile<L, IN>(smem, scratch, lane, A, gt * S, xhi, xlo, T, wb, rd, dbg);
     };
-    if constexpr (E::template bw_pair<L>()) {   // recompute both tiles together, then the two back-propagations (see bw_pair)
+    if constexpr (LIGHT) {
+      const float x0[3] = {lam_in, xa0, xb0}, x1[3] = {lam_in, xa1, xb1};
+      tile_backward(LA0, x0, g0, true);
+      tile_backward(LA1, x1, g1, true);
+    } else if constexpr (E::template bw_pair<L>()) {   // recompute both tiles together, then the two back-propagations (see bw_pair)
       const float x0[3] = {lam_in, xa0, xb0}, x1[3] = {lam_in, xa1, xb1};
       typename E::template TileAct<L, true> A0, A1;
       float p0, p1;
@@ -1528,7 +1634,7 @@ __device__ __forceinline__ void backward_phase(const pf_problem& P, int which, i
     __syncthreads();                               // the parked tiles are read
     bw_park<NR, L>(park + (size_t)wv * bw_park_floats<L>(), T, go, gbo, lane);
     __syncthreads();
-    bw_row_from_parked<NR, L, IN>(P, which, hp, park, kl, kx);
+    bw_row_from_parked<NR, L, IN, ROW_FRESH>(P, which, hp, park, kl, kx);
     if (PF_N32_DBG_ENABLE && stamps) stamps[2] = __builtin_amdgcn_s_memrealtime();
     return;
   }
@@ -1651,7 +1757,14 @@ constexpr size_t bw2_lds_bytes() {
 // eighths of the younger wave's tasks the older wave of its SIMD takes over (backward_phase, shift8), measured on MI355X
 // (profiles/r03_ab.txt): 0 / 1 / 2 / 3 -> backward launch 72.2 / 69.7 / 68.0 / 71.1 us
 constexpr int PF_BW_SHIFT = 2;
-template <int NRE, int NRA, int L, int IN, bool PATH = false>
+// Has the bucket pair the light forward form (k_net32_forward2 / backward_phase, LIGHT)?  Wherever the path backward exists,
+// in the split-f16 build: the bf16-operand build keeps the full forward (pf_net32.h: pf_n32_has_light_forward, the host's
+// side of this answer).  Not with a young net of bucket 12 and three inputs: there the light path backward spills six
+// registers where the path backward spills none to two; every other pair's holds its registers without a spill
+// (profiles/r17_light_forward_registers.txt).
+template <int NRE, int NRA, int L, int IN>
+constexpr bool n32_has_light() { return !BF && L == 2 && bw2_parked<NRE, NRA>() && !(NRE == 12 && IN == 3); }
+template <int NRE, int NRA, int L, int IN, bool PATH = false, bool LIGHT = false>
 __global__ __launch_bounds__((bw2_threads<NRE, NRA, L, IN>())) void k_net32_backward2(pf_problem P, int hp_e, int hp_a, int dbg_arg) {
   const int dbg = PF_N32_DBG_ENABLE ? dbg_arg : 0;
   const unsigned long long t_entry = PF_N32_DBG_ENABLE ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -1676,9 +1789,9 @@ __global__ __launch_bounds__((bw2_threads<NRE, NRA, L, IN>())) void k_net32_back
     // no barrier between the phases: a wave parks its young-net tiles and walks on (see backward_phase, MODE)
     float* park = reinterpret_cast<float*>(wscr + (size_t)(blockDim.x >> 6) * bw2_wave_scratch<NRE, NRA>());
     const float kl_e = pf_n32_lam_scale(P.lam), kx_e = __builtin_ldexpf(1.0f, P.coord_exp);
-    auto first_row = [&]() { bw_row_from_parked<NRE, L, IN>(P, 0, hp_e, park, kl_e, kx_e); };
-    backward_phase<NRE, L, IN, true, 1, int, PATH>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, park, 0, PF_BW_SHIFT);
-    backward_phase<NRA, L, IN, false, 2, decltype(first_row), false, PATH>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr,
+    auto first_row = [&]() { bw_row_from_parked<NRE, L, IN, LIGHT>(P, 0, hp_e, park, kl_e, kx_e); };
+    backward_phase<NRE, L, IN, true, 1, int, PATH, false, LIGHT>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, park, 0, PF_BW_SHIFT);
+    backward_phase<NRA, L, IN, false, 2, decltype(first_row), false, PATH, false, LIGHT>(P, 1, hp_a, dbg, smem + IMGPAD, cst, wscr,
                                                                            st ? st + 4 : nullptr, park, first_row, PF_BW_SHIFT);
   } else {
     backward_phase<NRE, L, IN, true, 0, int, PATH>(P, 0, hp_e, dbg, smem, cst, wscr, st ? st + 1 : nullptr, nullptr, 0, PF_BW_SHIFT);
@@ -1729,7 +1842,18 @@ int launch_fwd2_t(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o) {
   const size_t lds = 2 * (size_t)((pf_n32_bytes(L) + 255) & ~255) + (s2_half < 0 ? 0 : (size_t)p->n_theta_active * sizeof(float));
   if (lds > 64000) { pf_set_error("too many trainable parameters for the fused theta update"); return PF_ERR_UNSUPPORTED; }
   if (gu_nb > 0 && !pf_n32_fwd2_can_update_u(p, gu_nb)) { pf_set_error("fused forward: displacement update not possible on this problem"); return PF_ERR_UNSUPPORTED; }
-  hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_half >= 0 && o.calc_index ? s2_half + 2 : s2_half, gu_nb, o.gu_k);
+  const int s2_arg = s2_half >= 0 && o.calc_index ? s2_half + 2 : s2_half;
+  if (o.light) {
+    if constexpr (n32_has_light<NRE, NRA, L, IN>()) {
+      if (!p->elem_k) { pf_set_error("fused forward, light form: elem_k is needed"); return PF_ERR_ARG; }
+      hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN, true>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_arg, gu_nb, o.gu_k);
+    } else {
+      pf_set_error("fused forward: no light form for these nets");
+      return PF_ERR_UNSUPPORTED;
+    }
+  } else {
+    hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_arg, gu_nb, o.gu_k);
+  }
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_HIP;
 }
 template <int L, int IN>
@@ -1762,7 +1886,16 @@ int launch_bwd2_t(const pf_problem* p, hipStream_t s, int path) {
     //  no register left for the path task's inputs; pf_api.hip: can_fold_residual asks pf_n32_bwd2_has_path)
     if constexpr (bw2_parked<NRE, NRA>()) {
       if (!p->elem_k || !p->u_alt) { pf_set_error("fused backward, path form: elem_k and u_alt are needed"); return PF_ERR_ARG; }
-      hipLaunchKernelGGL((k_net32_backward2<NRE, NRA, L, IN, true>), dim3(nb), dim3(THREADS), lds, s, *p, hp_e, hp_a, dbg);
+      if (path == 2) {      // the light forward form: this launch also forms E and stores prop_e and the records
+        if constexpr (n32_has_light<NRE, NRA, L, IN>()) {
+          hipLaunchKernelGGL((k_net32_backward2<NRE, NRA, L, IN, true, true>), dim3(nb), dim3(THREADS), lds, s, *p, hp_e, hp_a, dbg);
+        } else {
+          pf_set_error("fused backward: no light forward form for these nets");
+          return PF_ERR_UNSUPPORTED;
+        }
+      } else {
+        hipLaunchKernelGGL((k_net32_backward2<NRE, NRA, L, IN, true>), dim3(nb), dim3(THREADS), lds, s, *p, hp_e, hp_a, dbg);
+      }
     } else {
       pf_set_error("fused backward: no path form for nets wider than 24");
       return PF_ERR_UNSUPPORTED;
@@ -1857,7 +1990,7 @@ int PF_N32_SYM(forward2_)(const pf_problem* p, hipStream_t s, const pf_fwd2_opts
 // Two hidden layers only (the reference's SimpleNN default and every example): with one or three the two phases in one
 // kernel no longer fit the register budget of their block shapes without spilling (checked in the compiler's asm), and
 // a spill reload in the task loop costs more than a launch boundary — those shapes keep the two launches.
-// path: the iteration graph's path form (backward_phase, PATH)
+// path: 1 = the iteration graph's path form (backward_phase, PATH), 2 = that with the light forward (LIGHT)
 int PF_N32_SYM(backward2_)(const pf_problem* p, hipStream_t s, int path) {
   const int L = p->net[0].n_hidden, IN = p->net[0].in_dim;
   if (L == 2 && IN == 3) return launch_bwd2<2, 3>(p, s, path);

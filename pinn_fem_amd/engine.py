@@ -346,6 +346,13 @@ class HipEngine:
         folded into the fused backward and theta-stage-1 launches (path meshes).  Inspects the mesh on the device."""
         return int(self.lib.pf_graph_form_info(self._ref()))
 
+    @_on_engine_stream
+    def graph_light_forward(self) -> int:
+        """1 where the iteration graph's path form runs with the light forward (the forward launch evaluates the E net only
+        at task edges, the fused backward stores prop_e and the other stiffness records), else 0.  Inspects the mesh on
+        the device."""
+        return int(self.lib.pf_graph_light_forward(self._ref()))
+
     # ---- solve_gd support ------------------------------------------------------------------------
     @_on_engine_stream
     def begin(self, u_initial, lam, config, max_iter: Optional[int] = None, want_history=True):
