@@ -582,6 +582,23 @@ int pf_gl_dyn_steps(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, int 
 int pf_gl_dyn_graph_create(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, int n_steps, void* stream,
                            void** graph_out);
 int pf_gl_dyn_energy(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, double* out4, void* stream);
+/* Tension-only (cable) elements in the explicit dynamics.  cable: dev unsigned char [n_elems], non-zero = the element
+ * carries no compression: where e - e0 < 0 it is slack, N = 0, it adds +-0.0 to f_int in its place in the incidence order
+ * (a dof whose elements are all slack gets f_int == 0.0 to the bit) and nothing to the strain energy.  Unflagged elements, and
+ * flagged ones in tension, are the bar's arithmetic: all-zero flags give the bits of the entry points above.  Each entry
+ * point is its namesake above with `cable` right behind `dyn`, in kernels of its own (the bar's are untouched), and refuses
+ * what the namesake refuses in the same way; a null cable is PF_ERR_ARG too, never a silent bar run.  pf_dyn is unchanged.
+ * pf_gl_dyn_energy_cable: out5[0..3] as out4, the strain energy without the slack elements; out5[4] = the number of slack
+ * elements at that state, an exact integer; out5: dev double [PF_DYN_CABLE_ENERGY_COUNT].  Only these four know cables:
+ * pf_gl_state*, the Newton solve and the sensitivities stay bars.  Additive: the version stays 9. */
+#define PF_DYN_CABLE_ENERGY_COUNT (5 + 5 * PF_MAX_NODE_BLOCKS)
+int pf_gl_dyn_start_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const unsigned char* cable, void* stream);
+int pf_gl_dyn_steps_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const unsigned char* cable, int n_steps,
+                          void* stream);
+int pf_gl_dyn_graph_create_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const unsigned char* cable,
+                                 int n_steps, void* stream, void** graph_out);
+int pf_gl_dyn_energy_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const unsigned char* cable, double* out5,
+                           void* stream);
 /* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */
 int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream);
 /* out (dev double [n_dofs]) = the diagonal of K_t from the element blocks of kt: per dof the sum of the diagonal entries

@@ -29,6 +29,7 @@ PF_COARSE_MAX_AGG, PF_COARSE_MODES = 256, 3
 PF_COARSE_MAX = PF_COARSE_MAX_AGG * PF_COARSE_MODES
 PF_PCG_MAX_RHS = 2
 PF_DYN_ENERGY_COUNT = 4 + 4 * PF_MAX_NODE_BLOCKS
+PF_DYN_CABLE_ENERGY_COUNT = 5 + 5 * PF_MAX_NODE_BLOCKS
 PF_GRAPH_CONT_HEAD, PF_GRAPH_NO_TAIL = 1, 2
 PF_GRAPH_FORM_FOLDED_RESIDUAL = 1
 PF_FUSED_FORWARD, PF_FUSED_BACKWARD, PF_FUSED_THETA_UPDATE, PF_FUSED_U_PINGPONG, PF_FUSED_U_UPDATE = 1, 2, 4, 8, 16
@@ -194,6 +195,10 @@ SYMBOLS = {
     "pf_gl_dyn_steps": (C.c_int, [_PP, _PG, _PD, C.c_int, C.c_void_p]),
     "pf_gl_dyn_graph_create": (C.c_int, [_PP, _PG, _PD, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "pf_gl_dyn_energy": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_void_p]),
+    "pf_gl_dyn_start_cable": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_void_p]),
+    "pf_gl_dyn_steps_cable": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_gl_dyn_graph_create_cable": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pf_gl_dyn_energy_cable": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_kt_v_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_kt_diag_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_pcgt_begin": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

@@ -118,12 +118,16 @@ def parse_problem(problem_file):
     #                                                 "axial_forces" and, with "groups", "identified_factors", "factor_std"
     #           "dynamics": {"t_end": T | "n_steps": N, "dt": dt, "dt_safety": s, "damping": alpha, "ramp_time": t,
     #                        "load_factor_initial": l0, "load_factor_final": l1, "record_every": k, "record_dofs": [...],
-    #                        "nodal_mass": m | [...], "rest_tolerance": r, "u_initial": [...], "v_initial": [...]}
+    #                        "nodal_mass": m | [...], "rest_tolerance": r, "cable_elements": "all" | [...],
+    #                        "u_initial": [...], "v_initial": [...]}
     #                                                 explicit time integration of the green-lagrange structure in place of
     #                                                 the static solve (fem/dynamics.py): central differences,
     #                                                 lumped mass from the material's density; the .res.json holds the last
     #                                                 step's displacements and reactions and gains "dynamics" (times,
-    #                                                 recorded displacements, energies, dt, steps, at_rest)
+    #                                                 recorded displacements, energies, dt, steps, at_rest);
+    #                                                 "cable_elements" are tension-only (slack, e - e0 < 0, they carry
+    #                                                 nothing), and "dynamics" then gains "slack_elements", the ids of
+    #                                                 those slack at the last step
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -236,7 +240,7 @@ def parse_problem(problem_file):
 
 _DYNAMICS_KEYS = {"dt": float, "dt_safety": float, "t_end": float, "n_steps": int, "damping": float, "ramp_time": float,
                   "load_factor_initial": float, "load_factor_final": float, "record_every": int, "record_dofs": list,
-                  "nodal_mass": None, "rest_tolerance": float}
+                  "nodal_mass": None, "rest_tolerance": float, "cable_elements": None}
 
 
 def _dynamics_block(block):
@@ -503,6 +507,8 @@ def _dynamics_problem(model, solver_config, block):
     from ..fem.dynamics import solve_dynamic
     res = solve_dynamic(model, solver_config, block["config"], u_initial=block["u_initial"], v_initial=block["v_initial"])
     log_print(f"Dynamics: {res.steps} steps of dt = {res.dt:.6g}, at rest: {res.at_rest}, residual {res.residual_norm:.3e}")
+    cables = ({} if block["config"].cable_elements is None
+              else {"slack_elements": np.flatnonzero(res.slack).tolist()})
     return {
         "success": True,
         "converged": bool(res.at_rest),
@@ -513,7 +519,7 @@ def _dynamics_problem(model, solver_config, block):
         "axial_forces": res.axial_forces.tolist(),
         "dynamics": {"times": res.times.tolist(), "recorded_displacements": res.recorded.tolist(), "energies": res.energies,
                      "velocities": res.velocities.flatten().tolist(), "residual_norm": res.residual_norm, "dt": res.dt,
-                     "steps": res.steps, "at_rest": bool(res.at_rest)},
+                     "steps": res.steps, "at_rest": bool(res.at_rest), **cables},
     }
 
 

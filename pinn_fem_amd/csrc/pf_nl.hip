@@ -37,6 +37,10 @@
 //   k_gl_dyn_clock      adds a sequence's length to the step number on the device, so that a captured sequence replays.
 //   k_gl_dyn_energy     per-block partials of the kinetic and strain energy, f_ext.u and max |v|; k_gl_dyn_energy_sum adds
 //                       them in one block.  pf_block_sum_d, a fixed order, no atomics.
+//   Tension-only (cable) elements: the <DIM, true> instantiations of the step and of the energy kernel read one flag per
+//   element, and a flagged element with e - e0 < 0 is slack: N = 0 by a select on the value, so it adds +-0.0 in its place
+//   in the incidence order, no strain energy, and 1 to a fifth partial, the slack count.  The <DIM, false> instantiations
+//   are the bar kernels, untouched: the flag is a template parameter, and their trailing operand is never read.
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>
@@ -320,20 +324,24 @@ __device__ __forceinline__ double dyn_strain(const pf_problem& P, const double* 
   return e0_in ? strain - e0_in[e] : strain;
 }
 
-// +-(ea (e - e0) / l0) d: k_gl_state's fe formed per incidence, so a step reads no element record
-template <int DIM>
+// +-(ea (e - e0) / l0) d: k_gl_state's fe formed per incidence, so a step reads no element record.  CABLE: an element
+// with cable[e] != 0 carries no compression: N / l0 = 0.0 where e - e0 < 0, a select on the value, so a slack element's term
+// is +-0.0 and the sum keeps its order
+template <int DIM, bool CABLE>
 struct dyn_term {
   const pf_problem& P;
   const double* __restrict__ d0_in;
   const double* __restrict__ u;
   const double* __restrict__ ea_in;
   const double* __restrict__ e0_in;
+  const unsigned char* __restrict__ cable;
   __device__ __forceinline__ void operator()(int code, double* out) const {
     const int e = code >> 1;
     const double sg = (code & 1) ? 1.0 : -1.0;
     double d0[DIM], du[DIM], l02, ea;
     const double se = dyn_strain<DIM>(P, d0_in, u, ea_in, e0_in, e, d0, du, l02, ea);
-    const double n_l0 = (ea * se) / sqrt(l02);
+    double n_l0 = (ea * se) / sqrt(l02);
+    if (CABLE) n_l0 = (cable[e] && se < 0.0) ? 0.0 : n_l0;
 #pragma unroll
     for (int c = 0; c < DIM; ++c) out[c] = sg * (n_l0 * (d0[c] + du[c]));
   }
@@ -345,9 +353,10 @@ __device__ __forceinline__ const double* dyn_u_at(const pf_dyn& D, long long n) 
 // Step n = *clock + k of the sequence, one node per thread:
 //   v <- c1 v + g (lam(t_n) f_ext - f_int(u_n)) / m,   u_{n+1} = u_n + dt v;   fixed dofs: v = 0, u = 0.
 // A thread reads and writes only its own dofs of v (in place); its neighbours read u_n, so u_{n+1} goes to the other buffer.
-template <int DIM>
+// cable: [n_elems] the tension-only flags, read by the CABLE instantiations alone (the bar's get nullptr)
+template <int DIM, bool CABLE>
 __global__ __launch_bounds__(256) void k_gl_dyn_step(pf_problem P, const double* __restrict__ d0_in, pf_dyn D, long long k,
-                                                     double c1, double g, double dt) {
+                                                     double c1, double g, double dt, const unsigned char* __restrict__ cable) {
   const pf_mesh& M = P.mesh;
   const long long n = *D.clock + k;
   const double* __restrict__ u_n = dyn_u_at(D, n);
@@ -355,7 +364,7 @@ __global__ __launch_bounds__(256) void k_gl_dyn_step(pf_problem P, const double*
   const double t = (double)n * D.dt;
   const double lam = D.t_ramp > 0.0 ? D.lam0 + (D.lam1 - D.lam0) * fmin(1.0, t / D.t_ramp) : D.lam1;
   PF_EACH_NODE(node, M)
-    node_gather<DIM, false>(M, node, nullptr, 0, dyn_term<DIM>{P, d0_in, u_n, D.ea, D.e0}, [&](int dof, double f_int) {
+    node_gather<DIM, false>(M, node, nullptr, 0, dyn_term<DIM, CABLE>{P, d0_in, u_n, D.ea, D.e0, cable}, [&](int dof, double f_int) {
       const bool fixed = dof_fixed(M, dof);
       const double v = c1 * D.v[dof] + g * ((lam * D.f_ext[dof] - f_int) * D.minv[dof]);
       D.v[dof] = fixed ? 0.0 : v;
@@ -383,14 +392,15 @@ __device__ __forceinline__ double block_max_d(double v, double* smem) {
 
 // Per block, partial sums at the state the clock points to (u_{n+1}, v_{n+1/2}): kinetic energy sum m v^2 / 2 (m = 1 / minv;
 // a dof at rest adds nothing, whatever its minv), strain energy sum E*A l0 (e - e0)^2 / 2, f_ext.u and max |v|.  Thread i
-// takes node i and element i.  part: [gridDim.x][4].
-template <int DIM>
+// takes node i and element i.  part: [gridDim.x][4].  CABLE: a slack element (cable[i] != 0 and e - e0 < 0, the step's own
+// decision) adds no strain energy and 1.0 to a fifth partial, an exact integer; part: [gridDim.x][5].
+template <int DIM, bool CABLE>
 __global__ __launch_bounds__(256) void k_gl_dyn_energy(pf_problem P, const double* __restrict__ d0_in, pf_dyn D,
-                                                       double* __restrict__ part) {
+                                                       double* __restrict__ part, const unsigned char* __restrict__ cable) {
   __shared__ double red[8];
   const pf_mesh& M = P.mesh;
   const double* __restrict__ u = dyn_u_at(D, *D.clock);
-  double kin = 0.0, se_sum = 0.0, work = 0.0, vmax = 0.0;
+  double kin = 0.0, se_sum = 0.0, work = 0.0, vmax = 0.0, n_slack = 0.0;
   const int count = M.n_nodes > M.n_elems ? M.n_nodes : M.n_elems;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
     if (i < M.n_nodes) {
@@ -406,28 +416,43 @@ __global__ __launch_bounds__(256) void k_gl_dyn_energy(pf_problem P, const doubl
     if (i < M.n_elems) {
       double d0[DIM], du[DIM], l02, ea;
       const double se = dyn_strain<DIM>(P, d0_in, u, D.ea, D.e0, i, d0, du, l02, ea);
-      se_sum += 0.5 * (ea * sqrt(l02)) * (se * se);
+      double se2 = se * se;
+      if (CABLE) {        // the select sits on the factor, so the sum keeps the bar's form (and its contraction) and gets +0.0
+        const bool slack = cable[i] && se < 0.0;
+        se2 = slack ? 0.0 : se2;
+        n_slack += slack ? 1.0 : 0.0;
+      }
+      se_sum += 0.5 * (ea * sqrt(l02)) * se2;
     }
   }
   const double s0 = pf_block_sum_d(kin, red), s1 = pf_block_sum_d(se_sum, red), s2 = pf_block_sum_d(work, red);
   const double s3 = block_max_d(vmax, red);
+  const double s4 = CABLE ? pf_block_sum_d(n_slack, red) : 0.0;
   if (threadIdx.x == 0) {
-    double* __restrict__ o = part + 4 * (size_t)blockIdx.x;
+    double* __restrict__ o = part + (CABLE ? 5 : 4) * (size_t)blockIdx.x;
     o[0] = s0; o[1] = s1; o[2] = s2; o[3] = s3;
+    if (CABLE) o[4] = s4;
   }
 }
 
-// out[0..2] = the sums of the nb block partials, thread t adding blocks t, t + 256, ... in that order; out[3] = their maximum
+// out[0..2] = the sums of the nb block partials, thread t adding blocks t, t + 256, ... in that order; out[3] = their maximum;
+// CABLE: five partials per block, out[4] = the sum of the fifth (the slack count), in the same order
+template <bool CABLE>
 __global__ __launch_bounds__(256) void k_gl_dyn_energy_sum(const double* __restrict__ part, int nb, double* __restrict__ out) {
   __shared__ double red[8];
-  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int b = (int)threadIdx.x; b < nb; b += (int)blockDim.x) {
-    const double* __restrict__ r = part + 4 * (size_t)b;
+    const double* __restrict__ r = part + (CABLE ? 5 : 4) * (size_t)b;
     a[0] += r[0]; a[1] += r[1]; a[2] += r[2]; a[3] = fmax(a[3], r[3]);
+    if (CABLE) a[4] += r[4];
   }
   const double s0 = pf_block_sum_d(a[0], red), s1 = pf_block_sum_d(a[1], red), s2 = pf_block_sum_d(a[2], red);
   const double s3 = block_max_d(a[3], red);
-  if (threadIdx.x == 0) { out[0] = s0; out[1] = s1; out[2] = s2; out[3] = s3; }
+  const double s4 = CABLE ? pf_block_sum_d(a[4], red) : 0.0;
+  if (threadIdx.x == 0) {
+    out[0] = s0; out[1] = s1; out[2] = s2; out[3] = s3;
+    if (CABLE) out[4] = s4;
+  }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -498,14 +523,16 @@ int dyn_check(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn
   return PF_OK;
 }
 
-// n_steps launches of the step with the coefficients (c1, gk), then the clock's: a single chain on s
-int dyn_enqueue(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, double c1, double gk,
-                hipStream_t s) {
+// n_steps launches of the step with the coefficients (c1, gk), then the clock's: a single chain on s.  cable: the
+// tension-only flags and the step's CABLE instantiation, or null and the bar step
+int dyn_enqueue(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, int n_steps,
+                double c1, double gk, hipStream_t s) {
   if (p->mesh.n_nodes > 0) {
     const dim3 grid(pf_node_blocks(p->mesh.n_nodes));
+    const auto k2 = cable ? k_gl_dyn_step<2, true> : k_gl_dyn_step<2, false>;
+    const auto k1 = cable ? k_gl_dyn_step<1, true> : k_gl_dyn_step<1, false>;
     for (int k = 0; k < n_steps; ++k)
-      if (const int rc = launch(who, p, k_gl_dyn_step<2>, k_gl_dyn_step<1>, grid, s, g->d0, *d, (long long)k, c1, gk, d->dt))
-        return rc;
+      if (const int rc = launch(who, p, k2, k1, grid, s, g->d0, *d, (long long)k, c1, gk, d->dt, cable)) return rc;
   }
   hipLaunchKernelGGL(k_gl_dyn_clock, dim3(1), dim3(64), 0, s, d->clock, (long long)n_steps);
   return launched(who);
@@ -518,52 +545,104 @@ void dyn_coefficients(const pf_dyn* d, double& c1, double& gk) {
   gk = d->dt / (1.0 + h);
 }
 
-}  // namespace
+// The four entry points, each stated once for the bar family (cable == null) and the cable family.  A _cable entry point
+// refuses a null cable first (cable_given), so a null here always means the bar family.
+int cable_given(const char* who, const unsigned char* cable) {
+  return cable ? PF_OK : gl_fail(PF_ERR_ARG, who, "null cable (the entry point without _cable is the run of bars)");
+}
 
-extern "C" {
-
-int pf_gl_dyn_start(const pf_problem* p, const pf_gl* g, const pf_dyn* d, void* stream) {
-  const char* who = "pf_gl_dyn_start";
+int dyn_start(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, void* stream) {
   if (const int rc = dyn_check(who, p, g, d)) return rc;
   long long clock = -1;
   if (hipMemcpyAsync(&clock, d->clock, sizeof(clock), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
       hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
     return gl_fail(PF_ERR_HIP, who, "reading the clock failed");
   if (clock != 0) return gl_fail(PF_ERR_ARG, who, "the clock must be 0 (the half kick starts a run)");
-  return dyn_enqueue(who, p, g, d, 1, 1.0 - 0.5 * d->alpha * d->dt, 0.5 * d->dt, (hipStream_t)stream);
+  return dyn_enqueue(who, p, g, d, cable, 1, 1.0 - 0.5 * d->alpha * d->dt, 0.5 * d->dt, (hipStream_t)stream);
 }
 
-int pf_gl_dyn_steps(const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, void* stream) {
-  const char* who = "pf_gl_dyn_steps";
+int dyn_steps(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, int n_steps,
+              void* stream) {
   if (const int rc = dyn_check(who, p, g, d)) return rc;
   if (n_steps < 1) return gl_fail(PF_ERR_ARG, who, "n_steps must be at least 1");
   double c1, gk;
   dyn_coefficients(d, c1, gk);
-  return dyn_enqueue(who, p, g, d, n_steps, c1, gk, (hipStream_t)stream);
+  return dyn_enqueue(who, p, g, d, cable, n_steps, c1, gk, (hipStream_t)stream);
 }
 
-int pf_gl_dyn_graph_create(const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, void* stream, void** graph_out) {
-  const char* who = "pf_gl_dyn_graph_create";
+int dyn_graph_create(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable,
+                     int n_steps, void* stream, void** graph_out) {
   if (const int rc = dyn_check(who, p, g, d)) return rc;
   if (n_steps < 1) return gl_fail(PF_ERR_ARG, who, "n_steps must be at least 1");
   if (!graph_out) return gl_fail(PF_ERR_ARG, who, "null pointer");
   double c1, gk;
   dyn_coefficients(d, c1, gk);
   return capture_graph((hipStream_t)stream, 0, hipStreamCaptureModeThreadLocal, graph_out,
-                       [&](pf_capture& cap) { return dyn_enqueue(who, p, g, d, n_steps, c1, gk, cap.s); });
+                       [&](pf_capture& cap) { return dyn_enqueue(who, p, g, d, cable, n_steps, c1, gk, cap.s); });
 }
 
-int pf_gl_dyn_energy(const pf_problem* p, const pf_gl* g, const pf_dyn* d, double* out4, void* stream) {
-  const char* who = "pf_gl_dyn_energy";
+// out: the results (4, with cable 5), then as many block partials per block
+int dyn_energy(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, double* out,
+               void* stream) {
   if (const int rc = dyn_check(who, p, g, d)) return rc;
-  if (!out4) return gl_fail(PF_ERR_ARG, who, "null pointer");
+  if (!out) return gl_fail(PF_ERR_ARG, who, "null pointer");
   const int count = p->mesh.n_nodes > p->mesh.n_elems ? p->mesh.n_nodes : p->mesh.n_elems;
   const int nb = pf_node_blocks(count);
-  if (const int rc = launch(who, p, k_gl_dyn_energy<2>, k_gl_dyn_energy<1>, dim3(nb), stream, g->d0, *d, out4 + 4)) return rc;
-  hipLaunchKernelGGL(k_gl_dyn_energy_sum, dim3(1), dim3(256), 0, (hipStream_t)stream, out4 + 4, nb, out4);
+  double* part = out + (cable ? 5 : 4);
+  const auto k2 = cable ? k_gl_dyn_energy<2, true> : k_gl_dyn_energy<2, false>;
+  const auto k1 = cable ? k_gl_dyn_energy<1, true> : k_gl_dyn_energy<1, false>;
+  if (const int rc = launch(who, p, k2, k1, dim3(nb), stream, g->d0, *d, part, cable)) return rc;
+  hipLaunchKernelGGL(cable ? k_gl_dyn_energy_sum<true> : k_gl_dyn_energy_sum<false>, dim3(1), dim3(256), 0, (hipStream_t)stream,
+                     (const double*)part, nb, out);
   return launched(who);
 }
 
+}  // namespace
+
+extern "C" {
+
+int pf_gl_dyn_start(const pf_problem* p, const pf_gl* g, const pf_dyn* d, void* stream) {
+  return dyn_start("pf_gl_dyn_start", p, g, d, nullptr, stream);
+}
+
+int pf_gl_dyn_steps(const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, void* stream) {
+  return dyn_steps("pf_gl_dyn_steps", p, g, d, nullptr, n_steps, stream);
+}
+
+int pf_gl_dyn_graph_create(const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, void* stream, void** graph_out) {
+  return dyn_graph_create("pf_gl_dyn_graph_create", p, g, d, nullptr, n_steps, stream, graph_out);
+}
+
+int pf_gl_dyn_energy(const pf_problem* p, const pf_gl* g, const pf_dyn* d, double* out4, void* stream) {
+  return dyn_energy("pf_gl_dyn_energy", p, g, d, nullptr, out4, stream);
+}
+
+int pf_gl_dyn_start_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, void* stream) {
+  const char* who = "pf_gl_dyn_start_cable";
+  if (const int rc = cable_given(who, cable)) return rc;
+  return dyn_start(who, p, g, d, cable, stream);
+}
+
+int pf_gl_dyn_steps_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, int n_steps,
+                          void* stream) {
+  const char* who = "pf_gl_dyn_steps_cable";
+  if (const int rc = cable_given(who, cable)) return rc;
+  return dyn_steps(who, p, g, d, cable, n_steps, stream);
+}
+
+int pf_gl_dyn_graph_create_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, int n_steps,
+                                 void* stream, void** graph_out) {
+  const char* who = "pf_gl_dyn_graph_create_cable";
+  if (const int rc = cable_given(who, cable)) return rc;
+  return dyn_graph_create(who, p, g, d, cable, n_steps, stream, graph_out);
+}
+
+int pf_gl_dyn_energy_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, double* out5,
+                           void* stream) {
+  const char* who = "pf_gl_dyn_energy_cable";
+  if (const int rc = cable_given(who, cable)) return rc;
+  return dyn_energy(who, p, g, d, cable, out5, stream);
+}
 
 int pf_gl_state(const pf_problem* p, const pf_gl* g, const double* u, void* stream) {
   return gl_state("pf_gl_state", p, g, nullptr, nullptr, u, stream);

@@ -826,25 +826,29 @@ class HipEngine:
             d["graphs"] = {}
 
     @_on_engine_stream
-    def dyn_begin(self, u0, v0, minv, dt, alpha, lam0, lam1, t_ramp, ea=None, e0=None, start=True):
+    def dyn_begin(self, u0, v0, minv, dt, alpha, lam0, lam1, t_ramp, ea=None, e0=None, start=True, cable=None):
         """Begin a central-difference run at step 0 (pf_dyn).  u0, v0, minv: float64 [n_dofs] (minv = 1 / lumped mass of
         the dof's node; the loads are the model's, at load factor 1); ea, e0: as gl_state.  start: v0 is the velocity at
         t = 0 and the half kick (pf_gl_dyn_start) turns it into v_{1/2} and u_1, the run then stands at step 1; False: v0 is
         taken as v_{-1/2} and the run stands at step 0.  The buffers live on the engine; the graphs of dyn_steps are kept
-        for as long as the scalars and the presence of ea / e0, which they bake in, stay the same."""
+        for as long as the scalars and the presence of ea / e0 / cable, which they bake in, stay the same.
+        cable: bool or uint8 [n_elems], True = the element is tension-only (no force and no strain energy where e - e0 < 0);
+        the run then goes through the pf_gl_dyn_*_cable entry points.  None: a run of bars through pf_gl_dyn_*."""
         nd, ne = self.plan.n_dofs, self.plan.n_elems
+        flags = None if cable is None else self._cable_flags(cable, ne)
         vec = {name: self._f64_vector("dyn_begin", name, t, nd, "dofs") for name, t in (("u0", u0), ("v0", v0), ("minv", minv))}
         opt = {name: None if t is None else self._f64_vector("dyn_begin", name, t, ne, "elements")
                for name, t in (("ea", ea), ("e0", e0))}
         scalars = tuple(float(x) for x in (dt, alpha, lam0, lam1, t_ramp))
-        key = scalars + (ea is None, e0 is None)
+        key = scalars + (ea is None, e0 is None, cable is None)
         d = self._dyn
         if d is None:
             f64 = dict(dtype=torch.float64, device=self.device)
             d = self._dyn = dict(graphs={}, key=None, rec=_capi.PfDyn(), n=0,
                                  f_ext=torch.from_numpy(np.ascontiguousarray(
                                      np.asarray(self.model.loads, dtype=np.float64).reshape(-1))).to(self.device),
-                                 out=torch.zeros(_capi.PF_DYN_ENERGY_COUNT, **f64),
+                                 out=torch.zeros(_capi.PF_DYN_CABLE_ENERGY_COUNT, **f64),
+                                 cable=torch.zeros(max(ne, 1), dtype=torch.uint8, device=self.device), with_cable=False,
                                  clock=torch.zeros(1, dtype=torch.int64, device=self.device),
                                  **{name: torch.zeros(max(nd, 1), **f64) for name in ("u0", "u1", "v", "minv")},
                                  **{name: torch.zeros(max(ne, 1), **f64) for name in ("ea", "e0")})
@@ -855,6 +859,7 @@ class HipEngine:
             d[name][:nd].copy_(vec[src])
         d["u1"].zero_()
         d["clock"].zero_()
+        d["slack_at"] = None
         for name, t in opt.items():
             if t is not None:
                 d[name][:ne].copy_(t)
@@ -864,11 +869,27 @@ class HipEngine:
         rec.e0 = None if e0 is None else d["e0"].data_ptr()
         rec.clock = d["clock"].data_ptr()
         rec.dt, rec.alpha, rec.lam0, rec.lam1, rec.t_ramp = scalars
+        d["with_cable"] = flags is not None
+        if flags is not None:
+            d["cable"][:ne].copy_(flags)
         d["n"] = 0
         if start:
-            _capi.check(self.lib.pf_gl_dyn_start(self._ref(), C.byref(self._gl_buffers()[4]), C.byref(rec), self._stream()),
-                        "pf_gl_dyn_start")
+            self._dyn_call(d, "pf_gl_dyn_start", self._stream())
             d["n"] = 1
+
+    def _cable_flags(self, cable, ne):
+        flags = cable if isinstance(cable, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cable))
+        if flags.dtype not in (torch.bool, torch.uint8) or flags.dim() != 1 or flags.numel() != ne:
+            raise ValueError(f"dyn_begin: cable must be bool or uint8 [{ne}] (one flag for each element), got "
+                             f"{flags.dtype} {tuple(flags.shape)}")
+        return flags.to(device=self.device, dtype=torch.uint8)
+
+    def _dyn_call(self, d, name, *args):
+        """lib.<name>(problem, element record, pf_dyn, *args), or its _cable namesake with the run's flags behind pf_dyn."""
+        head = (self._ref(), C.byref(self._gl_buffers()[4]), C.byref(d["rec"]))
+        if d["with_cable"]:
+            name, head = name + "_cable", head + (d["cable"].data_ptr(),)
+        _capi.check(getattr(self.lib, name)(*head, *args), name)
 
     def _dyn_ready(self, who):
         d = self._dyn
@@ -883,15 +904,14 @@ class HipEngine:
         d, n = self._dyn_ready("dyn_steps"), int(n)
         if n < 1:
             raise ValueError(f"dyn_steps: n must be at least 1, got {n}")
-        head = (self._ref(), C.byref(self._gl_buffers()[4]), C.byref(d["rec"]))
         if use_graph and os.environ.get("PINNFEM_GRAPH", "1") != "0":
             if n not in d["graphs"]:
                 g = C.c_void_p()
-                _capi.check(self.lib.pf_gl_dyn_graph_create(*head, n, self._stream(), C.byref(g)), "pf_gl_dyn_graph_create")
+                self._dyn_call(d, "pf_gl_dyn_graph_create", n, self._stream(), C.byref(g))
                 d["graphs"][n] = g
             _capi.check(self.lib.pf_graph_launch(d["graphs"][n], self._stream()), "pf_graph_launch")
         else:
-            _capi.check(self.lib.pf_gl_dyn_steps(*head, n, self._stream()), "pf_gl_dyn_steps")
+            self._dyn_call(d, "pf_gl_dyn_steps", n, self._stream())
         d["n"] += n
 
     @_on_engine_stream
@@ -903,11 +923,21 @@ class HipEngine:
     @_on_engine_stream
     def dyn_energy(self):
         """(kinetic energy sum m v^2 / 2, strain energy sum E*A l0 (e - e0)^2 / 2, f_ext.u at load factor 1, max |v|) at
-        the run's state (pf_gl_dyn_energy), on the host: it synchronises."""
+        the run's state (pf_gl_dyn_energy), on the host: it synchronises.  With cable flags the strain energy leaves the
+        slack elements out (pf_gl_dyn_energy_cable), and dyn_slack_count() reads their number."""
         d = self._dyn_ready("dyn_energy")
-        _capi.check(self.lib.pf_gl_dyn_energy(self._ref(), C.byref(self._gl_buffers()[4]), C.byref(d["rec"]),
-                                              d["out"].data_ptr(), self._stream()), "pf_gl_dyn_energy")
+        self._dyn_call(d, "pf_gl_dyn_energy", d["out"].data_ptr(), self._stream())
+        d["slack_at"] = d["n"]
         return tuple(float(x) for x in d["out"][:4].cpu())
+
+    @_on_engine_stream
+    def dyn_slack_count(self) -> int:
+        """The number of slack elements at the state of the last dyn_energy(), read from its buffer without another
+        launch; 0 in a run without cable flags."""
+        d = self._dyn_ready("dyn_slack_count")
+        if d.get("slack_at") != d["n"]:
+            raise RuntimeError("dyn_slack_count: call dyn_energy() at this state first")
+        return int(d["out"][4].cpu()) if d["with_cable"] else 0
 
     @_on_engine_stream
     def kt_v_f64(self, v: torch.Tensor, zero_fixed: bool = False, extra_fixed=None) -> torch.Tensor:

@@ -3,7 +3,7 @@
 against the composition the entry points before it allow (pf_gl_state_e0, pf_gl_fint and a torch update: six launches and
 two round trips through fe per step), each issued launch by launch ("eager") and as a replayed hipGraph.
 
-    dyn_scale.py [--steps 200] [--rounds 5] [--chains 1000 100000 1000000] [--warren 250 25000 250000]
+    dyn_scale.py [--steps 200] [--rounds 5] [--chains 1000 100000 1000000] [--warren 250 25000 250000] [--cable]
 
 Meshes: collinear chains (plan.chain_mesh: only ux is free) and Warren girders (plan.warren_mesh), every element with the
 pretension e0 = -1e-3, E*A = 1000, rho A = 0.5, the mesh's own loads scaled to 1e-3, alpha = 0.1, dt = half the bound at
@@ -12,7 +12,14 @@ vectors (r = lam F - f_int; v *= c1; v += r * (g minv) on the free dofs; u += dt
 eager form pays one Python call per launch, as a caller of those entry points would; the graph forms carry no host work.
 After a warm-up of every variant, `rounds` rounds time `steps` steps of each variant between two events, the variants
 alternated inside a round.  One JSON line per mesh: median, minimum and maximum microseconds per step of each variant, the
-ratios of the medians, and the largest difference between the two paths' displacements after the first `steps` steps."""
+ratios of the medians, and the largest difference between the two paths' displacements after the first `steps` steps.
+
+--cable times the tension-only step (pf_gl_dyn_steps_cable) against the bar step instead, on the same meshes, loads and dt,
+eager and as a graph, three runs alternated in the same way: bar (no flags), taut (every element flagged with the pretension
+e0 = -1e-3: the chains end the run without a slack element; the girders shorten, swing through and end with about half
+their elements slack) and half (every element flagged, e0 = +1e-3 on the odd elements, which are slack from the first step
+on).  The JSON line holds the slack counts at the end and the ratios of the medians to the bar's.  The rule is a select,
+so a step does the same work whatever is slack."""
 import argparse, ctypes as C, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,6 +37,7 @@ ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--chains", type=int, nargs="*", default=[1000, 100_000, 1_000_000])
 ap.add_argument("--warren", type=int, nargs="*", default=[250, 25_000, 250_000])
+ap.add_argument("--cable", action="store_true")
 args = ap.parse_args()
 E0, ALPHA = -1e-3, 0.1
 
@@ -128,7 +136,63 @@ def measure(name, mesh):
     torch.cuda.empty_cache()
 
 
+def measure_cable(name, mesh):
+    nodes, el, loads, fixed = mesh[:4]
+    model = FEMModel(nodes=nodes, elements=el, material=Material(2000.0, 0.5, 1.0), loads=1e-3 * loads, fixed_dofs=fixed,
+                     dimension=2)
+    nd, ne, K = model.ndof, model.nelm, args.steps
+    mass = lumped_mass(model)
+    taut_e0 = np.full(ne, E0)
+    half_e0 = np.where(np.arange(ne) % 2 == 1, -E0, E0)
+    flags = np.ones(ne, dtype=bool)
+    dt = 0.5 * 2.0 / omega_bound(model, np.zeros(ne), taut_e0, mass)
+    runs = {"bar": (taut_e0, None), "taut": (taut_e0, flags), "half": (half_e0, flags)}
+    engines = {k: HipEngine(model) for k in runs}           # a run's state lives on its engine
+    dev = engines["bar"].device
+    minv = torch.from_numpy(np.repeat(1.0 / mass, 2)).to(dev)
+    zero = torch.zeros(nd, dtype=torch.float64, device=dev)
+    for k, (e0, cable) in runs.items():
+        engines[k].dyn_begin(zero, zero, minv, dt, ALPHA, 1.0, 1.0, 0.0, None, torch.from_numpy(e0).to(dev), start=False,
+                             cable=cable)
+    variants = {}
+    for k in runs:
+        variants[k + "_eager"] = lambda k=k: engines[k].dyn_steps(K, use_graph=False)
+        variants[k + "_graph"] = lambda k=k: engines[k].dyn_steps(K, use_graph=True)
+    for fn in variants.values():                    # warm-up: every variant once (the graphs are captured here)
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for k, fn in variants.items():
+            eng = engines[k.split("_")[0]]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with eng.on_stream():
+                a.record(eng.stream)
+            fn()
+            with eng.on_stream():
+                b.record(eng.stream)
+            torch.cuda.synchronize()
+            times[k].append(1e3 * a.elapsed_time(b) / K)
+    row = {"mesh": name, "nodes": model.nnode, "elements": ne, "steps_per_region": K, "rounds": args.rounds, "dt": dt}
+    for k, eng in engines.items():
+        assert bool(torch.isfinite(eng.dyn_state()[0]).all())
+        eng.dyn_energy()
+        row[k + "_slack_elements"] = eng.dyn_slack_count()
+    for k, t in times.items():
+        row[k + "_us"] = {"median": float(np.median(t)), "min": float(np.min(t)), "max": float(np.max(t))}
+    med = lambda k: row[k + "_us"]["median"]
+    for k in ("taut", "half"):
+        row[k + "_over_bar_eager"] = med(k + "_eager") / med("bar_eager")
+        row[k + "_over_bar_graph"] = med(k + "_graph") / med("bar_graph")
+    print(json.dumps(row), flush=True)
+    for eng in engines.values():
+        eng._drop_dyn_graphs()
+    del engines
+    torch.cuda.empty_cache()
+
+
+run = measure_cable if args.cable else measure
 for n in args.chains:
-    measure(f"chain_{n}", chain_mesh(n))
+    run(f"chain_{n}", chain_mesh(n))
 for n in args.warren:
-    measure(f"warren_{n}", warren_mesh(n))
+    run(f"warren_{n}", warren_mesh(n))

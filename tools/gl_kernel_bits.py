@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""The bits of every Green-Lagrange kernel of pf_nl.hip (and of kt_diag and one tangent CG solve) on fixed seeded inputs.
+"""The bits of every Green-Lagrange kernel of pf_nl.hip (and of kt_diag and one tangent CG solve) on fixed seeded inputs, the
+explicit step and its energies last, after every other line (bars, then tension-only elements; --bars leaves the tension-only
+lines out, for a build from before they existed).
 
-    gl_kernel_bits.py
+    gl_kernel_bits.py [--bars]
 
 One line per engine call: mesh, call, variant, sha256 of the raw output bytes.  Two builds of the library compute the same
 bits exactly when a run of this file in a fresh process prints the same lines for both (profiles/r14_gl_once_compare.txt).
@@ -38,15 +40,17 @@ def meshes():
 
 
 def main():
+    late = []                                   # the explicit dynamics' lines: printed after every mesh's other lines
     for name, model in meshes():
         eng = HipEngine(model)
         ne, n = eng.plan.n_elems, eng.plan.n_dofs
         rng = np.random.default_rng(ne)
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(eng.device)
 
-        def show(call, variant, t):
+        def show(call, variant, t, out=None):
             torch.cuda.synchronize()
-            print(f"{name} {call} [{variant}] {hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()}", flush=True)
+            line = f"{name} {call} [{variant}] {hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()}"
+            print(line, flush=True) if out is None else out.append(line)
 
         ea, e0 = dev(np.exp2(rng.uniform(-3.0, 3.0, ne))), dev(1e-3 * rng.standard_normal(ne))
         a, coef = dev(rng.standard_normal(n)), dev(rng.standard_normal(ne))
@@ -87,6 +91,24 @@ def main():
         eng.gl_state(u, ea, e0)                 # the small field: the tangent is positive definite there
         x = eng.pcg_solve(eng.gl_group_rhs(groups)[0] + dev(model.loads).reshape(-1), tangent=True, u=u)[0]
         show("pcg_solve", "tangent, du 1e-9 ea e0", x)
+        # the explicit step and its energies, bars and then tension-only elements (every third element flagged); 33 steps
+        # from the large field, the half kick first, eager and as a graph
+        minv, v0 = dev(np.exp2(rng.uniform(-1.0, 1.0, n))), dev(0.1 * rng.standard_normal(n))
+        cable = np.arange(ne) % 3 == 0
+        u_large = dev(0.15 * field)
+        for tag, more in (("", {}), ("cable", dict(cable=cable)))[: 1 if "--bars" in sys.argv[1:] else 2]:
+            for variant, kw in (("", {}), ("ea e0", dict(ea=ea, e0=e0))):
+                for graph in (False, True):
+                    eng.dyn_begin(u_large, v0, minv, 1e-3, 0.5, 0.25, 1.5, 0.02, start=True, **kw, **more)
+                    eng.dyn_steps(32, use_graph=graph)
+                    label = " ".join(x for x in (tag, variant, "graph" if graph else "eager") if x)
+                    uu, vv, _ = eng.dyn_state()
+                    show("dyn_steps.u", label, uu, late)
+                    show("dyn_steps.v", label, vv, late)
+                show("dyn_energy", " ".join(x for x in (tag, variant) if x), torch.tensor(eng.dyn_energy(), dtype=torch.float64), late)
+                if more:
+                    late.append(f"{name} dyn_slack_count [{' '.join(x for x in (tag, variant) if x)}] {eng.dyn_slack_count()}")
+    print("\n".join(late), flush=True)
 
 
 if __name__ == "__main__":
