@@ -549,7 +549,7 @@ int pf_gl_prestress_rhs(const pf_problem* p, const pf_gl* g, const double* ea, c
  *               ascending incidence order (it reads no record of pf_gl_state and writes none)
  *   v_{n+1/2} = c1 v_{n-1/2} + gk (lam(t_n) f_ext - f_int(u_n)) minv     c1 = (1 - alpha dt/2) / (1 + alpha dt/2)
  *   u_{n+1}   = u_n + dt v_{n+1/2}                                       gk = dt / (1 + alpha dt/2)
- * and PF_DOF_FIXED dofs get v = 0.0, u = 0.0.  v is advanced in place; u_n is read from u0 for even n and from u1 for odd n
+ * and PF_DOF_FIXED dofs get v = 0.0, u = 0.0 (any other lam(t), and supports that move: pf_dyn_hist below).  v is advanced in place; u_n is read from u0 for even n and from u1 for odd n
  * and u_{n+1} is written to the other.  n lives on the device in *clock: launch k of a sequence uses *clock + k, and a
  * last one-thread launch adds the sequence's length, so a captured sequence can be replayed.  No atomics: the same bits on
  * every run, eager or replayed.  All arrays dev double, caller-owned. */
@@ -599,6 +599,34 @@ int pf_gl_dyn_graph_create_cable(const pf_problem* p, const pf_gl* g, const pf_d
                                  int n_steps, void* stream, void** graph_out);
 int pf_gl_dyn_energy_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const unsigned char* cable, double* out5,
                            void* stream);
+/* Load and support-motion time histories in the explicit dynamics.  The caller samples every history at the step times
+ * t_n = n dt once, before the run, and step n = *clock + k reads its samples by that number: no search and no interpolation
+ * on the device, and a replayed graph reads the samples of the steps it then stands at.  With i(n) = min(n, n_samples - 1)
+ * (a step beyond the table reads its last sample: the history is held),
+ *   lam     = lam[i(n)] where lam is given, otherwise pf_dyn's ramp as above
+ *   u_{n+1} = sup_amp[dof] * sup[i(n + 1)] on a PF_DOF_FIXED dof whose sup_amp is not 0.0 (one product), where sup is given;
+ *             every other fixed dof gets the bytes of 0.0 as above (a select on the amplitude, never 0.0 * s, which is -0.0
+ *             for a negative s).  v on a fixed dof stays 0.0 also where the dof moves: pf_gl_dyn_energy[_cable] are
+ *             unchanged, count no kinetic energy of a support and never divide by its minv.
+ * Free dofs are the step above but for where lam comes from.  pf_gl_dyn_start_hist is the half kick with lam[i(0)] and writes
+ * sup[i(1)]; u_0 on the moved dofs is the caller's (sup_amp * s(0)).  Each entry point is its namesake above with `hist`
+ * right behind `dyn` and `cable` behind that; here cable MAY be null, which means bars (the _cable entry points refuse a
+ * null).  The kernels are instantiations of their own: the entry points above run the code they ran before.  A null hist,
+ * lam and sup both null (never a silent plain run), sup without sup_amp, n_samples < 1 and everything the namesake refuses is
+ * PF_ERR_ARG, with a pf_last_error text that begins with the function's name, before anything is enqueued.  All arrays dev
+ * double, caller-owned, 16 bytes per step for both histories.  pf_dyn is unchanged.  Additive: the version stays 9. */
+typedef struct pf_dyn_hist {
+  const double* lam;      /* [n_samples] load factor of step n, lam[n] = lam(t_n); null: pf_dyn's ramp */
+  const double* sup;      /* [n_samples] support-motion scale s(t_n); null: the supports stay at 0 */
+  const double* sup_amp;  /* [n_dofs] amplitude per dof, read on PF_DOF_FIXED dofs only; required with sup */
+  long long n_samples;    /* an index beyond the last sample reads the last one (the history is held) */
+} pf_dyn_hist;
+int pf_gl_dyn_start_hist(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const pf_dyn_hist* hist,
+                         const unsigned char* cable, void* stream);
+int pf_gl_dyn_steps_hist(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const pf_dyn_hist* hist,
+                         const unsigned char* cable, int n_steps, void* stream);
+int pf_gl_dyn_graph_create_hist(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const pf_dyn_hist* hist,
+                                const unsigned char* cable, int n_steps, void* stream, void** graph_out);
 /* out = K_t v with the element blocks of kt (as pf_gl_state wrote them); otherwise pf_kv_f64 */
 int pf_kt_v_f64(const pf_problem* p, const double* kt, const double* v, double* out, int zero_fixed, void* stream);
 /* out (dev double [n_dofs]) = the diagonal of K_t from the element blocks of kt: per dof the sum of the diagonal entries

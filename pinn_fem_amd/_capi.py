@@ -124,11 +124,16 @@ class PfDyn(C.Structure):
                 ("t_ramp", C.c_double)]
 
 
+class PfDynHist(C.Structure):
+    _fields_ = [("lam", C.c_void_p), ("sup", C.c_void_p), ("sup_amp", C.c_void_p), ("n_samples", C.c_longlong)]
+
+
 # every symbol include/pinnfem_hip.h declares: name -> (restype, argtypes)
 _PP = C.POINTER(PfProblem)
 _PC = C.POINTER(PfCoarse)
 _PG = C.POINTER(PfGl)
 _PD = C.POINTER(PfDyn)
+_PH = C.POINTER(PfDynHist)
 SYMBOLS = {
     "pf_abi_version": (C.c_int, []),
     "pf_last_error": (C.c_char_p, []),
@@ -199,6 +204,9 @@ SYMBOLS = {
     "pf_gl_dyn_steps_cable": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_gl_dyn_graph_create_cable": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "pf_gl_dyn_energy_cable": (C.c_int, [_PP, _PG, _PD, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_gl_dyn_start_hist": (C.c_int, [_PP, _PG, _PD, _PH, C.c_void_p, C.c_void_p]),
+    "pf_gl_dyn_steps_hist": (C.c_int, [_PP, _PG, _PD, _PH, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_gl_dyn_graph_create_hist": (C.c_int, [_PP, _PG, _PD, _PH, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "pf_kt_v_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_kt_diag_f64": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_pcgt_begin": (C.c_int, [_PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

@@ -119,6 +119,8 @@ def parse_problem(problem_file):
     #           "dynamics": {"t_end": T | "n_steps": N, "dt": dt, "dt_safety": s, "damping": alpha, "ramp_time": t,
     #                        "load_factor_initial": l0, "load_factor_final": l1, "record_every": k, "record_dofs": [...],
     #                        "nodal_mass": m | [...], "rest_tolerance": r, "cable_elements": "all" | [...],
+    #                        "load_history": {"times": [...], "values": [...]},
+    #                        "support_motion": {"dofs": [...], "amplitudes": a | [...], "times": [...], "values": [...]},
     #                        "u_initial": [...], "v_initial": [...]}
     #                                                 explicit time integration of the green-lagrange structure in place of
     #                                                 the static solve (fem/dynamics.py): central differences,
@@ -127,7 +129,9 @@ def parse_problem(problem_file):
     #                                                 recorded displacements, energies, dt, steps, at_rest);
     #                                                 "cable_elements" are tension-only (slack, e - e0 < 0, they carry
     #                                                 nothing), and "dynamics" then gains "slack_elements", the ids of
-    #                                                 those slack at the last step
+    #                                                 those slack at the last step; "load_history" is lam(t) as a
+    #                                                 piecewise-linear table in place of the ramp, "support_motion" moves
+    #                                                 the listed fixed dofs, u[dof](t) = amplitude * s(t), s such a table
     accel = data.get("accel", {})
     chain = accel.get("synthetic_chain")
     if chain and not data.get("nodes"):
@@ -240,7 +244,15 @@ def parse_problem(problem_file):
 
 _DYNAMICS_KEYS = {"dt": float, "dt_safety": float, "t_end": float, "n_steps": int, "damping": float, "ramp_time": float,
                   "load_factor_initial": float, "load_factor_final": float, "record_every": int, "record_dofs": list,
-                  "nodal_mass": None, "rest_tolerance": float, "cable_elements": None}
+                  "nodal_mass": None, "rest_tolerance": float, "cable_elements": None, "load_history": "table",
+                  "support_motion": "motion"}
+
+
+def _history_table(block, more=()):
+    """{"times": [...], "values": [...]} (and the keys `more`) -> (times, values); what they hold is check_dynamics's."""
+    if not isinstance(block, dict) or set(block) != {"times", "values", *more}:
+        raise ValueError
+    return block["times"], block["values"]
 
 
 def _dynamics_block(block):
@@ -250,10 +262,12 @@ def _dynamics_block(block):
     if not isinstance(block, dict) or not set(block) <= set(_DYNAMICS_KEYS) | {"u_initial", "v_initial"}:
         raise ValueError("accel.dynamics must be an object with keys out of "
                          f"{sorted(set(_DYNAMICS_KEYS) | {'u_initial', 'v_initial'})}")
+    from ..fem.dynamics import SupportMotion
+    kinds = {None: lambda x: x, "table": _history_table,
+             "motion": lambda b: SupportMotion(b["dofs"], b["amplitudes"], _history_table(b, ("dofs", "amplitudes")))}
     try:
-        kw = {key: (block[key] if kind is None else kind(block[key])) for key, kind in _DYNAMICS_KEYS.items()
-              if block.get(key) is not None}
-    except (TypeError, ValueError):
+        kw = {key: kinds.get(kind, kind)(block[key]) for key, kind in _DYNAMICS_KEYS.items() if block.get(key) is not None}
+    except (TypeError, ValueError, KeyError):
         raise ValueError("accel.dynamics holds a value of the wrong type") from None
     return {"config": DynamicsConfig(**kw), "u_initial": block.get("u_initial"), "v_initial": block.get("v_initial")}
 

@@ -41,6 +41,9 @@
 //   element, and a flagged element with e - e0 < 0 is slack: N = 0 by a select on the value, so it adds +-0.0 in its place
 //   in the incidence order, no strain energy, and 1 to a fifth partial, the slack count.  The <DIM, false> instantiations
 //   are the bar kernels, untouched: the flag is a template parameter, and their trailing operand is never read.
+//   Time histories: the <DIM, CABLE, pf_dyn_hist> instantiations of the step read the load factor and the support-motion scale of
+//   their step from arrays the host sampled at the step times (pf_dyn_hist), by the step number of the device clock: two
+//   launch-uniform loads, no search, and a replayed graph reads the samples of the steps it then stands at.
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>
@@ -350,25 +353,54 @@ struct dyn_term {
 // the displacements of step n: the steps ping-pong between u0 and u1, step n reads buffer n & 1 and writes the other
 __device__ __forceinline__ const double* dyn_u_at(const pf_dyn& D, long long n) { return (n & 1) ? D.u1 : D.u0; }
 
+// the histories of a step: none, or the launch's operand
+__device__ __forceinline__ pf_dyn_hist dyn_hist_of() { return pf_dyn_hist{nullptr, nullptr, nullptr, 0}; }
+__device__ __forceinline__ pf_dyn_hist dyn_hist_of(const pf_dyn_hist& h) { return h; }
+
+// the sample of step n in a history of last + 1 samples: a step beyond the table reads its last entry (the history is held)
+__device__ __forceinline__ long long dyn_sample_at(long long n, long long last) { return n < 0 ? 0 : (n < last ? n : last); }
+
 // Step n = *clock + k of the sequence, one node per thread:
 //   v <- c1 v + g (lam(t_n) f_ext - f_int(u_n)) / m,   u_{n+1} = u_n + dt v;   fixed dofs: v = 0, u = 0.
 // A thread reads and writes only its own dofs of v (in place); its neighbours read u_n, so u_{n+1} goes to the other buffer.
 // cable: [n_elems] the tension-only flags, read by the CABLE instantiations alone (the bar's get nullptr)
-template <int DIM, bool CABLE>
+// HIST: empty, or pf_dyn_hist and one more operand, the time histories the host sampled at the step times (the <DIM, CABLE>
+// instantiations keep their operands and their code): lam = H.lam[i(n)] in place of the ramp where H.lam is given, and a fixed
+// dof with an amplitude a != 0.0 gets u_{n+1} = a H.sup[i(n + 1)], one product; i(n) = n held inside the table.  The two
+// samples are the same for the whole launch; sup_amp is read under `fixed` alone.  The select on a keeps the bytes of 0.0 on
+// a support that is not moved (0.0 * s is -0.0 for a negative s).  v on a fixed dof stays 0.0: the energy kernels never
+// divide by a support's minv.
+template <int DIM, bool CABLE, class... HIST>
 __global__ __launch_bounds__(256) void k_gl_dyn_step(pf_problem P, const double* __restrict__ d0_in, pf_dyn D, long long k,
-                                                     double c1, double g, double dt, const unsigned char* __restrict__ cable) {
+                                                     double c1, double g, double dt, const unsigned char* __restrict__ cable,
+                                                     HIST... hist) {
+  constexpr bool with_hist = sizeof...(HIST) > 0;
+  const pf_dyn_hist H = dyn_hist_of(hist...);
   const pf_mesh& M = P.mesh;
   const long long n = *D.clock + k;
   const double* __restrict__ u_n = dyn_u_at(D, n);
   double* __restrict__ u_next = const_cast<double*>(dyn_u_at(D, n + 1));
   const double t = (double)n * D.dt;
-  const double lam = D.t_ramp > 0.0 ? D.lam0 + (D.lam1 - D.lam0) * fmin(1.0, t / D.t_ramp) : D.lam1;
+  double lam = D.t_ramp > 0.0 ? D.lam0 + (D.lam1 - D.lam0) * fmin(1.0, t / D.t_ramp) : D.lam1;
+  double s_next = 0.0;
+  if (with_hist) {
+    const long long last = H.n_samples - 1;
+    if (H.lam) lam = H.lam[dyn_sample_at(n, last)];
+    if (H.sup) s_next = H.sup[dyn_sample_at(n + 1, last)];
+  }
   PF_EACH_NODE(node, M)
     node_gather<DIM, false>(M, node, nullptr, 0, dyn_term<DIM, CABLE>{P, d0_in, u_n, D.ea, D.e0, cable}, [&](int dof, double f_int) {
       const bool fixed = dof_fixed(M, dof);
       const double v = c1 * D.v[dof] + g * ((lam * D.f_ext[dof] - f_int) * D.minv[dof]);
       D.v[dof] = fixed ? 0.0 : v;
-      u_next[dof] = fixed ? 0.0 : u_n[dof] + dt * v;
+      double held = 0.0;
+      if (with_hist) {
+        if (fixed && H.sup) {
+          const double a = H.sup_amp[dof];
+          held = a != 0.0 ? a * s_next : 0.0;
+        }
+      }
+      u_next[dof] = fixed ? held : u_n[dof] + dt * v;
     });
 }
 
@@ -524,15 +556,20 @@ int dyn_check(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn
 }
 
 // n_steps launches of the step with the coefficients (c1, gk), then the clock's: a single chain on s.  cable: the
-// tension-only flags and the step's CABLE instantiation, or null and the bar step
-int dyn_enqueue(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, int n_steps,
-                double c1, double gk, hipStream_t s) {
+// tension-only flags and the step's CABLE instantiation, or null and the bar step.  hist: the time histories and the step's
+// HIST instantiation, or null and the step of the ramp and the supports at rest
+int dyn_enqueue(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const pf_dyn_hist* hist,
+                const unsigned char* cable, int n_steps, double c1, double gk, hipStream_t s) {
   if (p->mesh.n_nodes > 0) {
     const dim3 grid(pf_node_blocks(p->mesh.n_nodes));
     const auto k2 = cable ? k_gl_dyn_step<2, true> : k_gl_dyn_step<2, false>;
     const auto k1 = cable ? k_gl_dyn_step<1, true> : k_gl_dyn_step<1, false>;
+    const auto h2 = cable ? k_gl_dyn_step<2, true, pf_dyn_hist> : k_gl_dyn_step<2, false, pf_dyn_hist>;
+    const auto h1 = cable ? k_gl_dyn_step<1, true, pf_dyn_hist> : k_gl_dyn_step<1, false, pf_dyn_hist>;
     for (int k = 0; k < n_steps; ++k)
-      if (const int rc = launch(who, p, k2, k1, grid, s, g->d0, *d, (long long)k, c1, gk, d->dt, cable)) return rc;
+      if (const int rc = hist ? launch(who, p, h2, h1, grid, s, g->d0, *d, (long long)k, c1, gk, d->dt, cable, *hist)
+                              : launch(who, p, k2, k1, grid, s, g->d0, *d, (long long)k, c1, gk, d->dt, cable))
+        return rc;
   }
   hipLaunchKernelGGL(k_gl_dyn_clock, dim3(1), dim3(64), 0, s, d->clock, (long long)n_steps);
   return launched(who);
@@ -546,39 +583,49 @@ void dyn_coefficients(const pf_dyn* d, double& c1, double& gk) {
 }
 
 // The four entry points, each stated once for the bar family (cable == null) and the cable family.  A _cable entry point
-// refuses a null cable first (cable_given), so a null here always means the bar family.
+// refuses a null cable first (cable_given), so a null here always means the bar family.  start, steps and graph_create take
+// the time histories too: a _hist entry point refuses a bad record first (hist_given), so a null hist always means none.
 int cable_given(const char* who, const unsigned char* cable) {
   return cable ? PF_OK : gl_fail(PF_ERR_ARG, who, "null cable (the entry point without _cable is the run of bars)");
 }
 
-int dyn_start(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, void* stream) {
+int hist_given(const char* who, const pf_dyn_hist* h) {
+  if (!h) return gl_fail(PF_ERR_ARG, who, "null hist (the entry point without _hist is the run of the ramp)");
+  if (!h->lam && !h->sup) return gl_fail(PF_ERR_ARG, who, "hist holds neither lam nor sup (the entry point without _hist is that run)");
+  if (h->sup && !h->sup_amp) return gl_fail(PF_ERR_ARG, who, "sup without sup_amp");
+  if (h->n_samples < 1) return gl_fail(PF_ERR_ARG, who, "n_samples must be at least 1");
+  return PF_OK;
+}
+
+int dyn_start(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const pf_dyn_hist* hist,
+              const unsigned char* cable, void* stream) {
   if (const int rc = dyn_check(who, p, g, d)) return rc;
   long long clock = -1;
   if (hipMemcpyAsync(&clock, d->clock, sizeof(clock), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
       hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
     return gl_fail(PF_ERR_HIP, who, "reading the clock failed");
   if (clock != 0) return gl_fail(PF_ERR_ARG, who, "the clock must be 0 (the half kick starts a run)");
-  return dyn_enqueue(who, p, g, d, cable, 1, 1.0 - 0.5 * d->alpha * d->dt, 0.5 * d->dt, (hipStream_t)stream);
+  return dyn_enqueue(who, p, g, d, hist, cable, 1, 1.0 - 0.5 * d->alpha * d->dt, 0.5 * d->dt, (hipStream_t)stream);
 }
 
-int dyn_steps(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, int n_steps,
-              void* stream) {
+int dyn_steps(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const pf_dyn_hist* hist,
+              const unsigned char* cable, int n_steps, void* stream) {
   if (const int rc = dyn_check(who, p, g, d)) return rc;
   if (n_steps < 1) return gl_fail(PF_ERR_ARG, who, "n_steps must be at least 1");
   double c1, gk;
   dyn_coefficients(d, c1, gk);
-  return dyn_enqueue(who, p, g, d, cable, n_steps, c1, gk, (hipStream_t)stream);
+  return dyn_enqueue(who, p, g, d, hist, cable, n_steps, c1, gk, (hipStream_t)stream);
 }
 
-int dyn_graph_create(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable,
-                     int n_steps, void* stream, void** graph_out) {
+int dyn_graph_create(const char* who, const pf_problem* p, const pf_gl* g, const pf_dyn* d, const pf_dyn_hist* hist,
+                     const unsigned char* cable, int n_steps, void* stream, void** graph_out) {
   if (const int rc = dyn_check(who, p, g, d)) return rc;
   if (n_steps < 1) return gl_fail(PF_ERR_ARG, who, "n_steps must be at least 1");
   if (!graph_out) return gl_fail(PF_ERR_ARG, who, "null pointer");
   double c1, gk;
   dyn_coefficients(d, c1, gk);
   return capture_graph((hipStream_t)stream, 0, hipStreamCaptureModeThreadLocal, graph_out,
-                       [&](pf_capture& cap) { return dyn_enqueue(who, p, g, d, cable, n_steps, c1, gk, cap.s); });
+                       [&](pf_capture& cap) { return dyn_enqueue(who, p, g, d, hist, cable, n_steps, c1, gk, cap.s); });
 }
 
 // out: the results (4, with cable 5), then as many block partials per block
@@ -602,15 +649,15 @@ int dyn_energy(const char* who, const pf_problem* p, const pf_gl* g, const pf_dy
 extern "C" {
 
 int pf_gl_dyn_start(const pf_problem* p, const pf_gl* g, const pf_dyn* d, void* stream) {
-  return dyn_start("pf_gl_dyn_start", p, g, d, nullptr, stream);
+  return dyn_start("pf_gl_dyn_start", p, g, d, nullptr, nullptr, stream);
 }
 
 int pf_gl_dyn_steps(const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, void* stream) {
-  return dyn_steps("pf_gl_dyn_steps", p, g, d, nullptr, n_steps, stream);
+  return dyn_steps("pf_gl_dyn_steps", p, g, d, nullptr, nullptr, n_steps, stream);
 }
 
 int pf_gl_dyn_graph_create(const pf_problem* p, const pf_gl* g, const pf_dyn* d, int n_steps, void* stream, void** graph_out) {
-  return dyn_graph_create("pf_gl_dyn_graph_create", p, g, d, nullptr, n_steps, stream, graph_out);
+  return dyn_graph_create("pf_gl_dyn_graph_create", p, g, d, nullptr, nullptr, n_steps, stream, graph_out);
 }
 
 int pf_gl_dyn_energy(const pf_problem* p, const pf_gl* g, const pf_dyn* d, double* out4, void* stream) {
@@ -620,21 +667,21 @@ int pf_gl_dyn_energy(const pf_problem* p, const pf_gl* g, const pf_dyn* d, doubl
 int pf_gl_dyn_start_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, void* stream) {
   const char* who = "pf_gl_dyn_start_cable";
   if (const int rc = cable_given(who, cable)) return rc;
-  return dyn_start(who, p, g, d, cable, stream);
+  return dyn_start(who, p, g, d, nullptr, cable, stream);
 }
 
 int pf_gl_dyn_steps_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, int n_steps,
                           void* stream) {
   const char* who = "pf_gl_dyn_steps_cable";
   if (const int rc = cable_given(who, cable)) return rc;
-  return dyn_steps(who, p, g, d, cable, n_steps, stream);
+  return dyn_steps(who, p, g, d, nullptr, cable, n_steps, stream);
 }
 
 int pf_gl_dyn_graph_create_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, int n_steps,
                                  void* stream, void** graph_out) {
   const char* who = "pf_gl_dyn_graph_create_cable";
   if (const int rc = cable_given(who, cable)) return rc;
-  return dyn_graph_create(who, p, g, d, cable, n_steps, stream, graph_out);
+  return dyn_graph_create(who, p, g, d, nullptr, cable, n_steps, stream, graph_out);
 }
 
 int pf_gl_dyn_energy_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const unsigned char* cable, double* out5,
@@ -642,6 +689,27 @@ int pf_gl_dyn_energy_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* d,
   const char* who = "pf_gl_dyn_energy_cable";
   if (const int rc = cable_given(who, cable)) return rc;
   return dyn_energy(who, p, g, d, cable, out5, stream);
+}
+
+int pf_gl_dyn_start_hist(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const pf_dyn_hist* hist, const unsigned char* cable,
+                         void* stream) {
+  const char* who = "pf_gl_dyn_start_hist";
+  if (const int rc = hist_given(who, hist)) return rc;
+  return dyn_start(who, p, g, d, hist, cable, stream);
+}
+
+int pf_gl_dyn_steps_hist(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const pf_dyn_hist* hist, const unsigned char* cable,
+                         int n_steps, void* stream) {
+  const char* who = "pf_gl_dyn_steps_hist";
+  if (const int rc = hist_given(who, hist)) return rc;
+  return dyn_steps(who, p, g, d, hist, cable, n_steps, stream);
+}
+
+int pf_gl_dyn_graph_create_hist(const pf_problem* p, const pf_gl* g, const pf_dyn* d, const pf_dyn_hist* hist,
+                                const unsigned char* cable, int n_steps, void* stream, void** graph_out) {
+  const char* who = "pf_gl_dyn_graph_create_hist";
+  if (const int rc = hist_given(who, hist)) return rc;
+  return dyn_graph_create(who, p, g, d, hist, cable, n_steps, stream, graph_out);
 }
 
 int pf_gl_state(const pf_problem* p, const pf_gl* g, const double* u, void* stream) {

@@ -826,21 +826,29 @@ class HipEngine:
             d["graphs"] = {}
 
     @_on_engine_stream
-    def dyn_begin(self, u0, v0, minv, dt, alpha, lam0, lam1, t_ramp, ea=None, e0=None, start=True, cable=None):
+    def dyn_begin(self, u0, v0, minv, dt, alpha, lam0, lam1, t_ramp, ea=None, e0=None, start=True, cable=None,
+                  load_samples=None, support=None):
         """Begin a central-difference run at step 0 (pf_dyn).  u0, v0, minv: float64 [n_dofs] (minv = 1 / lumped mass of
         the dof's node; the loads are the model's, at load factor 1); ea, e0: as gl_state.  start: v0 is the velocity at
         t = 0 and the half kick (pf_gl_dyn_start) turns it into v_{1/2} and u_1, the run then stands at step 1; False: v0 is
         taken as v_{-1/2} and the run stands at step 0.  The buffers live on the engine; the graphs of dyn_steps are kept
-        for as long as the scalars and the presence of ea / e0 / cable, which they bake in, stay the same.
+        for as long as the scalars and the presence of ea / e0 / cable / histories, which they bake in, stay the same.
         cable: bool or uint8 [n_elems], True = the element is tension-only (no force and no strain energy where e - e0 < 0);
-        the run then goes through the pf_gl_dyn_*_cable entry points.  None: a run of bars through pf_gl_dyn_*."""
+        the run then goes through the pf_gl_dyn_*_cable entry points.  None: a run of bars through pf_gl_dyn_*.
+        load_samples: float64 [n], the load factor of step k in place of the ramp (lam0, lam1 and t_ramp are then not read);
+        support: a pair (amp [n_dofs], samples [n]): a fixed dof with amp != 0 is held at amp * samples[k] at step k.  A step
+        beyond a table reads its last sample; with both given the two tables have one length.  The engine keeps device
+        copies, and the run goes through the pf_gl_dyn_*_hist entry points (with the cable flags, if any).  u0 on the moved
+        dofs is the caller's.  With neither, every call is the call it was without these arguments."""
         nd, ne = self.plan.n_dofs, self.plan.n_elems
         flags = None if cable is None else self._cable_flags(cable, ne)
+        hist = self._dyn_histories(load_samples, support, nd)
         vec = {name: self._f64_vector("dyn_begin", name, t, nd, "dofs") for name, t in (("u0", u0), ("v0", v0), ("minv", minv))}
         opt = {name: None if t is None else self._f64_vector("dyn_begin", name, t, ne, "elements")
                for name, t in (("ea", ea), ("e0", e0))}
         scalars = tuple(float(x) for x in (dt, alpha, lam0, lam1, t_ramp))
-        key = scalars + (ea is None, e0 is None, cable is None)
+        key = scalars + (ea is None, e0 is None, cable is None, load_samples is not None, support is not None,
+                         0 if hist is None else hist["lam" if "lam" in hist else "sup"].numel())
         d = self._dyn
         if d is None:
             f64 = dict(dtype=torch.float64, device=self.device)
@@ -872,6 +880,17 @@ class HipEngine:
         d["with_cable"] = flags is not None
         if flags is not None:
             d["cable"][:ne].copy_(flags)
+        # the histories: device copies that keep their place for as long as their presence and length, which are in the key
+        if hist is None:
+            d["hist"] = None
+        else:
+            old = d.get("hist") or {}
+            h = d["hist"] = dict(rec=_capi.PfDynHist())
+            for name, t in hist.items():
+                keep = old.get(name)
+                h[name] = keep.copy_(t) if keep is not None and keep.numel() == t.numel() else t.clone()
+                setattr(h["rec"], name, h[name].data_ptr())
+            h["rec"].n_samples = h["lam" if "lam" in h else "sup"].numel()
         d["n"] = 0
         if start:
             self._dyn_call(d, "pf_gl_dyn_start", self._stream())
@@ -884,10 +903,42 @@ class HipEngine:
                              f"{flags.dtype} {tuple(flags.shape)}")
         return flags.to(device=self.device, dtype=torch.uint8)
 
+    def _dyn_histories(self, load_samples, support, nd):
+        """dyn_begin's load_samples and support, checked, as device vectors by pf_dyn_hist's names, or None."""
+        if load_samples is None and support is None:
+            return None
+
+        def samples(name, t):
+            t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))
+            if t.dtype != torch.float64 or t.dim() != 1 or t.numel() < 1:
+                raise ValueError(f"dyn_begin: {name} must be float64 [n] with n >= 1, got {t.dtype} {tuple(t.shape)}")
+            return t.to(self.device).contiguous()
+
+        keep = {}
+        if load_samples is not None:
+            keep["lam"] = samples("load_samples", load_samples)
+        if support is not None:
+            try:
+                amp, sup = support
+            except (TypeError, ValueError):
+                raise ValueError("dyn_begin: support must be a pair (amp [n_dofs], samples [n])") from None
+            keep["sup_amp"] = self._f64_vector("dyn_begin", "support amp", amp if isinstance(amp, torch.Tensor)
+                                               else torch.from_numpy(np.ascontiguousarray(amp)), nd, "dofs")
+            keep["sup"] = samples("support samples", sup)
+        if "lam" in keep and "sup" in keep and keep["lam"].numel() != keep["sup"].numel():
+            raise ValueError(f"dyn_begin: load_samples has {keep['lam'].numel()} samples and support {keep['sup'].numel()}: "
+                             "both are sampled at the same steps")
+        return keep
+
     def _dyn_call(self, d, name, *args):
-        """lib.<name>(problem, element record, pf_dyn, *args), or its _cable namesake with the run's flags behind pf_dyn."""
+        """lib.<name>(problem, element record, pf_dyn, *args), or its _cable namesake with the run's flags behind pf_dyn; with
+        histories its _hist namesake, where the histories' record and the flags (or null) ride behind pf_dyn.  The energies
+        know no histories."""
         head = (self._ref(), C.byref(self._gl_buffers()[4]), C.byref(d["rec"]))
-        if d["with_cable"]:
+        if d.get("hist") is not None and name != "pf_gl_dyn_energy":
+            name = name + "_hist"
+            head = head + (C.byref(d["hist"]["rec"]), d["cable"].data_ptr() if d["with_cable"] else None)
+        elif d["with_cable"]:
             name, head = name + "_cable", head + (d["cable"].data_ptr(),)
         _capi.check(getattr(self.lib, name)(*head, *args), name)
 

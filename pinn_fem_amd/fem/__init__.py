@@ -6,12 +6,14 @@ from .boundary import free_and_fixed_dofs
 __all__ = ["FEMModel", "Material", "Property", "ScalarProperty", "NNProperty", "to_property",
            "free_and_fixed_dofs", "IdentifyResult", "check_identify", "identify_nr", "misfit_and_gradient", "residuals_and_jacobian",
            "check_strains", "PrestressResult", "check_prestress", "identify_prestress", "residuals_and_jacobian_prestress",
-           "DynamicsConfig", "DynamicsResult", "check_dynamics", "solve_dynamic", "stable_time_step", "lumped_mass"]
+           "DynamicsConfig", "DynamicsResult", "check_dynamics", "solve_dynamic", "stable_time_step", "lumped_mass",
+           "SupportMotion"]
 
 _IDENTIFY = ("IdentifyResult", "check_identify", "identify_nr", "misfit_and_gradient", "residuals_and_jacobian",
              "check_strains")
 _PRESTRESS = ("PrestressResult", "check_prestress", "identify_prestress", "residuals_and_jacobian_prestress")
-_DYNAMICS = ("DynamicsConfig", "DynamicsResult", "check_dynamics", "solve_dynamic", "stable_time_step", "lumped_mass")
+_DYNAMICS = ("DynamicsConfig", "DynamicsResult", "check_dynamics", "solve_dynamic", "stable_time_step", "lumped_mass",
+             "SupportMotion")
 
 
 def __getattr__(name):

@@ -11,6 +11,11 @@ Material.density.  Scalar materials, one GPU, dimension 1 and 2.
 Tension-only (cable) elements, DynamicsConfig.cable_elements: a flagged element with e - e0 < 0 is slack and carries N = 0, no
 force and no strain energy (pf_gl_dyn_*_cable).  Only this module knows cables; a damped run with rest_tolerance comes to rest
 on the equilibrium of the structure without its slack elements.
+
+Time histories, DynamicsConfig.load_history and .support_motion: lam(t) and the scale s(t) of prescribed support displacements
+u[dof](t) = amplitude s(t), each a table (piecewise linear) or a callable.  The host samples them once at the step times
+t_n = n dt, 16 bytes per step for the two, and the step reads its samples by the step number of the device clock
+(pf_gl_dyn_*_hist): no search on the device, and a replayed graph reads the samples of the steps it stands at.
 """
 from __future__ import annotations
 
@@ -42,6 +47,17 @@ class DynamicsConfig:
     nodal_mass: Optional[object] = None     # a mass added at every node (a number) or one for each node
     rest_tolerance: Optional[float] = None  # stop at a record point with kinetic energy <= this x the largest recorded
     cable_elements: Optional[object] = None     # the tension-only elements: "all" or a list of element ids; None or []: all bars
+    load_history: Optional[object] = None   # lam(t) in place of the ramp: a pair (times, values) or a callable (history_samples);
+                                            # ramp_time and load_factor_initial / _final must then be at their defaults
+    support_motion: Optional["SupportMotion"] = None    # fixed dofs that follow a prescribed displacement
+
+
+@dataclass
+class SupportMotion:
+    """u[dof](t) = amplitude * s(t) on the listed fixed dofs."""
+    dofs: List[int]                         # distinct dofs, every one of them in model.fixed_dofs
+    amplitudes: object                      # a number, or one for each of dofs
+    history: object                         # s(t): a pair (times, values) or a callable, as DynamicsConfig.load_history
 
 
 @dataclass
@@ -108,6 +124,73 @@ def cable_mask(model, cable_elements) -> Optional[np.ndarray]:
     return mask
 
 
+def history_samples(history, t: np.ndarray, what: str = "history") -> np.ndarray:
+    """A time history at the times t (float64 [n]) as float64 [n].
+    A pair (times, values): times strictly increasing, the history piecewise linear between the knots,
+    v_j + (v_{j+1} - v_j) ((t - t_j) / (t_{j+1} - t_j)) for t_j < t < t_{j+1}, the knot's own value at a knot, the first value
+    before the first knot and the last value after the last.  A callable: called once with t, it returns an array of t's
+    shape.  Anything else, and any value that is not finite, is a ValueError naming `what`."""
+    t = np.asarray(t, dtype=np.float64)
+    if callable(history):
+        try:
+            out = np.asarray(history(t.copy()), dtype=np.float64)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"{what}: the callable did not return numbers ({err})") from None
+        if out.shape != t.shape:
+            raise ValueError(f"{what}: the callable returned the shape {out.shape} for times of the shape {t.shape}")
+        if not np.all(np.isfinite(out)):
+            raise ValueError(f"{what}: the callable returned a value that is not finite")
+        return np.ascontiguousarray(out)
+    try:
+        times, values = history
+        times, values = np.asarray(times, dtype=np.float64), np.asarray(values, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a pair (times, values) or a callable") from None
+    if times.ndim != 1 or values.ndim != 1 or times.size < 1 or times.size != values.size:
+        raise ValueError(f"{what}: times and values must be two lists of one length, at least 1, got the shapes "
+                         f"{times.shape} and {values.shape}")
+    if not (np.all(np.isfinite(times)) and np.all(np.isfinite(values))):
+        raise ValueError(f"{what}: times and values must be finite")
+    if np.any(np.diff(times) <= 0.0):
+        raise ValueError(f"{what}: times must be strictly increasing")
+    if times.size == 1:
+        return np.full(t.shape, values[0])
+    j = np.clip(np.searchsorted(times, t, side="right") - 1, 0, times.size - 2)         # t_j <= t < t_{j+1} inside the table
+    out = values[j] + (values[j + 1] - values[j]) * ((t - times[j]) / (times[j + 1] - times[j]))
+    out = np.where(t == times[j], values[j], out)
+    return np.where(t <= times[0], values[0], np.where(t >= times[-1], values[-1], out))
+
+
+def support_amplitudes(model, motion) -> np.ndarray:
+    """SupportMotion's dofs and amplitudes as the amplitude of every dof, float64 [n_dofs] (0.0: the dof is not moved).
+    Anything malformed is a ValueError."""
+    if not isinstance(motion, SupportMotion):
+        raise ValueError("support_motion must be a SupportMotion(dofs, amplitudes, history)")
+    try:
+        dofs = np.asarray(motion.dofs)
+        amp = np.asarray(motion.amplitudes, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("support_motion: dofs must be a list of dofs and amplitudes a number or a list of numbers") from None
+    if dofs.ndim != 1 or dofs.size < 1 or dofs.dtype.kind not in "iu":
+        raise ValueError("support_motion: dofs must be a list of at least one integer dof")
+    if np.unique(dofs).size != dofs.size:
+        raise ValueError("support_motion names a dof twice")
+    loose = np.setdiff1d(dofs, np.asarray(model.fixed_dofs, dtype=np.int64))
+    if loose.size:
+        raise ValueError(f"support_motion: dof {int(loose[0])} is not in fixed_dofs: only a support can be moved")
+    if amp.ndim > 1 or (amp.ndim == 1 and amp.size != dofs.size):
+        raise ValueError(f"support_motion: amplitudes must be a number or {dofs.size} numbers (one for each of dofs)")
+    if not np.all(np.isfinite(amp)):
+        raise ValueError("support_motion: amplitudes must be finite")
+    out = np.zeros(model.ndof)
+    out[dofs.astype(np.int64)] = amp
+    return out
+
+
+# the times check_dynamics tries a callable history on, before the step times are known
+_PROBE_TIMES = np.array([0.0, 0.5, 1.0])
+
+
 def check_dynamics(model, config: SolverConfig, dyn: DynamicsConfig) -> np.ndarray:
     """Everything solve_dynamic refuses, as a ValueError before an engine is built.  Returns the node masses."""
     if check_kinematics(config.kinematics) != "green-lagrange":
@@ -148,6 +231,14 @@ def check_dynamics(model, config: SolverConfig, dyn: DynamicsConfig) -> np.ndarr
         if arr.ndim > 1 or (arr.ndim == 1 and arr.size != model.nnode) or not np.all(np.isfinite(arr)) or np.any(arr < 0.0):
             raise ValueError(f"nodal_mass must be a non-negative number or {model.nnode} of them (one for each node)")
     cable_mask(model, dyn.cable_elements)
+    if dyn.load_history is not None:
+        if (dyn.ramp_time, dyn.load_factor_initial, dyn.load_factor_final) != (0.0, 0.0, 1.0):
+            raise ValueError("load_history takes the place of the ramp: ramp_time, load_factor_initial and load_factor_final "
+                             "must be left at their defaults")
+        history_samples(dyn.load_history, _PROBE_TIMES, "load_history")
+    if dyn.support_motion is not None:
+        support_amplitudes(model, dyn.support_motion)
+        history_samples(dyn.support_motion.history, _PROBE_TIMES, "support_motion.history")
     if not float(model.material.density.value()) > 0.0 and nodal is None:
         raise ValueError("solve_dynamic needs a positive material density or a nodal_mass: the structure has no mass")
     mass = lumped_mass(model, nodal)
@@ -200,7 +291,14 @@ def solve_dynamic(model, config: SolverConfig, dyn: DynamicsConfig, u_initial=No
     time, and so does a non-finite energy.  config.initial_strain is the e0 of every element, as in solve_nr.
     dyn.cable_elements are tension-only: slack (e - e0 < 0) they carry nothing, in the steps, the energies, the closing
     residual, the reactions and the axial forces; every record counts them ("slack_elements") and DynamicsResult.slack names
-    those of the last step."""
+    those of the last step.
+    dyn.load_history takes the place of the ramp and dyn.support_motion moves fixed dofs, u[dof](t) = amplitude s(t).  Both are
+    sampled once, at t_n = n dt for n = 0 .. n_steps + 1 (history_samples; a callable is called once with all of them, after
+    check_dynamics has tried it on three times of its own), 16 bytes per step for the two, and the steps read the samples by
+    their number; the records' load_factor and work, and the load factor of the closing residual and reactions, are those
+    samples.  u_initial on a moved dof is replaced by amplitude s(0).  With support motion the recorded `total` is not a
+    conserved quantity: the supports do work on the structure, and their own kinetic energy is not counted (v stays 0 on a
+    fixed dof)."""
     mass = check_dynamics(model, config, dyn)
     e0_np = check_initial_strain(config, model)
     cable = cable_mask(model, dyn.cable_elements)
@@ -239,7 +337,21 @@ def solve_dynamic(model, config: SolverConfig, dyn: DynamicsConfig, u_initial=No
     dofs_t = torch.from_numpy(dofs).to(dev)
     lam0, lam1, t_ramp = float(dyn.load_factor_initial), float(dyn.load_factor_final), float(dyn.ramp_time)
 
-    def lam_at(t):
+    # the histories at the step times: step n reads sample n, and writes the supports of step n + 1
+    t_samples = np.arange(n_steps + 2, dtype=np.float64) * dt
+    lam_samples = None if dyn.load_history is None else history_samples(dyn.load_history, t_samples, "load_history")
+    support = None
+    if dyn.support_motion is not None:
+        amp = support_amplitudes(model, dyn.support_motion)
+        support = (amp, history_samples(dyn.support_motion.history, t_samples, "support_motion.history"))
+        moved = amp != 0.0
+        s.u[torch.from_numpy(moved).to(dev)] = torch.from_numpy(amp[moved] * support[1][0]).to(dev)
+    hist = dict(load_samples=lam_samples, support=support)
+
+    def lam_at(n):
+        if lam_samples is not None:
+            return float(lam_samples[min(n, n_steps + 1)])
+        t = n * dt
         return lam0 + (lam1 - lam0) * min(1.0, t / t_ramp) if t_ramp > 0.0 else lam1
 
     times, recorded, energies = [], [], []
@@ -253,7 +365,7 @@ def solve_dynamic(model, config: SolverConfig, dyn: DynamicsConfig, u_initial=No
         if dt * wb > 2.0:
             raise RuntimeError(f"solve_dynamic: the time step {dt:.6g} is above the stability limit 2 / omega_bound = "
                                f"{2.0 / wb:.6g} at t = {t:.6g} (step {n})")
-        lam = lam_at(t)
+        lam = lam_at(n)
         times.append(t)
         recorded.append(u[dofs_t].cpu().numpy())
         energies.append(dict(kinetic=kin, strain=strain_e, work=lam * work, total=kin + strain_e - lam * work,
@@ -263,9 +375,9 @@ def solve_dynamic(model, config: SolverConfig, dyn: DynamicsConfig, u_initial=No
         kin_max = max(kin_max, kin)
 
     # the initial state: the start has not run yet, so its kinetic energy is that of v_initial
-    eng.dyn_begin(s.u, v0, minv, dt, float(dyn.damping), lam0, lam1, t_ramp, None, s.e0, start=False, cable=cable)
+    eng.dyn_begin(s.u, v0, minv, dt, float(dyn.damping), lam0, lam1, t_ramp, None, s.e0, start=False, cable=cable, **hist)
     record(0, s.u, *eng.dyn_energy(), w0, None if cable is None else slack_at(strains_at(s.u)).sum())
-    eng.dyn_begin(s.u, v0, minv, dt, float(dyn.damping), lam0, lam1, t_ramp, None, s.e0, start=True, cable=cable)
+    eng.dyn_begin(s.u, v0, minv, dt, float(dyn.damping), lam0, lam1, t_ramp, None, s.e0, start=True, cable=cable, **hist)
     done, at_rest = 1, False
     while True:
         target = min(n_steps, (done // every + 1) * every)
@@ -281,7 +393,7 @@ def solve_dynamic(model, config: SolverConfig, dyn: DynamicsConfig, u_initial=No
             break
         if done >= n_steps:
             break
-    lam_end = lam_at(done * dt)
+    lam_end = lam_at(done)
     strain = eng.gl_state(u, None, s.e0)
     slack = slack_at(strain.cpu().numpy())
     if slack.any():

@@ -3,7 +3,7 @@
 against the composition the entry points before it allow (pf_gl_state_e0, pf_gl_fint and a torch update: six launches and
 two round trips through fe per step), each issued launch by launch ("eager") and as a replayed hipGraph.
 
-    dyn_scale.py [--steps 200] [--rounds 5] [--chains 1000 100000 1000000] [--warren 250 25000 250000] [--cable]
+    dyn_scale.py [--steps 200] [--rounds 5] [--chains 1000 100000 1000000] [--warren 250 25000 250000] [--cable | --history]
 
 Meshes: collinear chains (plan.chain_mesh: only ux is free) and Warren girders (plan.warren_mesh), every element with the
 pretension e0 = -1e-3, E*A = 1000, rho A = 0.5, the mesh's own loads scaled to 1e-3, alpha = 0.1, dt = half the bound at
@@ -19,7 +19,12 @@ eager and as a graph, three runs alternated in the same way: bar (no flags), tau
 e0 = -1e-3: the chains end the run without a slack element; the girders shorten, swing through and end with about half
 their elements slack) and half (every element flagged, e0 = +1e-3 on the odd elements, which are slack from the first step
 on).  The JSON line holds the slack counts at the end and the ratios of the medians to the bar's.  The rule is a select,
-so a step does the same work whatever is slack."""
+so a step does the same work whatever is slack.
+
+--history times the step under time histories (pf_gl_dyn_steps_hist) against the bar step, on the same meshes, loads and dt,
+eager and as a graph, four runs alternated in the same way: bar (no history), load (a load history around 1), support (every
+fixed dof moved by 1e-4 times a history; the load factor is the bar's) and both.  The histories hold a sample for every step
+the run takes.  The JSON line holds the ratios of the medians to the bar's."""
 import argparse, ctypes as C, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,6 +43,7 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--chains", type=int, nargs="*", default=[1000, 100_000, 1_000_000])
 ap.add_argument("--warren", type=int, nargs="*", default=[250, 25_000, 250_000])
 ap.add_argument("--cable", action="store_true")
+ap.add_argument("--history", action="store_true")
 args = ap.parse_args()
 E0, ALPHA = -1e-3, 0.1
 
@@ -191,7 +197,66 @@ def measure_cable(name, mesh):
     torch.cuda.empty_cache()
 
 
-run = measure_cable if args.cable else measure
+def measure_history(name, mesh):
+    nodes, el, loads, fixed = mesh[:4]
+    model = FEMModel(nodes=nodes, elements=el, material=Material(2000.0, 0.5, 1.0), loads=1e-3 * loads, fixed_dofs=fixed,
+                     dimension=2)
+    nd, ne, K = model.ndof, model.nelm, args.steps
+    mass = lumped_mass(model)
+    e0_np = np.full(ne, E0)
+    dt = 0.5 * 2.0 / omega_bound(model, np.zeros(ne), e0_np, mass)
+    n_samples = K * (2 * args.rounds + 2) + 2           # warm-up and rounds, eager and graph, on one clock
+    t = np.arange(n_samples) * dt
+    lam, sup = 1.0 + 0.1 * np.sin(3.0 * t), np.sin(5.0 * t)
+    amp = np.zeros(nd)
+    amp[np.asarray(fixed, dtype=np.int64)] = 1e-4
+    runs = {"bar": {}, "load": dict(load_samples=lam), "support": dict(support=(amp, sup)),
+            "both": dict(load_samples=lam, support=(amp, sup))}
+    engines = {k: HipEngine(model) for k in runs}           # a run's state lives on its engine
+    dev = engines["bar"].device
+    minv = torch.from_numpy(np.repeat(1.0 / mass, 2)).to(dev)
+    zero = torch.zeros(nd, dtype=torch.float64, device=dev)
+    for k, hist in runs.items():
+        engines[k].dyn_begin(zero, zero, minv, dt, ALPHA, 1.0, 1.0, 0.0, None, torch.from_numpy(e0_np).to(dev), start=False, **hist)
+    variants = {}
+    for k in runs:
+        variants[k + "_eager"] = lambda k=k: engines[k].dyn_steps(K, use_graph=False)
+        variants[k + "_graph"] = lambda k=k: engines[k].dyn_steps(K, use_graph=True)
+    for fn in variants.values():                    # warm-up: every variant once (the graphs are captured here)
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for k, fn in variants.items():
+            eng = engines[k.split("_")[0]]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with eng.on_stream():
+                a.record(eng.stream)
+            fn()
+            with eng.on_stream():
+                b.record(eng.stream)
+            torch.cuda.synchronize()
+            times[k].append(1e3 * a.elapsed_time(b) / K)
+    row = {"mesh": name, "nodes": model.nnode, "elements": ne, "fixed_dofs": int(len(fixed)), "steps_per_region": K,
+           "rounds": args.rounds, "dt": dt, "samples": n_samples}
+    for k, eng in engines.items():
+        u, _, n = eng.dyn_state()
+        assert bool(torch.isfinite(u).all()) and n == n_samples - 2
+        row[k + "_max_abs_u"] = float(u.abs().max())
+    for k, t_us in times.items():
+        row[k + "_us"] = {"median": float(np.median(t_us)), "min": float(np.min(t_us)), "max": float(np.max(t_us))}
+    med = lambda k: row[k + "_us"]["median"]
+    for k in ("load", "support", "both"):
+        row[k + "_over_bar_eager"] = med(k + "_eager") / med("bar_eager")
+        row[k + "_over_bar_graph"] = med(k + "_graph") / med("bar_graph")
+    print(json.dumps(row), flush=True)
+    for eng in engines.values():
+        eng._drop_dyn_graphs()
+    del engines
+    torch.cuda.empty_cache()
+
+
+run = measure_cable if args.cable else measure_history if args.history else measure
 for n in args.chains:
     run(f"chain_{n}", chain_mesh(n))
 for n in args.warren:

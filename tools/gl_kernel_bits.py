@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """The bits of every Green-Lagrange kernel of pf_nl.hip (and of kt_diag and one tangent CG solve) on fixed seeded inputs, the
 explicit step and its energies last, after every other line (bars, then tension-only elements; --bars leaves the tension-only
-lines out, for a build from before they existed).
+lines out, for a build from before they existed), and behind them the step under load and support-motion histories
+(--no-history leaves those out, for a build from before they existed).
 
-    gl_kernel_bits.py [--bars]
+    gl_kernel_bits.py [--bars] [--no-history]
 
 One line per engine call: mesh, call, variant, sha256 of the raw output bytes.  Two builds of the library compute the same
 bits exactly when a run of this file in a fresh process prints the same lines for both (profiles/r14_gl_once_compare.txt).
@@ -41,6 +42,7 @@ def meshes():
 
 def main():
     late = []                                   # the explicit dynamics' lines: printed after every mesh's other lines
+    last = []                                   # the time histories' lines: printed after those
     for name, model in meshes():
         eng = HipEngine(model)
         ne, n = eng.plan.n_elems, eng.plan.n_dofs
@@ -108,7 +110,24 @@ def main():
                 show("dyn_energy", " ".join(x for x in (tag, variant) if x), torch.tensor(eng.dyn_energy(), dtype=torch.float64), late)
                 if more:
                     late.append(f"{name} dyn_slack_count [{' '.join(x for x in (tag, variant) if x)}] {eng.dyn_slack_count()}")
-    print("\n".join(late), flush=True)
+        if "--no-history" in sys.argv[1:] or "--bars" in sys.argv[1:]:
+            continue
+        # the same 33 steps under seeded histories of 20 samples (the last steps hold the last one): a load history, a
+        # support history (amplitudes on every other fixed dof), both; bars and tension-only elements, eager and as a graph
+        lam, sup = rng.uniform(0.25, 1.5, 20), rng.standard_normal(20)
+        amp = np.zeros(n)
+        amp[np.asarray(model.fixed_dofs, dtype=np.int64)[::2]] = 0.01
+        for tag, more in (("", {}), ("cable", dict(cable=cable))):
+            for variant, hist in (("load", dict(load_samples=lam)), ("support", dict(support=(amp, sup))),
+                                  ("load support", dict(load_samples=lam, support=(amp, sup)))):
+                for graph in (False, True):
+                    eng.dyn_begin(u_large, v0, minv, 1e-3, 0.5, 0.25, 1.5, 0.02, ea=ea, e0=e0, start=True, **hist, **more)
+                    eng.dyn_steps(32, use_graph=graph)
+                    label = " ".join(x for x in (tag, "history", variant, "graph" if graph else "eager") if x)
+                    uu, vv, _ = eng.dyn_state()
+                    show("dyn_steps.u", label, uu, last)
+                    show("dyn_steps.v", label, vv, last)
+    print("\n".join(late + last), flush=True)
 
 
 if __name__ == "__main__":
