@@ -259,6 +259,15 @@ int pf_graph_form_info(const pf_problem* p);
  * together.  Eager launches and every other graph form run the full forward.  pf_graph_form_info is not affected.
  * Additive: PF_ABI_VERSION stays 9. */
 int pf_graph_light_forward(const pf_problem* p);
+/* Do the node tasks of this problem's iteration graph address by node id?  1 / 0, or PF_ERR_ARG.  1: the graph runs its path
+ * form (PF_GRAPH_FORM_FOLDED_RESIDUAL) AND the node ids follow the path, conn[2e] == e and conn[2e+1] == e + 1 for every
+ * element (a bar meshed from one end to the other, a synthetic chain).  The displacement update inside the graph's forward
+ * launch then reads the records of elements n-1 and n and g_f at nodes n-1, n, n+1 for node n instead of walking adj_ptr,
+ * adj and adj_other: one round trip through memory instead of three, the adjacency is not read.  Same partition, same
+ * order of the sums, same bits, the u-norm monitor included.  A path with other node ids (reversed, shuffled) keeps the
+ * gather; so do eager launches, pf_graph_tail and every other graph form.  Decided by the same device pass as
+ * pf_graph_form_info.  pf_graph_form_info and pf_graph_light_forward are not affected.  Additive: PF_ABI_VERSION stays 9. */
+int pf_graph_ordered_path(const pf_problem* p);
 
 /* ---- building blocks (each replaces the cited reference lines) ------------------------ */
 /* torch-layout theta -> padded image (no reference analogue; internal layout change) */

@@ -147,6 +147,7 @@ SYMBOLS = {
     "pf_fusion_info": (C.c_int, [_PP]),
     "pf_graph_form_info": (C.c_int, [_PP]),
     "pf_graph_light_forward": (C.c_int, [_PP]),
+    "pf_graph_ordered_path": (C.c_int, [_PP]),
     "pf_pack_theta": (C.c_int, [_PP, C.c_void_p]),
     "pf_net_forward": (C.c_int, [_PP, C.c_int, C.c_void_p]),
     "pf_net_forward_all": (C.c_int, [_PP, C.c_void_p]),

@@ -548,7 +548,10 @@ static bool pad_index_is_canonical(const pf_problem* p) {
 // graph (a solve captures up to three), on the null stream — the mesh arrays are uploaded long before, and the synchronous
 // copy orders the answer.  A failed allocation, launch or copy answers "not a path": the graph then keeps its residual launch,
 // which is always correct; pf_last_error says so and pf_graph_form_info shows the form that was chosen.
-static bool mesh_is_path(const pf_problem* p) {
+// *ordered (where asked for): do the node ids follow the path as well, element e joining node e to node e + 1?  The same
+// kernel, the same copy: the second bit of the flag.
+static bool mesh_is_path(const pf_problem* p, bool* ordered = nullptr) {
+  if (ordered) *ordered = false;
   const pf_mesh& M = p->mesh;
   if (M.n_elems < 1 || M.n_nodes != M.n_elems + 1 || !M.conn || !M.adj_ptr || !M.adj || !M.dof_flags) return false;
   int* bad = nullptr;
@@ -561,7 +564,8 @@ static bool mesh_is_path(const pf_problem* p) {
             hipMemcpy(&h, bad, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
   (void)hipFree(bad);
   if (!ok) pf_set_error("path check of the mesh failed (HIP error): the iteration graph keeps its residual launch");
-  return ok && h == 0;
+  if (ordered) *ordered = ok && h == 0;
+  return ok && (h & 1) == 0;
 }
 
 // Can the iteration graph drop the residual launch (the PATH form)?  Wherever the forward launch carries the displacement
@@ -572,7 +576,10 @@ static bool can_fold_residual_static(const pf_problem* p) {
   return p->prop_double != 0 && p->elem_k != nullptr && p->u_alt != nullptr && can_fuse_gradu(p) && can_fuse_backward(p) &&
          can_fuse_theta_update(p) && pf_n32_bwd2_has_path(p) && p->n_iface == 0 && p->mesh.dim == p->net[0].in_dim - 1;
 }
-static bool can_fold_residual(const pf_problem* p) { return can_fold_residual_static(p) && mesh_is_path(p); }
+static bool can_fold_residual(const pf_problem* p, bool* ordered = nullptr) {
+  if (ordered) *ordered = false;
+  return can_fold_residual_static(p) && mesh_is_path(p, ordered);
+}
 // Does the path form run with the LIGHT forward (pf_net32.hip: k_net32_forward2 / backward_phase, LIGHT)?  Then the forward
 // launch evaluates the E net only for the elements at task edges and the backward launch, which recomputes the E net's hidden
 // layers anyway, stores prop_e and the other records.  forward(i) and backward(i) always complete together (the stop flag is
@@ -610,7 +617,7 @@ static pf_problem graph_iteration_view(const pf_problem& p, int i) {
 // state-changing step — the updates inside forward(i+1), or the replay's stand-alone tail — still starts behind stage 1(i),
 // reads the flag first and returns at once.
 static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_capture& c, bool calc_index = false,
-                                    bool head_cont = false, bool no_tail = false, bool fold = false) {
+                                    bool head_cont = false, bool no_tail = false, bool fold = false, bool ordered = false) {
   hipStream_t s = c.s;
   if (!(p->net[0].enabled || p->net[1].enabled)) {
     for (int i = 0; i < iters; ++i) {
@@ -642,6 +649,7 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
     if (fuse_gu && carries) {
       fo.gu_nb = pf_node_blocks(q.mesh.n_nodes);
       fo.gu_k = p->elem_k + (((i - 1) & 1) ? k_half : 0);   // the records iteration i-1 wrote (the other half)
+      fo.gu_ordered = fold && ordered ? 1 : 0;              // (the path form with node ids in path order: no adjacency)
     }
     // (DAG without the second property half: the forwards wait for gradu(i-1), an 11 us hole in the kernel trace)
     if (dag && i > 0 && p->prop_double == 0 && hipStreamWaitEvent(s, ep[1], 0) != hipSuccess)
@@ -697,6 +705,12 @@ int pf_graph_light_forward(const pf_problem* p) {
   return can_light_forward(p, can_fold_residual(p)) ? 1 : 0;
 }
 
+int pf_graph_ordered_path(const pf_problem* p) {
+  if (check_problem(p) != PF_OK) return PF_ERR_ARG;
+  bool ordered = false;
+  return can_fold_residual(p, &ordered) && ordered ? 1 : 0;
+}
+
 int pf_graph_create(const pf_problem* p, int iters_per_graph, void* stream, void** graph_out) {
   return pf_graph_create_ex(p, iters_per_graph, 0, stream, graph_out);
 }
@@ -713,10 +727,11 @@ int pf_graph_create_ex(const pf_problem* p, int iters_per_graph, int flags, void
   if ((flags & (PF_GRAPH_CONT_HEAD | PF_GRAPH_NO_TAIL)) && !can_chain_replays(p, iters_per_graph))
     return fail(PF_ERR_UNSUPPORTED, "pf_graph_create_ex: replays of this problem's graph cannot hand over their tail");
   const bool calc_index = can_fuse_theta_update(p) && pad_index_is_canonical(p);
-  const bool fold = can_fold_residual(p);
+  bool ordered = false;
+  const bool fold = can_fold_residual(p, &ordered);
   const bool head = (flags & PF_GRAPH_CONT_HEAD) != 0, no_tail = (flags & PF_GRAPH_NO_TAIL) != 0;
   return capture_graph((hipStream_t)stream, PF_CAP_EV * iters_per_graph, hipStreamCaptureModeThreadLocal, graph_out,
-                       [&](pf_capture& cap) { return enqueue_graph_iterations(p, iters_per_graph, cap, calc_index, head, no_tail, fold); });
+                       [&](pf_capture& cap) { return enqueue_graph_iterations(p, iters_per_graph, cap, calc_index, head, no_tail, fold, ordered); });
 }
 
 // the pending tail of a PF_GRAPH_NO_TAIL replay: what the last iteration of a plain replay ends with

@@ -411,12 +411,15 @@ PF_DECL_NET_LAUNCHERS(32)
 //                 that pf_problem.pad_index holds exactly that) instead of from the table
 //   gu_nb > 0     the displacement update of the previous iteration (pf_node.h) reading the stiffness records gu_k; gu_nb =
 //                 entries of the u-norm partial sums the bookkeeping reads
+//   gu_ordered    ... on an ordered path, with every operand address of a node task formed from the node id
 struct pf_fwd2_opts {
   int s2_half = -1;
   bool calc_index = false;
   int gu_nb = 0;
   const float* gu_k = nullptr;
   int light = 0;      // the light form (k_net32_forward2, LIGHT): the path backward that follows forms E and the records
+  int gu_ordered = 0; // with gu_nb: the mesh is a path whose node ids follow it (pf_api.hip: mesh_is_path), so the node tasks
+                      // address by node id instead of through the adjacency (pf_node.h: node_gradu_task_path)
 };
 // launchers of pf_net32.hip, one translation unit per register bucket (-DPF_NR=<nr>): nets of width <= 2*nr
 #define PF_DECL_NET32_LAUNCHERS(NRB)                                                       \

@@ -353,11 +353,14 @@ __global__ __launch_bounds__(PF_NODE_THREADS) void k_theta_stage1_path(pf_proble
 // One thread per element checks the CSR rows of its two nodes; any violation raises *bad.  Together with
 // n_nodes == n_elems + 1 (host) that is the whole property: the i nodes of the elements and the last j node are then
 // n_elems + 1 different nodes.  A dof that is shared between ranks disqualifies the mesh as well.
+// The same pass answers whether the node ids FOLLOW the path (element e joins node e to node e + 1: the ORDERED path, whose
+// node tasks need no adjacency, pf_node.h: node_gradu_task_path).  *bad: bit 0 = not a path, bit 1 = ids not in path order.
 __global__ __launch_bounds__(256) void k_path_check(pf_mesh M, int* bad) {
   const int n = M.n_elems;
-  bool wrong = false;
+  bool wrong = false, unordered = false;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
     const int i = M.conn[2 * e], j = M.conn[2 * e + 1];
+    unordered |= i != e || j != e + 1;
     if (i < 0 || i >= M.n_nodes || j < 0 || j >= M.n_nodes) { wrong = true; continue; }
     const int bi = M.adj_ptr[i], di = M.adj_ptr[i + 1] - bi;
     const int bj = M.adj_ptr[j], dj = M.adj_ptr[j + 1] - bj;
@@ -368,7 +371,8 @@ __global__ __launch_bounds__(256) void k_path_check(pf_mesh M, int* bad) {
     for (int c = 0; c < M.dim; ++c)
       wrong |= ((M.dof_flags[i * M.dim + c] | M.dof_flags[j * M.dim + c]) & (PF_DOF_SHARED | PF_DOF_GHOST)) != 0;
   }
-  if (wrong) *bad = 1;
+  const int bits = (wrong ? 1 : 0) | (unordered ? 2 : 0);
+  if (bits) atomicOr(bad, bits);
 }
 
 // MFMA32 engine: rebuild the split-f16 operand images of the enabled nets from `th` (the flat active
@@ -954,7 +958,8 @@ int pf_launch_theta_stage1_path(const pf_problem* p, hipStream_t s, int fin_prev
   return PF_CHECK_LAUNCH();
 }
 
-// *bad (device, zeroed by the caller) becomes 1 unless the mesh is an open path in element order (k_path_check)
+// *bad (device, zeroed by the caller): bit 0 unless the mesh is an open path in element order, bit 1 unless its node ids
+// follow the path (k_path_check)
 int pf_launch_path_check(const pf_problem* p, int* bad, hipStream_t s) {
   int nb = (p->mesh.n_elems + 255) / 256;
   if (nb > 1024) nb = 1024;

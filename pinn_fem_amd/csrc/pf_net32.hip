@@ -1033,7 +1033,9 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward(pf_problem P, int 
 // iteration on MI355X) and no second displacement vector.  Each task's sum of u_free^2 lands in LDS at the task's index
 // and the block adds them in index order: the monitor does not depend on which wave drew what.  The block's sum goes to
 // partials[PF_PART_U2 + block]; entries up to gu_nb (what the bookkeeping sums: pf_node_blocks) are zeroed.  gu_k: the
-// stiffness records of the previous iteration (the half this launch does NOT write).
+// stiffness records of the previous iteration (the half this launch does NOT write).  gu_ordered: the mesh is a path whose
+// node ids follow it, and a node task forms every address from the node id: one round trip, no adjacency (pf_node.h:
+// node_gradu_task_path); same partition, same queue, same s_u2 slots, same bits.
 // LIGHT (the iteration graph's path form with the light forward: pf_api.hip, can_light_forward): the backward launch that
 // follows recomputes the E net's hidden layers anyway and rebuilds every element's stiffness record itself, so it also forms
 // E and stores prop_e and the records (backward_phase, LIGHT).  What it needs from this launch is A for every element and the
@@ -1043,9 +1045,18 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward(pf_problem P, int 
 // tasks, which follow the block's regular tasks in the same queue (task ids t1 .. t1e-1), run today's full body and store the
 // record alone.  No location is written twice in an iteration: prop_a here, prop_e and every other record in the backward.
 #define PF_GU_MAX_TASKS 1024
+// k_net32_forward2's arguments as they lie in the kernarg segment (in order, each at its natural alignment): a node task
+// reads gu_ordered from there where it starts, like its view of P (kernarg_problem), instead of holding it in a scalar
+// register over the element loop
+struct fwd2_kernargs {
+  pf_problem P;
+  int dbg_arg, s2_half, gu_nb;
+  const float* gu_k;
+  int gu_ordered;
+};
 template <int NRE, int NRA, int L, int IN, bool LIGHT = false>
 __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int dbg_arg, int s2_half, int gu_nb,
-                                                               const float* __restrict__ gu_k) {
+                                                               const float* __restrict__ gu_k, int gu_ordered) {
   using EE = Eng<NRE>;
   using EA = Eng<NRA>;
   const bool calc_index = s2_half >= 2;       // (s2_half + 2: padded-image indices by arithmetic, pf_fwd2_opts.calc_index)
@@ -1117,9 +1128,20 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     // kernarg segment), behind an opaque move: left to the compiler, every pointer is loaded once at the top of the launch
     // and the element loop spills scalar registers (75 against 7 without the node tasks)
     const __attribute__((address_space(4))) pf_problem* pk = kernarg_problem();
-    const NodeView NV = node_view_from(pk);
     const GraduConsts GK = gradu_consts_from(pk);
-    float su = node_gradu_task<IN - 1, PF_GU_M>(NV, gu_k, GK, (nt0 + k) * GUN, lane);
+    float su;
+    // (wave-uniform: a kernel argument.  Only pairs whose fused backward has the path form are ever launched with it:
+    //  pf_net32.h, pf_n32_bwd2_has_path; the others do not carry the branch)
+    bool ordered = false;
+    if constexpr (EE::COMPACT && EA::COMPACT)
+      ordered = reinterpret_cast<const __attribute__((address_space(4))) fwd2_kernargs*>(pk)->gu_ordered != 0;
+    if (ordered) {              // an ordered path: every address from the node id
+      const NodeView NV = node_view_from<false>(pk);
+      su = node_gradu_task_path<IN - 1, PF_GU_M>(NV, gu_k, GK, (nt0 + k) * GUN, lane);
+    } else {
+      const NodeView NV = node_view_from(pk);
+      su = node_gradu_task<IN - 1, PF_GU_M>(NV, gu_k, GK, (nt0 + k) * GUN, lane);
+    }
     su = pf_wave_sum(su);
     if (lane == 0) s_u2[k] = su;
     return true;
@@ -1249,9 +1271,15 @@ __global__ __launch_bounds__(FW_THREADS) void k_net32_forward2(pf_problem P, int
     float* red = reinterpret_cast<float*>(s_u2 + PF_GU_MAX_TASKS - 16);
     __syncthreads();
     su = pf_block_sum(su, red);
-    if (threadIdx.x == 0) P.partials[PF_PART_U2 + blockIdx.x] = su;
-    for (int j = (int)blockIdx.x + (int)gridDim.x + (int)threadIdx.x * (int)gridDim.x; j < gu_nb; j += (int)blockDim.x * (int)gridDim.x)
-      P.partials[PF_PART_U2 + j] = 0.f;
+    // (what the write-out needs of the arguments is read HERE, like a node task's view: held from the top of the launch it
+    //  cost scalar registers over the element loop)
+    const __attribute__((address_space(4))) fwd2_kernargs* ke =
+        reinterpret_cast<const __attribute__((address_space(4))) fwd2_kernargs*>(kernarg_problem());
+    float* __restrict__ const partials = ke->P.partials;
+    const int n_u2 = ke->gu_nb;
+    if (threadIdx.x == 0) partials[PF_PART_U2 + blockIdx.x] = su;
+    for (int j = (int)blockIdx.x + (int)gridDim.x + (int)threadIdx.x * (int)gridDim.x; j < n_u2; j += (int)blockDim.x * (int)gridDim.x)
+      partials[PF_PART_U2 + j] = 0.f;
   }
 }
 
@@ -1846,13 +1874,13 @@ int launch_fwd2_t(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o) {
   if (o.light) {
     if constexpr (n32_has_light<NRE, NRA, L, IN>()) {
       if (!p->elem_k) { pf_set_error("fused forward, light form: elem_k is needed"); return PF_ERR_ARG; }
-      hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN, true>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_arg, gu_nb, o.gu_k);
+      hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN, true>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_arg, gu_nb, o.gu_k, o.gu_ordered);
     } else {
       pf_set_error("fused forward: no light form for these nets");
       return PF_ERR_UNSUPPORTED;
     }
   } else {
-    hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_arg, gu_nb, o.gu_k);
+    hipLaunchKernelGGL((k_net32_forward2<NRE, NRA, L, IN>), dim3(nb), dim3(FW_THREADS), lds, s, *p, dbg, s2_arg, gu_nb, o.gu_k, o.gu_ordered);
   }
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_HIP;
 }

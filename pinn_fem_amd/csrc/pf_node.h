@@ -37,12 +37,13 @@ struct NodeView {
   float *u, *m_u, *v_u, *grad_u;
   int n_nodes, use_data, fe_mode;
 };
-template <class PP>
+// ADJ = false: the view of a task that addresses by node id (node_gradu_task_path): the adjacency pointers are not loaded
+template <bool ADJ = true, class PP>
 __device__ __forceinline__ NodeView node_view_from(PP p) {
   NodeView V;
-  V.adj_ptr = p->mesh.adj_ptr;
-  V.adj = p->mesh.adj;
-  V.adj_other = p->adj_other;
+  V.adj_ptr = ADJ ? p->mesh.adj_ptr : nullptr;
+  V.adj = ADJ ? p->mesh.adj : nullptr;
+  V.adj_other = ADJ ? p->adj_other : nullptr;
   V.dof_flags = p->mesh.dof_flags;
   V.meas_val = p->mesh.meas_val;
   V.g_f = p->g_f;
@@ -75,6 +76,43 @@ __device__ __forceinline__ void dof_adam_u(const GraduConsts& K, float gu, float
   v = v + (K.b2w * gu) * gu;                      // addcmul_
   const float denom = sqrtf(v) / K.bc2s + K.eps;
   uo = uo + (-K.step_size) * (m / denom);         // addcdiv_
+}
+
+// ---- what a node task does behind its gather: dL/du, Adam, the clamp and the stores of its M x 64 nodes -------------------
+// One copy for both node tasks below (they differ only in how they find the operands of acc = (K^T g_f)[node]).
+// node: clamped into the mesh, ok: the lane's node exists (else nothing is stored or summed).  Returns the lane's sum of
+// u_free^2 over its nodes, m ascending.
+template <int DIM, int M>
+__device__ __forceinline__ float node_task_update(const NodeView& P, const GraduConsts& K, const int (&node)[M],
+                                                  const bool (&ok)[M], const unsigned (&fl)[M][2], const float (&acc)[M][2],
+                                                  const float (&meas)[M][2], const float (&uo)[M][2],
+                                                  const float (&mo)[M][2], const float (&vo)[M][2]) {
+  float sum_u2 = 0.f;
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const int dof = node[m] * DIM + c;
+      const unsigned f = fl[m][c];
+      const float gu = dof_grad_u(K, P.use_data && (f & PF_DOF_MEASURED), acc[m][c], meas[m][c], uo[m][c]);
+      float un = uo[m][c], mn = mo[m][c], vn = vo[m][c];
+      dof_adam_u(K, gu, un, mn, vn);
+      const bool fixed = (f & PF_DOF_FIXED) != 0;
+      if (ok[m]) {
+        if (P.grad_u) P.grad_u[dof] = gu;
+        if (fixed) {
+          if (uo[m][c] != 0.f) P.u[dof] = 0.f;      // solver.py:297-298
+        } else {
+          P.m_u[dof] = mn;
+          P.v_u[dof] = vn;
+          P.u[dof] = un;
+        }
+      }
+      { PF_NO_CONTRACT
+        if (ok[m] && !fixed) sum_u2 += un * un; }
+    }
+  }
+  return sum_u2;
 }
 
 // ---- M x 64 nodes per wave, every level of the gather in flight for all of them together -----------------------------
@@ -171,32 +209,68 @@ __device__ __forceinline__ float node_gradu_task(const NodeView& P, const float*
       for (int c = 0; c < DIM; ++c)
         asm volatile("" : "+v"(uo[m][c]), "+v"(meas[m][c]), "+v"(mo[m][c]), "+v"(vo[m][c]));
   }
-  float sum_u2 = 0.f;
+  return node_task_update<DIM, M>(P, K, node, ok, fl, acc, meas, uo, mo, vo);
+}
+
+// ---- the same task on an ORDERED PATH: every address from the node id -------------------------------------------------------
+// Where the mesh is a path (pf_api.hip: mesh_is_path) AND its node ids follow it, element e joining node e to node e + 1
+// (the synthetic chains, a bar meshed from one end to the other), the adjacency the task above chases is implied: node n
+// touches element n-1 at its j end and element n at its i end, and its far nodes are n-1 and n+1.  So the three dependent
+// round trips are ONE: the records of n-1 and n, g_f at n-1, n, n+1 and the node's own values all leave together, and the 20
+// bytes per node of adj_ptr / adj / adj_other are not read.  Indices past the path's ends are clamped to valid addresses
+// and their terms dropped by a select, as the gather drops a missing incidence: the end nodes get the bits of their single
+// incidence.  Same partition, same ke_rows_times, same 0 + fe(n-1) + fe(n) sequence, same node_task_update: same bits.
+// The neighbours' g_f come from loads, not from the lanes beside: they hit the lines the own values bring in, and a lane
+// shift would still need the edge lanes' loads.
+template <int DIM, int M>
+__device__ __forceinline__ float node_gradu_task_path(const NodeView& P, const float* __restrict__ elem_k,
+                                                      const GraduConsts& K, int node0, int lane) {
+  const int nn = P.n_nodes, ne = nn - 1;             // (a path: n_nodes == n_elems + 1, n_elems >= 1)
+  int node[M];
+  bool ok[M];
+  float vs[M][2], wb[M][2], wa[M][2], acc[M][2], uo[M][2], meas[M][2], mo[M][2], vo[M][2];
+  unsigned fl[M][2];
+  ElemK kb[M], ka[M];
+  const float* __restrict__ mvals = P.use_data ? P.meas_val : P.u;     // (a select, not a branch: never read without use_data)
 #pragma unroll
   for (int m = 0; m < M; ++m) {
+    const int n_ = node0 + m * 64 + lane;
+    ok[m] = n_ < nn;
+    node[m] = ok[m] ? n_ : nn - 1;
+    const int below = max(node[m] - 1, 0), above = min(node[m] + 1, nn - 1);
+    kb[m] = load_k_record<DIM>(elem_k, below);                 // element n-1
+    ka[m] = load_k_record<DIM>(elem_k, min(node[m], ne - 1));  // element n
+    load_vec<DIM>(P.g_f, below, wb[m]);
+    load_vec<DIM>(P.g_f, node[m], vs[m]);
+    load_vec<DIM>(P.g_f, above, wa[m]);
+    load_vec<DIM>(P.u, node[m], uo[m]);
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
-      const int dof = node[m] * DIM + c;
-      const unsigned f = fl[m][c];
-      const float gu = dof_grad_u(K, P.use_data && (f & PF_DOF_MEASURED), acc[m][c], meas[m][c], uo[m][c]);
-      float un = uo[m][c], mn = mo[m][c], vn = vo[m][c];
-      dof_adam_u(K, gu, un, mn, vn);
-      const bool fixed = (f & PF_DOF_FIXED) != 0;
-      if (ok[m]) {
-        if (P.grad_u) P.grad_u[dof] = gu;
-        if (fixed) {
-          if (uo[m][c] != 0.f) P.u[dof] = 0.f;      // solver.py:297-298
-        } else {
-          P.m_u[dof] = mn;
-          P.v_u[dof] = vn;
-          P.u[dof] = un;
-        }
-      }
-      { PF_NO_CONTRACT
-        if (ok[m] && !fixed) sum_u2 += un * un; }
+      fl[m][c] = P.dof_flags[node[m] * DIM + c];
+      meas[m][c] = mvals[node[m] * DIM + c];
+      mo[m][c] = P.m_u[node[m] * DIM + c];
+      vo[m][c] = P.v_u[node[m] * DIM + c];
+      acc[m][c] = 0.f;
     }
   }
-  return sum_u2;
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const bool has_b = node[m] > 0, has_a = node[m] < ne;
+    float fe[2];
+    ke_rows_times<DIM>(kb[m], 1, wb[m], vs[m], fe, P.fe_mode);
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const float t = acc[m][c] + fe[c];
+      acc[m][c] = has_b ? t : acc[m][c];
+    }
+    ke_rows_times<DIM>(ka[m], 0, vs[m], wa[m], fe, P.fe_mode);
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const float t = acc[m][c] + fe[c];
+      acc[m][c] = has_a ? t : acc[m][c];
+    }
+  }
+  return node_task_update<DIM, M>(P, K, node, ok, fl, acc, meas, uo, mo, vo);
 }
 
 // ---- the same gather for M nodes per THREAD (node kernels): (K(theta) v)[node] over the incident elements of each node,

@@ -353,6 +353,13 @@ class HipEngine:
         the device."""
         return int(self.lib.pf_graph_light_forward(self._ref()))
 
+    @_on_engine_stream
+    def graph_ordered_path(self) -> int:
+        """1 where the iteration graph runs its path form on a mesh whose node ids follow the path (element e joins node e
+        to node e + 1), so that its node tasks address by node id instead of through the adjacency, else 0.  Inspects the
+        mesh on the device."""
+        return int(self.lib.pf_graph_ordered_path(self._ref()))
+
     # ---- solve_gd support ------------------------------------------------------------------------
     @_on_engine_stream
     def begin(self, u_initial, lam, config, max_iter: Optional[int] = None, want_history=True):
