@@ -106,16 +106,16 @@ static int check_problem(const pf_problem* p) {
   }                                                               \
   return fail(PF_ERR_UNSUPPORTED, "net width outside 1..32");
 
-// MFMA32 engine: one translation unit per register bucket
-#define PF_NR_SWITCH(PREFIX)                                      \
-  switch (pf_net32_bucket(p->net[which].width)) {                 \
-    case 2: return PREFIX##2(p, which, s);                        \
-    case 4: return PREFIX##4(p, which, s);                        \
-    case 6: return PREFIX##6(p, which, s);                        \
-    case 8: return PREFIX##8(p, which, s);                        \
-    case 10: return PREFIX##10(p, which, s);                      \
-    case 12: return PREFIX##12(p, which, s);                      \
-    case 15: return PREFIX##15(p, which, s);                      \
+// MFMA32 engine: one translation unit per register bucket; the width of net NET picks it, the launcher gets the rest
+#define PF_NR_SWITCH(PREFIX, NET, ...)                            \
+  switch (pf_net32_bucket(p->net[NET].width)) {                   \
+    case 2: return PREFIX##2(__VA_ARGS__);                        \
+    case 4: return PREFIX##4(__VA_ARGS__);                        \
+    case 6: return PREFIX##6(__VA_ARGS__);                        \
+    case 8: return PREFIX##8(__VA_ARGS__);                        \
+    case 10: return PREFIX##10(__VA_ARGS__);                      \
+    case 12: return PREFIX##12(__VA_ARGS__);                      \
+    case 15: return PREFIX##15(__VA_ARGS__);                      \
   }                                                               \
   return fail(PF_ERR_UNSUPPORTED, "MFMA32 engine: net width outside 1..30");
 
@@ -128,20 +128,9 @@ static int net_forward(const pf_problem* p, int which, hipStream_t s, int write_
   q.elem_k = nullptr;
   return net_forward_impl(&q, which, s, s2_half);
 }
-#define PF_NR_SWITCH_FWD(PREFIX)                                  \
-  switch (pf_net32_bucket(p->net[which].width)) {                 \
-    case 2: return PREFIX##2(p, which, s, s2_half);               \
-    case 4: return PREFIX##4(p, which, s, s2_half);               \
-    case 6: return PREFIX##6(p, which, s, s2_half);               \
-    case 8: return PREFIX##8(p, which, s, s2_half);               \
-    case 10: return PREFIX##10(p, which, s, s2_half);             \
-    case 12: return PREFIX##12(p, which, s, s2_half);             \
-    case 15: return PREFIX##15(p, which, s, s2_half);             \
-  }                                                               \
-  return fail(PF_ERR_UNSUPPORTED, "MFMA32 engine: net width outside 1..30");
 static int net_forward_impl(const pf_problem* p, int which, hipStream_t s, int s2_half) {
-  if (p->wg_mode == PF_WG_MFMA32 && p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH_FWD(pf_launch_net32b_forward_) }
-  if (p->wg_mode == PF_WG_MFMA32) { PF_NR_SWITCH_FWD(pf_launch_net32_forward_) }
+  if (p->wg_mode == PF_WG_MFMA32 && p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH(pf_launch_net32b_forward_, which, p, which, s, s2_half) }
+  if (p->wg_mode == PF_WG_MFMA32) { PF_NR_SWITCH(pf_launch_net32_forward_, which, p, which, s, s2_half) }
   if (s2_half >= 0) return fail(PF_ERR_ARG, "the fused parameter update exists in the MFMA32 engine only");
   if (p->wg_mode == PF_WG_MFMA44) { PF_WIDTH_SWITCH(pf_launch_net44_forward_) }
   PF_WIDTH_SWITCH(pf_launch_net_forward_)
@@ -153,24 +142,13 @@ static bool can_fuse_forward(const pf_problem* p) {
   return p->wg_mode == PF_WG_MFMA32 && p->net[0].enabled && p->net[1].enabled &&
          p->net[0].n_hidden == p->net[1].n_hidden && p->net[0].in_dim == p->net[1].in_dim;
 }
-#define PF_NR0_SWITCH(PREFIX)                                     \
-  switch (pf_net32_bucket(p->net[0].width)) {                     \
-    case 2: return PREFIX##2(p, s, o);  \
-    case 4: return PREFIX##4(p, s, o);  \
-    case 6: return PREFIX##6(p, s, o);  \
-    case 8: return PREFIX##8(p, s, o);  \
-    case 10: return PREFIX##10(p, s, o);  \
-    case 12: return PREFIX##12(p, s, o);  \
-    case 15: return PREFIX##15(p, s, o);  \
-  }                                                               \
-  return fail(PF_ERR_UNSUPPORTED, "MFMA32 engine: net width outside 1..30");
 static int net_forward2(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o = pf_fwd2_opts()) {
-  if (p->mlp_dtype == PF_MLP_BF16) { PF_NR0_SWITCH(pf_launch_net32b_forward2_) }
-  PF_NR0_SWITCH(pf_launch_net32_forward2_)
+  if (p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH(pf_launch_net32b_forward2_, 0, p, s, o) }
+  PF_NR_SWITCH(pf_launch_net32_forward2_, 0, p, s, o)
 }
 // the forward pass of every enabled net: the properties and, with the MFMA32 engine, the stiffness records.
-// s2_half >= 0: the FIRST launch also runs the parameter update of the previous iteration (can_fuse_theta_update)
-// o.gu_nb (only with can_fuse_gradu; fused launch only): see pf_fwd2_opts
+// s2_half >= 0: the FIRST launch also runs the parameter update of the previous iteration (graph_form.fuse_s2)
+// o.gu_nb (only with graph_form.fuse_gu; fused launch only): see pf_fwd2_opts
 static int net_forward_all(const pf_problem* p, hipStream_t s, const pf_fwd2_opts& o = pf_fwd2_opts()) {
   if (can_fuse_forward(p)) return net_forward2(p, s, o);
   int s2_half = o.s2_half >= 0 && o.calc_index ? o.s2_half + 2 : o.s2_half;      // (+ 2: see k_net32_forward)
@@ -182,23 +160,10 @@ static int net_forward_all(const pf_problem* p, hipStream_t s, const pf_fwd2_opt
     }
   return PF_OK;
 }
-// Can the iteration graph fold the parameter update of iteration t into the forward launch of t+1?  MFMA32 engine with
-// the second state half present.
-static bool can_fuse_theta_update(const pf_problem* p) {
-  return p->wg_mode == PF_WG_MFMA32 && p->theta_alt != nullptr && p->n_theta_active > 0 &&
-         (p->net[0].enabled || p->net[1].enabled);
-}
-
-// Can the iteration graph fold the displacement update (dL/du + Adam(u) + clamp) of iteration t into the fused forward
-// launch of t+1 (pf_net32.hip: k_net32_forward2, gu_nb; pf_node.h)?  The graph is then a plain chain: no side branch, no
-// fork, no join, no second displacement vector.
-static bool can_fuse_gradu(const pf_problem* p) {
-  return can_fuse_forward(p) && pf_n32_fwd2_can_update_u(p, pf_node_blocks(p->mesh.n_nodes));
-}
 
 static int net_backward(const pf_problem* p, int which, hipStream_t s) {
-  if (p->wg_mode == PF_WG_MFMA32 && p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH(pf_launch_net32b_backward_) }
-  if (p->wg_mode == PF_WG_MFMA32) { PF_NR_SWITCH(pf_launch_net32_backward_) }
+  if (p->wg_mode == PF_WG_MFMA32 && p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH(pf_launch_net32b_backward_, which, p, which, s) }
+  if (p->wg_mode == PF_WG_MFMA32) { PF_NR_SWITCH(pf_launch_net32_backward_, which, p, which, s) }
   if (p->wg_mode == PF_WG_MFMA44) { PF_WIDTH_SWITCH(pf_launch_net44_backward_) }
   PF_WIDTH_SWITCH(pf_launch_net_backward_)
 }
@@ -207,8 +172,8 @@ static int net_backward(const pf_problem* p, int which, hipStream_t s) {
 static bool fuse_gea_for(const pf_problem* p) { return p->wg_mode == PF_WG_MFMA44 || p->wg_mode == PF_WG_MFMA32; }
 // backward that also computes and stores the element adjoint g_ea
 static int net_backward_gea(const pf_problem* p, int which, hipStream_t s) {
-  if (p->wg_mode == PF_WG_MFMA32 && p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH(pf_launch_net32b_backward_gea_) }
-  if (p->wg_mode == PF_WG_MFMA32) { PF_NR_SWITCH(pf_launch_net32_backward_gea_) }
+  if (p->wg_mode == PF_WG_MFMA32 && p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH(pf_launch_net32b_backward_gea_, which, p, which, s) }
+  if (p->wg_mode == PF_WG_MFMA32) { PF_NR_SWITCH(pf_launch_net32_backward_gea_, which, p, which, s) }
   PF_WIDTH_SWITCH(pf_launch_net44_backward_gea_)
 }
 
@@ -217,21 +182,10 @@ static int net_backward_gea(const pf_problem* p, int which, hipStream_t s) {
 static bool can_fuse_backward(const pf_problem* p) {
   return can_fuse_forward(p) && p->net[0].n_hidden == 2 && fuse_gea_for(p);
 }
-// path: the launch also forms r and g_f (the iteration graph's path form: can_fold_residual)
+// path: the launch also forms r and g_f (the iteration graph's path form: graph_form.fold)
 static int net_backward2(const pf_problem* p, hipStream_t s, int path = 0) {
-#define PF_NR0_SWITCH_B(PREFIX)                                   \
-  switch (pf_net32_bucket(p->net[0].width)) {                     \
-    case 2: return PREFIX##2(p, s, path);                         \
-    case 4: return PREFIX##4(p, s, path);                         \
-    case 6: return PREFIX##6(p, s, path);                         \
-    case 8: return PREFIX##8(p, s, path);                         \
-    case 10: return PREFIX##10(p, s, path);                       \
-    case 12: return PREFIX##12(p, s, path);                       \
-    case 15: return PREFIX##15(p, s, path);                       \
-  }                                                               \
-  return fail(PF_ERR_UNSUPPORTED, "MFMA32 engine: net width outside 1..30");
-  if (p->mlp_dtype == PF_MLP_BF16) { PF_NR0_SWITCH_B(pf_launch_net32b_backward2_) }
-  PF_NR0_SWITCH_B(pf_launch_net32_backward2_)
+  if (p->mlp_dtype == PF_MLP_BF16) { PF_NR_SWITCH(pf_launch_net32b_backward2_, 0, p, s, path) }
+  PF_NR_SWITCH(pf_launch_net32_backward2_, 0, p, s, path)
 }
 
 #define PF_TRY(expr, what)                       \
@@ -261,6 +215,52 @@ static int enqueue_backwards(const pf_problem* p, hipStream_t s, hipEvent_t adj_
     if (fuse_gea && k == first && !mark()) return fail(PF_ERR_HIP, "graph edge failed");
   }
   return PF_OK;
+}
+
+// The form of a problem's iteration graph (enqueue_graph_iterations): every decision that depends neither on the replay
+// length nor on the pf_graph_create_ex flags.  pf_fusion_info, the pf_graph_* queries and the capture all read this record,
+// so what is reported is what is captured.  (Comments in the kernel sources name three of its fields by the helpers they
+// replace: can_fold_residual = fold, can_light_forward = light, can_fuse_gradu with elem_k and prop_double = fuse_gu.)
+struct graph_form {
+  bool any_net;      // a net is enabled (else the graph is the eager iteration, `iters` times)
+  bool fwd2, bwd2;   // both nets in one forward / backward launch (can_fuse_forward, can_fuse_backward)
+  bool fuse_s2;      // the forward launch of t+1 runs the parameter update of t: MFMA32 engine with the second state half
+  bool fuse_gu;      // ... and the displacement update of t (dL/du + Adam(u) + clamp; pf_net32.hip: k_net32_forward2, gu_nb;
+                     // pf_node.h): it reads the records of t = the other half, hence prop_double.  The graph is then ONE CHAIN
+  bool dag;          // else, from PF_GRAPH_DAG_MIN_ELEMS elements on: the displacement update on the side branch
+  bool u_alt;        // the second displacement vector is there (DAG: the ping-pong; PATH form: it holds r)
+  bool fold;         // the PATH form, no residual launch.  graph_form_static: everything but the mesh allows it: wherever
+                     // the forward launch carries both updates (so theta stage 1 is a launch of every iteration) and the
+                     // backward is the fused two-phase launch with the path variant, on one GPU, with u_alt free to hold r.
+                     // graph_form_probed: ... and the mesh is a path (mesh_is_path)
+  bool ordered;      // PATH form whose node ids follow the path: node tasks without the adjacency (graph_form_probed)
+  bool light;        // PATH form with the LIGHT forward (pf_net32.hip: k_net32_forward2 / backward_phase, LIGHT): the forward
+                     // launch evaluates the E net only for the elements at task edges and the backward launch, which recomputes
+                     // the E net's hidden layers anyway, stores prop_e and the other records.  forward(i) and backward(i)
+                     // always complete together (the stop flag is only raised behind backward(i), in stage 1), and every
+                     // reader of prop_e, prop_a and the records — forward(i+1)'s node tasks, the replay's tail,
+                     // pf_graph_tail, a continuation head, the results — runs behind backward(i): it sees the bytes the full
+                     // forward writes.  (static: where fold is static; probed: final)
+  bool calc_index;   // the update prologue computes the padded-image index (pad_index_is_canonical; graph_form_probed)
+  int tn_ready;      // k_theta_stage2 leaves the theta-norm monitor in the state (MFMA32 engine)
+};
+
+// The part of the record that needs no device work.  No HIP call: pf_fusion_info is answered from it outside any stream.
+static graph_form graph_form_static(const pf_problem* p) {
+  graph_form f = {};
+  f.any_net = p->net[0].enabled || p->net[1].enabled;
+  f.fwd2 = can_fuse_forward(p);
+  f.bwd2 = can_fuse_backward(p);
+  f.fuse_s2 = p->wg_mode == PF_WG_MFMA32 && p->theta_alt != nullptr && p->n_theta_active > 0 && f.any_net;
+  f.fuse_gu = p->prop_double != 0 && p->elem_k != nullptr && f.fwd2 &&
+              pf_n32_fwd2_can_update_u(p, pf_node_blocks(p->mesh.n_nodes));
+  f.dag = !f.fuse_gu && p->mesh.n_elems >= PF_GRAPH_DAG_MIN_ELEMS;
+  f.u_alt = p->u_alt != nullptr;
+  f.fold = f.fuse_gu && f.u_alt && f.bwd2 && f.fuse_s2 && pf_n32_bwd2_has_path(p) && p->n_iface == 0 &&
+           p->mesh.dim == p->net[0].in_dim - 1;
+  f.light = f.fold && pf_n32_has_light_forward(p);      // (fold: both nets are enabled)
+  f.tn_ready = p->wg_mode == PF_WG_MFMA32 ? 1 : 0;
+  return f;
 }
 
 extern "C" {
@@ -331,12 +331,13 @@ long long pf_partials_count(const pf_problem* p) {
 
 int pf_fusion_info(const pf_problem* p) {
   if (check_problem(p) != PF_OK) return PF_ERR_ARG;
+  const graph_form f = graph_form_static(p);
   int m = 0;
-  if (can_fuse_forward(p)) m |= PF_FUSED_FORWARD;
-  if (can_fuse_backward(p)) m |= PF_FUSED_BACKWARD;
-  if (can_fuse_theta_update(p)) m |= PF_FUSED_THETA_UPDATE;
-  if (p->prop_double != 0 && p->elem_k != nullptr && can_fuse_gradu(p)) m |= PF_FUSED_U_UPDATE;
-  else if (p->u_alt != nullptr && p->mesh.n_elems >= PF_GRAPH_DAG_MIN_ELEMS) m |= PF_FUSED_U_PINGPONG;
+  if (f.fwd2) m |= PF_FUSED_FORWARD;
+  if (f.bwd2) m |= PF_FUSED_BACKWARD;
+  if (f.fuse_s2) m |= PF_FUSED_THETA_UPDATE;
+  if (f.fuse_gu) m |= PF_FUSED_U_UPDATE;
+  if (f.dag && f.u_alt) m |= PF_FUSED_U_PINGPONG;
   return m;
 }
 
@@ -499,8 +500,8 @@ int pf_gd_iterations(const pf_problem* p, int n_iter, void* stream) {
 //
 // ONE CHAIN (below PF_GRAPH_DAG_MIN_ELEMS elements, and wherever the forward launch can carry the displacement update):
 // every launch on c.s, no events: forward, residual, backwards, theta stage 1, gradu.  The forward launch of iteration i
-// also runs the parameter update of i-1 (can_fuse_theta_update; fwd_theta_prologue) and, where it can, the displacement
-// update of i-1 (dL/du + Adam(u) + clamp: can_fuse_gradu; it reads the stiffness records of i-1 = the other half, which is
+// also runs the parameter update of i-1 (graph_form.fuse_s2; fwd_theta_prologue) and, where it can, the displacement
+// update of i-1 (dL/du + Adam(u) + clamp: graph_form.fuse_gu; it reads the stiffness records of i-1 = the other half, which is
 // why it needs prop_double); node_residual's block 0 runs the bookkeeping of i-1 (pf_mesh.hip: k_node_residual,
 // fin_prev) from the other half of the residual's partial sums (pf_problem.part_half).  Only the replay's last iteration
 // keeps the stand-alone parameter and displacement updates, in place, and the bookkeeping follows as a launch of its own.
@@ -568,26 +569,17 @@ static bool mesh_is_path(const pf_problem* p, bool* ordered = nullptr) {
   return ok && (h & 1) == 0;
 }
 
-// Can the iteration graph drop the residual launch (the PATH form)?  Wherever the forward launch carries the displacement
-// update today (one chain: can_fuse_gradu with elem_k and prop_double), the backward is the fused two-phase launch and the
-// parameter update rides in the forward launch (so theta stage 1 is a launch of every iteration), on one GPU, with the second
-// displacement vector free to hold r — and the mesh is a path.
-static bool can_fold_residual_static(const pf_problem* p) {
-  return p->prop_double != 0 && p->elem_k != nullptr && p->u_alt != nullptr && can_fuse_gradu(p) && can_fuse_backward(p) &&
-         can_fuse_theta_update(p) && pf_n32_bwd2_has_path(p) && p->n_iface == 0 && p->mesh.dim == p->net[0].in_dim - 1;
-}
-static bool can_fold_residual(const pf_problem* p, bool* ordered = nullptr) {
-  if (ordered) *ordered = false;
-  return can_fold_residual_static(p) && mesh_is_path(p, ordered);
-}
-// Does the path form run with the LIGHT forward (pf_net32.hip: k_net32_forward2 / backward_phase, LIGHT)?  Then the forward
-// launch evaluates the E net only for the elements at task edges and the backward launch, which recomputes the E net's hidden
-// layers anyway, stores prop_e and the other records.  forward(i) and backward(i) always complete together (the stop flag is
-// only raised behind backward(i), in stage 1), and every reader of prop_e, prop_a and the records — forward(i+1)'s node
-// tasks, the replay's tail, pf_graph_tail, a continuation head, the results — runs behind backward(i): it sees the bytes the
-// full forward writes.
-static bool can_light_forward(const pf_problem* p, bool fold) {
-  return fold && p->net[0].enabled && p->net[1].enabled && pf_n32_has_light_forward(p);
+// The whole record: the static part, completed by the probes.  No probe runs unless the static part already allows what it
+// decides: one path probe where the path form is possible, one copy of the index table (with_index: graph creation) where the
+// forward launch has the update prologue.  A failed probe answers "not a path" and leaves its message in pf_last_error.
+static graph_form graph_form_probed(const pf_problem* p, bool with_index) {
+  graph_form f = graph_form_static(p);
+  f.calc_index = with_index && f.fuse_s2 && pad_index_is_canonical(p);
+  bool ordered = false;
+  f.fold = f.fold && mesh_is_path(p, &ordered);
+  f.ordered = f.fold && ordered;
+  f.light = f.light && f.fold;
+  return f;
 }
 
 // The buffers iteration i of the graph works on.  Properties and stiffness records ping-pong between iterations
@@ -608,7 +600,7 @@ static pf_problem graph_iteration_view(const pf_problem& p, int i) {
 // no_tail replay); no_tail: the replay ends behind the last iteration's gradient-row reduction, its parameter update,
 // displacement update and bookkeeping stay pending (pf_graph_create_ex).  Both only in the one-chain form.
 //
-// PATH form (fold; can_fold_residual, decided at graph creation): THREE launches per iteration, forward -> backward -> theta
+// PATH form (graph_form.fold, decided at graph creation): THREE launches per iteration, forward -> backward -> theta
 // stage 1.  The backward launch forms r and g_f of its elements' nodes itself (pf_net32.hip: backward_phase, PATH); the
 // residual's loss sums and the bookkeeping of i-1 ride in the theta-stage-1 launch of i (pf_mesh.hip: k_theta_stage1_path),
 // with the same partition and order of the sums, so nothing changes a bit.  The stop is then raised one launch later than
@@ -616,23 +608,20 @@ static pf_problem graph_iteration_view(const pf_problem& p, int i) {
 // scratch all the same (g_f, r in u_alt, g_ea, gradient rows, partial sums of the half nobody will read), and every
 // state-changing step — the updates inside forward(i+1), or the replay's stand-alone tail — still starts behind stage 1(i),
 // reads the flag first and returns at once.
-static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_capture& c, bool calc_index = false,
-                                    bool head_cont = false, bool no_tail = false, bool fold = false, bool ordered = false) {
+static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_capture& c, const graph_form& f, int flags) {
   hipStream_t s = c.s;
-  if (!(p->net[0].enabled || p->net[1].enabled)) {
+  if (!f.any_net) {
     for (int i = 0; i < iters; ++i) {
       int rc = enqueue_iteration(p, 1, 0, s, nullptr);
       if (rc != PF_OK) return rc;
     }
     return PF_OK;
   }
-  const bool fuse_gu = p->prop_double != 0 && p->elem_k != nullptr && can_fuse_gradu(p);
-  const bool dag = !fuse_gu && p->mesh.n_elems >= PF_GRAPH_DAG_MIN_ELEMS;
-  const bool upp = dag && p->u_alt != nullptr && (iters % 2) == 0;    // DAG with the second displacement vector
-  const bool fuse_s2 = can_fuse_theta_update(p);
-  const int tn_ready = p->wg_mode == PF_WG_MFMA32 ? 1 : 0;   // k_theta_stage2 leaves the theta-norm monitor in the state
+  const bool head_cont = (flags & PF_GRAPH_CONT_HEAD) != 0, no_tail = (flags & PF_GRAPH_NO_TAIL) != 0;
+  const bool fuse_gu = f.fuse_gu, dag = f.dag, fuse_s2 = f.fuse_s2, fold = f.fold, light = f.light;
+  const bool upp = dag && f.u_alt && (iters % 2) == 0;                // DAG with the second displacement vector
+  const int tn_ready = f.tn_ready;
   const size_t k_half = (size_t)p->mesh.n_elems * (p->mesh.dim == 2 ? 3 : 1);   // floats of one half of the records
-  const bool light = can_light_forward(p, fold);
   for (int i = 0; i < iters; ++i) {
     hipEvent_t* e = c.ev + PF_CAP_EV * i;
     hipEvent_t* ep = c.ev + PF_CAP_EV * (i - 1);
@@ -645,11 +634,11 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
     const bool carries = i > 0 || head_cont;      // this iteration's forward / residual carry the previous iteration's work
     pf_fwd2_opts fo;
     if (fuse_s2 && carries) fo.s2_half = (i - 1) & 1;       // (i = 0 in a continuation: the previous replay's last = half 1)
-    fo.calc_index = calc_index;
+    fo.calc_index = f.calc_index;
     if (fuse_gu && carries) {
       fo.gu_nb = pf_node_blocks(q.mesh.n_nodes);
       fo.gu_k = p->elem_k + (((i - 1) & 1) ? k_half : 0);   // the records iteration i-1 wrote (the other half)
-      fo.gu_ordered = fold && ordered ? 1 : 0;              // (the path form with node ids in path order: no adjacency)
+      fo.gu_ordered = f.ordered ? 1 : 0;                    // (the path form with node ids in path order: no adjacency)
     }
     // (DAG without the second property half: the forwards wait for gradu(i-1), an 11 us hole in the kernel trace)
     if (dag && i > 0 && p->prop_double == 0 && hipStreamWaitEvent(s, ep[1], 0) != hipSuccess)
@@ -697,53 +686,48 @@ static int enqueue_graph_iterations(const pf_problem* p, int iters, const pf_cap
 
 int pf_graph_form_info(const pf_problem* p) {
   if (check_problem(p) != PF_OK) return PF_ERR_ARG;
-  return can_fold_residual(p) ? PF_GRAPH_FORM_FOLDED_RESIDUAL : 0;
+  return graph_form_probed(p, false).fold ? PF_GRAPH_FORM_FOLDED_RESIDUAL : 0;
 }
 
 int pf_graph_light_forward(const pf_problem* p) {
   if (check_problem(p) != PF_OK) return PF_ERR_ARG;
-  return can_light_forward(p, can_fold_residual(p)) ? 1 : 0;
+  return graph_form_probed(p, false).light ? 1 : 0;
 }
 
 int pf_graph_ordered_path(const pf_problem* p) {
   if (check_problem(p) != PF_OK) return PF_ERR_ARG;
-  bool ordered = false;
-  return can_fold_residual(p, &ordered) && ordered ? 1 : 0;
+  return graph_form_probed(p, false).ordered ? 1 : 0;
 }
 
 int pf_graph_create(const pf_problem* p, int iters_per_graph, void* stream, void** graph_out) {
   return pf_graph_create_ex(p, iters_per_graph, 0, stream, graph_out);
 }
 
-// can the iteration graph of this problem be cut into replays that hand their last iteration's updates to the next one?
-static bool can_chain_replays(const pf_problem* p, int iters) {
-  return (iters % 2) == 0 && p->prop_double != 0 && p->elem_k != nullptr && can_fuse_gradu(p) && can_fuse_theta_update(p);
-}
+// can the iteration graph of this form be cut into replays that hand their last iteration's updates to the next one?
+static bool can_chain_replays(const graph_form& f, int iters) { return (iters % 2) == 0 && f.fuse_gu && f.fuse_s2; }
 
 int pf_graph_create_ex(const pf_problem* p, int iters_per_graph, int flags, void* stream, void** graph_out) {
   int rc = check_gd(p);
   if (rc) return rc;
   if (!graph_out || iters_per_graph < 1) return fail(PF_ERR_ARG, "pf_graph_create_ex: bad argument");
-  if ((flags & (PF_GRAPH_CONT_HEAD | PF_GRAPH_NO_TAIL)) && !can_chain_replays(p, iters_per_graph))
+  if ((flags & (PF_GRAPH_CONT_HEAD | PF_GRAPH_NO_TAIL)) && !can_chain_replays(graph_form_static(p), iters_per_graph))
     return fail(PF_ERR_UNSUPPORTED, "pf_graph_create_ex: replays of this problem's graph cannot hand over their tail");
-  const bool calc_index = can_fuse_theta_update(p) && pad_index_is_canonical(p);
-  bool ordered = false;
-  const bool fold = can_fold_residual(p, &ordered);
-  const bool head = (flags & PF_GRAPH_CONT_HEAD) != 0, no_tail = (flags & PF_GRAPH_NO_TAIL) != 0;
+  const graph_form f = graph_form_probed(p, true);
   return capture_graph((hipStream_t)stream, PF_CAP_EV * iters_per_graph, hipStreamCaptureModeThreadLocal, graph_out,
-                       [&](pf_capture& cap) { return enqueue_graph_iterations(p, iters_per_graph, cap, calc_index, head, no_tail, fold, ordered); });
+                       [&](pf_capture& cap) { return enqueue_graph_iterations(p, iters_per_graph, cap, f, flags); });
 }
 
 // the pending tail of a PF_GRAPH_NO_TAIL replay: what the last iteration of a plain replay ends with
 int pf_graph_tail(const pf_problem* p, int iters_per_graph, void* stream) {
   int rc = check_gd(p);
   if (rc) return rc;
-  if (!can_chain_replays(p, iters_per_graph)) return fail(PF_ERR_UNSUPPORTED, "pf_graph_tail: not a chained replay");
+  const graph_form f = graph_form_static(p);
+  if (!can_chain_replays(f, iters_per_graph)) return fail(PF_ERR_UNSUPPORTED, "pf_graph_tail: not a chained replay");
   hipStream_t s = (hipStream_t)stream;
   const pf_problem q = graph_iteration_view(*p, iters_per_graph - 1);   // the last iteration's halves
   PF_TRY(pf_launch_theta_stage2(&q, 1, s), "theta_stage2");
   PF_TRY(pf_launch_node_gradu(&q, 1, s, 0, nullptr), "node_gradu");
-  PF_TRY(pf_launch_finalize(&q, 0, 0, s, q.wg_mode == PF_WG_MFMA32 ? 1 : 0), "finalize");
+  PF_TRY(pf_launch_finalize(&q, 0, 0, s, f.tn_ready), "finalize");
   return PF_OK;
 }
 

@@ -17,45 +17,19 @@ import numpy as np
 import pytest
 import torch
 
+from graph_driver import CHAIN_MASK, FOLDED, Expect, graph_vs_eager
+from graph_driver import warren as _warren, zigzag as _zigzag
+
 pytestmark = pytest.mark.gpu
 
-FOLDED = 1
-CHAIN_MASK = 1 + 2 + 4 + 16
+# (every run below: fe_mode 0, alpha_physics = 0.37 so that g_f != r; ordered: from the model's own connectivity)
+PATH = Expect(CHAIN_MASK, FOLDED, ordered="ids")
 # a mesh that is not a path: the same fused launches, no folded residual (read from the parent commit's library on the
 # Warren girders below: pf_fusion_info 23, pf_graph_form_info 0)
-WARREN_MASK, WARREN_FORM = 23, 0
+WARREN = Expect(23, 0, ordered="ids")
 # one net: only the parameter update rides in the forward launch; from 200000 elements on the graph is the DAG with two
 # displacement vectors (read from the parent commit's library as well)
-ONE_NET_MASK, ONE_NET_MASK_DAG, ONE_NET_FORM = 4, 4 + 8, 0
-
-
-def _nets(dim, we=20, wa=15):
-    from pinn_fem_amd.fem.model import Material
-    from pinn_fem_amd.fem.properties import NNProperty
-    from pinn_fem_amd.nets import SimpleNN
-    torch.manual_seed(5)
-    return Material(NNProperty(SimpleNN(2, we, dim + 1), dim + 1, True, 1.5), NNProperty(SimpleNN(2, wa, dim + 1), dim + 1, True, 0.7))
-
-
-def _zigzag(n, seed=3):
-    """A two-net model (20 / 15 wide) on an open zigzag path of n elements (c2, cs and s2 all live), a random load on every
-    dof, fixed dofs at both ends and one in the interior, measurements at every third node."""
-    from pinn_fem_amd.fem.model import FEMModel
-    rng = np.random.default_rng(seed)
-    pos = np.arange(n + 1)
-    x = np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 1.5, n))]) * (3.0 / max(n, 1))
-    nodes = np.zeros((n + 1, 2))
-    nodes[:, 0] = x
-    nodes[:, 1] = (pos % 2) * (0.7 * 3.0 / max(n, 1)) + 0.1 * x
-    elements = np.stack([pos[:-1], pos[1:]], 1)
-    loads = rng.normal(size=2 * (n + 1)) * 0.1
-    fixed = [0, 1, 2 * n + 1]
-    if n >= 2:
-        fixed.append(2 * (n // 2) + 1)
-    nd = pos[pos % 3 == 1] if n >= 2 else pos
-    md = (nd[:, None] * 2 + np.arange(2)[None, :]).reshape(-1)
-    mv = rng.normal(size=md.size) * 0.02
-    return FEMModel(nodes, elements, _nets(2), loads, np.unique(np.array(fixed)), dimension=2), mv, md
+ONE_NET, ONE_NET_DAG = Expect(4, 0, ordered="ids"), Expect(4 + 8, 0, ordered="ids")
 
 
 def _one_net(n, seed=3):
@@ -69,99 +43,37 @@ def _one_net(n, seed=3):
     return FEMModel(two.nodes, two.elements, mat, two.loads, two.fixed_dofs, dimension=2), mv, md
 
 
-def _warren(panels):
-    from pinn_fem_amd.fem.model import FEMModel
-    from pinn_fem_amd.plan import warren_mesh
-    nodes, elements, loads, fixed, mv, md = warren_mesh(panels)
-    return FEMModel(nodes, elements, _nets(2), loads, fixed, dimension=2), mv, md
-
-
-def _state(eng, rows):
-    st = eng.state()
-    return (eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.m_t.cpu().numpy().copy(),
-            eng.v_t.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(), eng.v_u.cpu().numpy().copy(),
-            (st.iter, st.done, st.converged, st.theta_half, st.u_half), eng.history(rows).copy())
-
-
-def _assert_same(a, b, bitwise_monitor=False):
-    for x, y in zip(a[:-2], b[:-2]):
-        assert np.array_equal(x, y)
-    assert a[-2] == b[-2]
-    ha, hb = a[-1], b[-1]
-    assert ha.shape == hb.shape
-    cols = [c for c in range(ha.shape[1]) if c != 3]        # every column except the u-norm monitor
-    assert np.array_equal(ha[:, cols], hb[:, cols])
-    if bitwise_monitor:     # (forms whose displacement update is the stand-alone kernel in the graph and in eager launches)
-        assert np.array_equal(ha[:, 3], hb[:, 3])
-    else:
-        assert np.allclose(ha[:, 3], hb[:, 3], rtol=2e-6, atol=0.0)
-    assert np.all(np.isfinite(ha))
-
-
-def _graph_vs_eager(make, mask, form, chained=False):
-    """Two whole replays and an eager remainder of 3 (chained: three chained replays, the tail deferred to flush())
-    against the same iterations launched eagerly.  alpha_physics = 0.37, so that g_f != r."""
-    from pinn_fem_amd.engine import HipEngine
-    from pinn_fem_amd.fem.solver import SolverConfig
-    outs = []
-    for use_graph in (True, False):
-        model, mv, md = make()
-        eng = HipEngine(model, mv, md, fe_mode=0)
-        cfg = SolverConfig(max_iterations=200, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4,
-                           alpha_physics=0.37, alpha_data=100.0)
-        eng.begin(None, 0.3, cfg, want_history=True)
-        assert eng.fusion_info() == mask
-        assert eng.graph_form_info() == form
-        k = eng.GRAPH_ITERS
-        if chained:
-            n_it = 3 * k
-            if use_graph:
-                assert eng.prepare_graph(chained=True)
-                eng.iterate(n_it, defer_tail=True)
-                eng.flush()
-            else:
-                eng.iterate(n_it, use_graph=False)
-        else:
-            n_it = 2 * k + 3
-            eng.iterate(n_it, use_graph=use_graph)
-        torch.cuda.synchronize()
-        assert eng.state().iter == n_it
-        outs.append(_state(eng, n_it))
-        del eng
-    _assert_same(outs[0], outs[1], bitwise_monitor=not (mask & 16))
-
-
 @pytest.mark.parametrize("n", [1, 63, 64, 65])
 def test_loop_lane_and_task_edges(n):
     """A single lane, a lane tail, exactly one task, a second task of one element (every other wave of block 0 requests
     clamped coordinates nobody reads)."""
-    _graph_vs_eager(lambda: _zigzag(n), CHAIN_MASK, FOLDED)
+    graph_vs_eager(lambda: _zigzag(n), PATH)
 
 
 def test_loop_blocks_with_and_without_tasks():
     """4100 elements: 65 element tasks, one per block for 65 blocks, the rest of the grid with none; 33 node tasks: blocks
     with both kinds of task, with element tasks only, and with nothing."""
-    _graph_vs_eager(lambda: _zigzag(4100), CHAIN_MASK, FOLDED)
+    graph_vs_eager(lambda: _zigzag(4100), PATH)
 
 
 @pytest.mark.parametrize("n", [262144, 262144 + 64])
 def test_loop_one_task_per_wave(n):
     """262144: every wave of the grid has exactly one task and no draw from the queue succeeds.  64 more: 4097 tasks, 17 per
     block on 241 blocks, each with one wave that draws a second task."""
-    _graph_vs_eager(lambda: _zigzag(n), CHAIN_MASK, FOLDED)
+    graph_vs_eager(lambda: _zigzag(n), PATH)
 
 
 def test_loop_several_draws_per_wave():
     """131585 elements (test_path_head.py's handicap size): 2057 tasks, 9 per block on 228 blocks and 5 on the last, several
     draws per block, and the unconditional request past t1 in every block."""
-    _graph_vs_eager(lambda: _zigzag(131585), CHAIN_MASK, FOLDED)
+    graph_vs_eager(lambda: _zigzag(131585), PATH)
 
 
 @pytest.mark.parametrize("panels", [300, 3000])
 def test_loop_warren_girder(panels):
     """A mesh that is not a path (Warren girder, node degree 4): the four-launch form, whose forward launch carries
     degree-4 node tasks beside the element tasks."""
-    _graph_vs_eager(lambda: _warren(panels), WARREN_MASK, WARREN_FORM)
+    graph_vs_eager(lambda: _warren(panels), WARREN)
 
 
 @pytest.mark.parametrize("mesh", ["zigzag4100", "warren3000"])
@@ -169,9 +81,9 @@ def test_loop_chained_replays(mesh):
     """Three chained replays, the tail deferred to flush(): iteration 0 of a continued replay runs the loop on what the
     replay before it left."""
     if mesh == "zigzag4100":
-        _graph_vs_eager(lambda: _zigzag(4100), CHAIN_MASK, FOLDED, chained=True)
+        graph_vs_eager(lambda: _zigzag(4100), PATH, mode="chained")
     else:
-        _graph_vs_eager(lambda: _warren(3000), WARREN_MASK, WARREN_FORM, chained=True)
+        graph_vs_eager(lambda: _warren(3000), WARREN, mode="chained")
 
 
 @pytest.mark.parametrize("n", [65, 4100, 100000, 262144 + 65])
@@ -179,7 +91,7 @@ def test_one_net_rounds(n):
     """k_net32_forward (E = NN, A constant): one task and a second of one element, 65 tasks, the ex3 side configuration's
     size (1563 tasks on 4096 waves: one round), and 4098 tasks on 4096 waves: a second round in which two waves of block 0
     work and every other wave holds clamped coordinates, with the lockstep barriers of both rounds."""
-    _graph_vs_eager(lambda: _one_net(n), ONE_NET_MASK_DAG if n >= 200000 else ONE_NET_MASK, ONE_NET_FORM)
+    graph_vs_eager(lambda: _one_net(n), ONE_NET_DAG if n >= 200000 else ONE_NET)
 
 
 def test_forward_values_against_float64():

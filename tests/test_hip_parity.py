@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from graph_driver import PF_FUSED_U_UPDATE, Expect, assert_history_same, graph_vs_eager
 from helpers import (_random_truss, example_problem, load_npz, load_run, mesh_problem, orc, product_example,
                      product_model, rel_err, theta_from)
 
@@ -961,31 +962,6 @@ def test_bf16_mlp_hybrid_example_tolerance(ex):
 # ---- BASELINE-size checks of the product path ----------------------------------------------------
 
 
-def _assert_history_equal(a, b):
-    """Histories of the iteration graph and of eager launches: every column bit for bit, except the u-norm monitor
-    (column 3) — the graph's displacement update runs inside the forward launch and adds the block partials of
-    sum u_free^2 in another (fixed) grouping than the stand-alone kernel: same sum to float32 round-off."""
-    cols = [c for c in range(a.shape[1]) if c != 3]
-    assert np.array_equal(a[:, cols], b[:, cols])
-    assert np.allclose(a[:, 3], b[:, 3], rtol=2e-6, atol=0.0)
-
-
-def _assert_history_bitwise(a, b):
-    """Histories of an iteration graph whose displacement update is the stand-alone k_node_gradu (every form without
-    PF_FUSED_U_UPDATE: the same kernel, the same block partials, the same bookkeeping sum as the eager launches) and of
-    eager launches: every column bit for bit, the u-norm monitor included."""
-    assert a.shape == b.shape
-    assert np.array_equal(a, b)
-
-
-def _assert_history_for(mask, a, b):
-    """The history comparison that the graph form `mask` (pf_fusion_info) promises."""
-    if mask & 16:
-        _assert_history_equal(a, b)
-    else:
-        _assert_history_bitwise(a, b)
-
-
 def test_full_size_graph_equals_eager_bitwise():
     """10^6 elements, ex4 shape, default element-force formulation: 40 iterations replayed as the one-chain hipGraph
     (the product path of bench.py: the parameter and displacement updates ride in the next forward launch) and the same
@@ -1008,7 +984,7 @@ def test_full_size_graph_equals_eager_bitwise():
         del eng
     assert np.array_equal(outs[0][0], outs[1][0])
     assert np.array_equal(outs[0][1], outs[1][1])
-    _assert_history_equal(outs[0][2], outs[1][2])
+    assert_history_same(PF_FUSED_U_UPDATE, outs[0][2], outs[1][2])
     assert np.all(np.isfinite(outs[0][2])) and outs[0][2][-1, 0] < outs[0][2][0, 0]      # and the loss went down
 
 
@@ -1023,13 +999,11 @@ def test_graph_equals_eager_meshes(mesh, n, fe):
     of degree 300 (150 gather rounds in one lane of a node task), element forces in the reference and in the difference
     form."""
     from bench import build_model
-    from pinn_fem_amd.engine import HipEngine
     from pinn_fem_amd.fem.model import FEMModel, Material
     from pinn_fem_amd.fem.properties import NNProperty
-    from pinn_fem_amd.fem.solver import SolverConfig
     from pinn_fem_amd.nets import SimpleNN
-    outs = []
-    for use_graph in (True, False):
+
+    def make():
         if mesh == "bar1d":
             rng = np.random.default_rng(11)
             torch.manual_seed(5)
@@ -1053,21 +1027,10 @@ def test_graph_equals_eager_meshes(mesh, n, fe):
                                                        NNProperty(SimpleNN(2, 15, 3), 3, True, 0.3)), loads, fixed)
         else:
             model, mv, md, _ = build_model(n, "ex4", mesh=mesh)
-        cfg = SolverConfig(max_iterations=60, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4)
-        eng = HipEngine(model, mv, md, fe_mode=fe)
-        assert eng.fusion_info() == 1 + 2 + 4 + 16              # the displacement update rides in the forward launch
-        eng.begin(None, 0.1, cfg, want_history=True)
-        n_it = 2 * eng.GRAPH_ITERS + 3                          # two whole replays and a part of one
-        eng.iterate(n_it, use_graph=use_graph)
-        torch.cuda.synchronize()
-        assert eng.state().iter == n_it
-        outs.append((eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(),
-                     eng.v_u.cpu().numpy().copy(), eng.m_t.cpu().numpy().copy(), eng.history(n_it).copy()))
-        del eng
-    for a, b in zip(outs[0][:-1], outs[1][:-1]):
-        assert np.array_equal(a, b)
-    _assert_history_equal(outs[0][-1], outs[1][-1])
-    assert np.all(np.isfinite(outs[0][-1]))
+        return model, mv, md
+
+    # (the displacement update rides in the forward launch; two whole replays and a part of one)
+    graph_vs_eager(make, Expect(1 + 2 + 4 + 16), fe=fe, load_factor=0.1, alpha_physics=None, alpha_data=None, max_it=60)
 
 
 @pytest.mark.parametrize("le,la,we,wa,dim,n,mask", [
@@ -1085,13 +1048,11 @@ def test_graph_equals_eager_net_shapes(le, la, we, wa, dim, n, mask):
     it there; the displacement update is the stand-alone kernel — on the side branch of the DAG (250000 elements, with the
     displacement ping-pong) and on the main chain (60000), so every history column is compared bit for bit.
     Equal depths other than 2 do not fuse the backward passes (pf_fusion_info: 1 + 4 + 16)."""
-    from pinn_fem_amd.engine import HipEngine
     from pinn_fem_amd.fem.model import FEMModel, Material
     from pinn_fem_amd.fem.properties import NNProperty
-    from pinn_fem_amd.fem.solver import SolverConfig
     from pinn_fem_amd.nets import SimpleNN
-    outs = []
-    for use_graph in (True, False):
+
+    def make():
         rng = np.random.default_rng(7)
         torch.manual_seed(9)
         if dim == 2:
@@ -1108,23 +1069,10 @@ def test_graph_equals_eager_net_shapes(le, la, we, wa, dim, n, mask):
         model = FEMModel(nodes, elements, Material(NNProperty(SimpleNN(le, we, dim + 1), dim + 1, True, 1.5),
                                                    NNProperty(SimpleNN(la, wa, dim + 1), dim + 1, True, 0.7)),
                          loads, fixed, dimension=dim)
-        cfg = SolverConfig(max_iterations=60, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4)
-        eng = HipEngine(model, mv, md)
-        eng.begin(None, 0.2, cfg, want_history=True)
-        assert eng.fusion_info() == mask
-        n_it = 2 * eng.GRAPH_ITERS + 1
-        eng.iterate(n_it, use_graph=use_graph)
-        torch.cuda.synchronize()
-        assert eng.state().iter == n_it
-        assert eng.graph_creates == (1 if use_graph else 0)
-        outs.append((eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.m_t.cpu().numpy().copy(),
-                     eng.v_t.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(), eng.v_u.cpu().numpy().copy(),
-                     eng.history(n_it).copy()))
-        del eng
-    for a, b in zip(outs[0][:-1], outs[1][:-1]):
-        assert np.array_equal(a, b)
-    _assert_history_for(mask, outs[0][-1], outs[1][-1])
-    assert np.all(np.isfinite(outs[0][-1]))
+        return model, mv, md
+
+    graph_vs_eager(make, Expect(mask), fe=None, load_factor=0.2, alpha_physics=None, alpha_data=None, max_it=60, remainder=1,
+                   graph_creates=1)
 
 
 def _graph_form_model(kind, n):
@@ -1202,36 +1150,11 @@ def test_graph_forms_equal_eager(case):
     engines); bf16 matrix products; odd replay lengths and length 1 (parity of the state halves); the fused displacement
     update with the stand-alone parameter update (theta_alt = NULL).  Without PF_FUSED_U_UPDATE the displacement update is
     the eager launches' kernel, so the u-norm column is compared bit for bit too."""
-    from pinn_fem_amd.engine import HipEngine
-    from pinn_fem_amd.fem.solver import SolverConfig
     kind, n, kw, length, tweak, mask = GRAPH_FORMS[case]
-    outs = []
-    for use_graph in (True, False):
-        model, mv, md = _graph_form_model(kind, n)
-        eng = HipEngine(model, mv, md, **kw)
-        assert eng.GRAPH_ITERS == (20 if n >= 200_000 else 10)      # (switches at the DAG threshold too)
-        if length is not None:
-            eng.GRAPH_ITERS = length
-        cfg = SolverConfig(max_iterations=60, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4)
-        eng.begin(None, 0.1, cfg, want_history=True)
-        if tweak is not None:
-            tweak(eng.P)                                        # the graph is captured from this record by iterate()
-        assert eng.fusion_info() == mask
-        n_it = 2 * eng.GRAPH_ITERS + 3                          # two whole replays and a part of one
-        eng.iterate(n_it, use_graph=use_graph)
-        torch.cuda.synchronize()
-        st = eng.state()
-        assert st.iter == n_it and st.theta_half == 0 and st.u_half == 0
-        assert eng.graph_creates == (1 if use_graph else 0)
-        outs.append((eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.m_t.cpu().numpy().copy(),
-                     eng.v_t.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(), eng.v_u.cpu().numpy().copy(),
-                     (st.iter, st.done, st.converged), eng.history(n_it).copy()))
-        del eng
-    for a, b in zip(outs[0][:-2], outs[1][:-2]):
-        assert np.array_equal(a, b)
-    assert outs[0][-2] == outs[1][-2]
-    _assert_history_for(mask, outs[0][-1], outs[1][-1])
-    assert np.all(np.isfinite(outs[0][-1]))
+    graph_vs_eager(lambda: _graph_form_model(kind, n), Expect(mask), engine_kw=kw, fe=None, tweak=tweak, graph_iters=length,
+                   default_iters=20 if n >= 200_000 else 10,         # (switches at the DAG threshold too)
+                   load_factor=0.1, alpha_physics=None, alpha_data=None, max_it=60, home=("theta_half", "u_half"),
+                   graph_creates=1)
 
 
 @pytest.mark.parametrize("n,max_it,tol,n_call,expect", [(250_000, 200, 0.0, 3 * 20 + 7, 67), (250_000, 200, 1e30, 60, 12),
@@ -1267,7 +1190,7 @@ def test_chained_replays_equal_plain_replays(n, max_it, tol, n_call, expect):
         del eng
     for a, b in zip(outs[0][:-2], outs[1][:-2]):
         assert np.array_equal(a, b)
-    _assert_history_equal(outs[0][-2], outs[1][-2])         # (a plain replay's last displacement update is the stand-alone kernel)
+    assert_history_same(PF_FUSED_U_UPDATE, outs[0][-2], outs[1][-2])         # (a plain replay's last displacement update is the stand-alone kernel)
     assert outs[0][-1] == outs[1][-1]
 
 
@@ -1284,22 +1207,8 @@ def test_graph_stop_in_mid_replay_equals_eager(max_it, tol, expect, work, mask):
     with the displacement ping-pong, where an odd count leaves the final u in u_alt and k_u_home brings it home."""
     from bench import build_model
     from pinn_fem_amd import _capi
-    from pinn_fem_amd.engine import HipEngine
-    from pinn_fem_amd.fem.solver import SolverConfig
-    outs = []
-    for use_graph in (True, False):
-        model, mv, md, _ = build_model(250_000, work)
-        cfg = SolverConfig(max_iterations=max_it, tolerance=tol, learning_rate_u=0.01, learning_rate_theta=5e-4)
-        eng = HipEngine(model, mv, md)
-        assert eng.fusion_info() == mask
-        eng.begin(None, 0.1, cfg, want_history=True)
-        eng.iterate(2 * eng.GRAPH_ITERS, use_graph=use_graph)
-        torch.cuda.synchronize()
-        st = eng.state()
-        assert st.iter == expect and st.done == 1 and st.theta_half == 0
-        outs.append((eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.m_t.cpu().numpy().copy(),
-                     eng.v_t.cpu().numpy().copy(), eng.m_u.cpu().numpy().copy(), eng.v_u.cpu().numpy().copy(),
-                     (st.done, st.converged), eng.history(expect).copy()))
+
+    def stored_images(eng, use_graph, n_it):
         # the nets' operand images belong to the final theta: a property evaluation from the stored images (no re-pack)
         # equals one after re-packing
         ne = eng.plan.n_elems
@@ -1318,11 +1227,11 @@ def test_graph_stop_in_mid_replay_equals_eager(max_it, tol, expect, work, mask):
             if spec.enabled:
                 assert np.all(np.isfinite(repacked[k]))
                 assert np.array_equal(stored[k], repacked[k]), k
-        del eng
-    for a, b in zip(outs[0][:-2], outs[1][:-2]):
-        assert np.array_equal(a, b)
-    assert outs[0][-2] == outs[1][-2]
-    _assert_history_for(mask, outs[0][-1], outs[1][-1])
+        return []
+
+    graph_vs_eager(lambda: build_model(250_000, work)[:3], Expect(mask), fe=None, load_factor=0.1, alpha_physics=None,
+                   alpha_data=None, mode="stop", max_it=max_it, tol=tol, stop_at=expect, home=("theta_half",),
+                   extra=stored_images)
 
 
 def test_full_size_loss_and_grads_vs_oracle_prefix():
@@ -1508,7 +1417,7 @@ def test_beyond_infinity_cache_1e7_elements():
         assert eng.state().iter == eng.GRAPH_ITERS
         outs.append((eng.u.cpu().numpy().copy(), eng.theta.flat.cpu().numpy().copy(), eng.history(eng.GRAPH_ITERS).copy()))
     assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
-    _assert_history_equal(outs[0][2], outs[1][2])
+    assert_history_same(PF_FUSED_U_UPDATE, outs[0][2], outs[1][2])
     assert np.all(np.isfinite(outs[0][2]))
     # (1) equilibrium of the element forces at a smooth displacement field
     x = np.arange(n + 1, dtype=np.float64)

@@ -13,91 +13,30 @@ run that ends inside or at the end of a replay (chained replays with flush(), a 
 iteration n - 1 — what the eager run holds in its first half — in half (n - 1) & 1.  After a stop in mid-replay the graph has
 run one more forward / backward pair than the eager launches (the stop is raised behind the backward launch: the other half,
 g_ea and g_f are scratch there, as before this form), so g_ea and g_f are compared in the other two modes only."""
-import numpy as np
 import pytest
-import torch
 
-from test_path_form import CHAIN_MASK, FOLDED, _assert_same, _path_model, _state
+from graph_driver import CHAIN_MASK, FOLDED, Expect, graph_vs_eager, path_model, ring, two_net_model
 
 gpu = pytest.mark.gpu      # (per test: the declaration test at the end needs no GPU)
-
-
-def _material(dim, we=20, wa=15, pos_e=True, pos_a=True, scale_e=1.5, scale_a=0.7):
-    from pinn_fem_amd.fem.model import Material
-    from pinn_fem_amd.fem.properties import NNProperty
-    from pinn_fem_amd.nets import SimpleNN
-    torch.manual_seed(5)
-    return Material(NNProperty(SimpleNN(2, we, dim + 1), dim + 1, pos_e, scale_e),
-                    NNProperty(SimpleNN(2, wa, dim + 1), dim + 1, pos_a, scale_a))
-
-
-def _model(n, geom="bar", reverse=False, meas="all", **net):
-    """test_path_form's path model, with other nets where asked for."""
-    from pinn_fem_amd.fem.model import FEMModel
-    m0, mv, md = _path_model(n, geom, reverse=reverse, meas=meas)
-    if not net:
-        return m0, mv, md
-    dim = 1 if geom == "bar1d" else 2
-    return FEMModel(m0.nodes, m0.elements, _material(dim, **net), m0.loads, m0.fixed_dofs, dimension=dim), mv, md
 
 
 def _buffers(eng, half, with_adjoint):
     """prop_e, prop_a and the stiffness records of one half, and (with_adjoint) g_ea and g_f, as bytes-exact arrays."""
     ne = eng.plan.n_elems
     kw = 3 if eng.plan.dim == 2 else 1
-    out = [eng.prop_e[half * ne:(half + 1) * ne].cpu().numpy().copy(), eng.prop_a[half * ne:(half + 1) * ne].cpu().numpy().copy(),
-           eng.elem_k[half * ne * kw:(half + 1) * ne * kw].cpu().numpy().copy()]
+    out = [("prop_e", eng.prop_e[half * ne:(half + 1) * ne]), ("prop_a", eng.prop_a[half * ne:(half + 1) * ne]),
+           ("elem_k", eng.elem_k[half * ne * kw:(half + 1) * ne * kw])]
     if with_adjoint:
-        out += [eng.g_ea[:ne].cpu().numpy().copy(), eng.g_f.cpu().numpy().copy()]
-    return out
+        out += [("g_ea", eng.g_ea[:ne]), ("g_f", eng.g_f)]
+    return [(name, t.cpu().numpy().copy()) for name, t in out]
 
 
-def _graph_vs_eager(make, fe=0, mode="plain", graph_iters=None, max_it=200, tol=0.0, expect=None, light=1, form=FOLDED):
-    from pinn_fem_amd.engine import HipEngine
-    from pinn_fem_amd.fem.solver import SolverConfig
-    outs, bufs = [], []
-    for use_graph in (True, False):
-        model, mv, md = make()
-        eng = HipEngine(model, mv, md, fe_mode=fe)
-        if graph_iters is not None:
-            eng.GRAPH_ITERS = graph_iters
-        cfg = SolverConfig(max_iterations=max_it, tolerance=tol, learning_rate_u=0.01, learning_rate_theta=5e-4,
-                           alpha_physics=0.37, alpha_data=100.0)
-        eng.begin(None, 0.3, cfg, want_history=True)
-        assert eng.fusion_info() == CHAIN_MASK
-        assert eng.graph_form_info() == form
-        assert eng.graph_light_forward() == light
-        k = eng.GRAPH_ITERS
-        assert k % 2 == 0
-        if mode == "plain":                                  # two whole replays and an eager remainder
-            n_it = 2 * k + 3
-            eng.iterate(n_it, use_graph=use_graph)
-            half = 0
-        elif mode == "chained":                              # three chained replays, the tail deferred to flush()
-            n_it = 3 * k
-            if use_graph:
-                assert eng.prepare_graph(chained=True)
-                eng.iterate(n_it, defer_tail=True)
-                eng.flush()
-            else:
-                eng.iterate(n_it, use_graph=False)
-            half = (n_it - 1) & 1 if use_graph else 0
-        else:                                                # a stop raised in mid-replay
-            eng.iterate(2 * k, use_graph=use_graph)
-            n_it = expect
-            half = (n_it - 1) & 1 if use_graph else 0
-        torch.cuda.synchronize()
-        st = eng.state()
-        assert st.iter == n_it
-        if mode == "stop":
-            assert st.done == 1
-        outs.append(_state(eng, n_it))
-        bufs.append(_buffers(eng, half, mode != "stop"))
-        del eng
-    _assert_same(outs[0], outs[1])
-    for name, a, b in zip(("prop_e", "prop_a", "elem_k", "g_ea", "g_f"), bufs[0], bufs[1]):
-        assert a.tobytes() == b.tobytes(), name
-        assert np.all(np.isfinite(a)), name
+def _light_vs_eager(make, fe=0, mode="plain", light=1, form=FOLDED, **kw):
+    """The shared driver, with the buffers of the half that holds the last iteration's values (module docstring)."""
+    def extra(eng, use_graph, n_it):
+        half = (n_it - 1) & 1 if use_graph and mode != "plain" else 0
+        return _buffers(eng, half, mode != "stop")
+    graph_vs_eager(make, Expect(CHAIN_MASK, form, light=light, ordered="ids"), fe=fe, mode=mode, extra=extra, **kw)
 
 
 @gpu
@@ -106,21 +45,21 @@ def _graph_vs_eager(make, fe=0, mode="plain", graph_iters=None, max_it=200, tol=
 def test_light_graph_equals_eager_task_and_wave_edges(n, geom, fe):
     """Task edges (63 .. 65, 127 .. 129), the mesh's two ends (1, 2), n not a multiple of 64, and 2048 elements = 32 tasks,
     where the packed edge elements first fill a whole wave (2047: one short, 2049: one slot of a second edge task)."""
-    _graph_vs_eager(lambda: _model(n, geom), fe=fe)
+    _light_vs_eager(lambda: path_model(n, geom), fe=fe)
 
 
 @gpu
 @pytest.mark.parametrize("geom,reverse,fe", [("bar1d", False, 1), ("zigzag", True, 0)])
 def test_light_graph_equals_eager_1d_and_reversed_ids(geom, reverse, fe):
     """One dof per node (a one-float stiffness record), and node ids running against the path."""
-    _graph_vs_eager(lambda: _model(4099, geom, reverse=reverse, meas="third"), fe=fe)
+    _light_vs_eager(lambda: path_model(4099, geom, reverse=reverse, meas="third"), fe=fe)
 
 
 @gpu
 def test_light_graph_equals_eager_second_task():
     """131137 elements = 2048 x 64 + 64 + 1: the elder waves of the backward launch take extra tasks (PF_BW_SHIFT), some
     blocks of the forward launch hold more than one edge task, the last task holds one element."""
-    _graph_vs_eager(lambda: _model(131_137, "bar", meas="third"))
+    _light_vs_eager(lambda: path_model(131_137, "bar", meas="third"))
 
 
 @gpu
@@ -128,15 +67,15 @@ def test_light_graph_equals_eager_second_task():
 def test_light_chained_replays_equal_eager(n, geom):
     """Chained replays with the tail deferred to flush(): a continuation head's node tasks read the records the replay
     before it left, pf_graph_tail's displacement update those of the last iteration."""
-    _graph_vs_eager(lambda: _model(n, geom, reverse=True), mode="chained")
+    _light_vs_eager(lambda: path_model(n, geom, reverse=True), mode="chained")
 
 
 @gpu
 @pytest.mark.parametrize("max_it,tol,expect", [(40, 1e30, 12), (13, 0.0, 13), (27, 0.0, 27)])
 def test_light_stop_in_mid_replay_equals_eager(max_it, tol, expect):
     """A stop raised inside a replay at an even (12) and at odd counts (13; 27 in the second replay), replays of 20."""
-    _graph_vs_eager(lambda: _model(4099, "zigzag", meas="third"), mode="stop", graph_iters=20, max_it=max_it, tol=tol,
-                    expect=expect)
+    _light_vs_eager(lambda: path_model(4099, "zigzag", meas="third"), mode="stop", graph_iters=20, max_it=max_it, tol=tol,
+                    stop_at=expect)
 
 
 @gpu
@@ -147,7 +86,7 @@ def test_light_stop_in_mid_replay_equals_eager(max_it, tol, expect):
 def test_light_net_variants(n, net):
     """enforce_positive off on E, on A and on both (the backward's own output value takes the z branch), scales != 1, and
     other bucket pairs that have the form (widths 16 and 3: register buckets 8 and 2; 13 and 24: buckets 8 and 12)."""
-    _graph_vs_eager(lambda: _model(n, "zigzag", **net), fe=1)
+    _light_vs_eager(lambda: path_model(n, "zigzag", **net), fe=1)
 
 
 @gpu
@@ -155,7 +94,7 @@ def test_light_net_variants(n, net):
 def test_wider_nets_keep_the_full_forward(n):
     """Widths 27 and 30 (past the buckets whose fused backward has the path form): the four-launch chain as before, the query
     answers 0, and graph == eager."""
-    _graph_vs_eager(lambda: _model(n, "zigzag", we=27, wa=30), light=0, form=0)
+    _light_vs_eager(lambda: path_model(n, "zigzag", we=27, wa=30), light=0, form=0)
 
 
 @gpu
@@ -164,7 +103,7 @@ def test_young_net_of_bucket_12_keeps_the_full_forward(n):
     """A young net 21 .. 24 wide on a 2-D mesh (register bucket 12, three inputs): its light backward would spill registers
     the path backward holds (profiles/r17_light_forward_registers.txt), so the pair stays on the path form with the full
     forward by dispatch: the query answers 0, the form and graph == eager are unchanged."""
-    _graph_vs_eager(lambda: _model(n, "zigzag", we=24, wa=3), light=0)
+    _light_vs_eager(lambda: path_model(n, "zigzag", we=24, wa=3), light=0)
 
 
 @gpu
@@ -172,7 +111,6 @@ def test_young_net_of_bucket_12_keeps_the_full_forward(n):
 def test_query_is_zero_off_the_path_form(kind):
     from bench import build_model
     from pinn_fem_amd.engine import HipEngine
-    from test_path_form import _ring, _two_net_model
     if kind == "sharded":
         from pinn_fem_amd.dist import build_shard_backend
         model, mv, md, _ = build_model(5000, "ex4")
@@ -184,7 +122,7 @@ def test_query_is_zero_off_the_path_form(kind):
         elif kind == "ex3":
             model, mv, md, _ = build_model(5000, "ex3")
         else:
-            model, mv, md = _two_net_model(*_ring(300))
+            model, mv, md = two_net_model(*ring(300))
         eng = HipEngine(model, mv, md)
         assert eng.fusion_info() == (4 if kind == "ex3" else CHAIN_MASK)
     assert eng.graph_form_info() == 0

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_path_form import CHAIN_MASK, FOLDED, _assert_same, _path_model, _state
+from graph_driver import CHAIN_MASK, FOLDED, Expect, graph_vs_eager, path_model, ring, two_net_model
 
 gpu = pytest.mark.gpu      # (per test: the declaration test at the end needs no GPU)
 
@@ -23,7 +23,7 @@ def _swapped_pair(n, geom="bar", meas="all"):
     """The ordered path of n elements with the ids of two interior nodes swapped: nodes, elements, loads, fixed and measured
     dofs renumbered together, so it is the same problem and still a path in element order, but conn[2e] != e at the pair."""
     from pinn_fem_amd.fem.model import FEMModel
-    m0, mv, md = _path_model(n, geom, meas=meas)
+    m0, mv, md = path_model(n, geom, meas=meas)
     dim = 1 if geom == "bar1d" else 2
     a, b = n // 3, n // 3 + 2
     assert 0 < a < b < n
@@ -40,44 +40,7 @@ def _swapped_pair(n, geom="bar", meas="all"):
     return model, mv, (None if md is None else dof[md])
 
 
-def _graph_vs_eager(make, ordered, fe=0, alpha_data=100.0, mode="plain", graph_iters=None, max_it=200, tol=0.0, expect=None):
-    from pinn_fem_amd.engine import HipEngine
-    from pinn_fem_amd.fem.solver import SolverConfig
-    outs = []
-    for use_graph in (True, False):
-        model, mv, md = make()
-        eng = HipEngine(model, mv, md, fe_mode=fe)
-        if graph_iters is not None:
-            eng.GRAPH_ITERS = graph_iters
-        cfg = SolverConfig(max_iterations=max_it, tolerance=tol, learning_rate_u=0.01, learning_rate_theta=5e-4,
-                           alpha_physics=0.37, alpha_data=alpha_data)
-        eng.begin(None, 0.3, cfg, want_history=True)
-        assert eng.fusion_info() == CHAIN_MASK
-        assert eng.graph_form_info() == FOLDED
-        assert eng.graph_ordered_path() == ordered
-        k = eng.GRAPH_ITERS
-        if mode == "plain":                                  # two whole replays and an eager remainder
-            n_it = 2 * k + 3
-            eng.iterate(n_it, use_graph=use_graph)
-        elif mode == "chained":                              # three chained replays, the tail deferred to flush()
-            n_it = 3 * k
-            if use_graph:
-                assert eng.prepare_graph(chained=True)
-                eng.iterate(n_it, defer_tail=True)
-                eng.flush()
-            else:
-                eng.iterate(n_it, use_graph=False)
-        else:                                                # a stop raised in mid-replay
-            eng.iterate(2 * k, use_graph=use_graph)
-            n_it = expect
-        torch.cuda.synchronize()
-        st = eng.state()
-        assert st.iter == n_it
-        if mode == "stop":
-            assert st.done == 1
-        outs.append(_state(eng, n_it))
-        del eng
-    _assert_same(outs[0], outs[1])
+ORDERED, GATHER = Expect(CHAIN_MASK, FOLDED, ordered=1), Expect(CHAIN_MASK, FOLDED, ordered=0)
 
 
 @gpu
@@ -86,7 +49,7 @@ def _graph_vs_eager(make, ordered, fe=0, alpha_data=100.0, mode="plain", graph_i
 def test_ordered_graph_equals_eager_node_task_and_end_node_edges(n, geom, fe):
     """The mesh's end nodes (one incidence each; n = 1: nothing but end nodes), the wave edge inside a task, one node short
     of a task, a full task, one and two nodes into the next one, and the same at the second and the eighth task edge."""
-    _graph_vs_eager(lambda: _path_model(n, geom), 1, fe=fe)
+    graph_vs_eager(lambda: path_model(n, geom), ORDERED, fe=fe)
 
 
 @gpu
@@ -97,20 +60,20 @@ def test_ordered_graph_equals_eager_block_partition(geom, meas, fe, alpha_data):
     """131137 elements: the forward launch's blocks hold several node tasks each and the last task holds few nodes.
     Measurements at every third node, one dof per node (a one-float record; both element-force formulations), no
     measurements, the data term switched off."""
-    _graph_vs_eager(lambda: _path_model(131_137, geom, meas=meas), 1, fe=fe, alpha_data=alpha_data)
+    graph_vs_eager(lambda: path_model(131_137, geom, meas=meas), ORDERED, fe=fe, alpha_data=alpha_data)
 
 
 @gpu
 def test_ordered_chained_replays_equal_eager():
     """Chained replays with the tail deferred to flush(): a continuation head's node tasks read the records the replay before
     it left."""
-    _graph_vs_eager(lambda: _path_model(4099, "zigzag"), 1, mode="chained")
+    graph_vs_eager(lambda: path_model(4099, "zigzag"), ORDERED, mode="chained")
 
 
 @gpu
 def test_ordered_stop_in_mid_replay_equals_eager():
     """max_iterations met at an odd count inside a replay of 20."""
-    _graph_vs_eager(lambda: _path_model(4099, "zigzag", meas="third"), 1, mode="stop", graph_iters=20, max_it=13, expect=13)
+    graph_vs_eager(lambda: path_model(4099, "zigzag", meas="third"), ORDERED, mode="stop", graph_iters=20, max_it=13, stop_at=13)
 
 
 @gpu
@@ -119,8 +82,8 @@ def test_ordered_stop_in_mid_replay_equals_eager():
 def test_other_node_ids_keep_the_gather(kind, n):
     """A path whose node ids run against it, and one whose ids are in order except for two interior nodes: the path form
     with the gather, query 0, graph == eager."""
-    make = (lambda: _path_model(n, "zigzag", reverse=True)) if kind == "reversed" else (lambda: _swapped_pair(n, "zigzag"))
-    _graph_vs_eager(make, 0, fe=1)
+    make = (lambda: path_model(n, "zigzag", reverse=True)) if kind == "reversed" else (lambda: _swapped_pair(n, "zigzag"))
+    graph_vs_eager(make, GATHER, fe=1)
 
 
 @gpu
@@ -128,13 +91,12 @@ def test_other_node_ids_keep_the_gather(kind, n):
 def test_query_is_zero_off_the_path_form(kind):
     from bench import build_model
     from pinn_fem_amd.engine import HipEngine
-    from test_path_form import _ring, _two_net_model
     if kind == "warren":
         model, mv, md, _ = build_model(5000, "ex4", mesh="warren")
     elif kind == "ex3":
         model, mv, md, _ = build_model(5000, "ex3")
     else:
-        model, mv, md = _two_net_model(*_ring(300))
+        model, mv, md = two_net_model(*ring(300))
     eng = HipEngine(model, mv, md)
     assert eng.fusion_info() == (4 if kind == "ex3" else CHAIN_MASK)
     assert eng.graph_form_info() == 0
@@ -152,7 +114,7 @@ def test_u_norm_monitor_of_the_ordered_form():
     from pinn_fem_amd.fem.solver import SolverConfig
     cfg = SolverConfig(max_iterations=200, tolerance=0.0, learning_rate_u=0.01, learning_rate_theta=5e-4,
                        alpha_physics=0.37, alpha_data=100.0)
-    model, mv, md = _path_model(4099, "zigzag")
+    model, mv, md = path_model(4099, "zigzag")
     eng = HipEngine(model, mv, md)
     eng.begin(None, 0.3, cfg, want_history=True)
     assert eng.graph_ordered_path() == 1
@@ -161,7 +123,7 @@ def test_u_norm_monitor_of_the_ordered_form():
     torch.cuda.synchronize()
     got = float(eng.history(2 * k)[2 * k - 2, 3])
     del eng
-    model, mv, md = _path_model(4099, "zigzag")
+    model, mv, md = path_model(4099, "zigzag")
     eng = HipEngine(model, mv, md)
     eng.begin(None, 0.3, cfg, want_history=True)
     eng.iterate(2 * k - 1, use_graph=False)
