@@ -493,6 +493,24 @@ int pf_gl_state_ea(const pf_problem* p, const pf_gl* g, const double* ea, const 
  * pf_gl_state's (pf_gl_state_ea's) bits.  A null e0 is PF_ERR_ARG, never a silent unstrained solve.  Additive: the
  * version stays 9. */
 int pf_gl_state_e0(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const double* u, void* stream);
+/* pf_gl_state* with tension-only (cable) elements, the static counterpart of pf_gl_dyn_*_cable and the same rule: an
+ * element with cable[e] != 0 and e - e0 < 0 (e - 0.0 where e0 is null; the subtraction of pf_gl_state_e0) is slack.  A
+ * slack element writes strain[e] = e, fe = +0.0 and a tangent block of +0.0 (0.0 is selected for N / l0 and for
+ * E*A / l0^3, a select on the value); every other element writes pf_gl_state*'s bits.  It is the bar kernel's <DIM, true>
+ * instantiation; the bar entry points launch <DIM, false>, untouched.  Whatever reads kt and fe follows (pf_gl_fint,
+ * pf_kt_v_f64, pf_kt_diag_f64, pf_pcgt_*, pf_pcg2t_*, pf_coarse_setup_t).
+ *   ea, e0  dev double [n_elems], each nullable as in pf_gl_state_e0 / pf_gl_state
+ *   cable   dev unsigned char [n_elems], 0 = a bar
+ *   slack   dev unsigned char [n_elems], in/out: on entry the set of the previous call (the caller clears it to start a
+ *           solve), on exit the current one (1 = slack)
+ *   counts  dev double [PF_GL_CABLE_COUNT]: counts[0] = the number of slack elements, counts[1] = the number of elements
+ *           whose flag differs from its entry value, exact integers; behind them the per-block partials they are the
+ *           fixed-order sums of (no atomics: the same bytes on every repeat)
+ * A null cable, slack or counts is PF_ERR_ARG, never a silent run of bars; nothing is enqueued on an error.  n_elems == 0
+ * writes zero counts.  Two launches on the stream.  Additive: the version stays 9, pf_gl and pf_problem are unchanged. */
+#define PF_GL_CABLE_COUNT (2 + 2 * PF_MAX_NODE_BLOCKS)
+int pf_gl_state_cable(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const unsigned char* cable,
+                      unsigned char* slack, double* counts, const double* u, void* stream);
 /* Sensitivity of a misfit J(u) to every element's E*A through the adjoint a (K_t(u) a = dJ/du on the free dofs, zero on
  * the fixed ones): s_e = -(e / l0) d.(a_j - a_i) with d = d0 + u_j - u_i and e the strain as pf_gl_state forms it.  It
  * does not contain E*A and reads g->d0 only.  out (dev double [n_elems]) = s (accumulate 0) or out + s (accumulate 1:
@@ -598,8 +616,8 @@ int pf_gl_dyn_energy(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, dou
  * point is its namesake above with `cable` right behind `dyn`, in kernels of its own (the bar's are untouched), and refuses
  * what the namesake refuses in the same way; a null cable is PF_ERR_ARG too, never a silent bar run.  pf_dyn is unchanged.
  * pf_gl_dyn_energy_cable: out5[0..3] as out4, the strain energy without the slack elements; out5[4] = the number of slack
- * elements at that state, an exact integer; out5: dev double [PF_DYN_CABLE_ENERGY_COUNT].  Only these four know cables:
- * pf_gl_state*, the Newton solve and the sensitivities stay bars.  Additive: the version stays 9. */
+ * elements at that state, an exact integer; out5: dev double [PF_DYN_CABLE_ENERGY_COUNT].  Of the dynamics only these four
+ * know cables; pf_gl_state_cable is the static counterpart, and the sensitivities stay bars.  Additive: the version stays 9. */
 #define PF_DYN_CABLE_ENERGY_COUNT (5 + 5 * PF_MAX_NODE_BLOCKS)
 int pf_gl_dyn_start_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const unsigned char* cable, void* stream);
 int pf_gl_dyn_steps_cable(const pf_problem* p, const pf_gl* g, const pf_dyn* dyn, const unsigned char* cable, int n_steps,

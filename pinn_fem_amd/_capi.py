@@ -30,6 +30,7 @@ PF_COARSE_MAX = PF_COARSE_MAX_AGG * PF_COARSE_MODES
 PF_PCG_MAX_RHS = 2
 PF_DYN_ENERGY_COUNT = 4 + 4 * PF_MAX_NODE_BLOCKS
 PF_DYN_CABLE_ENERGY_COUNT = 5 + 5 * PF_MAX_NODE_BLOCKS
+PF_GL_CABLE_COUNT = 2 + 2 * PF_MAX_NODE_BLOCKS
 PF_GRAPH_CONT_HEAD, PF_GRAPH_NO_TAIL = 1, 2
 PF_GRAPH_FORM_FOLDED_RESIDUAL = 1
 PF_FUSED_FORWARD, PF_FUSED_BACKWARD, PF_FUSED_THETA_UPDATE, PF_FUSED_U_PINGPONG, PF_FUSED_U_UPDATE = 1, 2, 4, 8, 16
@@ -188,6 +189,8 @@ SYMBOLS = {
     "pf_gl_state": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p]),
     "pf_gl_state_ea": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_gl_state_e0": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_gl_state_cable": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "pf_gl_sens": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_gl_sens_e0": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_group_sum_f64": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

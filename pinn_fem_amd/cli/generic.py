@@ -92,6 +92,10 @@ def parse_problem(problem_file):
     #                                                 N = E*A (e - e0); e0 < 0 pretension, alpha dT thermal, lack of fit
     #                                                 (L_natural - l0) / l0; in full at every load factor; the
     #                                                 .res.json gains "axial_forces"
+    #           "cable_elements": "all" | [ids]       tension-only elements of the green-lagrange Newton solve (load control):
+    #                                                 slack (e - e0 < 0) they carry nothing, and the solve iterates on the
+    #                                                 slack set; the .res.json gains "slack_elements" (the ids) and
+    #                                                 "axial_forces"; "dynamics" takes them as its own where it names none
     #           "identify_nr": {"groups": [...]|null, "levels": [{"load_factor": l, "dofs": [...], "u": [...]}, ...],
     #                           "max_evaluations": N, "method": "lbfgs"|"gauss-newton", "damping": mu}
     #                                                 identify one factor on E*A per group of elements (null: per element)
@@ -346,7 +350,12 @@ def _solver_config_from(data):
     is_number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
     if e0 is not None and not (is_number(e0) or (isinstance(e0, list) and all(is_number(v) for v in e0))):
         raise ValueError("accel.initial_strain must be a number or a list of n_elems numbers")
+    cables = accel.get("cable_elements")
+    if cables is not None and cables != "all" and not (isinstance(cables, list) and all(
+            isinstance(v, int) and not isinstance(v, bool) for v in cables)):
+        raise ValueError('accel.cable_elements must be "all" or a list of element ids')
     return SolverConfig(
+        cable_elements=cables,
         initial_strain=None if e0 is None else (float(e0) if is_number(e0) else [float(v) for v in e0]),
         nr_control="load" if control is None else "displacement",
         nr_control_dof=None if control is None else int(control["dof"]),
@@ -486,8 +495,10 @@ def solve_problem(parsed_data):
     }
     if result.path is not None:             # displacement control: (control displacement, load factor) per increment
         output["equilibrium_path"] = result.path
-    if result.axial_forces is not None and not compact:     # accel.initial_strain: N = E*A (e - e0) of every element
+    if result.axial_forces is not None and not compact:     # accel.initial_strain / cable_elements: N of every element
         output["axial_forces"] = result.axial_forces.tolist()
+    if result.slack is not None:            # accel.cable_elements: the ids of the slack elements at the final state
+        output["slack_elements"] = np.flatnonzero(result.slack).tolist()
     if compact:
         # §8(f) rank 1: at 10^6 nodes the reference's JSON lists (every coordinate three times per
         # property) would be hundreds of MB; arrays go to a side file, the JSON keeps the small fields
@@ -521,7 +532,7 @@ def _dynamics_problem(model, solver_config, block):
     from ..fem.dynamics import solve_dynamic
     res = solve_dynamic(model, solver_config, block["config"], u_initial=block["u_initial"], v_initial=block["v_initial"])
     log_print(f"Dynamics: {res.steps} steps of dt = {res.dt:.6g}, at rest: {res.at_rest}, residual {res.residual_norm:.3e}")
-    cables = ({} if block["config"].cable_elements is None
+    cables = ({} if block["config"].cable_elements is None and solver_config.cable_elements is None
               else {"slack_elements": np.flatnonzero(res.slack).tolist()})
     return {
         "success": True,

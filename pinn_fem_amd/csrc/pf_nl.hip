@@ -18,6 +18,9 @@
 // Element kernels, one element (or gauge) per thread, grid-stride:
 //   k_gl_state       strain, fe and B records out.  ea and e0 are nullable, the same decision in every thread; e - e0[e]
 //                    is formed once, after e, and takes e's place in N; the strain written out stays e.
+//                    The <DIM, true, gl_cable_set> instantiations apply the tension-only rule of the dynamics (below) to
+//                    N / l0 and E*A / l0^3 by a select, keep the slack set (in/out) and write per-block partials of the
+//                    number of slack elements and of changed flags; k_gl_cable_counts adds them in one block.
 //   k_gl_sens        dJ/d(E*A) from the state u and an adjoint a: -((e - e0) / l0) d.(a_j - a_i); may accumulate.
 //   k_gl_strain_jvp  (d_e / l0^2).(v_j - v_i) at the measured elements, the row of v in blockIdx.y; an element id outside
 //                    the mesh writes 0.0 and reads nothing.
@@ -78,10 +81,22 @@ __device__ __forceinline__ void load_gl_geo(const pf_mesh& M, const double* d0_i
   node_diff<DIM>(u, ni, nj, du);
 }
 
-template <int DIM>
+// what the CABLE instantiations of k_gl_state read and write beside the bar's operands
+struct gl_cable_set {
+  const unsigned char* __restrict__ cable;   // [n_elems] the tension-only flags
+  unsigned char* __restrict__ slack;         // [n_elems] in: the previous call's set; out: this call's (1 = slack)
+  double* __restrict__ part;                 // [gridDim.x][2] out: the block's slack elements and changed flags
+};
+
+// CABLE: an element with cable[e] != 0 and e - e0 < 0 is slack (the rule of dyn_term): it carries no N and no E*A, by a
+// select on the value, so its fe and kt are +0.0 and its strain stays e; every other element keeps the bar's values.
+// SET: empty, or gl_cable_set and one more operand (the <DIM, false> instantiations are the bar kernels, untouched).
+template <int DIM, bool CABLE, class... SET>
 __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const double* __restrict__ u,
-                                                  const double* __restrict__ ea_in, const double* __restrict__ e0_in) {
+                                                  const double* __restrict__ ea_in, const double* __restrict__ e0_in,
+                                                  SET... set) {
   const pf_mesh& M = P.mesh;
+  [[maybe_unused]] double n_slack = 0.0, n_changed = 0.0;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < M.n_elems; e += gridDim.x * blockDim.x) {
     int ni, nj;
     double d0[DIM], du[DIM];
@@ -98,18 +113,46 @@ __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const d
     double d[DIM];
 #pragma unroll
     for (int c = 0; c < DIM; ++c) d[c] = d0[c] + du[c];
+    // CABLE selects +0.0 for every value a slack element stores (on the stored values: 0.0 for N / l0 and E*A / l0^3 alone
+    // would leave them the signs of d); the bar's `put` is the identity
+    [[maybe_unused]] bool slack = false;
+    if constexpr (CABLE) {
+      const gl_cable_set& S = (set, ...);
+      slack = S.cable[e] && se < 0.0;
+      n_slack += slack ? 1.0 : 0.0;
+      n_changed += (S.slack[e] != 0) != slack ? 1.0 : 0.0;
+      S.slack[e] = slack ? 1 : 0;
+    }
+    const auto put = [&](double x) { return CABLE && slack ? 0.0 : x; };
     G.strain[e] = strain;
     if (DIM == 2) {
-      reinterpret_cast<double2*>(G.fe)[e] = make_double2(n_l0 * d[0], n_l0 * d[DIM - 1]);
+      reinterpret_cast<double2*>(G.fe)[e] = make_double2(put(n_l0 * d[0]), put(n_l0 * d[DIM - 1]));
       double* __restrict__ b = G.kt + 3 * (size_t)e;
-      b[0] = k * (d[0] * d[0]) + n_l0;
-      b[1] = k * (d[0] * d[DIM - 1]);
-      b[2] = k * (d[DIM - 1] * d[DIM - 1]) + n_l0;
+      b[0] = put(k * (d[0] * d[0]) + n_l0);
+      b[1] = put(k * (d[0] * d[DIM - 1]));
+      b[2] = put(k * (d[DIM - 1] * d[DIM - 1]) + n_l0);
     } else {
-      G.fe[e] = n_l0 * d[0];
-      G.kt[e] = k * (d[0] * d[0]) + n_l0;
+      G.fe[e] = put(n_l0 * d[0]);
+      G.kt[e] = put(k * (d[0] * d[0]) + n_l0);
     }
   }
+  if constexpr (CABLE) {
+    __shared__ double red[8];
+    const gl_cable_set& S = (set, ...);
+    const double s0 = pf_block_sum_d(n_slack, red), s1 = pf_block_sum_d(n_changed, red);     // exact integers
+    if (threadIdx.x == 0) { S.part[2 * (size_t)blockIdx.x] = s0; S.part[2 * (size_t)blockIdx.x + 1] = s1; }
+  }
+}
+
+// counts[0..1] = the sums of the nb block partials behind them (counts + 2), thread t adding blocks t, t + 256, ... in that
+// order: k_gl_dyn_energy_sum's pattern
+__global__ __launch_bounds__(256) void k_gl_cable_counts(double* __restrict__ counts, int nb) {
+  __shared__ double red[8];
+  const double* __restrict__ part = counts + 2;
+  double a0 = 0.0, a1 = 0.0;
+  for (int b = (int)threadIdx.x; b < nb; b += (int)blockDim.x) { a0 += part[2 * b]; a1 += part[2 * b + 1]; }
+  const double s0 = pf_block_sum_d(a0, red), s1 = pf_block_sum_d(a1, red);
+  if (threadIdx.x == 0) { counts[0] = s0; counts[1] = s1; }
 }
 
 template <int DIM>
@@ -531,7 +574,7 @@ int gl_state(const char* who, const pf_problem* p, const pf_gl* g, const double*
              void* stream) {
   if (!mesh_ok(p) || !g || !g->d0 || !g->kt || !g->fe || !g->strain || !u) return gl_fail(PF_ERR_ARG, who, "bad argument");
   if (p->mesh.n_elems == 0) return PF_OK;
-  return launch(who, p, k_gl_state<2>, k_gl_state<1>, dim3(elem_blocks(p->mesh.n_elems)), stream, *g, u, ea, e0);
+  return launch(who, p, k_gl_state<2, false>, k_gl_state<1, false>, dim3(elem_blocks(p->mesh.n_elems)), stream, *g, u, ea, e0);
 }
 
 int gl_sens(const char* who, const pf_problem* p, const pf_gl* g, const double* e0, const double* u, const double* a,
@@ -724,6 +767,26 @@ int pf_gl_state_ea(const pf_problem* p, const pf_gl* g, const double* ea, const 
 int pf_gl_state_e0(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const double* u, void* stream) {
   if (!e0) return gl_fail(PF_ERR_ARG, "pf_gl_state_e0", "null e0 (pf_gl_state / pf_gl_state_ea are the unstrained solves)");
   return gl_state("pf_gl_state_e0", p, g, ea, e0, u, stream);
+}
+
+int pf_gl_state_cable(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const unsigned char* cable,
+                      unsigned char* slack, double* counts, const double* u, void* stream) {
+  const char* who = "pf_gl_state_cable";
+  if (!cable || !slack || !counts)
+    return gl_fail(PF_ERR_ARG, who, "null cable, slack or counts (pf_gl_state / pf_gl_state_ea / pf_gl_state_e0 are the run of bars)");
+  if (!mesh_ok(p) || !g || !g->d0 || !g->kt || !g->fe || !g->strain || !u) return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (p->mesh.n_elems == 0) {
+    if (hipMemsetAsync(counts, 0, 2 * sizeof(double), (hipStream_t)stream) != hipSuccess)
+      return gl_fail(PF_ERR_HIP, who, "clearing the counts failed");
+    return PF_OK;
+  }
+  const int nb = elem_blocks(p->mesh.n_elems);
+  const gl_cable_set set{cable, slack, counts + 2};
+  if (const int rc = launch(who, p, k_gl_state<2, true, gl_cable_set>, k_gl_state<1, true, gl_cable_set>, dim3(nb), stream, *g,
+                            u, ea, e0, set))
+    return rc;
+  hipLaunchKernelGGL(k_gl_cable_counts, dim3(1), dim3(256), 0, (hipStream_t)stream, counts, nb);
+  return launched(who);
 }
 
 int pf_gl_sens(const pf_problem* p, const pf_gl* g, const double* u, const double* a, int accumulate, double* out,

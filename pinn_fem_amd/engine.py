@@ -226,6 +226,7 @@ class HipEngine:
         self.pcg_batch_solves = 0       # pcg_solve_batch calls so far
         self._fixed_views = {}          # extra fixed dofs (tuple) -> (device dof_flags copy, PfProblem view, host fixed mask)
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
+        self._gl_cable = None           # gl_state_cable: [device flags, slack set, counts, whether a cable state has run]
         self._dyn = None                # explicit dynamics: buffers, pf_dyn record, step count and graphs of the run (dyn_begin)
         self._group_csr = None          # group_sum: (key of the group map, n_groups, device CSR pointer, device element ids)
         self._group_maps = {}           # _device_group_map: method name -> (key of its last map, n_groups, device int32 ids)
@@ -687,6 +688,57 @@ class HipEngine:
         return self._gl[3][: self.plan.n_elems]
 
     @_on_engine_stream
+    def gl_state_cable(self, u: torch.Tensor, cable, ea: Optional[torch.Tensor] = None,
+                       e0: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gl_state with tension-only elements (pf_gl_state_cable).  cable: bool or uint8 [n_elems]; a flagged element with
+        e - e0 < 0 is slack, its force and tangent block are +0.0.  ea, e0: as gl_state's.  The engine owns the slack set and
+        its counts: gl_slack_counts() and gl_slack_mask() read those of the last call, gl_slack_clear() empties the set at the
+        start of a solve.  Returns the total strains e [n_elems], the buffer gl_state returns.  (A method of its own:
+        gl_state keeps its parameters and its calls.)"""
+        who = "gl_state_cable"
+        uu = self._f64_vector(who, "u", u, self.plan.n_dofs, "dofs")
+        rec = self._gl_buffers()[4]
+        ee = None if ea is None else self._f64_vector(who, "ea", ea, self.plan.n_elems, "elements")
+        zz = None if e0 is None else self._f64_vector(who, "e0", e0, self.plan.n_elems, "elements")
+        c = self._gl_cable_buffers()
+        c[0] = self._cable_flags(cable, self.plan.n_elems, who)
+        flags = c[0] if self.plan.n_elems else c[1]         # (an empty mesh: any non-null pointer, nothing reads it)
+        _capi.check(self.lib.pf_gl_state_cable(self._ref(), C.byref(rec), None if ee is None else ee.data_ptr(),
+                                               None if zz is None else zz.data_ptr(), flags.data_ptr(), c[1].data_ptr(),
+                                               c[2].data_ptr(), uu.data_ptr(), self._stream()), "pf_gl_state_cable")
+        c[3] = True
+        return self._gl[3][: self.plan.n_elems]
+
+    def _gl_cable_buffers(self):
+        if self._gl_cable is None:
+            slack = torch.zeros(max(self.plan.n_elems, 1), dtype=torch.uint8, device=self.device)
+            counts = torch.zeros(_capi.PF_GL_CABLE_COUNT, dtype=torch.float64, device=self.device)
+            self._gl_cable = [None, slack, counts, False]
+        return self._gl_cable
+
+    def _gl_cable_ready(self, who):
+        if self._gl_cable is None or not self._gl_cable[3]:
+            raise RuntimeError(f"{who}: no cable state yet; call gl_state_cable(u, cable) first")
+        return self._gl_cable
+
+    @_on_engine_stream
+    def gl_slack_clear(self):
+        """Empty the slack set gl_state_cable keeps: the start of a solve."""
+        self._gl_cable_buffers()[1].zero_()
+
+    @_on_engine_stream
+    def gl_slack_counts(self):
+        """(number of slack elements, number of elements whose flag changed against the set before) of the last
+        gl_state_cable: one read of 16 bytes."""
+        n = self._gl_cable_ready("gl_slack_counts")[2][:2].cpu()
+        return int(n[0]), int(n[1])
+
+    @_on_engine_stream
+    def gl_slack_mask(self) -> np.ndarray:
+        """The slack elements of the last gl_state_cable, bool [n_elems] on the host."""
+        return self._gl_cable_ready("gl_slack_mask")[1][: self.plan.n_elems].cpu().numpy().astype(bool)
+
+    @_on_engine_stream
     def gl_sensitivity(self, u: torch.Tensor, a: torch.Tensor, out: Optional[torch.Tensor] = None,
                        e0: Optional[torch.Tensor] = None) -> torch.Tensor:
         """dJ/d(E*A) of every element [n_elems] from the displacements u and the adjoint a of a misfit J (K_t(u) a =
@@ -903,10 +955,10 @@ class HipEngine:
             self._dyn_call(d, "pf_gl_dyn_start", self._stream())
             d["n"] = 1
 
-    def _cable_flags(self, cable, ne):
+    def _cable_flags(self, cable, ne, who="dyn_begin"):
         flags = cable if isinstance(cable, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cable))
         if flags.dtype not in (torch.bool, torch.uint8) or flags.dim() != 1 or flags.numel() != ne:
-            raise ValueError(f"dyn_begin: cable must be bool or uint8 [{ne}] (one flag for each element), got "
+            raise ValueError(f"{who}: cable must be bool or uint8 [{ne}] (one flag for each element), got "
                              f"{flags.dtype} {tuple(flags.shape)}")
         return flags.to(device=self.device, dtype=torch.uint8)
 

@@ -9,8 +9,9 @@ It follows a structure through a limit point of the load, where solve_nr refuses
 Material.density.  Scalar materials, one GPU, dimension 1 and 2.
 
 Tension-only (cable) elements, DynamicsConfig.cable_elements: a flagged element with e - e0 < 0 is slack and carries N = 0, no
-force and no strain energy (pf_gl_dyn_*_cable).  Only this module knows cables; a damped run with rest_tolerance comes to rest
-on the equilibrium of the structure without its slack elements.
+force and no strain energy (pf_gl_dyn_*_cable).  A damped run with rest_tolerance comes to rest on the equilibrium of the
+structure without its slack elements (solve_nr with SolverConfig.cable_elements reaches it by an active-set Newton iteration;
+where DynamicsConfig.cable_elements is None, solve_dynamic takes the cables flagged there).
 
 Time histories, DynamicsConfig.load_history and .support_motion: lam(t) and the scale s(t) of prescribed support displacements
 u[dof](t) = amplitude s(t), each a table (piecewise linear) or a callable.  The host samples them once at the step times
@@ -26,7 +27,8 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .solver import (SolverConfig, _axial_forces, _newton_setup, _world_size, check_initial_strain, check_kinematics)
+from .solver import (SolverConfig, _axial_forces, _newton_setup, _world_size, cable_mask, check_initial_strain,  # noqa: F401
+                     check_kinematics)
 
 # steps of one captured hipGraph: a record interval longer than this is replayed in pieces
 GRAPH_STEPS = 500
@@ -46,7 +48,8 @@ class DynamicsConfig:
     record_dofs: Optional[List[int]] = None     # the dofs whose displacements are recorded; None: all of them
     nodal_mass: Optional[object] = None     # a mass added at every node (a number) or one for each node
     rest_tolerance: Optional[float] = None  # stop at a record point with kinetic energy <= this x the largest recorded
-    cable_elements: Optional[object] = None     # the tension-only elements: "all" or a list of element ids; None or []: all bars
+    cable_elements: Optional[object] = None     # the tension-only elements: "all" or a list of element ids; None: those of
+                                            # SolverConfig.cable_elements; [] (or None there too): all bars
     load_history: Optional[object] = None   # lam(t) in place of the ramp: a pair (times, values) or a callable (history_samples);
                                             # ramp_time and load_factor_initial / _final must then be at their defaults
     support_motion: Optional["SupportMotion"] = None    # fixed dofs that follow a prescribed displacement
@@ -97,31 +100,20 @@ def _nodes_with_a_free_dof(model) -> np.ndarray:
     return free.reshape(model.nnode, model.dimension).any(axis=1)
 
 
-def cable_mask(model, cable_elements) -> Optional[np.ndarray]:
-    """DynamicsConfig.cable_elements as a bool [n_elems], or None where nothing is flagged (None, an empty list).  Anything
-    else than "all" or a list of distinct element ids is a ValueError."""
-    ne = int(model.nelm)
-    if cable_elements is None:
-        return None
-    if isinstance(cable_elements, str):
-        if cable_elements != "all":
-            raise ValueError(f'cable_elements must be "all" or a list of element ids, got {cable_elements!r}')
-        return np.ones(ne, dtype=bool) if ne else None
-    try:
-        ids = np.asarray(cable_elements)
-    except (TypeError, ValueError):
-        raise ValueError('cable_elements must be "all" or a list of element ids') from None
-    if ids.ndim != 1 or (ids.size and (ids.dtype.kind not in "iu")):
-        raise ValueError(f"cable_elements must be a list of integer element ids in 0..{ne - 1}")
-    if ids.size == 0:
-        return None
-    if ids.min() < 0 or ids.max() >= ne:
-        raise ValueError(f"cable_elements must be element ids in 0..{ne - 1}, got {int(ids.min())}..{int(ids.max())}")
-    if np.unique(ids).size != ids.size:
-        raise ValueError("cable_elements names an element twice")
-    mask = np.zeros(ne, dtype=bool)
-    mask[ids.astype(np.int64)] = True
-    return mask
+def dynamic_cables(model, config: SolverConfig, dyn: "DynamicsConfig") -> Optional[np.ndarray]:
+    """The tension-only elements of a dynamic run as cable_mask's bool [n_elems] or None: dyn.cable_elements when it is
+    given, otherwise config.cable_elements, so a structure's cables are flagged once.  Both given and different is a
+    ValueError."""
+    own = cable_mask(model, dyn.cable_elements)
+    inherited = cable_mask(model, getattr(config, "cable_elements", None))
+    if dyn.cable_elements is None:
+        return inherited
+    if getattr(config, "cable_elements", None) is not None and not np.array_equal(
+            np.zeros(model.nelm, dtype=bool) if own is None else own,
+            np.zeros(model.nelm, dtype=bool) if inherited is None else inherited):
+        raise ValueError("DynamicsConfig.cable_elements and SolverConfig.cable_elements name different elements: give the "
+                         "cables once, or the same set twice")
+    return own
 
 
 def history_samples(history, t: np.ndarray, what: str = "history") -> np.ndarray:
@@ -230,7 +222,7 @@ def check_dynamics(model, config: SolverConfig, dyn: DynamicsConfig) -> np.ndarr
             raise ValueError(f"nodal_mass must be a number or {model.nnode} numbers (one for each node)") from None
         if arr.ndim > 1 or (arr.ndim == 1 and arr.size != model.nnode) or not np.all(np.isfinite(arr)) or np.any(arr < 0.0):
             raise ValueError(f"nodal_mass must be a non-negative number or {model.nnode} of them (one for each node)")
-    cable_mask(model, dyn.cable_elements)
+    dynamic_cables(model, config, dyn)
     if dyn.load_history is not None:
         if (dyn.ramp_time, dyn.load_factor_initial, dyn.load_factor_final) != (0.0, 0.0, 1.0):
             raise ValueError("load_history takes the place of the ramp: ramp_time, load_factor_initial and load_factor_final "
@@ -301,7 +293,7 @@ def solve_dynamic(model, config: SolverConfig, dyn: DynamicsConfig, u_initial=No
     fixed dof)."""
     mass = check_dynamics(model, config, dyn)
     e0_np = check_initial_strain(config, model)
-    cable = cable_mask(model, dyn.cable_elements)
+    cable = dynamic_cables(model, config, dyn)
     s = _newton_setup(model, e0_np, u_initial)
     eng, dev, ndof = s.eng, s.eng.device, model.ndof
     v0 = torch.zeros(ndof, dtype=torch.float64, device=dev)

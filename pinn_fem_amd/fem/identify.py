@@ -90,6 +90,8 @@ def check_identify(model: FEMModel, config: SolverConfig, levels, groups=None, q
                          "E*A override (its stiffness is the model's own); solve_gd identifies on the linear element.")
     if _solver.check_control(config, model) == "displacement":
         raise ValueError("identification runs under load control only: nr_control 'displacement' is not supported.")
+    if _solver.cable_mask(model, getattr(config, "cable_elements", None)) is not None:
+        raise ValueError("identification does not support cable_elements: the sensitivities treat every element as a bar.")
     if model.material.has_trainable_params():
         raise ValueError("identification needs scalar materials (no NN parameters): the base E*A is the model's scalar one.")
     if _solver._world_size() > 1:

@@ -66,6 +66,10 @@ class SolverConfig:
     # values, a Green-Lagrange strain e0 with N = E*A (e - e0).  e0 < 0 is a pretension (T = -E*A e0), thermal loading is
     # e0 = alpha dT, lack of fit e0 = (L_natural - l0) / l0.  It acts in full at every load factor
     initial_strain: Optional[object] = None
+    # the tension-only (cable) elements of the Green-Lagrange solve_nr: None, "all" or a list of element ids (cable_mask).
+    # A flagged element with e - e0 < 0 is slack and carries nothing; the Newton loop iterates on the slack set
+    # (_newton_loop).  solve_dynamic takes its cables from here when DynamicsConfig.cable_elements is not given
+    cable_elements: Optional[object] = None
 
 
 KINEMATICS = ("linear", "green-lagrange")
@@ -151,6 +155,56 @@ def check_initial_strain(config, model):
     return arr
 
 
+def cable_mask(model, cable_elements) -> Optional[np.ndarray]:
+    """SolverConfig.cable_elements / DynamicsConfig.cable_elements as a bool [n_elems], or None where nothing is flagged
+    (None, an empty list).  Anything else than "all" or a list of distinct element ids is a ValueError."""
+    ne = int(model.nelm)
+    if cable_elements is None:
+        return None
+    if isinstance(cable_elements, str):
+        if cable_elements != "all":
+            raise ValueError(f'cable_elements must be "all" or a list of element ids, got {cable_elements!r}')
+        return np.ones(ne, dtype=bool) if ne else None
+    try:
+        ids = np.asarray(cable_elements)
+    except (TypeError, ValueError):
+        raise ValueError('cable_elements must be "all" or a list of element ids') from None
+    if ids.ndim != 1 or (ids.size and (ids.dtype.kind not in "iu")):
+        raise ValueError(f"cable_elements must be a list of integer element ids in 0..{ne - 1}")
+    if ids.size == 0:
+        return None
+    if ids.min() < 0 or ids.max() >= ne:
+        raise ValueError(f"cable_elements must be element ids in 0..{ne - 1}, got {int(ids.min())}..{int(ids.max())}")
+    if np.unique(ids).size != ids.size:
+        raise ValueError("cable_elements names an element twice")
+    mask = np.zeros(ne, dtype=bool)
+    mask[ids.astype(np.int64)] = True
+    return mask
+
+
+def check_cables(config, model, method: str = "nr"):
+    """config.cable_elements as cable_mask's bool [n_elems], or None when nothing is flagged.  Cables belong to the
+    Green-Lagrange Newton solve under load control, with scalar materials on one GPU: everything else is a ValueError
+    before an engine is built."""
+    cable = cable_mask(model, getattr(config, "cable_elements", None))
+    if cable is None:
+        return None
+    if config.kinematics != "green-lagrange":
+        raise ValueError("cable_elements needs kinematics 'green-lagrange': solve_gd and the linear solve_nr know no "
+                         "tension-only element and would silently solve the structure of bars.")
+    if method not in ("nr", "hybrid"):
+        raise ValueError(f"cable_elements belongs to the Green-Lagrange Newton solve (solve_nr): method {method!r} is "
+                         "untouched by it.")
+    if getattr(config, "nr_control", "load") == "displacement":
+        raise ValueError("cable_elements does not support nr_control 'displacement': there is no displacement control "
+                         "with cables; use load control (solve()'s increments) or solve_dynamic.")
+    if model.material.has_trainable_params():
+        raise ValueError("cable_elements needs scalar materials (no NN parameters).")
+    if _world_size() > 1:
+        raise ValueError("cable_elements does not support a sharded (multi-GPU) run.")
+    return cable
+
+
 def _axial_forces(model, strain, e0):
     """N = E*A (e - e0) of every element on the host, from the strains a gl_state returned; E*A is the model's scalar one
     as the device forms it (each factor rounded to float32 first)."""
@@ -176,8 +230,11 @@ class SolverResult:
     # displacement control (solve() with nr_control = "displacement"): one {control_displacement, load_factor,
     # iterations} per increment, the equilibrium path; None otherwise
     path: Optional[list] = None
-    # Green-Lagrange solve_nr with config.initial_strain: N = E*A (e - e0) of every element at the final state; None
-    # otherwise
+    # Green-Lagrange solve_nr with config.cable_elements: bool [n_elems], the slack elements at the final state; None
+    # without cables
+    slack: Optional[np.ndarray] = None
+    # Green-Lagrange solve_nr with config.initial_strain or config.cable_elements: N = E*A (e - e0) of every element at
+    # the final state, 0.0 in a slack cable; None otherwise
     axial_forces: Optional[np.ndarray] = None
 
 
@@ -427,13 +484,14 @@ class _NewtonSetup(NamedTuple):
     e0_np: Optional[np.ndarray]             # check_initial_strain's array, or None
     e0: Optional[torch.Tensor]              # the same on the device
     u: torch.Tensor                         # the start vector, float64 [n_dofs] on the device, zero on the fixed dofs
+    cable: Optional[torch.Tensor] = None    # check_cables' flags on the device (uint8 [n_elems]), or None: all bars
 
 
-def _newton_setup(model, e0_np, u_initial=None) -> _NewtonSetup:
+def _newton_setup(model, e0_np, u_initial=None, cable_np=None) -> _NewtonSetup:
     """The one host setup of solve_nr under either control and of fem/identify.py.  e0_np: check_initial_strain's
     result; like every check_* it is the caller's to run first, this is where the engine is built.  u_initial: a tensor
-    or an array [n_dofs] (its fixed dofs are ignored); None: zeros.  It launches nothing but torch's own copies and
-    fills; _pre_check is the first to touch the kernels."""
+    or an array [n_dofs] (its fixed dofs are ignored); None: zeros.  cable_np: check_cables' result.  It launches nothing
+    but torch's own copies and fills; _pre_check is the first to touch the kernels."""
     eng = _engine_for(model, None, None)
     dev, ndof = eng.device, model.ndof
     free = _free_mask(model)
@@ -446,7 +504,15 @@ def _newton_setup(model, e0_np, u_initial=None) -> _NewtonSetup:
         u[torch.from_numpy(~free).to(dev)] = 0.0
     loads = torch.from_numpy(np.ascontiguousarray(np.asarray(model.loads, dtype=float).reshape(-1))).to(dev)
     return _NewtonSetup(eng, free, torch.from_numpy(free).to(dev), loads, e0_np,
-                        None if e0_np is None else torch.from_numpy(e0_np).to(dev), u)
+                        None if e0_np is None else torch.from_numpy(e0_np).to(dev), u,
+                        None if cable_np is None else torch.from_numpy(cable_np.astype(np.uint8)).to(dev))
+
+
+def _gl_state(s: _NewtonSetup, u, ea=None):
+    """The element state of a Newton solve at u: the cable state where the setup carries flags, the bar state otherwise."""
+    if s.cable is not None:
+        return s.eng.gl_state_cable(u, s.cable, ea, s.e0)
+    return s.eng.gl_state(u, ea, s.e0)
 
 
 def _pre_check(s: _NewtonSetup, ea=None, held=()):
@@ -455,12 +521,15 @@ def _pre_check(s: _NewtonSetup, ea=None, held=()):
     there (solver.py:462-467).  With initial strains the geometric stiffness may be all that holds a dof (a taut
     string), so the tangent at the starting state decides, not the linear diagonal: it must be positive on every free
     dof that is not held (a free dof that only a slack or compressed member holds is a mechanism).  That branch leaves
-    the gl_state of (s.u, ea, s.e0) on the engine."""
-    if s.e0 is None:
+    the gl_state of (s.u, ea, s.e0) on the engine.  With cable flags it is taken too, with or without e0, on the cable
+    state from a cleared slack set: an unstrained cable at u = 0 has e - e0 = 0, is taut and counts with its bar block."""
+    if s.e0 is None and s.cable is None:
         if bool((s.eng.diag_k().cpu().numpy()[s.free] == 0.0).any()):
             raise RuntimeError("Tangent stiffness became singular during solve")
         return
-    s.eng.gl_state(s.u, ea, s.e0)
+    if s.cable is not None:
+        s.eng.gl_slack_clear()
+    _gl_state(s, s.u, ea)
     dg = s.eng.kt_diag().cpu().numpy()
     free = s.free.copy()
     free[list(held)] = False
@@ -475,13 +544,30 @@ def _newton_loop(s, model, config, f_ext, u, green_lagrange, ea=None):
     """The Newton iteration of solve_nr from u at the load f_ext: u += K^-1 (f_ext - f_int(u)) by CG until
     |du| / max(|u|, min_denominator) <= tolerance.  s: the _newton_setup (its engine, free mask and initial strain);
     ea (Green-Lagrange only): E*A of every element in place of the model's (fem/identify.py).  Returns (u, converged,
-    |du|/|u|, max strain of the linear branch, index of the last iteration, CG iterations)."""
+    |du|/|u|, max strain of the linear branch, index of the last iteration, CG iterations).
+
+    With s.cable (tension-only elements) it is an active-set (semismooth) Newton iteration: every iteration forms the
+    cable state at u (pf_gl_state_cable: a flagged element with e - e0 < 0 is slack, no force and no tangent block),
+    solves with its tangent and reads the two counts the kernel leaves, 16 bytes.  It has converged when the
+    displacement test holds AND the slack set of this iteration's state is the one of the state before (the first
+    iteration's count against the cleared set does not count).  There is no line search and no damping: a set that keeps
+    changing runs to max_iterations and returns converged = False like any other solve that does not converge, and
+    solve()'s load increments (n_increments) are the remedy.  Whenever the set changed, the tangent's diagonal is read
+    before the CG solve: a free dof that only slack cables hold is a mechanism and raises RuntimeError."""
     eng = s.eng
     has_converged, residual_norm, max_e, ite = False, float("inf"), 0.0, -1
     cg0 = eng.pcg_iterations
+    if s.cable is not None:
+        eng.gl_slack_clear()
     for ite in range(config.max_iterations):
+        set_changed = False
         if green_lagrange:
-            eng.gl_state(u, ea, s.e0)       # the history's max |e| is read once, from the state at the final u
+            _gl_state(s, u, ea)                     # the history's max |e| is read once, from the state at the final u
+            if s.cable is not None:
+                n_changed = eng.gl_slack_counts()[1]
+                if n_changed:
+                    _check_slack_mechanism(s, ite)
+                set_changed = ite > 0 and n_changed > 0
             rhs = f_ext - eng.gl_fint()
             du, _, ok, rr, bb = eng.pcg_solve(rhs, tangent=True, preconditioner=config.nr_preconditioner,
                                              n_aggregates=config.nr_aggregates, u=u)
@@ -493,10 +579,22 @@ def _newton_loop(s, model, config, f_ext, u, green_lagrange, ea=None):
         _check_cg_step(green_lagrange, rhs, du, ok, rr, bb, s.free_t)
         u = u + du
         residual_norm = float(torch.linalg.norm(du)) / max(float(torch.linalg.norm(u)), config.min_denominator)
-        if residual_norm <= config.tolerance:
+        if residual_norm <= config.tolerance and not set_changed:
             has_converged = True
             break
     return u, has_converged, residual_norm, max_e, ite, eng.pcg_iterations - cg0
+
+
+def _check_slack_mechanism(s, ite):
+    """After a change of the slack set: the tangent of the cable state on the engine must keep a positive diagonal on
+    every free dof (_pre_check's rule; one launch and one read)."""
+    dg = s.eng.kt_diag().cpu().numpy()
+    bad = np.flatnonzero(s.free & ~(dg > 0.0))
+    if bad.size:
+        raise RuntimeError(f"Tangent stiffness is not positive definite in Newton iteration {ite + 1}: its diagonal is "
+                           f"{dg[bad[0]]:.6g} at free dof {int(bad[0])}, which only slack cables hold (a mechanism; "
+                           f"{bad.size} such dof{'s' if bad.size > 1 else ''}).  The static solve cannot carry a "
+                           "structure through a slack mechanism: use solve_dynamic with rest_tolerance")
 
 
 # what load control says when _check_cg_step refuses a solve: (the residual does not come down, rhs.x <= 0)
@@ -544,10 +642,17 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     config.initial_strain (Green-Lagrange only; check_initial_strain) gives every element an eigenstrain e0,
     N = E*A (e - e0): it goes into every gl_state call, in full at every load factor, the pre-check then reads the tangent's
     diagonal at the starting state (a free dof with a diagonal <= 0 raises RuntimeError "... not positive definite ...")
-    and the result carries axial_forces."""
+    and the result carries axial_forces.
+
+    config.cable_elements (Green-Lagrange, load control only; check_cables) flags tension-only elements: the Newton loop
+    iterates on the slack set (_newton_loop), the closing state is the cable state, and the result carries slack (bool
+    [n_elems]) and axial_forces with 0.0 on the slack elements; the history row counts them ("slack_elements").  An
+    element that flips in the closing state has a force of zero within the tolerance; nothing more is iterated.  A set
+    that does not settle returns converged = False: use solve() with more increments."""
     config = config or SolverConfig()
     green_lagrange = check_kinematics(config.kinematics, config.nr_preconditioner) == "green-lagrange"
     e0_np = check_initial_strain(config, model)
+    cable_np = check_cables(config, model)
     if check_control(config, model) == "displacement":
         return _solve_nr_displacement(model, config, target_load_factor, u_initial, e0_np)
     if model.material.has_trainable_params():
@@ -556,23 +661,28 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     if green_lagrange:
         if _world_size() > 1:
             raise ValueError("kinematics 'green-lagrange' does not support a sharded (multi-GPU) run.")
-    s = _newton_setup(model, e0_np, u_initial if green_lagrange else None)
+    s = _newton_setup(model, e0_np, u_initial if green_lagrange else None, cable_np)
     _pre_check(s)
     eng, load_factor = s.eng, target_load_factor
     f_ext = float(load_factor) * s.loads
     u, has_converged, residual_norm, max_e, ite, _ = _newton_loop(s, model, config, f_ext, s.u, green_lagrange)
-    axial = None
+    axial = slack = None
     if green_lagrange:
-        strain = eng.gl_state(u, None, s.e0)          # state at the final u: its strain, and f_int for the reactions
+        strain = _gl_state(s, u)                          # state at the final u: its strain, and f_int for the reactions
         max_e = float(strain.abs().max()) if model.nelm else 0.0
         reactions = (eng.gl_fint() - f_ext).cpu().numpy()
-        if s.e0 is not None:
-            axial = _axial_forces(model, strain, s.e0_np)
+        if s.e0 is not None or s.cable is not None:
+            axial = _axial_forces(model, strain, 0.0 if s.e0_np is None else s.e0_np)
+        if s.cable is not None:
+            slack = eng.gl_slack_mask()
+            axial = np.where(slack, 0.0, axial)
     else:
         reactions = (eng.kv_f64(u) - f_ext).cpu().numpy()
     history = [{"load_factor": float(load_factor), "iterations": float(ite + 1), "residual": float(residual_norm),
                 "max_strain": float(max_e), "converged": float(1.0 if has_converged else 0.0)}]
-    return _result(model, u.cpu().numpy(), reactions, s.free, has_converged, history, axial_forces=axial)
+    if slack is not None:
+        history[-1]["slack_elements"] = float(slack.sum())
+    return _result(model, u.cpu().numpy(), reactions, s.free, has_converged, history, axial_forces=axial, slack=slack)
 
 
 def _solve_nr_displacement(model, config, control_factor, u_initial, e0_np=None) -> SolverResult:
@@ -695,6 +805,7 @@ def solve_hybrid(
     config = config or SolverConfig()
     check_kinematics(config.kinematics, config.nr_preconditioner)
     check_control(config, method="hybrid")
+    check_cables(config, model, "hybrid")
     _say("=== HYBRID SOLVER ===")
     _say(f"Target load factor: {target_load_factor}")
     gd_result = None
@@ -780,6 +891,7 @@ def solve(
     if check_initial_strain(config, model) is not None and method in ("gd", "full-nr"):
         raise ValueError(f"initial_strain belongs to the Green-Lagrange Newton solve (solve_nr): method {method!r} is "
                          "untouched by it.")
+    check_cables(config, model, method)
     path = [] if displacement_control else None
     _say(f"\n{'Inc':>4} | {'Load Factor':>12} | {'Status':>10}")
     _say("-" * 40)
