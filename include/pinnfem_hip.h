@@ -511,6 +511,51 @@ int pf_gl_state_e0(const pf_problem* p, const pf_gl* g, const double* ea, const 
 #define PF_GL_CABLE_COUNT (2 + 2 * PF_MAX_NODE_BLOCKS)
 int pf_gl_state_cable(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const unsigned char* cable,
                       unsigned char* slack, double* counts, const double* u, void* stream);
+/* pf_gl_state* with elastoplastic elements: one-dimensional rate-independent plasticity with linear isotropic hardening,
+ * written in the Green-Lagrange strain and its conjugate force.  Per element, with ey > 0 the yield strain
+ * sigma_y / E (+inf: the element never yields), kappa >= 0 the hardening ratio H / E and (ep_n, al_n) the committed
+ * plastic strain and accumulated plastic strain:
+ *   e    as pf_gl_state forms it;  se = e - e0 (e0 nullable, as pf_gl_state_e0)
+ *   tr   = se - ep_n
+ *   r    = ey + kappa * al_n
+ *   f    = |tr| - r
+ *   plastic  <=>  f > 2^-40 * r
+ *   dg   = plastic ? f / (1 + kappa) : 0 ;   sg = tr < 0 ? -1 : +1
+ *   ep   = plastic ? ep_n + dg * sg : ep_n        al = plastic ? al_n + dg : al_n
+ *   s    = plastic ? tr - dg * sg   : tr          (the strain that carries stress)
+ *   N    = E*A * s ;  fe = (N / l0) d
+ *   B    = (E*A_t / l0^3) d d^T + (N / l0) I ,  E*A_t = plastic ? E*A * kappa / (1 + kappa) : E*A
+ * The return map is exact for linear hardening, so B is the consistent tangent.  The selects act on values: an element
+ * that is not plastic stores pf_gl_state*'s bits (with ep_n = 0 those of the bar entry point with the same ea and e0; with
+ * e0 null and a committed ep_n those of pf_gl_state_e0 at e0 := ep_n); g->strain stays the total strain e.  The relative threshold keeps an element that ended
+ * an increment on the yield surface (f = +-round-off of r there) elastic on an unloading step; the stress it may carry in
+ * excess is 2^-40 of its yield stress.  Every operation of the map is rounded on its own.
+ * The evaluation always starts from the committed (ep_n, al_n), never from a previous call's (ep, al): those go to
+ * buffers of their own, and a commit is the caller's swap of the two pointer pairs, not a launch.
+ *   ey, kappa, ep_n, al_n   dev double [n_elems], in
+ *   ep, al                  dev double [n_elems], out; ep == ep_n or al == al_n (an update in place) is PF_ERR_ARG
+ *   yielding                dev unsigned char [n_elems], in/out: the previous call's flags in, this call's out (1 = plastic)
+ *   counts                  dev double [PF_GL_CABLE_COUNT]: counts[0] = the number of plastic elements, counts[1] = the
+ *                           number whose flag differs from its entry value, exact integers, the fixed-order sums of the
+ *                           per-block partials behind them (no atomics), as pf_gl_state_cable's
+ * ea, e0: as pf_gl_state_cable's.  A null pl or a null pointer in it is PF_ERR_ARG, never a silent elastic run; nothing is
+ * enqueued on an error.  n_elems == 0 writes zero counts.  Two launches on the stream.  It is the <DIM, false,
+ * gl_plastic_set> instantiation of the bar kernel; the bar and cable entry points launch theirs, untouched.  Whatever reads
+ * kt and fe follows (pf_gl_fint, pf_kt_v_f64, pf_kt_diag_f64, pf_pcgt_*, pf_pcg2t_*, pf_coarse_setup_t); the
+ * sensitivities and the dynamics stay elastic.  Additive: the version stays 9, pf_gl and pf_problem are unchanged;
+ * pf_sizeof(8) is sizeof(pf_gl_plastic). */
+typedef struct pf_gl_plastic {
+  const double* ey;
+  const double* kappa;
+  const double* ep_n;
+  const double* al_n;
+  double* ep;
+  double* al;
+  unsigned char* yielding;
+  double* counts;
+} pf_gl_plastic;
+int pf_gl_state_plastic(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const pf_gl_plastic* pl,
+                        const double* u, void* stream);
 /* Sensitivity of a misfit J(u) to every element's E*A through the adjoint a (K_t(u) a = dJ/du on the free dofs, zero on
  * the fixed ones): s_e = -(e / l0) d.(a_j - a_i) with d = d0 + u_j - u_i and e the strain as pf_gl_state forms it.  It
  * does not contain E*A and reads g->d0 only.  out (dev double [n_elems]) = s (accumulate 0) or out + s (accumulate 1:

@@ -118,6 +118,11 @@ class PfGl(C.Structure):
     _fields_ = [("d0", C.c_void_p), ("kt", C.c_void_p), ("fe", C.c_void_p), ("strain", C.c_void_p)]
 
 
+class PfGlPlastic(C.Structure):
+    _fields_ = [("ey", C.c_void_p), ("kappa", C.c_void_p), ("ep_n", C.c_void_p), ("al_n", C.c_void_p),
+                ("ep", C.c_void_p), ("al", C.c_void_p), ("yielding", C.c_void_p), ("counts", C.c_void_p)]
+
+
 class PfDyn(C.Structure):
     _fields_ = [("minv", C.c_void_p), ("f_ext", C.c_void_p), ("ea", C.c_void_p), ("e0", C.c_void_p),
                 ("u0", C.c_void_p), ("u1", C.c_void_p), ("v", C.c_void_p), ("clock", C.c_void_p),
@@ -191,6 +196,7 @@ SYMBOLS = {
     "pf_gl_state_e0": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_gl_state_cable": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    "pf_gl_state_plastic": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.POINTER(PfGlPlastic), C.c_void_p, C.c_void_p]),
     "pf_gl_sens": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_gl_sens_e0": (C.c_int, [_PP, _PG, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_group_sum_f64": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -298,7 +304,7 @@ def load():
         fn.argtypes = args
     if lib.pf_abi_version() != PF_ABI_VERSION:
         raise PinnFemHipError("libpinnfem_hip.so ABI version mismatch; rebuild the library")
-    for idx, st in enumerate((PfMesh, PfNet, PfState, PfProblem, PfScalarId, PfCoarse, PfGl, PfDyn)):
+    for idx, st in enumerate((PfMesh, PfNet, PfState, PfProblem, PfScalarId, PfCoarse, PfGl, PfDyn, PfGlPlastic)):
         if lib.pf_sizeof(idx) != C.sizeof(st):
             raise PinnFemHipError(
                 f"struct layout mismatch for {st.__name__}: C {lib.pf_sizeof(idx)} vs ctypes {C.sizeof(st)}")

@@ -96,6 +96,16 @@ def parse_problem(problem_file):
     #                                                 slack (e - e0 < 0) they carry nothing, and the solve iterates on the
     #                                                 slack set; the .res.json gains "slack_elements" (the ids) and
     #                                                 "axial_forces"; "dynamics" takes them as its own where it names none
+    #           "plasticity": {"yield_strain": ey | [...], "hardening_ratio": k | [...]}  elastoplastic elements of the
+    #                                                 green-lagrange Newton solve (load control, bars): yield strain
+    #                                                 sigma_y / E (null in the list: an elastic element) and H / E of linear
+    #                                                 isotropic hardening; the state goes from increment to
+    #                                                 increment, and the .res.json gains "plastic_strain",
+    #                                                 "accumulated_plastic_strain", "yielding_elements" (ids),
+    #                                                 "axial_forces" and "load_path"
+    #           "load_factors": [l_1, l_2, ...]       the load factors the increments walk (method "nr") in place of the
+    #                                                 ramp of n_increments steps: load, unload, reverse, reload; the
+    #                                                 .res.json gains "load_path"
     #           "identify_nr": {"groups": [...]|null, "levels": [{"load_factor": l, "dofs": [...], "u": [...]}, ...],
     #                           "max_evaluations": N, "method": "lbfgs"|"gauss-newton", "damping": mu}
     #                                                 identify one factor on E*A per group of elements (null: per element)
@@ -354,7 +364,26 @@ def _solver_config_from(data):
     if cables is not None and cables != "all" and not (isinstance(cables, list) and all(
             isinstance(v, int) and not isinstance(v, bool) for v in cables)):
         raise ValueError('accel.cable_elements must be "all" or a list of element ids')
+    plasticity = accel.get("plasticity")
+    ey, kappa = None, 0.0
+    if plasticity is not None:
+        shape = ('accel.plasticity must be {"yield_strain": ey | [ey_0, ..] (null in the list: an elastic element), '
+                 '"hardening_ratio": k | [k_0, ..]}')
+        if not isinstance(plasticity, dict) or "yield_strain" not in plasticity or not set(plasticity) <= {
+                "yield_strain", "hardening_ratio"}:
+            raise ValueError(shape)
+        ey, kappa = plasticity["yield_strain"], plasticity.get("hardening_ratio", 0.0)
+        if isinstance(ey, list) and all(v is None or is_number(v) for v in ey):
+            ey = [float("inf") if v is None else float(v) for v in ey]
+        elif not is_number(ey):
+            raise ValueError(shape)
+        if not (is_number(kappa) or (isinstance(kappa, list) and all(is_number(v) for v in kappa))):
+            raise ValueError(shape)
+    factors = accel.get("load_factors")
+    if factors is not None and not (isinstance(factors, list) and factors and all(is_number(v) for v in factors)):
+        raise ValueError("accel.load_factors must be a non-empty list of numbers")
     return SolverConfig(
+        yield_strain=ey, hardening_ratio=kappa, load_factors=factors,
         cable_elements=cables,
         initial_strain=None if e0 is None else (float(e0) if is_number(e0) else [float(v) for v in e0]),
         nr_control="load" if control is None else "displacement",
@@ -499,6 +528,13 @@ def solve_problem(parsed_data):
         output["axial_forces"] = result.axial_forces.tolist()
     if result.slack is not None:            # accel.cable_elements: the ids of the slack elements at the final state
         output["slack_elements"] = np.flatnonzero(result.slack).tolist()
+    if result.plastic_strain is not None:   # accel.plasticity: the committed state and the ids that yielded in the last increment
+        output["yielding_elements"] = np.flatnonzero(result.yielding).tolist()
+        if not compact:
+            output["plastic_strain"] = result.plastic_strain.tolist()
+            output["accumulated_plastic_strain"] = result.accumulated_plastic_strain.tolist()
+    if result.load_path is not None:        # accel.load_factors / plasticity: one row per increment
+        output["load_path"] = result.load_path
     if compact:
         # §8(f) rank 1: at 10^6 nodes the reference's JSON lists (every coordinate three times per
         # property) would be hundreds of MB; arrays go to a side file, the JSON keeps the small fields
@@ -506,6 +542,9 @@ def solve_problem(parsed_data):
                   "reactions": result.reactions.flatten()}
         if result.axial_forces is not None:
             arrays["axial_forces"] = result.axial_forces
+        if result.plastic_strain is not None:
+            arrays["plastic_strain"] = result.plastic_strain
+            arrays["accumulated_plastic_strain"] = result.accumulated_plastic_strain
         if result.nn_parameters:
             output["nn_parameters"] = {k: v.tolist() for k, v in result.nn_parameters.items()}
             cent = (model.nodes[model.elements[:, 0]] + model.nodes[model.elements[:, 1]]) / 2.0

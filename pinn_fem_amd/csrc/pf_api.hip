@@ -278,6 +278,7 @@ int pf_sizeof(int what) {
     case 5: return (int)sizeof(pf_coarse);
     case 6: return (int)sizeof(pf_gl);
     case 7: return (int)sizeof(pf_dyn);
+    case 8: return (int)sizeof(pf_gl_plastic);
   }
   return PF_ERR_ARG;
 }

@@ -21,6 +21,12 @@
 //                    The <DIM, true, gl_cable_set> instantiations apply the tension-only rule of the dynamics (below) to
 //                    N / l0 and E*A / l0^3 by a select, keep the slack set (in/out) and write per-block partials of the
 //                    number of slack elements and of changed flags; k_gl_cable_counts adds them in one block.
+//                    The <DIM, false, gl_plastic_set> instantiations are the elastoplastic element: 1-D
+//                    rate-independent plasticity with linear isotropic hardening in e and its conjugate force.  The
+//                    return map (gl_return_map) starts from the committed (ep_n, al_n) of the caller, never from a
+//                    previous iterate, and writes the trial (ep, al) to buffers of their own; N = E*A s with s the
+//                    elastic part of e - e0, and B takes E*A kappa / (1 + kappa) in its material term where the element
+//                    is plastic: the consistent tangent, since the map is exact.  Flags and counts as the cable's.
 //   k_gl_sens        dJ/d(E*A) from the state u and an adjoint a: -((e - e0) / l0) d.(a_j - a_i); may accumulate.
 //   k_gl_strain_jvp  (d_e / l0^2).(v_j - v_i) at the measured elements, the row of v in blockIdx.y; an element id outside
 //                    the mesh writes 0.0 and reads nothing.
@@ -50,6 +56,7 @@
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>
+#include <type_traits>
 #include "pf_common.h"
 #include "pf_graph.h"
 
@@ -88,15 +95,54 @@ struct gl_cable_set {
   double* __restrict__ part;                 // [gridDim.x][2] out: the block's slack elements and changed flags
 };
 
+// what the <DIM, false, gl_plastic_set> instantiations of k_gl_state read and write beside the bar's operands: pf_gl_plastic's
+// arrays, and the block partials behind its counts
+struct gl_plastic_set {
+  const double* __restrict__ ey;             // [n_elems] yield strain, +inf = never yields
+  const double* __restrict__ kappa;          // [n_elems] hardening ratio H / E
+  const double* __restrict__ ep_n;           // [n_elems] committed plastic strain
+  const double* __restrict__ al_n;           // [n_elems] committed accumulated plastic strain
+  double* __restrict__ ep;                   // [n_elems] out: the trial plastic strain (never ep_n: the host refuses it)
+  double* __restrict__ al;                   // [n_elems] out: the trial accumulated plastic strain
+  unsigned char* __restrict__ yielding;      // [n_elems] in: the previous call's flags; out: this call's (1 = plastic)
+  double* __restrict__ part;                 // [gridDim.x][2] out: the block's plastic elements and changed flags
+};
+
+// The return map of 1-D plasticity with linear isotropic hardening from the committed (ep_n, al_n), exact for it:
+//   tr = se - ep_n,  r = ey + kappa al_n,  f = |tr| - r,  plastic <=> f > 2^-40 r,  dg = f / (1 + kappa),
+//   (ep, al) = (ep_n + dg sign(tr), al_n + dg),  s = tr - dg sign(tr),  E*A_t = E*A kappa / (1 + kappa),
+// each a select on the value, so an element that is not plastic gets tr, E*A, ep_n and al_n back to the bit.  Every
+// operation is rounded on its own (no contraction): the branch an element takes is the one the host's float64 takes.
+// Returns whether the element is plastic.
+__device__ __forceinline__ bool gl_return_map(double se, double ea, double ey, double kappa, double ep_n, double al_n,
+                                              double& s, double& ea_t, double& ep, double& al) {
+#pragma clang fp contract(off)
+  const double tr = se - ep_n;
+  const double r = ey + kappa * al_n;
+  const double f = fabs(tr) - r;
+  const bool plastic = f > 0x1p-40 * r;
+  const double dg = f / (1.0 + kappa);
+  const double step = tr < 0.0 ? -dg : dg;
+  s = plastic ? tr - step : tr;
+  ea_t = plastic ? ea * kappa / (1.0 + kappa) : ea;
+  ep = plastic ? ep_n + step : ep_n;
+  al = plastic ? al_n + dg : al_n;
+  return plastic;
+}
+
 // CABLE: an element with cable[e] != 0 and e - e0 < 0 is slack (the rule of dyn_term): it carries no N and no E*A, by a
 // select on the value, so its fe and kt are +0.0 and its strain stays e; every other element keeps the bar's values.
-// SET: empty, or gl_cable_set and one more operand (the <DIM, false> instantiations are the bar kernels, untouched).
+// SET: empty, or gl_cable_set (CABLE) or gl_plastic_set (not CABLE) and one more operand.  With gl_plastic_set the strain that
+// carries stress and the E*A of the material term go through gl_return_map; the <DIM, false> instantiations are the bar
+// kernels, untouched: there `s` and `ea_t` are se and ea themselves.
 template <int DIM, bool CABLE, class... SET>
 __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const double* __restrict__ u,
                                                   const double* __restrict__ ea_in, const double* __restrict__ e0_in,
                                                   SET... set) {
+  constexpr bool PLASTIC = (std::is_same_v<SET, gl_plastic_set> || ...);
+  static_assert(!(CABLE && PLASTIC), "a cable set or a plastic set, not both");
   const pf_mesh& M = P.mesh;
-  [[maybe_unused]] double n_slack = 0.0, n_changed = 0.0;
+  [[maybe_unused]] double n_set = 0.0, n_changed = 0.0;     // the slack (or plastic) elements, the changed flags
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < M.n_elems; e += gridDim.x * blockDim.x) {
     int ni, nj;
     double d0[DIM], du[DIM];
@@ -108,8 +154,18 @@ __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const d
     const double l0 = sqrt(l02);
     const double strain = (2.0 * d0du + dudu) / (2.0 * l02);
     const double se = e0_in ? strain - e0_in[e] : strain;     // the strain that carries stress; e - 0.0 is e to the bit
-    const double n_l0 = (ea * se) / l0;              // N / l0
-    const double k = ea / (l02 * l0);                // E*A / l0^3
+    double s = se, ea_t = ea;                        // PLASTIC: the elastic part of se and the tangent modulus
+    if constexpr (PLASTIC) {
+      const gl_plastic_set& S = (set, ...);
+      double ep, al;
+      const bool plastic = gl_return_map(se, ea, S.ey[e], S.kappa[e], S.ep_n[e], S.al_n[e], s, ea_t, ep, al);
+      S.ep[e] = ep; S.al[e] = al;
+      n_set += plastic ? 1.0 : 0.0;
+      n_changed += (S.yielding[e] != 0) != plastic ? 1.0 : 0.0;
+      S.yielding[e] = plastic ? 1 : 0;
+    }
+    const double n_l0 = (ea * s) / l0;               // N / l0
+    const double k = ea_t / (l02 * l0);              // E*A / l0^3 (PLASTIC: E*A_t / l0^3)
     double d[DIM];
 #pragma unroll
     for (int c = 0; c < DIM; ++c) d[c] = d0[c] + du[c];
@@ -119,7 +175,7 @@ __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const d
     if constexpr (CABLE) {
       const gl_cable_set& S = (set, ...);
       slack = S.cable[e] && se < 0.0;
-      n_slack += slack ? 1.0 : 0.0;
+      n_set += slack ? 1.0 : 0.0;
       n_changed += (S.slack[e] != 0) != slack ? 1.0 : 0.0;
       S.slack[e] = slack ? 1 : 0;
     }
@@ -136,10 +192,10 @@ __global__ __launch_bounds__(256) void k_gl_state(pf_problem P, pf_gl G, const d
       G.kt[e] = put(k * (d[0] * d[0]) + n_l0);
     }
   }
-  if constexpr (CABLE) {
+  if constexpr (CABLE || PLASTIC) {
     __shared__ double red[8];
-    const gl_cable_set& S = (set, ...);
-    const double s0 = pf_block_sum_d(n_slack, red), s1 = pf_block_sum_d(n_changed, red);     // exact integers
+    const auto& S = (set, ...);
+    const double s0 = pf_block_sum_d(n_set, red), s1 = pf_block_sum_d(n_changed, red);     // exact integers
     if (threadIdx.x == 0) { S.part[2 * (size_t)blockIdx.x] = s0; S.part[2 * (size_t)blockIdx.x + 1] = s1; }
   }
 }
@@ -786,6 +842,30 @@ int pf_gl_state_cable(const pf_problem* p, const pf_gl* g, const double* ea, con
                             u, ea, e0, set))
     return rc;
   hipLaunchKernelGGL(k_gl_cable_counts, dim3(1), dim3(256), 0, (hipStream_t)stream, counts, nb);
+  return launched(who);
+}
+
+int pf_gl_state_plastic(const pf_problem* p, const pf_gl* g, const double* ea, const double* e0, const pf_gl_plastic* pl,
+                        const double* u, void* stream) {
+  const char* who = "pf_gl_state_plastic";
+  if (!pl || !pl->ey || !pl->kappa || !pl->ep_n || !pl->al_n || !pl->ep || !pl->al || !pl->yielding || !pl->counts)
+    return gl_fail(PF_ERR_ARG, who, "null plastic record or a null pointer in it (pf_gl_state / pf_gl_state_ea / pf_gl_state_e0 "
+                                    "are the elastic run)");
+  if (pl->ep == pl->ep_n || pl->al == pl->al_n)
+    return gl_fail(PF_ERR_ARG, who, "ep == ep_n or al == al_n: the trial state is written beside the committed one, never in "
+                                    "place (a commit swaps the two pointers)");
+  if (!mesh_ok(p) || !g || !g->d0 || !g->kt || !g->fe || !g->strain || !u) return gl_fail(PF_ERR_ARG, who, "bad argument");
+  if (p->mesh.n_elems == 0) {
+    if (hipMemsetAsync(pl->counts, 0, 2 * sizeof(double), (hipStream_t)stream) != hipSuccess)
+      return gl_fail(PF_ERR_HIP, who, "clearing the counts failed");
+    return PF_OK;
+  }
+  const int nb = elem_blocks(p->mesh.n_elems);
+  const gl_plastic_set set{pl->ey, pl->kappa, pl->ep_n, pl->al_n, pl->ep, pl->al, pl->yielding, pl->counts + 2};
+  if (const int rc = launch(who, p, k_gl_state<2, false, gl_plastic_set>, k_gl_state<1, false, gl_plastic_set>, dim3(nb), stream,
+                            *g, u, ea, e0, set))
+    return rc;
+  hipLaunchKernelGGL(k_gl_cable_counts, dim3(1), dim3(256), 0, (hipStream_t)stream, pl->counts, nb);
   return launched(who);
 }
 

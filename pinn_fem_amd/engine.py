@@ -227,6 +227,7 @@ class HipEngine:
         self._fixed_views = {}          # extra fixed dofs (tuple) -> (device dof_flags copy, PfProblem view, host fixed mask)
         self._gl = None                 # Green-Lagrange element buffers (d0, kt, fe, strain) and their pf_gl record
         self._gl_cable = None           # gl_state_cable: [device flags, slack set, counts, whether a cable state has run]
+        self._gl_plastic = None         # gl_state_plastic: the committed and trial (ep, alpha), flags, counts (_gl_plastic_buffers)
         self._dyn = None                # explicit dynamics: buffers, pf_dyn record, step count and graphs of the run (dyn_begin)
         self._group_csr = None          # group_sum: (key of the group map, n_groups, device CSR pointer, device element ids)
         self._group_maps = {}           # _device_group_map: method name -> (key of its last map, n_groups, device int32 ids)
@@ -737,6 +738,87 @@ class HipEngine:
     def gl_slack_mask(self) -> np.ndarray:
         """The slack elements of the last gl_state_cable, bool [n_elems] on the host."""
         return self._gl_cable_ready("gl_slack_mask")[1][: self.plan.n_elems].cpu().numpy().astype(bool)
+
+    @_on_engine_stream
+    def gl_state_plastic(self, u: torch.Tensor, ey, kappa, ea: Optional[torch.Tensor] = None,
+                         e0: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gl_state with elastoplastic elements (pf_gl_state_plastic).  ey: the yield strain of every element
+        [n_elems] (inf: never yields), kappa: the hardening ratio H / E [n_elems]; ea, e0: as gl_state's.  The engine owns the
+        committed (ep, alpha), the trial pair the kernel writes, the flags and the counts.  Every call starts from the
+        committed state: gl_plastic_commit() makes the last call's trial state the committed one (a swap of the buffers),
+        gl_plastic_reset() sets it, gl_plastic_counts() and gl_plastic_state() read the last call's.  Returns the total
+        strains e [n_elems], the buffer gl_state returns."""
+        who = "gl_state_plastic"
+        ne = self.plan.n_elems
+        uu = self._f64_vector(who, "u", u, self.plan.n_dofs, "dofs")
+        rec = self._gl_buffers()[4]
+        ee = None if ea is None else self._f64_vector(who, "ea", ea, ne, "elements")
+        zz = None if e0 is None else self._f64_vector(who, "e0", e0, ne, "elements")
+        yy, kk = (self._f64_vector(who, name, torch.as_tensor(v), ne, "elements") for name, v in (("ey", ey), ("kappa", kappa)))
+        p = self._gl_plastic_buffers()
+        pl = _capi.PfGlPlastic()
+        filler = p["counts"]                                 # (an empty mesh: any non-null pointer, nothing reads it)
+        pl.ey, pl.kappa = (yy.data_ptr(), kk.data_ptr()) if ne else (filler.data_ptr(), filler.data_ptr())
+        pl.ep_n, pl.al_n = p["committed"][0].data_ptr(), p["committed"][1].data_ptr()
+        pl.ep, pl.al = p["trial"][0].data_ptr(), p["trial"][1].data_ptr()
+        pl.yielding, pl.counts = p["yielding"].data_ptr(), p["counts"].data_ptr()
+        _capi.check(self.lib.pf_gl_state_plastic(self._ref(), C.byref(rec), None if ee is None else ee.data_ptr(),
+                                                 None if zz is None else zz.data_ptr(), C.byref(pl), uu.data_ptr(),
+                                                 self._stream()), "pf_gl_state_plastic")
+        p["formed"] = True
+        return self._gl[3][:ne]
+
+    def _gl_plastic_buffers(self):
+        if self._gl_plastic is None:
+            ne = max(self.plan.n_elems, 1)
+            f64 = dict(dtype=torch.float64, device=self.device)
+            self._gl_plastic = dict(committed=[torch.zeros(ne, **f64), torch.zeros(ne, **f64)],
+                                    trial=[torch.zeros(ne, **f64), torch.zeros(ne, **f64)],
+                                    yielding=torch.zeros(ne, dtype=torch.uint8, device=self.device),
+                                    counts=torch.zeros(_capi.PF_GL_CABLE_COUNT, **f64), formed=False)
+        return self._gl_plastic
+
+    def _gl_plastic_ready(self, who):
+        if self._gl_plastic is None or not self._gl_plastic["formed"]:
+            raise RuntimeError(f"{who}: no plastic state formed since the last commit or reset; call "
+                               "gl_state_plastic(u, ey, kappa) first")
+        return self._gl_plastic
+
+    @_on_engine_stream
+    def gl_plastic_reset(self, ep=None, alpha=None):
+        """Set the committed plastic state ((ep, alpha) [n_elems] each, zeros by default) and clear the flags: the start of
+        a solve or of a load program."""
+        p = self._gl_plastic_buffers()
+        ne = self.plan.n_elems
+        for buf, name, v in zip(p["committed"], ("ep", "alpha"), (ep, alpha)):
+            if v is None:
+                buf.zero_()
+            else:
+                buf[:ne].copy_(self._f64_vector("gl_plastic_reset", name, torch.as_tensor(v), ne, "elements"))
+        p["yielding"].zero_()
+        p["formed"] = False
+
+    def gl_plastic_commit(self):
+        """The trial (ep, alpha) of the last gl_state_plastic becomes the committed state: the two buffer pairs change
+        places, nothing is launched.  Raises where no plastic state was formed since the last commit or reset."""
+        p = self._gl_plastic_ready("gl_plastic_commit")
+        p["committed"], p["trial"] = p["trial"], p["committed"]
+        p["formed"] = False
+
+    @_on_engine_stream
+    def gl_plastic_counts(self):
+        """(number of plastic elements, number of elements whose flag changed against the call before) of the last
+        gl_state_plastic: one read of 16 bytes."""
+        n = self._gl_plastic_ready("gl_plastic_counts")["counts"][:2].cpu()
+        return int(n[0]), int(n[1])
+
+    @_on_engine_stream
+    def gl_plastic_state(self):
+        """(ep, alpha, yielding) of the last gl_state_plastic on the host: float64 [n_elems] twice and bool [n_elems]."""
+        p = self._gl_plastic_ready("gl_plastic_state")
+        ne = self.plan.n_elems
+        return (p["trial"][0][:ne].cpu().numpy(), p["trial"][1][:ne].cpu().numpy(),
+                p["yielding"][:ne].cpu().numpy().astype(bool))
 
     @_on_engine_stream
     def gl_sensitivity(self, u: torch.Tensor, a: torch.Tensor, out: Optional[torch.Tensor] = None,

@@ -223,6 +223,9 @@ def check_dynamics(model, config: SolverConfig, dyn: DynamicsConfig) -> np.ndarr
         if arr.ndim > 1 or (arr.ndim == 1 and arr.size != model.nnode) or not np.all(np.isfinite(arr)) or np.any(arr < 0.0):
             raise ValueError(f"nodal_mass must be a non-negative number or {model.nnode} of them (one for each node)")
     dynamic_cables(model, config, dyn)
+    if getattr(config, "yield_strain", None) is not None:
+        raise ValueError("solve_dynamic does not support yield_strain: the step kernels are elastic and would silently "
+                         "answer for the structure that never yields.")
     if dyn.load_history is not None:
         if (dyn.ramp_time, dyn.load_factor_initial, dyn.load_factor_final) != (0.0, 0.0, 1.0):
             raise ValueError("load_history takes the place of the ramp: ramp_time, load_factor_initial and load_factor_final "

@@ -92,6 +92,9 @@ def check_identify(model: FEMModel, config: SolverConfig, levels, groups=None, q
         raise ValueError("identification runs under load control only: nr_control 'displacement' is not supported.")
     if _solver.cable_mask(model, getattr(config, "cable_elements", None)) is not None:
         raise ValueError("identification does not support cable_elements: the sensitivities treat every element as a bar.")
+    if getattr(config, "yield_strain", None) is not None:
+        raise ValueError("identification does not support yield_strain: its Newton solves and sensitivities are elastic "
+                         "and would silently answer for the structure that never yields.")
     if model.material.has_trainable_params():
         raise ValueError("identification needs scalar materials (no NN parameters): the base E*A is the model's scalar one.")
     if _solver._world_size() > 1:

@@ -70,6 +70,14 @@ class SolverConfig:
     # A flagged element with e - e0 < 0 is slack and carries nothing; the Newton loop iterates on the slack set
     # (_newton_loop).  solve_dynamic takes its cables from here when DynamicsConfig.cable_elements is not given
     cable_elements: Optional[object] = None
+    # elastoplastic elements of the Green-Lagrange solve_nr (check_plasticity): yield_strain is sigma_y / E,
+    # None (elastic, the default), one number or n_elems of them, inf = that element never yields; hardening_ratio is
+    # H / E >= 0 (linear isotropic hardening), a number or n_elems of them
+    yield_strain: Optional[object] = None
+    hardening_ratio: object = 0.0
+    # the load factors solve() walks with method "nr", one Newton solve each, in place of the linear ramp of n_increments
+    # steps: a load program that may unload, reverse and reload.  None: the ramp
+    load_factors: Optional[object] = None
 
 
 KINEMATICS = ("linear", "green-lagrange")
@@ -205,6 +213,88 @@ def check_cables(config, model, method: str = "nr"):
     return cable
 
 
+def _per_element(value, ne, name):
+    """A number or ne numbers as a float64 array [ne]; anything else is a ValueError."""
+    try:
+        arr = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number or {ne} numbers (one for each element)") from None
+    if arr.ndim == 0:
+        arr = np.full(ne, float(arr))
+    arr = np.ascontiguousarray(arr.reshape(-1))
+    if arr.size != ne:
+        raise ValueError(f"{name} has {arr.size} entries, the model has {ne} elements")
+    return arr
+
+
+def check_plasticity(config, model, method: str = "nr"):
+    """(yield strain, hardening ratio) as float64 arrays [n_elems] each, or None where config.yield_strain is None.
+    Plasticity belongs to the Green-Lagrange Newton solve under load control, on bars, with scalar materials on one GPU:
+    linear kinematics, another method than 'nr' / 'hybrid', nr_control 'displacement', cable_elements, NN materials, a
+    sharded run, a wrong length, a yield strain that is not > 0 (inf is the elastic element) and a hardening ratio that is
+    negative or not finite are each a ValueError before an engine is built.  initial_strain is supported."""
+    if getattr(config, "yield_strain", None) is None:
+        return None
+    if config.kinematics != "green-lagrange":
+        raise ValueError("yield_strain needs kinematics 'green-lagrange': solve_gd and the linear solve_nr know no "
+                         "plasticity and would silently solve the elastic structure.")
+    if method not in ("nr", "hybrid"):
+        raise ValueError(f"yield_strain belongs to the Green-Lagrange Newton solve (solve_nr): method {method!r} is "
+                         "untouched by it.")
+    if getattr(config, "nr_control", "load") == "displacement":
+        raise ValueError("yield_strain does not support nr_control 'displacement': there is no displacement control "
+                         "with plasticity; use load control (solve()'s increments or load_factors).")
+    if cable_mask(model, getattr(config, "cable_elements", None)) is not None:
+        raise ValueError("yield_strain does not support cable_elements: an element is elastoplastic or tension-only, "
+                         "not both.")
+    if model.material.has_trainable_params():
+        raise ValueError("yield_strain needs scalar materials (no NN parameters).")
+    if _world_size() > 1:
+        raise ValueError("yield_strain does not support a sharded (multi-GPU) run.")
+    ey = _per_element(config.yield_strain, model.nelm, "yield_strain")
+    kappa = _per_element(getattr(config, "hardening_ratio", 0.0), model.nelm, "hardening_ratio")
+    if not np.all(ey > 0.0):                                # (NaN fails the comparison too)
+        raise ValueError("yield_strain must be positive (sigma_y / E; inf: the element never yields)")
+    if not np.all(np.isfinite(kappa) & (kappa >= 0.0)):
+        raise ValueError("hardening_ratio must be finite and not negative (H / E; 0: perfect plasticity)")
+    return ey, kappa
+
+
+def check_plastic_state(plastic_state, ne):
+    """solve_nr's plastic_state as (ep, alpha), float64 [ne] each: a pair of the right length, finite, alpha >= 0."""
+    try:
+        ep, alpha = plastic_state
+        ep, alpha = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (ep, alpha))
+    except (TypeError, ValueError):
+        raise ValueError("plastic_state must be a pair (ep, alpha) of arrays, one value for each element") from None
+    if ep.size != ne or alpha.size != ne:
+        raise ValueError(f"plastic_state has {ep.size} and {alpha.size} entries, the model has {ne} elements")
+    if not (np.all(np.isfinite(ep)) and np.all(np.isfinite(alpha))):
+        raise ValueError("plastic_state holds non-finite values")
+    if np.any(alpha < 0.0):
+        raise ValueError("plastic_state: the accumulated plastic strain alpha must not be negative")
+    return ep, alpha
+
+
+def check_load_factors(config, method: str = "nr"):
+    """config.load_factors as a list of floats, or None when it is not given.  It belongs to solve() with method 'nr'
+    under load control; an empty or non-finite sequence is a ValueError."""
+    lf = getattr(config, "load_factors", None)
+    if lf is None:
+        return None
+    if method != "nr":
+        raise ValueError(f"load_factors belongs to solve() with method 'nr': method {method!r} walks the linear ramp.")
+    if getattr(config, "nr_control", "load") == "displacement":
+        raise ValueError("load_factors does not support nr_control 'displacement': the factors are load factors.")
+    try:
+        arr = np.asarray(lf, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("load_factors must be a sequence of numbers") from None
+    if arr.ndim != 1 or arr.size == 0 or not np.all(np.isfinite(arr)):
+        raise ValueError("load_factors must be a non-empty sequence of finite numbers")
+    return [float(v) for v in arr]
+
+
 def _axial_forces(model, strain, e0):
     """N = E*A (e - e0) of every element on the host, from the strains a gl_state returned; E*A is the model's scalar one
     as the device forms it (each factor rounded to float32 first)."""
@@ -233,8 +323,17 @@ class SolverResult:
     # Green-Lagrange solve_nr with config.cable_elements: bool [n_elems], the slack elements at the final state; None
     # without cables
     slack: Optional[np.ndarray] = None
+    # Green-Lagrange solve_nr with config.yield_strain: the committed plastic strain and accumulated plastic strain of
+    # every element at the final state (the pair the next increment takes as plastic_state), the elements that yielded in
+    # this increment (bool); None without plasticity
+    plastic_strain: Optional[np.ndarray] = None
+    accumulated_plastic_strain: Optional[np.ndarray] = None
+    yielding: Optional[np.ndarray] = None
+    # solve() with config.load_factors or config.yield_strain: one {load_factor, iterations, yielding_elements} per
+    # increment (yielding_elements is 0.0 without plasticity); None otherwise
+    load_path: Optional[list] = None
     # Green-Lagrange solve_nr with config.initial_strain or config.cable_elements: N = E*A (e - e0) of every element at
-    # the final state, 0.0 in a slack cable; None otherwise
+    # the final state, 0.0 in a slack cable; with config.yield_strain N = E*A (e - e0 - ep); None otherwise
     axial_forces: Optional[np.ndarray] = None
 
 
@@ -484,14 +583,15 @@ class _NewtonSetup(NamedTuple):
     e0_np: Optional[np.ndarray]             # check_initial_strain's array, or None
     e0: Optional[torch.Tensor]              # the same on the device
     u: torch.Tensor                         # the start vector, float64 [n_dofs] on the device, zero on the fixed dofs
+    plastic: Optional[tuple] = None         # check_plasticity's (ey, kappa) on the device, or None: elastic elements
     cable: Optional[torch.Tensor] = None    # check_cables' flags on the device (uint8 [n_elems]), or None: all bars
 
 
-def _newton_setup(model, e0_np, u_initial=None, cable_np=None) -> _NewtonSetup:
+def _newton_setup(model, e0_np, u_initial=None, cable_np=None, plastic_np=None) -> _NewtonSetup:
     """The one host setup of solve_nr under either control and of fem/identify.py.  e0_np: check_initial_strain's
     result; like every check_* it is the caller's to run first, this is where the engine is built.  u_initial: a tensor
-    or an array [n_dofs] (its fixed dofs are ignored); None: zeros.  cable_np: check_cables' result.  It launches nothing
-    but torch's own copies and fills; _pre_check is the first to touch the kernels."""
+    or an array [n_dofs] (its fixed dofs are ignored); None: zeros.  cable_np: check_cables' result; plastic_np:
+    check_plasticity's.  It launches nothing but torch's own copies and fills; _pre_check is the first to touch the kernels."""
     eng = _engine_for(model, None, None)
     dev, ndof = eng.device, model.ndof
     free = _free_mask(model)
@@ -505,13 +605,17 @@ def _newton_setup(model, e0_np, u_initial=None, cable_np=None) -> _NewtonSetup:
     loads = torch.from_numpy(np.ascontiguousarray(np.asarray(model.loads, dtype=float).reshape(-1))).to(dev)
     return _NewtonSetup(eng, free, torch.from_numpy(free).to(dev), loads, e0_np,
                         None if e0_np is None else torch.from_numpy(e0_np).to(dev), u,
-                        None if cable_np is None else torch.from_numpy(cable_np.astype(np.uint8)).to(dev))
+                        plastic=None if plastic_np is None else tuple(torch.from_numpy(v).to(dev) for v in plastic_np),
+                        cable=None if cable_np is None else torch.from_numpy(cable_np.astype(np.uint8)).to(dev))
 
 
 def _gl_state(s: _NewtonSetup, u, ea=None):
-    """The element state of a Newton solve at u: the cable state where the setup carries flags, the bar state otherwise."""
+    """The element state of a Newton solve at u: the cable state where the setup carries flags, the plastic state from the
+    engine's committed (ep, alpha) where it carries yield strains, the bar state otherwise."""
     if s.cable is not None:
         return s.eng.gl_state_cable(u, s.cable, ea, s.e0)
+    if s.plastic is not None:
+        return s.eng.gl_state_plastic(u, s.plastic[0], s.plastic[1], ea, s.e0)
     return s.eng.gl_state(u, ea, s.e0)
 
 
@@ -522,8 +626,10 @@ def _pre_check(s: _NewtonSetup, ea=None, held=()):
     string), so the tangent at the starting state decides, not the linear diagonal: it must be positive on every free
     dof that is not held (a free dof that only a slack or compressed member holds is a mechanism).  That branch leaves
     the gl_state of (s.u, ea, s.e0) on the engine.  With cable flags it is taken too, with or without e0, on the cable
-    state from a cleared slack set: an unstrained cable at u = 0 has e - e0 = 0, is taut and counts with its bar block."""
-    if s.e0 is None and s.cable is None:
+    state from a cleared slack set: an unstrained cable at u = 0 has e - e0 = 0, is taut and counts with its bar block.
+    With yield strains it is taken too, on the plastic state from the committed (ep, alpha) the caller has just set on the
+    engine (gl_plastic_reset): a perfectly plastic element that yields at the starting state holds nothing."""
+    if s.e0 is None and s.cable is None and s.plastic is None:
         if bool((s.eng.diag_k().cpu().numpy()[s.free] == 0.0).any()):
             raise RuntimeError("Tangent stiffness became singular during solve")
         return
@@ -553,7 +659,13 @@ def _newton_loop(s, model, config, f_ext, u, green_lagrange, ea=None):
     iteration's count against the cleared set does not count).  There is no line search and no damping: a set that keeps
     changing runs to max_iterations and returns converged = False like any other solve that does not converge, and
     solve()'s load increments (n_increments) are the remedy.  Whenever the set changed, the tangent's diagonal is read
-    before the CG solve: a free dof that only slack cables hold is a mechanism and raises RuntimeError."""
+    before the CG solve: a free dof that only slack cables hold is a mechanism and raises RuntimeError.
+
+    With s.plastic (elastoplastic elements) every iteration forms the plastic state at u from the engine's committed
+    (ep, alpha) (pf_gl_state_plastic), never from the iterate before.  Its tangent is the consistent one, so the
+    displacement test alone stops the loop.  Whenever a flag changed against the state before (the pre-check's, in the
+    first iteration), the tangent's diagonal is read before the CG solve: a free dof with a diagonal <= 0 is a plastic
+    mechanism (collapse) and raises RuntimeError.  Nothing is committed here: solve_nr commits its closing state."""
     eng = s.eng
     has_converged, residual_norm, max_e, ite = False, float("inf"), 0.0, -1
     cg0 = eng.pcg_iterations
@@ -568,6 +680,8 @@ def _newton_loop(s, model, config, f_ext, u, green_lagrange, ea=None):
                 if n_changed:
                     _check_slack_mechanism(s, ite)
                 set_changed = ite > 0 and n_changed > 0
+            elif s.plastic is not None and eng.gl_plastic_counts()[1]:
+                _check_plastic_mechanism(s, ite)
             rhs = f_ext - eng.gl_fint()
             du, _, ok, rr, bb = eng.pcg_solve(rhs, tangent=True, preconditioner=config.nr_preconditioner,
                                              n_aggregates=config.nr_aggregates, u=u)
@@ -597,6 +711,17 @@ def _check_slack_mechanism(s, ite):
                            "structure through a slack mechanism: use solve_dynamic with rest_tolerance")
 
 
+def _check_plastic_mechanism(s, ite):
+    """After a change of the yielding set: _check_slack_mechanism's rule on the plastic state on the engine."""
+    dg = s.eng.kt_diag().cpu().numpy()
+    bad = np.flatnonzero(s.free & ~(dg > 0.0))
+    if bad.size:
+        raise RuntimeError(f"Tangent stiffness is not positive definite in Newton iteration {ite + 1}: its diagonal is "
+                           f"{dg[bad[0]]:.6g} at free dof {int(bad[0])}, which only yielding elements hold (a plastic "
+                           f"mechanism, collapse; {bad.size} such dof{'s' if bad.size > 1 else ''}).  The load is beyond "
+                           "what the structure carries: reduce it, or give the elements a hardening_ratio")
+
+
 # what load control says when _check_cg_step refuses a solve: (the residual does not come down, rhs.x <= 0)
 _LOAD_REFUSALS = ("Tangent stiffness became singular during solve",
                   "Tangent stiffness is not positive definite (limit point or buckling): the CG solve of "
@@ -618,7 +743,7 @@ def _check_cg_step(spd, rhs, x, ok, rr, bb, free_t, refusals=_LOAD_REFUSALS):
             raise RuntimeError(refusals[1])
 
 
-def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> SolverResult:
+def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None, plastic_state=None) -> SolverResult:
     """Classical Newton-Raphson for scalar materials (solver.py:408-512), SURVEY.md §8(f) rank 3.
 
     The reference assembles the dense float64 tangent (fem/assembly.py:16-75) and calls
@@ -648,11 +773,26 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     iterates on the slack set (_newton_loop), the closing state is the cable state, and the result carries slack (bool
     [n_elems]) and axial_forces with 0.0 on the slack elements; the history row counts them ("slack_elements").  An
     element that flips in the closing state has a force of zero within the tolerance; nothing more is iterated.  A set
-    that does not settle returns converged = False: use solve() with more increments."""
+    that does not settle returns converged = False: use solve() with more increments.
+
+    config.yield_strain / config.hardening_ratio (Green-Lagrange, load control, bars; check_plasticity) make the elements
+    elastoplastic.  plastic_state: the committed (ep, alpha) the solve starts from, a pair of arrays
+    [n_elems]; None: zeros.  Every iteration forms the plastic state from that committed pair.  The closing state at the
+    final u is the one that is committed: the result carries it as plastic_strain and accumulated_plastic_strain (the
+    next increment's plastic_state), yielding (bool [n_elems], the elements that yielded in this solve's closing state),
+    axial_forces = E*A (e - e0 - ep), and the history row counts "yielding_elements".  An unconverged solve commits
+    nothing and returns the state it was given.  A free dof that only yielding elements without hardening hold is a
+    plastic mechanism: RuntimeError."""
     config = config or SolverConfig()
     green_lagrange = check_kinematics(config.kinematics, config.nr_preconditioner) == "green-lagrange"
     e0_np = check_initial_strain(config, model)
     cable_np = check_cables(config, model)
+    plastic_np = check_plasticity(config, model)
+    if plastic_state is not None and plastic_np is None:
+        raise ValueError("plastic_state needs config.yield_strain: without it the solve is elastic and would ignore it.")
+    if plastic_np is not None:
+        plastic_state = check_plastic_state(plastic_state if plastic_state is not None
+                                            else (np.zeros(model.nelm), np.zeros(model.nelm)), model.nelm)
     if check_control(config, model) == "displacement":
         return _solve_nr_displacement(model, config, target_load_factor, u_initial, e0_np)
     if model.material.has_trainable_params():
@@ -661,12 +801,15 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
     if green_lagrange:
         if _world_size() > 1:
             raise ValueError("kinematics 'green-lagrange' does not support a sharded (multi-GPU) run.")
-    s = _newton_setup(model, e0_np, u_initial if green_lagrange else None, cable_np)
+    s = _newton_setup(model, e0_np, u_initial if green_lagrange else None, cable_np, plastic_np)
+    if s.plastic is not None:
+        s.eng.gl_plastic_reset(*plastic_state)            # the committed state every evaluation of this solve starts from
     _pre_check(s)
     eng, load_factor = s.eng, target_load_factor
     f_ext = float(load_factor) * s.loads
     u, has_converged, residual_norm, max_e, ite, _ = _newton_loop(s, model, config, f_ext, s.u, green_lagrange)
     axial = slack = None
+    plastic = {}
     if green_lagrange:
         strain = _gl_state(s, u)                          # state at the final u: its strain, and f_int for the reactions
         max_e = float(strain.abs().max()) if model.nelm else 0.0
@@ -676,13 +819,24 @@ def solve_nr(model, config=None, target_load_factor=1.0, u_initial=None) -> Solv
         if s.cable is not None:
             slack = eng.gl_slack_mask()
             axial = np.where(slack, 0.0, axial)
+        if s.plastic is not None:
+            ep, alpha, yielding = eng.gl_plastic_state()  # of the closing state: the one that is committed
+            axial = _axial_forces(model, strain, ep if s.e0_np is None else s.e0_np + ep)
+            if has_converged:
+                eng.gl_plastic_commit()
+            else:
+                ep, alpha = plastic_state
+            plastic = dict(plastic_strain=ep, accumulated_plastic_strain=alpha, yielding=yielding)
     else:
         reactions = (eng.kv_f64(u) - f_ext).cpu().numpy()
     history = [{"load_factor": float(load_factor), "iterations": float(ite + 1), "residual": float(residual_norm),
                 "max_strain": float(max_e), "converged": float(1.0 if has_converged else 0.0)}]
     if slack is not None:
         history[-1]["slack_elements"] = float(slack.sum())
-    return _result(model, u.cpu().numpy(), reactions, s.free, has_converged, history, axial_forces=axial, slack=slack)
+    if plastic:
+        history[-1]["yielding_elements"] = float(plastic["yielding"].sum())
+    return _result(model, u.cpu().numpy(), reactions, s.free, has_converged, history, axial_forces=axial, slack=slack,
+                   **plastic)
 
 
 def _solve_nr_displacement(model, config, control_factor, u_initial, e0_np=None) -> SolverResult:
@@ -800,12 +954,16 @@ def solve_hybrid(
     measured_dofs: Optional[List[int]] = None,
     target_load_factor: float = 1.0,
     u_initial: Optional[torch.Tensor] = None,
+    plastic_state=None,
 ) -> SolverResult:
-    """Hybrid solver (solver.py:520-692).  With NN materials phase 2 is GD again (:594-651)."""
+    """Hybrid solver (solver.py:520-692).  With NN materials phase 2 is GD again (:594-651).  plastic_state: solve_nr's,
+    handed to the Newton phase (the GD phase is the linear elastic warm start it always was; with config.yield_strain its
+    early return on a tight GD convergence is not taken, so the answer always comes from the plastic Newton solve)."""
     config = config or SolverConfig()
     check_kinematics(config.kinematics, config.nr_preconditioner)
     check_control(config, method="hybrid")
     check_cables(config, model, "hybrid")
+    plastic = check_plasticity(config, model, "hybrid") is not None
     _say("=== HYBRID SOLVER ===")
     _say(f"Target load factor: {target_load_factor}")
     gd_result = None
@@ -819,10 +977,12 @@ def solve_hybrid(
             gd_result = solve_gd(model, gd_config, measured_disp, measured_dofs, target_load_factor,
                                  u_initial, skip_preconditioning=True)
             _say(f"  GD Phase: {gd_result.history[-1]['iteration']} iterations")
-            if (gd_result.converged
+            if (gd_result.converged and not plastic
                     and gd_result.history[-1].get("residual_norm", 1.0) < config.tolerance):
                 _say("  GD achieved tight convergence, skipping NR phase")
                 return gd_result
+            # (with yield_strain the Newton phase always runs: the GD answer is the linear elastic one and carries no
+            # plastic state, however tightly it converged)
         except NotImplementedError:
             raise
         except Exception as e:  # solver.py:584-586
@@ -840,7 +1000,7 @@ def solve_hybrid(
         warm_dtype = torch.float64 if config.kinematics == "green-lagrange" else torch.float32
         u_warm = (torch.tensor(gd_result.displacements.flatten(), dtype=warm_dtype)
                   if gd_result else u_initial)
-        nr_result = solve_nr(model, config, target_load_factor, u_warm)
+        nr_result = solve_nr(model, config, target_load_factor, u_warm, plastic_state)
         nr_iterations = nr_result.history[-1].get("iterations", 1) if nr_result.history else 1
         _say(f"  NR Phase: {nr_iterations} iterations")
         if gd_result:
@@ -892,14 +1052,21 @@ def solve(
         raise ValueError(f"initial_strain belongs to the Green-Lagrange Newton solve (solve_nr): method {method!r} is "
                          "untouched by it.")
     check_cables(config, model, method)
+    plastic = check_plasticity(config, model, method) is not None
+    load_factors = check_load_factors(config, method)
+    if load_factors is None:
+        load_factors = [config.load_factor_initial + (iinc / config.n_increments) * (
+            config.load_factor_final - config.load_factor_initial) for iinc in range(1, config.n_increments + 1)]
+        load_path = [] if plastic else None
+    else:
+        load_path = []
+    more = {}                               # with plasticity: the committed state the next increment starts from
     path = [] if displacement_control else None
     _say(f"\n{'Inc':>4} | {'Load Factor':>12} | {'Status':>10}")
     _say("-" * 40)
     result = None
     u_current = None
-    for iinc in range(1, config.n_increments + 1):
-        load_factor = config.load_factor_initial + (iinc / config.n_increments) * (
-            config.load_factor_final - config.load_factor_initial)
+    for iinc, load_factor in enumerate(load_factors, 1):
         _say(f"{iinc:>4} | {load_factor:>12.4f} | {'WARM_START' if u_current is not None else 'COLD_START':>10}")
         u_initial_torch = None
         if u_current is not None:
@@ -914,10 +1081,10 @@ def solve(
             result = solve_gd(model, config, measured_disp, measured_dofs,
                               target_load_factor=load_factor, u_initial=u_initial_torch)
         elif method == "nr":
-            result = solve_nr(model, config, target_load_factor=load_factor, u_initial=u_initial_torch)
+            result = solve_nr(model, config, target_load_factor=load_factor, u_initial=u_initial_torch, **more)
         elif method == "hybrid":
             result = solve_hybrid(model, config, measured_disp, measured_dofs,
-                                  target_load_factor=load_factor, u_initial=u_initial_torch)
+                                  target_load_factor=load_factor, u_initial=u_initial_torch, **more)
         elif method == "full-nr":
             result = solve_full_nr(model, config, measured_disp, measured_dofs,
                                    target_load_factor=load_factor)
@@ -928,6 +1095,12 @@ def solve(
             # load_factor above is the control factor; the record's is the solved one
             path.append({key: result.history[-1][key] for key in ("control_displacement", "load_factor", "iterations")})
             result.path = path
+        if plastic and result.plastic_strain is not None:
+            more = {"plastic_state": (result.plastic_strain, result.accumulated_plastic_strain)}
+        if load_path is not None:
+            load_path.append({"load_factor": float(load_factor), "iterations": result.history[-1].get("iterations", 0.0),
+                              "yielding_elements": result.history[-1].get("yielding_elements", 0.0)})
+            result.load_path = load_path
         status = "CONVERGED" if result.converged else "FAILED"
         _say(f"{iinc:4d} | {load_factor:12.6f} | {status:>10}")
         if not result.converged:
